@@ -8,6 +8,11 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+# torch first: its bundled HIP runtime carries the soname libamdhip64.so.7 that the library links against, so the dlopen below
+# binds to the runtime torch drives the GPU with.  Loaded the other way round, the process maps a second HIP / HSA runtime and
+# the library's launches find no device.
+import torch  # noqa: F401
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MEANT_LIB_PATH: load another build of the same ABI (A/B measurements of one kernel against an older build)
 LIB_PATH = os.environ.get("MEANT_LIB_PATH") or os.path.join(_HERE, "libmeant_hip.so")

@@ -65,7 +65,7 @@ def _side_stream(device):
 # default four hardware queues (main and the language stream end up sharing one) and 42.4 ms -- the "fifth-stream cliff" of round 3 --
 # once every stream has a queue of its own (GPU_MAX_HW_QUEUES=8): three compute queues, one of them high priority, plus the
 # collective's.  Without the priority stream (language stack on the caller's stream, two compute queues + the collective's):
-# 39.5 ms on four queues, 38.3 ms on eight, the best of all: bench.py exports GPU_MAX_HW_QUEUES=8 for such launches.
+# 39.5 ms on four queues, 38.3 ms on eight; bench.py leaves the runtime's default queue count alone (the slots are shared by the card's processes).
 # MEANT_LANG_PRIORITY=1 forces the priority stream on.
 _multi = int(_os.environ.get("WORLD_SIZE", "1") or "1") > 1 or _os.environ.get("MEANT_REDUCE_ALWAYS") == "1"
 LANG_PRIORITY = _os.environ.get("MEANT_LANG_PRIORITY", "0" if _multi else "1") != "0"

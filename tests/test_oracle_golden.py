@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from oracle import meant_oracle as O
+from tests.util import norm_floor
 
 TOL = 2e-5   # fp32 CPU <-> fp32 CPU, different op order
 
@@ -98,9 +99,12 @@ def _check_module(g, mod, args):
     np.testing.assert_allclose(y.detach().numpy(), g["y"], atol=TOL)
     np.testing.assert_allclose(x.grad.numpy(), g["dx"], atol=5e-5)
     params = dict(mod.named_parameters())
+    # a gradient that is structurally zero (temporal's key bias `v.bias`: the softmax is shift-invariant) holds rounding noise that
+    # depends on the host's BLAS, so its norm is compared against max(ref, floor) like everywhere else (tests/util.py:norm_floor)
+    floor = norm_floor(g["grad_norms"], torch.float32)
     for name, ref in zip(g["grad_names"], g["grad_norms"]):
         p = params[str(name)]
-        assert abs(p.grad.double().norm().item() - ref) <= 1e-4 * max(ref, 1e-3), name
+        assert abs(p.grad.double().norm().item() - ref) <= 1e-4 * max(ref, 1e-3, floor), name
         ga = g["grad__" + str(name)]
         got = p.grad if p.grad.numel() <= 4096 else p.grad[:4]
         np.testing.assert_allclose(got.numpy(), ga, atol=1e-4, rtol=1e-4)

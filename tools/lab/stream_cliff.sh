@@ -10,10 +10,6 @@ for rep in 1 2; do
   done
 done
 for n in 0 1 2; do
-  GPU_MAX_HW_QUEUES=8 python3 $R/bench.py --steps 8 --warmup 3 --no-cpu-baseline --extra-streams $n > $O/q8_$n.log 2>/dev/null
-  echo "GPU_MAX_HW_QUEUES=8, extra streams $n: $(line $O/q8_$n.log)"
-done
-for n in 0 1 2; do
   MEANT_LANG_PRIORITY=0 python3 $R/bench.py --steps 8 --warmup 3 --no-cpu-baseline --extra-streams $n > $O/noprio_$n.log 2>/dev/null
   echo "language stack without stream priority, extra streams $n: $(line $O/noprio_$n.log)"
 done

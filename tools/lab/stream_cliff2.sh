@@ -6,12 +6,10 @@ run() { tag=$1; shift; env "$@" python3 $R/bench.py --steps 8 --warmup 3 --no-cp
 for rep in 1 2 3; do
   run plain_$rep X=1
   run reduce_$rep MEANT_REDUCE_ALWAYS=1
-  run reduce_q8_$rep MEANT_REDUCE_ALWAYS=1 GPU_MAX_HW_QUEUES=8
   run reduce_noprio_$rep MEANT_REDUCE_ALWAYS=1 MEANT_LANG_PRIORITY=0
-  run reduce_q8_noprio_$rep MEANT_REDUCE_ALWAYS=1 GPU_MAX_HW_QUEUES=8 MEANT_LANG_PRIORITY=0
   run reduce_onestream_$rep MEANT_REDUCE_ALWAYS=1 MEANT_TWO_STREAMS=0
 done
-for cfg in "reduce_q8 GPU_MAX_HW_QUEUES=8" "reduce_noprio MEANT_LANG_PRIORITY=0" "reduce_q8_noprio GPU_MAX_HW_QUEUES=8 MEANT_LANG_PRIORITY=0"; do
+for cfg in "reduce_noprio MEANT_LANG_PRIORITY=0"; do
   set -- $cfg; tag=$1; shift
   for kv in "$@"; do export $kv; done
   MEANT_REDUCE_ALWAYS=1 rocprofv3 --kernel-trace -d $O/trace_$tag -o x -- python3 $R/bench.py --steps 4 --warmup 2 --no-cpu-baseline > $O/trace_$tag.log 2>&1
