@@ -94,7 +94,10 @@ int64_t meant_debug_nt_steals(void);
  * y = scale * x * rinv,  rinv = 1 / (||x||_2 / sqrt(d) + eps)   (eps outside the sqrt)
  * x,y: act [rows, d]; scale: float [d]; rinv: float [rows] (saved for backward).
  * Optional fused inverted dropout on y (meant/meant.py:105,107): keep-prob 1-p, mask regenerated
- * in backward from (seed, element index); p == 0 disables it. */
+ * in backward from (seed, element index); p == 0 disables it.
+ * Any d > 0: d % 8 == 0 and d <= 2048 take the one-row-per-wave and packed kernels (16-byte aligned x, y, scale); every
+ * other width a one-row-per-workgroup kernel (16-byte alignment when d % 8 == 0, element alignment otherwise).  The same
+ * holds for the backward, the partial forms and LayerNorm below. */
 int meant_rmsnorm_fwd(const void* x, const float* scale, void* y, float* rinv, int64_t rows, int64_t d,
                       float eps, float drop_p, uint64_t seed, int dtype, void* stream);
 /* dx: act [rows, d]; dscale: float [d] (overwritten); workspace: meant_rmsnorm_bwd_ws(rows, d) bytes.
@@ -109,7 +112,8 @@ int meant_rmsnorm_bwd(const void* dy, const void* x, const float* scale, const f
 
 /* ---- RMSNorm, partial / bias forms of the reference class ------- utils/rms_norm.py:44-57 (RMSNorm(d, p, bias))
  * statistics over the first d_part = int(d * p) elements of a row (1 <= d_part <= d), y = scale * x / (rms_part + eps) + offset
- * (offset float [d] or NULL).  No MEANT model constructs these; served by the generic one-row-per-wave kernels. */
+ * (offset float [d] or NULL).  No MEANT model constructs these; served by the generic one-row-per-wave kernels (d % 8 == 0,
+ * d <= 2048) and the one-row-per-workgroup kernels (any other d > 0). */
 int meant_rmsnorm_partial_fwd(const void* x, const float* scale, const float* offset, void* y, float* rinv, int64_t rows,
                               int64_t d, int64_t d_part, float eps, int dtype, void* stream);
 int meant_rmsnorm_partial_bwd(const void* dy, const void* x, const float* scale, const float* rinv, void* dx, float* dscale,

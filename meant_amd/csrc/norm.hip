@@ -732,6 +732,384 @@ __global__ __launch_bounds__(NORM_THREADS) void layernorm_bwd_kernel(const T* __
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Wide and odd-width rows: every shape the kernels above do not take (d > 2048, or d % 8 != 0).  One 256-thread workgroup
+// per row, grid-stride over rows with at most norm_blocks(rows) workgroups (so the backward's per-block partial rows fit
+// meant_rmsnorm_bwd_ws).  Thread t owns chunks t, t + 256, ... of V elements of a row: V = 8 (16-byte loads) when d % 8 == 0;
+// V = 1 otherwise -- a row of such a width is not 16-byte aligned, and these shapes take element loads throughout (a
+// correctness route, not a tuned one).  A slice of WIDE_SLICE elements is WIDE_CPT chunks per thread: a row of one slice
+// (d <= 8192) stays in registers between the reduction and the write (one read and one write per element); a longer row is
+// read again, slice by slice, for each later pass (expected from L2).  Row sums: wave_sum, then a fixed-order combine of
+// the four waves through LDS.
+constexpr int WIDE_SLICE = 8192;
+template <int V> constexpr int WIDE_CPT = WIDE_SLICE / (NORM_THREADS * V);
+constexpr int64_t NORM_MAX_D = 2147483647LL - WIDE_SLICE;   // the column index of a slice chunk stays an int
+
+// first column of chunk c of slice s of this thread
+template <int V> __device__ __forceinline__ int wide_col(int s, int c) { return s * WIDE_SLICE + ((int)threadIdx.x + c * NORM_THREADS) * V; }
+
+template <typename T, int V> __device__ __forceinline__ void wide_load(const T* p, float (&f)[V]) {
+  if constexpr (V == 8) {
+    const Vec8<T> v = load8<T>(p);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) f[i] = v.get(i);
+  } else f[0] = to_f(p[0]);
+}
+template <typename T, int V> __device__ __forceinline__ void wide_store(T* p, const float (&f)[V]) {
+  if constexpr (V == 8) {
+    Vec8<T> o;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) o.set(i, f[i]);
+    store8<T>(p, o);
+  } else p[0] = from_f<T>(f[0]);
+}
+// V consecutive fp32 parameters (gain, offset, bias)
+template <int V> __device__ __forceinline__ void wide_param(const float* p, float (&f)[V]) {
+  if constexpr (V == 8) {
+    const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { f[i] = a[i]; f[i + 4] = b[i]; }
+  } else f[0] = p[0];
+}
+// keep-multipliers of the V elements from flat index e by the rule of keep_scale8: element e is decided by the draw for
+// e >> 3, its part e & 7, whatever the row's width (V = 8: e is a multiple of 8)
+template <int V> __device__ __forceinline__ void wide_keep(float p, uint64_t seed, uint64_t e, float (&m)[V]) {
+  if (!(p > 0.f)) {
+#pragma unroll
+    for (int i = 0; i < V; ++i) m[i] = 1.f;
+    return;
+  }
+  float km[8];
+  keep_scale8(p, seed, e & ~7ull, km);
+  if constexpr (V == 8) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) m[i] = km[i];
+  } else {
+    const int q = (int)(e & 7);
+    float s = km[0];
+#pragma unroll
+    for (int j = 1; j < 8; ++j) s = q == j ? km[j] : s;      // a select chain, not a dynamic index into a private array
+    m[0] = s;
+  }
+}
+// sum over the workgroup, the same value in every thread (red: 4 floats of LDS)
+__device__ __forceinline__ float block_sum(float v, float* red) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  const float s = (red[0] + red[1]) + (red[2] + red[3]);
+  __syncthreads();
+  return s;
+}
+
+// the arguments and the result of rmsnorm_fwd_kernel, any d
+template <typename T, int V>
+__global__ __launch_bounds__(NORM_THREADS) void rmsnorm_fwd_wide_kernel(const T* __restrict__ x, const float* __restrict__ scale,
+                                                                         T* __restrict__ y, float* __restrict__ rinv_out, int64_t rows,
+                                                                         int d, float eps, float drop_p, uint64_t seed, int d_part,
+                                                                         const float* __restrict__ offset) {
+  __shared__ float red[4];
+  constexpr int CPT = WIDE_CPT<V>;
+  const int ns = (d + WIDE_SLICE - 1) / WIDE_SLICE;
+  const float inv_sqrt_d = rsqrtf((float)d_part);
+  for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
+    const T* xr = x + row * d;
+    T* yr = y + row * d;
+    float v[CPT][V];
+    float ss = 0.f;
+    for (int s = 0; s < ns; ++s) {
+#pragma unroll
+      for (int c = 0; c < CPT; ++c) {
+        const int col = wide_col<V>(s, c);
+        if (col < d) {
+          wide_load<T, V>(xr + col, v[c]);
+#pragma unroll
+          for (int i = 0; i < V; ++i) ss += col + i < d_part ? v[c][i] * v[c][i] : 0.f;
+        }
+      }
+    }
+    ss = block_sum(ss, red);
+    const float r = 1.0f / (sqrtf(ss) * inv_sqrt_d + eps);
+    if (threadIdx.x == 0) rinv_out[row] = r;
+    for (int s = 0; s < ns; ++s) {
+#pragma unroll
+      for (int c = 0; c < CPT; ++c) {
+        const int col = wide_col<V>(s, c);
+        if (col < d) {
+          if (ns > 1) wide_load<T, V>(xr + col, v[c]);
+          float g[V], km[V], o[V];
+          wide_param<V>(scale + col, g);
+          wide_keep<V>(drop_p, seed, (uint64_t)row * d + col, km);
+#pragma unroll
+          for (int i = 0; i < V; ++i) o[i] = g[i] * (v[c][i] * r) * km[i] + (offset ? offset[col + i] : 0.f);
+          wide_store<T, V>(yr + col, o);
+        }
+      }
+    }
+  }
+}
+
+// one chunk of the RMSNorm backward's inputs: x, the masked dy, and gain * masked dy
+template <typename T, int V>
+__device__ __forceinline__ void rms_bwd_in(const T* dy, const T* x, const float* scale, int64_t off, int col, float drop_p, uint64_t seed,
+                                           float (&xv)[V], float (&dyv)[V], float (&gd)[V]) {
+  float g[V], km[V];
+  wide_load<T, V>(x + off + col, xv);
+  wide_load<T, V>(dy + off + col, dyv);
+  wide_param<V>(scale + col, g);
+  wide_keep<V>(drop_p, seed, (uint64_t)off + col, km);
+#pragma unroll
+  for (int i = 0; i < V; ++i) { dyv[i] *= km[i]; gd[i] = g[i] * dyv[i]; }
+}
+
+// the arguments and the results of rmsnorm_bwd_kernel, any d (OFF: partial_off is written).  The gain (and offset) gradient
+// sums of the block's rows stay in registers for a one-slice row; for a longer row they are kept in the block's own partial
+// row itself (each column read and written by one thread only, no atomics)
+template <typename T, int V, bool OFF>
+__global__ __launch_bounds__(NORM_THREADS) void rmsnorm_bwd_wide_kernel(const T* __restrict__ dy, const T* __restrict__ x,
+                                                                         const float* __restrict__ scale, const float* __restrict__ rinv,
+                                                                         T* __restrict__ dx, float* __restrict__ partial, int64_t rows,
+                                                                         int d, float eps, float drop_p, uint64_t seed,
+                                                                         const T* __restrict__ dres, const T* __restrict__ gelu_pre,
+                                                                         int d_part, float* __restrict__ partial_off) {
+  __shared__ float red[4];
+  constexpr int CPT = WIDE_CPT<V>;
+  const int ns = (d + WIDE_SLICE - 1) / WIDE_SLICE;
+  const bool resident = ns == 1;
+  float* prow = partial + (int64_t)blockIdx.x * d;
+  float* orow = OFF ? partial_off + (int64_t)blockIdx.x * d : nullptr;
+  float gacc[CPT][V], oacc[OFF ? CPT : 1][V];
+#pragma unroll
+  for (int c = 0; c < CPT; ++c)
+#pragma unroll
+    for (int i = 0; i < V; ++i) { gacc[c][i] = 0.f; if (OFF) oacc[c][i] = 0.f; }
+  if (!resident) {
+    for (int s = 0; s < ns; ++s)
+#pragma unroll
+      for (int c = 0; c < CPT; ++c) {
+        const int col = wide_col<V>(s, c);
+        if (col < d) {
+#pragma unroll
+          for (int i = 0; i < V; ++i) { prow[col + i] = 0.f; if (OFF) orow[col + i] = 0.f; }
+        }
+      }
+  }
+  for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
+    const int64_t off = row * d;
+    const float r = rinv[row];
+    float xv[CPT][V], gd[CPT][V];
+    float cdot = 0.f;
+    for (int s = 0; s < ns; ++s) {
+#pragma unroll
+      for (int c = 0; c < CPT; ++c) {
+        const int col = wide_col<V>(s, c);
+        if (col < d) {
+          float dyv[V];
+          rms_bwd_in<T, V>(dy, x, scale, off, col, drop_p, seed, xv[c], dyv, gd[c]);
+#pragma unroll
+          for (int i = 0; i < V; ++i) {
+            cdot += gd[c][i] * xv[c][i];
+            const float ga = dyv[i] * xv[c][i] * r;
+            if (resident) { gacc[c][i] += ga; if (OFF) oacc[c][i] += dyv[i]; }
+            else { prow[col + i] += ga; if (OFF) orow[col + i] += dyv[i]; }
+          }
+        }
+      }
+    }
+    cdot = block_sum(cdot, red);
+    const float nsd = (1.0f / r - eps) * (float)d_part;     // ||x_part|| * sqrt(d_part)
+    const float k = nsd > 0.f ? cdot * r * r / nsd : 0.f;
+    for (int s = 0; s < ns; ++s) {
+#pragma unroll
+      for (int c = 0; c < CPT; ++c) {
+        const int col = wide_col<V>(s, c);
+        if (col < d) {
+          if (!resident) {
+            float dyv[V];
+            rms_bwd_in<T, V>(dy, x, scale, off, col, drop_p, seed, xv[c], dyv, gd[c]);
+          }
+          float o[V];
+#pragma unroll
+          for (int i = 0; i < V; ++i) o[i] = r * gd[c][i] - (col + i < d_part ? k * xv[c][i] : 0.f);
+          if (dres) {
+            float rv[V];
+            wide_load<T, V>(dres + off + col, rv);
+#pragma unroll
+            for (int i = 0; i < V; ++i) o[i] = from_f<T>(o[i]) + rv[i];       // rounded as the generic kernel's Vec8 sum
+          }
+          if (gelu_pre) {
+            float pv[V];
+            wide_load<T, V>(gelu_pre + off + col, pv);
+#pragma unroll
+            for (int i = 0; i < V; ++i) o[i] = from_f<T>(o[i]) * gelu_grad_t<T>(pv[i]);
+          }
+          wide_store<T, V>(dx + off + col, o);
+        }
+      }
+    }
+  }
+  if (resident) {
+#pragma unroll
+    for (int c = 0; c < CPT; ++c) {
+      const int col = wide_col<V>(0, c);
+      if (col < d) {
+#pragma unroll
+        for (int i = 0; i < V; ++i) { prow[col + i] = gacc[c][i]; if (OFF) orow[col + i] = oacc[c][i]; }
+      }
+    }
+  }
+}
+
+// the arguments and the result of layernorm_fwd_kernel, any d; the variance is taken about the mean in a pass of its own
+template <typename T, int V>
+__global__ __launch_bounds__(NORM_THREADS) void layernorm_fwd_wide_kernel(const T* __restrict__ x, const float* __restrict__ gamma,
+                                                                           const float* __restrict__ beta, T* __restrict__ y,
+                                                                           float* __restrict__ stats, int64_t rows, int d, float eps) {
+  __shared__ float red[4];
+  constexpr int CPT = WIDE_CPT<V>;
+  const int ns = (d + WIDE_SLICE - 1) / WIDE_SLICE;
+  for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
+    const T* xr = x + row * d;
+    T* yr = y + row * d;
+    float v[CPT][V];
+    float sm = 0.f;
+    for (int s = 0; s < ns; ++s) {
+#pragma unroll
+      for (int c = 0; c < CPT; ++c) {
+        const int col = wide_col<V>(s, c);
+        if (col < d) {
+          wide_load<T, V>(xr + col, v[c]);
+#pragma unroll
+          for (int i = 0; i < V; ++i) sm += v[c][i];
+        }
+      }
+    }
+    const float mean = block_sum(sm, red) / (float)d;
+    float q = 0.f;
+    for (int s = 0; s < ns; ++s) {
+#pragma unroll
+      for (int c = 0; c < CPT; ++c) {
+        const int col = wide_col<V>(s, c);
+        if (col < d) {
+          if (ns > 1) wide_load<T, V>(xr + col, v[c]);
+#pragma unroll
+          for (int i = 0; i < V; ++i) { const float t = v[c][i] - mean; q += t * t; }
+        }
+      }
+    }
+    const float rstd = rsqrtf(block_sum(q, red) / (float)d + eps);
+    if (threadIdx.x == 0) { stats[row * 2] = mean; stats[row * 2 + 1] = rstd; }
+    for (int s = 0; s < ns; ++s) {
+#pragma unroll
+      for (int c = 0; c < CPT; ++c) {
+        const int col = wide_col<V>(s, c);
+        if (col < d) {
+          if (ns > 1) wide_load<T, V>(xr + col, v[c]);
+          float g[V], b[V], o[V];
+          wide_param<V>(gamma + col, g);
+          wide_param<V>(beta + col, b);
+#pragma unroll
+          for (int i = 0; i < V; ++i) o[i] = (v[c][i] - mean) * rstd * g[i] + b[i];
+          wide_store<T, V>(yr + col, o);
+        }
+      }
+    }
+  }
+}
+
+// one chunk of the LayerNorm backward's inputs: x-hat, dy, gamma * dy
+template <typename T, int V>
+__device__ __forceinline__ void ln_bwd_in(const T* dy, const T* x, const float* gamma, int64_t off, int col, float mean, float rstd,
+                                          float (&xh)[V], float (&dyv)[V], float (&gd)[V]) {
+  float xv[V], g[V];
+  wide_load<T, V>(x + off + col, xv);
+  wide_load<T, V>(dy + off + col, dyv);
+  wide_param<V>(gamma + col, g);
+#pragma unroll
+  for (int i = 0; i < V; ++i) { xh[i] = (xv[i] - mean) * rstd; gd[i] = dyv[i] * g[i]; }
+}
+
+// the arguments and the results of layernorm_bwd_kernel (partial[2][gridDim][d]), any d; gradient sums as in rmsnorm_bwd_wide_kernel
+template <typename T, int V>
+__global__ __launch_bounds__(NORM_THREADS) void layernorm_bwd_wide_kernel(const T* __restrict__ dy, const T* __restrict__ x,
+                                                                           const float* __restrict__ gamma, const float* __restrict__ stats,
+                                                                           T* __restrict__ dx, float* __restrict__ partial, int64_t rows,
+                                                                           int d) {
+  __shared__ float red[4];
+  constexpr int CPT = WIDE_CPT<V>;
+  const int ns = (d + WIDE_SLICE - 1) / WIDE_SLICE;
+  const bool resident = ns == 1;
+  float* grow = partial + (int64_t)blockIdx.x * d;
+  float* brow = partial + ((int64_t)gridDim.x + blockIdx.x) * d;
+  float ga[CPT][V], ba[CPT][V];
+#pragma unroll
+  for (int c = 0; c < CPT; ++c)
+#pragma unroll
+    for (int i = 0; i < V; ++i) { ga[c][i] = 0.f; ba[c][i] = 0.f; }
+  if (!resident) {
+    for (int s = 0; s < ns; ++s)
+#pragma unroll
+      for (int c = 0; c < CPT; ++c) {
+        const int col = wide_col<V>(s, c);
+        if (col < d) {
+#pragma unroll
+          for (int i = 0; i < V; ++i) { grow[col + i] = 0.f; brow[col + i] = 0.f; }
+        }
+      }
+  }
+  for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
+    const int64_t off = row * d;
+    const float mean = stats[row * 2], rstd = stats[row * 2 + 1];
+    float xh[CPT][V], gd[CPT][V];
+    float s1 = 0.f, s2 = 0.f;
+    for (int s = 0; s < ns; ++s) {
+#pragma unroll
+      for (int c = 0; c < CPT; ++c) {
+        const int col = wide_col<V>(s, c);
+        if (col < d) {
+          float dyv[V];
+          ln_bwd_in<T, V>(dy, x, gamma, off, col, mean, rstd, xh[c], dyv, gd[c]);
+#pragma unroll
+          for (int i = 0; i < V; ++i) {
+            s1 += gd[c][i];
+            s2 += gd[c][i] * xh[c][i];
+            if (resident) { ga[c][i] += dyv[i] * xh[c][i]; ba[c][i] += dyv[i]; }
+            else { grow[col + i] += dyv[i] * xh[c][i]; brow[col + i] += dyv[i]; }
+          }
+        }
+      }
+    }
+    s1 = block_sum(s1, red) / (float)d;
+    s2 = block_sum(s2, red) / (float)d;
+    for (int s = 0; s < ns; ++s) {
+#pragma unroll
+      for (int c = 0; c < CPT; ++c) {
+        const int col = wide_col<V>(s, c);
+        if (col < d) {
+          if (!resident) {
+            float dyv[V];
+            ln_bwd_in<T, V>(dy, x, gamma, off, col, mean, rstd, xh[c], dyv, gd[c]);
+          }
+          float o[V];
+#pragma unroll
+          for (int i = 0; i < V; ++i) o[i] = rstd * (gd[c][i] - s1 - xh[c][i] * s2);
+          wide_store<T, V>(dx + off + col, o);
+        }
+      }
+    }
+  }
+  if (resident) {
+#pragma unroll
+    for (int c = 0; c < CPT; ++c) {
+      const int col = wide_col<V>(0, c);
+      if (col < d) {
+#pragma unroll
+        for (int i = 0; i < V; ++i) { grow[col + i] = ga[c][i]; brow[col + i] = ba[c][i]; }
+      }
+    }
+  }
+}
+
 inline int packed_blocks(int64_t groups) {
   int64_t b = ceil_div(groups, 4);
   return (int)(b < 1 ? 1 : (b > NORM_PACKED_BLOCKS ? NORM_PACKED_BLOCKS : b));
@@ -748,16 +1126,60 @@ inline int norm_blocks(int64_t rows) {
   int64_t b = ceil_div(rows, 4);
   return (int)(b < 1 ? 1 : (b > NORM_MAX_BLOCKS ? NORM_MAX_BLOCKS : b));
 }
+// the widths of the one-wave-per-row and packed kernels; every other d > 0 goes to the *_wide_kernel family
+inline bool norm_narrow(int64_t d) { return d % 8 == 0 && d <= MAXC * 512; }
+// alignment a wide-route kernel needs: 16 bytes for the 8-element loads (d % 8 == 0), the element's own otherwise
+inline bool wide_aligned(const void* p, int64_t d, size_t elt) {
+  return d % 8 == 0 ? meant_aligned16(p) : (reinterpret_cast<uintptr_t>(p) % elt) == 0;
+}
+inline size_t dtype_bytes(int dtype) { return dtype == MEANT_BF16 ? 2 : 4; }
+
+int rmsnorm_fwd_wide(const void* x, const float* scale, void* y, float* rinv, int64_t rows, int64_t d, float eps, float drop_p, uint64_t seed,
+                     int64_t d_part, const float* offset, int dtype, void* stream, const char* name) {
+#define LAUNCH_FW(VV)                                                                                                         \
+  DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((rmsnorm_fwd_wide_kernel<T, VV>), dim3(norm_blocks(rows)), dim3(NORM_THREADS), 0,        \
+                                              (hipStream_t)stream, (const T*)x, scale, (T*)y, rinv, rows, (int)d, eps, drop_p, seed,   \
+                                              (int)d_part, offset))
+  if (d % 8 == 0) LAUNCH_FW(8); else LAUNCH_FW(1);
+#undef LAUNCH_FW
+  MEANT_LAUNCH_CHECK(name);
+  return MEANT_OK;
+}
+
+// dscale (and doffset, if not null) from the per-block partial rows in `workspace` (meant_rmsnorm_bwd_ws bytes)
+int rmsnorm_bwd_wide(const void* dy, const void* x, const float* scale, const float* rinv, void* dx, float* dscale, float* doffset,
+                     int64_t rows, int64_t d, int64_t d_part, float eps, float drop_p, uint64_t seed, const void* dres, const void* gelu_pre,
+                     int dtype, void* workspace, void* stream, const char* name) {
+  const int nb = norm_blocks(rows);
+  float* part1 = (float*)workspace;
+  float* part2 = doffset ? part1 + (size_t)nb * d : nullptr;
+#define LAUNCH_BW(VV, OO)                                                                                                     \
+  DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((rmsnorm_bwd_wide_kernel<T, VV, OO>), dim3(nb), dim3(NORM_THREADS), 0, (hipStream_t)stream, \
+                                              (const T*)dy, (const T*)x, scale, rinv, (T*)dx, part1, rows, (int)d, eps, drop_p, seed,  \
+                                              (const T*)dres, (const T*)gelu_pre, (int)d_part, part2))
+  if (d % 8 == 0) { if (doffset) LAUNCH_BW(8, true); else LAUNCH_BW(8, false); }
+  else { if (doffset) LAUNCH_BW(1, true); else LAUNCH_BW(1, false); }
+#undef LAUNCH_BW
+  MEANT_LAUNCH_CHECK(name);
+  int rc = colsum_launch(part1, d, dscale, nb, d, MEANT_F32, 0, (hipStream_t)stream);
+  if (rc || !doffset) return rc;
+  return colsum_launch(part2, d, doffset, nb, d, MEANT_F32, 0, (hipStream_t)stream);
+}
 
 }  // namespace
 
 extern "C" int meant_rmsnorm_fwd(const void* x, const float* scale, void* y, float* rinv, int64_t rows, int64_t d,
                                  float eps, float drop_p, uint64_t seed, int dtype, void* stream) {
   MEANT_REQUIRE(x && scale && y && rinv, MEANT_ERR_ARG, "rmsnorm_fwd: null pointer");
-  MEANT_REQUIRE(rows >= 0 && d > 0 && d % 8 == 0 && d <= MAXC * 512, MEANT_ERR_UNSUPPORTED,
-                "rmsnorm_fwd: d=%lld must be a multiple of 8 and <= %d", (long long)d, MAXC * 512);
-  MEANT_REQUIRE(meant_aligned16(x) && meant_aligned16(y) && meant_aligned16(scale), MEANT_ERR_ARG, "rmsnorm_fwd: 16-byte alignment");
+  MEANT_REQUIRE(rows >= 0 && d > 0 && d <= NORM_MAX_D, MEANT_ERR_UNSUPPORTED, "rmsnorm_fwd: unsupported d=%lld", (long long)d);
   MEANT_REQUIRE(drop_p >= 0.f && drop_p < 1.f, MEANT_ERR_ARG, "rmsnorm_fwd: drop_p out of range");
+  if (!norm_narrow(d)) {
+    const size_t eb = dtype_bytes(dtype);
+    MEANT_REQUIRE(wide_aligned(x, d, eb) && wide_aligned(y, d, eb) && wide_aligned(scale, d, 4), MEANT_ERR_ARG, "rmsnorm_fwd: alignment");
+    if (rows == 0) return MEANT_OK;
+    return rmsnorm_fwd_wide(x, scale, y, rinv, rows, d, eps, drop_p, seed, d, nullptr, dtype, stream, "rmsnorm_fwd");
+  }
+  MEANT_REQUIRE(meant_aligned16(x) && meant_aligned16(y) && meant_aligned16(scale), MEANT_ERR_ARG, "rmsnorm_fwd: 16-byte alignment");
   if (rows == 0) return MEANT_OK;
   int R, C;
   norm_packing(rows, d, R, C);
@@ -788,8 +1210,15 @@ extern "C" int meant_rmsnorm_bwd(const void* dy, const void* x, const float* sca
                                  const void* dres, const void* gelu_pre, int dtype, void* workspace, size_t workspace_bytes,
                                  void* stream) {
   MEANT_REQUIRE(dy && x && scale && rinv && dx && dscale && workspace, MEANT_ERR_ARG, "rmsnorm_bwd: null pointer");
-  MEANT_REQUIRE(rows > 0 && d > 0 && d % 8 == 0 && d <= MAXC * 512, MEANT_ERR_UNSUPPORTED, "rmsnorm_bwd: unsupported d=%lld", (long long)d);
+  MEANT_REQUIRE(rows > 0 && d > 0 && d <= NORM_MAX_D, MEANT_ERR_UNSUPPORTED, "rmsnorm_bwd: unsupported d=%lld", (long long)d);
   MEANT_REQUIRE(workspace_bytes >= meant_rmsnorm_bwd_ws(rows, d), MEANT_ERR_WORKSPACE, "rmsnorm_bwd: workspace too small");
+  if (!norm_narrow(d)) {
+    const size_t eb = dtype_bytes(dtype);
+    MEANT_REQUIRE(wide_aligned(dy, d, eb) && wide_aligned(x, d, eb) && wide_aligned(dx, d, eb) && wide_aligned(scale, d, 4) &&
+                  (!dres || wide_aligned(dres, d, eb)) && (!gelu_pre || wide_aligned(gelu_pre, d, eb)), MEANT_ERR_ARG, "rmsnorm_bwd: alignment");
+    return rmsnorm_bwd_wide(dy, x, scale, rinv, dx, dscale, nullptr, rows, d, d, eps, drop_p, seed, dres, gelu_pre, dtype, workspace, stream,
+                            "rmsnorm_bwd");
+  }
   int R, C;
   norm_packing(rows, d, R, C);
   if (R) {
@@ -816,8 +1245,14 @@ extern "C" int meant_rmsnorm_bwd(const void* dy, const void* x, const float* sca
 extern "C" int meant_rmsnorm_partial_fwd(const void* x, const float* scale, const float* offset, void* y, float* rinv, int64_t rows,
                                          int64_t d, int64_t d_part, float eps, int dtype, void* stream) {
   MEANT_REQUIRE(x && scale && y && rinv, MEANT_ERR_ARG, "rmsnorm_partial_fwd: null pointer");
-  MEANT_REQUIRE(rows >= 0 && d > 0 && d % 8 == 0 && d <= MAXC * 512 && d_part >= 1 && d_part <= d, MEANT_ERR_UNSUPPORTED,
-                "rmsnorm_partial_fwd: d=%lld must be a multiple of 8 and <= %d, 1 <= d_part=%lld <= d", (long long)d, MAXC * 512, (long long)d_part);
+  MEANT_REQUIRE(rows >= 0 && d > 0 && d <= NORM_MAX_D && d_part >= 1 && d_part <= d, MEANT_ERR_UNSUPPORTED,
+                "rmsnorm_partial_fwd: d=%lld, d_part=%lld: need 1 <= d_part <= d", (long long)d, (long long)d_part);
+  if (!norm_narrow(d)) {
+    const size_t eb = dtype_bytes(dtype);
+    MEANT_REQUIRE(wide_aligned(x, d, eb) && wide_aligned(y, d, eb) && wide_aligned(scale, d, 4), MEANT_ERR_ARG, "rmsnorm_partial_fwd: alignment");
+    if (rows == 0) return MEANT_OK;
+    return rmsnorm_fwd_wide(x, scale, y, rinv, rows, d, eps, 0.f, 0, d_part, offset, dtype, stream, "rmsnorm_partial_fwd");
+  }
   MEANT_REQUIRE(meant_aligned16(x) && meant_aligned16(y) && meant_aligned16(scale), MEANT_ERR_ARG, "rmsnorm_partial_fwd: 16-byte alignment");
   if (rows == 0) return MEANT_OK;
   DISPATCH_DTYPE(dtype, T,
@@ -831,8 +1266,15 @@ extern "C" int meant_rmsnorm_partial_bwd(const void* dy, const void* x, const fl
                                          float* doffset, int64_t rows, int64_t d, int64_t d_part, float eps, int dtype, void* workspace,
                                          size_t workspace_bytes, void* stream) {
   MEANT_REQUIRE(dy && x && scale && rinv && dx && dscale && workspace, MEANT_ERR_ARG, "rmsnorm_partial_bwd: null pointer");
-  MEANT_REQUIRE(rows > 0 && d > 0 && d % 8 == 0 && d <= MAXC * 512 && d_part >= 1 && d_part <= d, MEANT_ERR_UNSUPPORTED, "rmsnorm_partial_bwd: unsupported shape");
+  MEANT_REQUIRE(rows > 0 && d > 0 && d <= NORM_MAX_D && d_part >= 1 && d_part <= d, MEANT_ERR_UNSUPPORTED, "rmsnorm_partial_bwd: unsupported shape");
   MEANT_REQUIRE(workspace_bytes >= meant_rmsnorm_bwd_ws(rows, d), MEANT_ERR_WORKSPACE, "rmsnorm_partial_bwd: workspace too small");
+  if (!norm_narrow(d)) {
+    const size_t eb = dtype_bytes(dtype);
+    MEANT_REQUIRE(wide_aligned(dy, d, eb) && wide_aligned(x, d, eb) && wide_aligned(dx, d, eb) && wide_aligned(scale, d, 4), MEANT_ERR_ARG,
+                  "rmsnorm_partial_bwd: alignment");
+    return rmsnorm_bwd_wide(dy, x, scale, rinv, dx, dscale, doffset, rows, d, d_part, eps, 0.f, 0, nullptr, nullptr, dtype, workspace, stream,
+                            "rmsnorm_partial_bwd");
+  }
   const int nb = norm_blocks(rows);
   float* part1 = (float*)workspace;
   float* part2 = doffset ? part1 + (size_t)nb * d : nullptr;
@@ -959,7 +1401,19 @@ extern "C" int meant_rmsnorm_bwd_chain(const void* dy, int dy_pooled, const void
 extern "C" int meant_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* stats,
                                    int64_t rows, int64_t d, float eps, int dtype, void* stream) {
   MEANT_REQUIRE(x && gamma && beta && y && stats, MEANT_ERR_ARG, "layernorm_fwd: null pointer");
-  MEANT_REQUIRE(rows > 0 && d % 8 == 0 && d <= MAXC * 512, MEANT_ERR_UNSUPPORTED, "layernorm_fwd: unsupported d=%lld", (long long)d);
+  MEANT_REQUIRE(rows > 0 && d > 0 && d <= NORM_MAX_D, MEANT_ERR_UNSUPPORTED, "layernorm_fwd: unsupported d=%lld", (long long)d);
+  if (!norm_narrow(d)) {
+    const size_t eb = dtype_bytes(dtype);
+    MEANT_REQUIRE(wide_aligned(x, d, eb) && wide_aligned(y, d, eb) && wide_aligned(gamma, d, 4) && wide_aligned(beta, d, 4), MEANT_ERR_ARG,
+                  "layernorm_fwd: alignment");
+#define LAUNCH_LNW(VV)                                                                                                        \
+    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((layernorm_fwd_wide_kernel<T, VV>), dim3(norm_blocks(rows)), dim3(NORM_THREADS), 0,      \
+                                                (hipStream_t)stream, (const T*)x, gamma, beta, (T*)y, stats, rows, (int)d, eps))
+    if (d % 8 == 0) LAUNCH_LNW(8); else LAUNCH_LNW(1);
+#undef LAUNCH_LNW
+    MEANT_LAUNCH_CHECK("layernorm_fwd");
+    return MEANT_OK;
+  }
   DISPATCH_DTYPE(dtype, T,
                  hipLaunchKernelGGL(layernorm_fwd_kernel<T>, dim3(norm_blocks(rows)), dim3(NORM_THREADS), 0, (hipStream_t)stream,
                                     (const T*)x, gamma, beta, (T*)y, stats, rows, (int)d, eps));
@@ -971,12 +1425,23 @@ extern "C" int meant_layernorm_bwd(const void* dy, const void* x, const float* g
                                    float* dgamma, float* dbeta, int64_t rows, int64_t d, int dtype, void* workspace,
                                    size_t workspace_bytes, void* stream) {
   MEANT_REQUIRE(dy && x && gamma && stats && dx && dgamma && dbeta && workspace, MEANT_ERR_ARG, "layernorm_bwd: null pointer");
-  MEANT_REQUIRE(rows > 0 && d % 8 == 0 && d <= MAXC * 512, MEANT_ERR_UNSUPPORTED, "layernorm_bwd: unsupported d=%lld", (long long)d);
+  MEANT_REQUIRE(rows > 0 && d > 0 && d <= NORM_MAX_D, MEANT_ERR_UNSUPPORTED, "layernorm_bwd: unsupported d=%lld", (long long)d);
   MEANT_REQUIRE(workspace_bytes >= meant_rmsnorm_bwd_ws(rows, d), MEANT_ERR_WORKSPACE, "layernorm_bwd: workspace too small");
   const int nb = norm_blocks(rows);
-  DISPATCH_DTYPE(dtype, T,
-                 hipLaunchKernelGGL(layernorm_bwd_kernel<T>, dim3(nb), dim3(NORM_THREADS), 0, (hipStream_t)stream, (const T*)dy,
-                                    (const T*)x, gamma, stats, (T*)dx, (float*)workspace, rows, (int)d));
+  if (!norm_narrow(d)) {
+    const size_t eb = dtype_bytes(dtype);
+    MEANT_REQUIRE(wide_aligned(dy, d, eb) && wide_aligned(x, d, eb) && wide_aligned(dx, d, eb) && wide_aligned(gamma, d, 4), MEANT_ERR_ARG,
+                  "layernorm_bwd: alignment");
+#define LAUNCH_LNBW(VV)                                                                                                       \
+    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((layernorm_bwd_wide_kernel<T, VV>), dim3(nb), dim3(NORM_THREADS), 0, (hipStream_t)stream, \
+                                                (const T*)dy, (const T*)x, gamma, stats, (T*)dx, (float*)workspace, rows, (int)d))
+    if (d % 8 == 0) LAUNCH_LNBW(8); else LAUNCH_LNBW(1);
+#undef LAUNCH_LNBW
+  } else {
+    DISPATCH_DTYPE(dtype, T,
+                   hipLaunchKernelGGL(layernorm_bwd_kernel<T>, dim3(nb), dim3(NORM_THREADS), 0, (hipStream_t)stream, (const T*)dy,
+                                      (const T*)x, gamma, stats, (T*)dx, (float*)workspace, rows, (int)d));
+  }
   MEANT_LAUNCH_CHECK("layernorm_bwd");
   int rc = colsum_launch(workspace, d, dgamma, nb, d, MEANT_F32, 0, (hipStream_t)stream);
   if (rc) return rc;

@@ -99,7 +99,9 @@ def resolve_compute_dtype(module: nn.Module, like: Optional[torch.Tensor]) -> to
 class RMSNorm(nn.Module):
     """utils/rms_norm.py:16-57.  The full-width, bias-free form (p = -1, bias = False) that every MEANT model uses runs on the packed
     / fused kernels; the partial form (0 <= p <= 1: statistics over the first int(d p) elements, :44-50) and the bias form (a learned
-    `offset`, :35-37, :54-55) run on the generic one-row-per-wave kernels (meant_rmsnorm_partial_*), without the fusions."""
+    `offset`, :35-37, :54-55) run on the generic one-row-per-wave kernels (meant_rmsnorm_partial_*), without the fusions.  Any d > 0: widths
+    above 2048 or not a multiple of 8 take the one-row-per-workgroup kernels (csrc/norm.hip); the module passes any_width=True, the ops
+    themselves keep d % 8 == 0 by default (ops._norm_width)."""
 
     def __init__(self, d, p=-1., eps=1e-8, bias=False):
         super().__init__()
@@ -114,14 +116,14 @@ class RMSNorm(nn.Module):
             d_part = int(self.d * self.p) if partial else self.d
             if d_part < 1:
                 raise ValueError(f"meant_amd.RMSNorm: p = {self.p} leaves no element to take the statistics over (d = {self.d})")
-            y = ops.rmsnorm_partial(x, self.scale, self.offset if self.bias else None, d_part, self.eps)
+            y = ops.rmsnorm_partial(x, self.scale, self.offset if self.bias else None, d_part, self.eps, any_width=True)
             return ops.dropout(y, drop_p, seed) if drop_p > 0.0 else y
-        return ops.rmsnorm(x, self.scale, self.eps, drop_p, seed)
+        return ops.rmsnorm(x, self.scale, self.eps, drop_p, seed, any_width=True)
 
 
 class LayerNorm(nn.LayerNorm):
     def forward(self, x):
-        return ops.layernorm(x, self.weight, self.bias, self.eps)
+        return ops.layernorm(x, self.weight, self.bias, self.eps, any_width=True)
 
 
 class Linear(nn.Linear):

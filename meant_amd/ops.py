@@ -141,6 +141,16 @@ weights = _WeightCache()
 
 
 # ---------------------------------------------------------------------------------------------
+def _norm_width(d: int, any_width: bool, what: str) -> None:
+    """The norm ops below take d % 8 == 0 unless the caller opts in: the widths of the model path (the embedding and the GEMM
+    epilogues around these norms need them; a whole model at an odd width is not supported).  The norm modules (RMSNorm, LayerNorm,
+    utils/rms_norm.py:16-57) take any d > 0 and pass any_width=True: the library serves the other widths with its one-row-per-workgroup
+    kernels (csrc/norm.hip)."""
+    if d % 8 and not any_width:
+        raise _lib.MeantHipError(f"meant_amd.ops.{what}: d = {d} is not a multiple of 8 (any_width=True, as the norm modules pass, "
+                                 "takes any width)")
+
+
 def _rmsnorm_fwd_raw(x, scale, eps, drop_p, seed):
     d = x.shape[-1]
     rows = x.numel() // d
@@ -180,7 +190,8 @@ class _RMSNorm(torch.autograd.Function):
         return dx, dscale, None, None, None
 
 
-def rmsnorm(x, scale, eps=1e-8, drop_p=0.0, seed=0):
+def rmsnorm(x, scale, eps=1e-8, drop_p=0.0, seed=0, any_width=False):
+    _norm_width(x.shape[-1], any_width, "rmsnorm")
     return _RMSNorm.apply(x, scale, float(eps), float(drop_p), int(seed))
 
 
@@ -221,7 +232,8 @@ class _RMSNormPartial(torch.autograd.Function):
         return dx, dscale, doff, None, None
 
 
-def rmsnorm_partial(x, scale, offset, d_part, eps=1e-8):
+def rmsnorm_partial(x, scale, offset, d_part, eps=1e-8, any_width=False):
+    _norm_width(x.shape[-1], any_width, "rmsnorm_partial")
     return _RMSNormPartial.apply(x, scale, offset, int(d_part), float(eps))
 
 
@@ -249,7 +261,8 @@ class _RMSNormFork(torch.autograd.Function):
         return dx, dscale, None
 
 
-def rmsnorm_fork(x, scale, eps=1e-8):
+def rmsnorm_fork(x, scale, eps=1e-8, any_width=False):
+    _norm_width(x.shape[-1], any_width, "rmsnorm_fork")
     return _RMSNormFork.apply(x, scale, float(eps))
 
 
@@ -306,8 +319,9 @@ class _LinearPre(torch.autograd.Function):
         return (dx.view(ctx.in_shape) if dx is not None else None), dw, db
 
 
-def linear_gelu_rmsnorm(x, weight, bias, scale, eps=1e-8, drop_p=0.0, seed=0):
-    """RMSNorm(gelu(x W^T + b)) as two fused calls forward and two backward (meant/meant.py:64 / :107)."""
+def linear_gelu_rmsnorm(x, weight, bias, scale, eps=1e-8, drop_p=0.0, seed=0, any_width=False):
+    """RMSNorm(gelu(x W^T + b)) as two fused calls forward and two backward (meant/meant.py:64 / :107); the norm's width is N."""
+    _norm_width(weight.shape[0], any_width, "linear_gelu_rmsnorm")
     a, pre = _LinearPre.apply(x, weight, bias)
     return _GeluRMSNorm.apply(a, pre, scale, float(eps), float(drop_p), int(seed))
 
@@ -651,7 +665,8 @@ class _LayerNorm(torch.autograd.Function):
         return dx, dg, db, None
 
 
-def layernorm(x, gamma, beta, eps=1e-5):
+def layernorm(x, gamma, beta, eps=1e-5, any_width=False):
+    _norm_width(x.shape[-1], any_width, "layernorm")
     return _LayerNorm.apply(x, gamma, beta, float(eps))
 
 
