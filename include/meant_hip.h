@@ -291,9 +291,12 @@ int meant_gather_rows_rot(const void* src, const int32_t* idx, void* dst, int64_
 int meant_group_scatter(const void* ddst, const int32_t* index, void* dsrc, int64_t B, int64_t L, int64_t G, int64_t S,
                         int64_t W, int dtype, void* stream);
 /* cls query: out[b, h*Dh .. +Dh] (row stride ld_out) = softmax_j(scale q[b, 0, h] . k[b, j, h] + (1 - key_mask[b, j]) * -1e9)
- * v[b, j, h] over all L rows of the packed qkv [B, L, 3*H*Dh] (:116-119, cls_mask :252-253).  stats: float [B, H, 2].
- * The backward ADDS to dqkv (the buffer meant_group_scatter has filled): dq of row 0, dk and dv of every row.
- * Dh in {32, 64, 128, 256}; L bounded by the LDS score buffer (~19 k tokens). */
+ * v[b, j, h] over all L rows of the packed qkv [B, L, 3*H*Dh] (:116-119, cls_mask :252-253); a key with key_mask 0 gets the
+ * score -1e9 itself and no score gradient (masked_fill), so every key masked gives uniform weights.  stats: float [B, H, 2]
+ * (max score, log of the sum of exp(score - max)).  The backward ADDS to dqkv (the buffer meant_group_scatter has filled): dq
+ * of row 0, dk and dv of every row; ld_dout % 8 == 0.  Dh % 8 == 0, Dh <= 256; L bounded by the LDS score buffer,
+ * (L + 4 + rpi*Dh) floats forward and (2L + 4 + rpi*Dh) backward within 159 KiB, rpi = 256 / (Dh / 8) (~38 k / ~19 k
+ * tokens); a longer L returns MEANT_ERR_UNSUPPORTED before any launch. */
 int meant_attn_cls_fwd(const void* qkv, void* out, int64_t ld_out, float* stats, const float* key_mask, int64_t B, int64_t L,
                        int H, int Dh, float scale, int dtype, void* stream);
 int meant_attn_cls_bwd(const void* qkv, const void* out, int64_t ld_out, const void* dout, int64_t ld_dout,
@@ -302,7 +305,8 @@ int meant_attn_cls_bwd(const void* qkv, const void* out, int64_t ld_out, const v
 
 /* time token shift of the patch tokens of x act [B, 1 + frames*n, d] (PreTokenShift, src/meant/timesformer_pytorch.py:28-53):
  * columns [0, d/3) from the next frame, [d/3, 2d/3) unchanged, [2d/3, 3(d/3)) from the previous frame, zeros beyond the
- * clip's ends; the cls row and any remainder columns pass through.  transpose != 0: the adjoint (backward).  x != y. */
+ * clip's ends; the cls row and any remainder columns pass through.  d % 8 == 0.  transpose != 0: the adjoint (backward).
+ * x != y. */
 int meant_token_shift(const void* x, void* y, int64_t B, int64_t frames, int64_t n, int64_t d, int transpose, int dtype,
                       void* stream);
 /* inverted dropout y = x * keep / (1 - p) (nn.Dropout at :70,:101): counter-based mask from (seed, element index), so the

@@ -113,6 +113,14 @@ __global__ __launch_bounds__(DIV_THREADS) void group_scatter_cls_kernel(const T*
 // block = (head h, video b), 256 threads.  LDS: p[L] floats (+ ds[L] in the backward), then small reduction areas.
 constexpr float CLS_PAD = -1e9f;                     // (1 - mask) * -1e9 on the scaled score, as the text path's padding term
 
+// the score of key j: a key with mask 0 gets CLS_PAD itself (the reference's masked_fill, timesformer_pytorch.py:82-84), so a
+// video whose every key is masked gets uniform weights whatever the raw scores are
+__device__ __forceinline__ float cls_mask_score(float s, const float* key_mask, int64_t i) {
+  if (!key_mask) return s;
+  const float m = key_mask[i];
+  return m == 0.f ? CLS_PAD : s + (1.0f - m) * CLS_PAD;
+}
+
 __device__ __forceinline__ float block_reduce(float v, float* red, bool is_max) {
   v = is_max ? wave_max(v) : wave_sum(v);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -143,8 +151,7 @@ __global__ __launch_bounds__(DIV_THREADS) void attn_cls_fwd_kernel(const T* __re
 #pragma unroll
       for (int k = 0; k < 8; ++k) s += kv.get(k) * qv.get(k);
     }
-    s *= scale;
-    if (key_mask) s += (1.0f - key_mask[b * L + j]) * CLS_PAD;
+    s = cls_mask_score(s * scale, key_mask, b * L + j);
     p[j] = s;
     mx = fmaxf(mx, s);
   }
@@ -158,19 +165,22 @@ __global__ __launch_bounds__(DIV_THREADS) void attn_cls_fwd_kernel(const T* __re
   sum = block_reduce(sum, red, false);                // (its barriers also publish p[])
   if (tid == 0) { stats[(b * H + h) * 2] = mx; stats[(b * H + h) * 2 + 1] = __logf(sum); }
   // out[d] = sum_j p_j v[j][d] / sum: a thread owns 8 columns of the rows j = rg, rg + rpi, ... (16-byte loads), the
-  // rpi = 256 / (Dh / 8) row groups are combined through LDS
+  // rpi = 256 / (Dh / 8) row groups are combined through LDS.  When Dh / 8 does not divide 256 (Dh = 96: rpi = 21), the
+  // threads past rpi row groups take no row and write no partial.
   const int nc = Dh >> 3, rpi = DIV_THREADS / nc;
   const int c8 = (tid % nc) * 8, rg = tid / nc;
   float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (int j = rg; j < L; j += rpi) {
+  for (int j = rg; rg < rpi && j < L; j += rpi) {
     const Vec8<T> vv = load8<T>(base + (int64_t)j * ld + 2 * D + c8);
     const float pj = p[j];
 #pragma unroll
     for (int k = 0; k < 8; ++k) acc[k] += pj * vv.get(k);
   }
   float* part = red + 4;                             // [rpi][Dh]
+  if (rg < rpi) {
 #pragma unroll
-  for (int k = 0; k < 8; ++k) part[rg * Dh + c8 + k] = acc[k];
+    for (int k = 0; k < 8; ++k) part[rg * Dh + c8 + k] = acc[k];
+  }
   __syncthreads();
   if (tid < Dh) {
     float o = 0.f;
@@ -208,20 +218,22 @@ __global__ __launch_bounds__(DIV_THREADS) void attn_cls_bwd_kernel(const T* __re
 #pragma unroll
       for (int k = 0; k < 8; ++k) { s += kv.get(k) * qv.get(k); dp += vv.get(k) * dv.get(k); }
     }
-    s *= scale;
-    if (key_mask) s += (1.0f - key_mask[b * L + j]) * CLS_PAD;
+    const bool dead = key_mask && key_mask[b * L + j] == 0.f;
+    s = cls_mask_score(s * scale, key_mask, b * L + j);
     const float pj = __expf((s - mx) - lsum);
     p[j] = pj;
-    ds[j] = pj * (dp - delta) * scale;               // d score_j * scale
+    ds[j] = dead ? 0.f : pj * (dp - delta) * scale;  // d score_j * scale; a masked score is a constant
+
   }
   __syncthreads();
   // dK[j] += ds_j q, dV[j] += p_j dout, dQ = sum_j ds_j k[j]: a thread owns 8 columns of the rows j = rg, rg + rpi, ...
-  // (16-byte read-modify-writes; the (video, head) blocks touch disjoint columns, so nothing races)
+  // (16-byte read-modify-writes; the (video, head) blocks touch disjoint columns, so nothing races); threads past rpi row
+  // groups take no row, as in the forward
   const int nc = Dh >> 3, rpi = DIV_THREADS / nc;
   const int c8 = (tid % nc) * 8, rg = tid / nc;
   const Vec8<T> qv = load8<T>(base + c8), dov = load8<T>(dor + c8);
   float dq[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (int j = rg; j < L; j += rpi) {
+  for (int j = rg; rg < rpi && j < L; j += rpi) {
     const int64_t o = (int64_t)j * ld;
     const Vec8<T> kv = load8<T>(base + o + D + c8);
     Vec8<T> gk = load8<T>(dbase + o + D + c8), gv = load8<T>(dbase + o + 2 * D + c8);
@@ -236,8 +248,10 @@ __global__ __launch_bounds__(DIV_THREADS) void attn_cls_bwd_kernel(const T* __re
     store8<T>(dbase + o + 2 * D + c8, gv);
   }
   float* part = red + 4;                             // [rpi][Dh]
+  if (rg < rpi) {
 #pragma unroll
-  for (int k = 0; k < 8; ++k) part[rg * Dh + c8 + k] = dq[k];
+    for (int k = 0; k < 8; ++k) part[rg * Dh + c8 + k] = dq[k];
+  }
   __syncthreads();
   if (tid < Dh) {
     float o = 0.f;
@@ -248,7 +262,14 @@ __global__ __launch_bounds__(DIV_THREADS) void attn_cls_bwd_kernel(const T* __re
 
 // time token shift (src/meant/timesformer_pytorch.py:28-53): of the patch tokens [b, f, n, d] the first d/3 columns come from
 // the NEXT frame, the second third stays, the third third comes from the PREVIOUS frame (zeros beyond the clip's ends); the
-// cls row and the columns past 3 * (d / 3) pass through.  transpose = the adjoint (the two shifts swap).
+// cls row and the columns past 3 * (d / 3) pass through.  transpose = the adjoint (the two shifts swap).  A thread moves 8
+// columns: one 16-byte copy when d / 3 is a multiple of 8 (no vector straddles a third), else element by element.
+__device__ __forceinline__ int shift_of(int col, int chunk, int transpose) {
+  const int which = col / chunk;                       // 0, 1, 2: shifted thirds; >= 3: the remainder columns
+  const int sh = which == 0 ? 1 : (which == 2 ? -1 : 0);  // source frame = frame + sh
+  return transpose ? -sh : sh;
+}
+
 template <typename T>
 __global__ __launch_bounds__(DIV_THREADS) void token_shift_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t B, int f, int n, int d,
                                                                    int chunk, int transpose) {
@@ -259,10 +280,19 @@ __global__ __launch_bounds__(DIV_THREADS) void token_shift_kernel(const T* __res
     const int64_t row = i / nch, b = row / L, t = row - b * L;
     int64_t src = row;
     bool zero = false;
+    if (t > 0 && (chunk & 7)) {                        // a vector may straddle a third: each column finds its own source
+      const int fr = (int)((t - 1) / n);
+      Vec8<T> v;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int col = ch * 8 + k, sh = shift_of(col, chunk, transpose), fi = fr + sh;
+        v.set(k, fi < 0 || fi >= f ? 0.f : to_f(x[(row + (int64_t)sh * n) * d + col]));
+      }
+      store8<T>(y + row * d + ch * 8, v);
+      continue;
+    }
     if (t > 0) {
-      const int which = (ch * 8) / chunk;              // 0, 1, 2: shifted thirds; >= 3: the remainder columns
-      int sh = which == 0 ? 1 : (which == 2 ? -1 : 0); // source frame = frame + sh
-      if (transpose) sh = -sh;
+      const int sh = shift_of(ch * 8, chunk, transpose);
       const int fi = (int)((t - 1) / n) + sh;
       zero = fi < 0 || fi >= f;
       src = row + (int64_t)sh * n;
@@ -337,9 +367,10 @@ extern "C" int meant_group_scatter(const void* ddst, const int32_t* index, void*
 }
 
 static int cls_check(const char* name, int64_t B, int64_t L, int H, int Dh, size_t& lds, int arrays) {
-  MEANT_REQUIRE(B > 0 && B <= 65535 && L > 0 && H > 0 && H <= 65535 && (Dh == 32 || Dh == 64 || Dh == 128 || Dh == 256), MEANT_ERR_UNSUPPORTED,
-                "%s: head dim %d must be 32, 64, 128 or 256 (B=%lld, L=%lld, H=%d)", name, Dh, (long long)B, (long long)L, H);
-  lds = ((size_t)arrays * L + 4 + DIV_THREADS * 8) * sizeof(float);     // scores (+ d scores), reduction words, [row groups][Dh] partials
+  MEANT_REQUIRE(B > 0 && B <= 65535 && L > 0 && H > 0 && H <= 65535 && Dh > 0 && Dh <= 256 && Dh % 8 == 0, MEANT_ERR_UNSUPPORTED,
+                "%s: head dim %d must be a multiple of 8 in [8, 256] (B=%lld, L=%lld, H=%d)", name, Dh, (long long)B, (long long)L, H);
+  const int rpi = DIV_THREADS / (Dh / 8);                               // row groups of the P.V / dQ loops
+  lds = ((size_t)arrays * L + 4 + (size_t)rpi * Dh) * sizeof(float);    // scores (+ d scores), reduction words, [row groups][Dh] partials
   MEANT_REQUIRE(lds <= 160 * 1024 - 1024, MEANT_ERR_UNSUPPORTED, "%s: L=%lld tokens do not fit the LDS score buffer", name, (long long)L);
   return MEANT_OK;
 }
@@ -365,7 +396,9 @@ extern "C" int meant_attn_cls_fwd(const void* qkv, void* out, int64_t ld_out, fl
 
 extern "C" int meant_attn_cls_bwd(const void* qkv, const void* out, int64_t ld_out, const void* dout, int64_t ld_dout, const float* stats,
                                   const float* key_mask, void* dqkv, int64_t B, int64_t L, int H, int Dh, float scale, int dtype, void* stream) {
-  DIV_REQ(qkv && out && dout && stats && dqkv && meant_aligned16(qkv) && meant_aligned16(dout), "attn_cls_bwd: bad argument");
+  DIV_REQ(qkv && out && dout && stats && dqkv && ld_out >= (int64_t)H * Dh && ld_dout >= (int64_t)H * Dh && ld_dout % 8 == 0 && meant_aligned16(qkv) &&
+              meant_aligned16(dout) && meant_aligned16(dqkv),
+          "attn_cls_bwd: bad argument (ld_dout must be a multiple of 8)");
   size_t lds;
   int rc = cls_check("attn_cls_bwd", B, L, H, Dh, lds, 2);
   if (rc) return rc;
@@ -382,8 +415,8 @@ extern "C" int meant_attn_cls_bwd(const void* qkv, const void* out, int64_t ld_o
 }
 
 extern "C" int meant_token_shift(const void* x, void* y, int64_t B, int64_t frames, int64_t n, int64_t d, int transpose, int dtype, void* stream) {
-  DIV_REQ(x && y && x != y && B > 0 && frames > 0 && n > 0 && d >= 24 && d % 8 == 0 && (d / 3) % 8 == 0 && frames * n < (1LL << 30),
-          "token_shift: bad argument (d / 3 must be a multiple of 8)");
+  DIV_REQ(x && y && x != y && B > 0 && frames > 0 && n > 0 && d >= 8 && d % 8 == 0 && d < (1LL << 30) && frames * n < (1LL << 30),
+          "token_shift: bad argument (d must be a positive multiple of 8)");
   DIV_REQ(meant_aligned16(x) && meant_aligned16(y), "token_shift: 16-byte alignment");
   const int64_t total = B * (1 + frames * n) * (d / 8);
   int64_t nb = ceil_div(total, DIV_THREADS);
