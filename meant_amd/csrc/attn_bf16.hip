@@ -1,4 +1,4 @@
-// K3/K4: fused (flash-style) attention core for the bf16 tier, head dims 64 and 128, gfx950 MFMA 32x32x16.
+// K3/K4: fused (flash-style) attention core for the bf16 tier, head dims 64, 96, 128, 160, 192 and 256, gfx950 MFMA 32x32x16.
 // Replaces the reference's eager scores->softmax->PV chain (meant/attention.py:43-57,
 // meant/xPosAttention.py:41-63) and its flash-attn dependency (meant/flash_attention.py:42,
 // meant/xPosAttention_flash.py:40) with eager semantics: scale 1/sqrt(dim), causal -inf, additive
@@ -87,12 +87,14 @@ struct FwdArgs {
 // and there are half as many launches.  (Persistent forms were tried for both directions: a work queue around the backward
 // bodies costs ~80 spilled SGPRs and the dQ kernel's third wave per SIMD; the persistent forward of round 1, which streamed
 // K/V tiles across item boundaries, measures 1.57 ms on the causal text shape against 1.45 ms for pairs, and was removed.)
-#define ATTN_PAIR_LOOP(NBLK, FIRST_HEAVY_IS_LAST)                                                              \
+// HH: heads in the launch (the dK/dV kernel at head dim 256 runs two workgroups per head, one per column half)
+#define ATTN_PAIR_LOOP(NBLK, FIRST_HEAVY_IS_LAST) ATTN_PAIR_LOOP_H(NBLK, FIRST_HEAVY_IS_LAST, H)
+#define ATTN_PAIR_LOOP_H(NBLK, FIRST_HEAVY_IS_LAST, HH)                                                       \
   {                                                                                                       \
     int p__, h__, g__;                                                                                    \
     const int nblk__ = (NBLK);                                                                            \
     const int npair__ = a.causal ? (nblk__ + 1) / 2 : nblk__;      /* without the mask all blocks are alike */       \
-    if (!attn_item(npair__, H, a.G, p__, h__, g__)) return;                                               \
+    if (!attn_item(npair__, (HH), a.G, p__, h__, g__)) return;                                            \
     const int hi__ = a.causal ? nblk__ - 1 - p__ : p__;                                                   \
     process((FIRST_HEAVY_IS_LAST) ? hi__ : p__, h__, g__);                                                \
     if (hi__ != p__) {                                                                                    \
@@ -104,7 +106,7 @@ struct FwdArgs {
 // ------------------------------------------------------------------------------------------------
 // forward
 template <int HD_>
-__global__ __launch_bounds__(256, 2) void attn_fwd_kernel(FwdArgs a) {
+__global__ __launch_bounds__(256, HD_ <= 128 ? 2 : 1) void attn_fwd_kernel(FwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // two buffers of [K: NH sub-tiles | V: NH sub-tiles] (a sub-tile = 64 keys x 64 of the head's 64 NH columns), then
   // bias[2][64] floats, then 4 per-wave patches of 32x144 B (NH = 2: the patches reuse the tile space after the loop)
@@ -300,7 +302,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(FwdArgs a) {
 // backward, pass 1: dQ (and delta).  Same geometry as the forward.
 
 template <int HD_>
-__global__ __launch_bounds__(256, HD_ == 64 ? 3 : 2) void attn_bwd_dq_kernel(BwdArgs a) {
+__global__ __launch_bounds__(256, HD_ == 64 ? 3 : HD_ <= 128 ? 2 : 1) void attn_bwd_dq_kernel(BwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int HD = HD_, NH = (HD + 63) / 64, KS = HD / 16, OB = HD / 32, BUF_B = 2 * NH * TILE_B;   // sub-tiles, k-steps, 32-column output blocks    // as in the forward
   float* bias_s = reinterpret_cast<float*>(smem + 2 * BUF_B);
@@ -511,7 +513,11 @@ __device__ __forceinline__ unsigned long long lab_now() {
   return t;
 }
 #endif
-template <int HD_>
+// NSPLIT > 1 (head dim 256): NSPLIT workgroups per (block, head), each owning NH / NSPLIT sub-tiles of the dK / dV columns.
+// Each recomputes S and dP over the whole head dim (K and V fragments stay whole), so the 128 KiB of dK / dV accumulators
+// per lane that do not fit next to them shrink to 64 KiB -- one wave per SIMD without spills, for 1.5x the MFMA work of
+// the pass.  See DESIGN "Native head dims 160, 192, 256".
+template <int HD_, int NSPLIT = 1>
 __global__ __launch_bounds__(256, HD_ <= 96 ? 2 : 1) void attn_bwd_dkv_kernel(BwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
 #ifdef ATTN_LAB_STAMP
@@ -520,12 +526,16 @@ __global__ __launch_bounds__(256, HD_ <= 96 ? 2 : 1) void attn_bwd_dkv_kernel(Bw
 #endif
   // two buffers of [Q: NH sub-tiles | dO: NH sub-tiles], stats[2][4][64] floats, 4 patches (NH = 2: in the tile space)
   constexpr int HD = HD_, NH = (HD + 63) / 64, KS = HD / 16, OB = HD / 32, BUF_B = 2 * NH * TILE_B;   // sub-tiles, k-steps, 32-column output blocks
+  constexpr int NHL = NH / NSPLIT, OBL = OB / NSPLIT, CHL = HD / 8 / NSPLIT;   // sub-tiles, output blocks, 16-byte chunks of dK / dV owned
+  static_assert(NH % NSPLIT == 0 && OB % NSPLIT == 0, "dK/dV column split must be whole sub-tiles");
   float* stats = reinterpret_cast<float*>(smem + 2 * BUF_B);
   char* patches = NH == 1 ? smem + 2 * BUF_B + 2 * 4 * 64 * 4 : smem;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int S = a.S, H = a.H, D = H * HD;
   const int64_t ld = 3 * (int64_t)D;
-  auto process = [&](int kb, int h, int g) __attribute__((always_inline)) {
+  auto process = [&](int kb, int hs, int g) __attribute__((always_inline)) {
+  const int h = NSPLIT == 1 ? hs : hs / NSPLIT, part = NSPLIT == 1 ? 0 : hs % NSPLIT;   // head, column part
+  const int sub0 = part * NHL;                       // first dK / dV sub-tile (64 columns) of this workgroup
   const int kb0 = kb * 128;                          // block's first key
   const int key0 = kb0 + wave * 32;                  // wave's first key
   const int mykey = key0 + (lane & 31);
@@ -559,9 +569,9 @@ __global__ __launch_bounds__(256, HD_ <= 96 ? 2 : 1) void attn_bwd_dkv_kernel(Bw
   if (block_dead) {
     bf16* dkp = a.dqkv + (int64_t)g * S * ld + D + h * HD;
     const u32x4 z = {0u, 0u, 0u, 0u};
-    for (int idx = tid; idx < 128 * 2 * (HD / 8); idx += 256) {      // 128 keys x (dK | dV) x HD/8 16-byte chunks
-      const int row = idx / (2 * (HD / 8)), c = idx % (2 * (HD / 8));
-      if (kb0 + row < S) *reinterpret_cast<u32x4*>(dkp + (int64_t)(kb0 + row) * ld + (c / (HD / 8)) * D + (c % (HD / 8)) * 8) = z;
+    for (int idx = tid; idx < 128 * 2 * CHL; idx += 256) {      // 128 keys x (dK | dV) x CHL owned 16-byte chunks
+      const int row = idx / (2 * CHL), c = idx % (2 * CHL);
+      if (kb0 + row < S) *reinterpret_cast<u32x4*>(dkp + (int64_t)(kb0 + row) * ld + (c / CHL) * D + sub0 * DH + (c % CHL) * 8) = z;
     }
     return;
   }
@@ -583,9 +593,9 @@ __global__ __launch_bounds__(256, HD_ <= 96 ? 2 : 1) void attn_bwd_dkv_kernel(Bw
   float bkey = 0.f;                                    // key bias (log2 units; -inf past S); zero by construction when PLAIN
   if (!PLAIN) bkey = mykey < ntile * KV_TILE ? a.bias2[(int64_t)g * ntile * KV_TILE + mykey] : -INFINITY;
 
-  f32x16 dkacc[2 * NH], dvacc[2 * NH];
+  f32x16 dkacc[2 * NHL], dvacc[2 * NHL];
 #pragma unroll
-  for (int b = 0; b < OB; ++b)
+  for (int b = 0; b < OBL; ++b)
 #pragma unroll
     for (int e = 0; e < 16; ++e) { dkacc[b][e] = 0.f; dvacc[b][e] = 0.f; }
 
@@ -670,6 +680,16 @@ __global__ __launch_bounds__(256, HD_ <= 96 ? 2 : 1) void attn_bwd_dkv_kernel(Bw
       auto kstep = [&](auto KSI) {
         constexpr int ks = decltype(KSI)::value;
         if constexpr (ks < KS) {
+          if constexpr (HD > 128 && ks % 4 == 0) {
+            // head dims 160-256: the row fragments of one 64-column sub-tile at a time (a block's worth, 2 x KS x 4 registers,
+            // would not fit beside the K / V fragments and the accumulators); the fence keeps hipcc from hoisting the rest
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int k = ks; k < (ks + 4 < KS ? ks + 4 : KS); ++k) {
+              qv[k] = *reinterpret_cast<const bf16x8*>(Qb + sq * 4096 + (k >> 2) * TILE_B + foff[k & 3]);
+              dv[k] = *reinterpret_cast<const bf16x8*>(dOb + sq * 4096 + (k >> 2) * TILE_B + foff[k & 3]);
+            }
+          }
           // fragments were issued in the order q0 d0 q1 d1 ...: when at most `younger` + 2 (KS - 1 - ks) reads are outstanding,
           // this k-step's pair has landed
           if constexpr (HD == 64) lds_wait_frags<(younger + 2 * (KS - 1 - ks) > 15 ? 15 : younger + 2 * (KS - 1 - ks))>(qv[ks], dv[ks]);
@@ -680,6 +700,9 @@ __global__ __launch_bounds__(256, HD_ <= 96 ? 2 : 1) void attn_bwd_dkv_kernel(Bw
       kstep(std::integral_constant<int, 0>{}); kstep(std::integral_constant<int, 1>{}); kstep(std::integral_constant<int, 2>{});
       kstep(std::integral_constant<int, 3>{}); kstep(std::integral_constant<int, 4>{}); kstep(std::integral_constant<int, 5>{});
       kstep(std::integral_constant<int, 6>{}); kstep(std::integral_constant<int, 7>{});
+      kstep(std::integral_constant<int, 8>{}); kstep(std::integral_constant<int, 9>{}); kstep(std::integral_constant<int, 10>{});
+      kstep(std::integral_constant<int, 11>{}); kstep(std::integral_constant<int, 12>{}); kstep(std::integral_constant<int, 13>{});
+      kstep(std::integral_constant<int, 14>{}); kstep(std::integral_constant<int, 15>{});
     };
     auto weights = [&](auto SQ, bf16x8 (&pf)[2], bf16x8 (&dsf)[2]) {
       constexpr int sq = decltype(SQ)::value;
@@ -722,9 +745,9 @@ __global__ __launch_bounds__(256, HD_ <= 96 ? 2 : 1) void attn_bwd_dkv_kernel(Bw
     };
     auto products = [&](auto SQ, const bf16x8 (&pf)[2], const bf16x8 (&dsf)[2]) {
       constexpr int sq = decltype(SQ)::value;
-      const unsigned qaddr = lds_addr(Qb) + sq * 4096, doaddr = lds_addr(dOb) + sq * 4096;
+      const unsigned qaddr = lds_addr(Qb) + sq * 4096 + sub0 * TILE_B, doaddr = lds_addr(dOb) + sq * 4096 + sub0 * TILE_B;
 #pragma unroll
-      for (int hf = 0; hf < NH; ++hf) {
+      for (int hf = 0; hf < NHL; ++hf) {
         u32x2 dlo[2][2], dhi[2][2], qlo[2][2], qhi[2][2];
         tr_issue<0>(doaddr + hf * TILE_B, troff, 0, dlo[0][0], dhi[0][0]);
         tr_issue<0>(doaddr + hf * TILE_B, troff, 1, dlo[0][1], dhi[0][1]);
@@ -744,7 +767,7 @@ __global__ __launch_bounds__(256, HD_ <= 96 ? 2 : 1) void attn_bwd_dkv_kernel(Bw
         for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
           for (int b = 0; b < 2; ++b)
-            if (2 * hf + b < OB) {
+            if (2 * hf + b < OBL) {
               dvacc[2 * hf + b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pack_tr(dlo[s2][b], dhi[s2][b]), pf[s2], dvacc[2 * hf + b], 0, 0, 0);
               dkacc[2 * hf + b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pack_tr(qlo[s2][b], qhi[s2][b]), dsf[s2], dkacc[2 * hf + b], 0, 0, 0);
             }
@@ -775,12 +798,12 @@ __global__ __launch_bounds__(256, HD_ <= 96 ? 2 : 1) void attn_bwd_dkv_kernel(Bw
     } else {
       // wider heads: one block at a time -- the second block's score / dP accumulators in flight would cost the second
       // wave per SIMD (96) or spill (128)
-      frags(B0, q0, d0);
+      if (HD <= 128) frags(B0, q0, d0);
       scores(B0, NONE, q0, d0);
       weights(B0, pf0, dsf0);
       products(B0, pf0, dsf0);
       __builtin_amdgcn_sched_barrier(0);
-      frags(B1, q1, d1);
+      if (HD <= 128) frags(B1, q1, d1);
       scores(B1, NONE, q1, d1);
       weights(B1, pf1, dsf1);
       products(B1, pf1, dsf1);
@@ -823,18 +846,19 @@ __global__ __launch_bounds__(256, HD_ <= 96 ? 2 : 1) void attn_bwd_dkv_kernel(Bw
   // dV first: it needs no rotary tables, so its LDS round trip and stores go out while dK's table rows are on their way
   char* patch = patches + wave * (32 * 144);
 #pragma unroll
-  for (int hf = 0; hf < NH; ++hf) {
+  for (int hf = 0; hf < NHL; ++hf) {
     if (hf) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); }
-    store_transposed(reinterpret_cast<const f32x16(&)[2]>(dvacc[2 * hf]), 1.0f, patch, a.dqkv + (int64_t)g * S * ld + 2 * D + h * HD + DH * hf,
-                     ld, key0, S, lane, OB - 2 * hf >= 2 ? 2 : 1);
+    store_transposed(reinterpret_cast<const f32x16(&)[2]>(dvacc[2 * hf]), 1.0f, patch, a.dqkv + (int64_t)g * S * ld + 2 * D + h * HD + DH * (sub0 + hf),
+                     ld, key0, S, lane, OBL - 2 * hf >= 2 ? 2 : 1);
   }
-  if (a.rot.ka) rotary_adjoint_regs(reinterpret_cast<f32x16(&)[2]>(dkacc[0]), a.rot.ka, a.rot.kb, a.rot.R, krow, lane);
+  // rotary lanes are the first rot.R <= 64 columns of a head: part 0's first sub-tile
+  if (a.rot.ka && part == 0) rotary_adjoint_regs(reinterpret_cast<f32x16(&)[2]>(dkacc[0]), a.rot.ka, a.rot.kb, a.rot.R, krow, lane);
 #pragma unroll
-  for (int hf = 0; hf < NH; ++hf) {
+  for (int hf = 0; hf < NHL; ++hf) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    store_transposed(reinterpret_cast<const f32x16(&)[2]>(dkacc[2 * hf]), a.scale, patch, a.dqkv + (int64_t)g * S * ld + D + h * HD + DH * hf,
-                     ld, key0, S, lane, OB - 2 * hf >= 2 ? 2 : 1);
+    store_transposed(reinterpret_cast<const f32x16(&)[2]>(dkacc[2 * hf]), a.scale, patch, a.dqkv + (int64_t)g * S * ld + D + h * HD + DH * (sub0 + hf),
+                     ld, key0, S, lane, OBL - 2 * hf >= 2 ? 2 : 1);
   }
 #ifdef ATTN_LAB_STAMP
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -844,7 +868,7 @@ __global__ __launch_bounds__(256, HD_ <= 96 ? 2 : 1) void attn_bwd_dkv_kernel(Bw
   if (block_plain) body(std::true_type{});
   else body(std::false_type{});
   };   // process
-  ATTN_PAIR_LOOP(a.nblk, false)
+  ATTN_PAIR_LOOP_H(a.nblk, false, H * NSPLIT)
 }
 
 constexpr int BWD_DKV_LDS = 4 * TILE_B + 2 * 4 * 64 * 4 + 4 * 32 * 144;
@@ -852,7 +876,37 @@ constexpr int FWD_LDS = 4 * TILE_B + 2 * 64 * 4 + 4 * 32 * 144;
 // head dim 128 (NH = 2): twice the tile space, the output patches live in it (2 workgroups per CU by LDS)
 constexpr int BWD_DKV_LDS2 = 8 * TILE_B + 2 * 4 * 64 * 4;
 constexpr int FWD_LDS2 = 8 * TILE_B + 2 * 64 * 4;
-__host__ inline bool native_dh(int Dh) { return Dh == 64 || Dh == 96 || Dh == 128; }
+// head dims 160, 192, 256 (NH = 3, 3, 4 sub-tiles): double-buffered K|V (Q|dO) tiles of 96 / 128 KiB plus the bias (stats)
+// rows, the output patches in the tile space; one workgroup per CU
+constexpr int wide_fwd_lds(int HD) { return 2 * 2 * ((HD + 63) / 64) * TILE_B + 2 * 64 * 4; }
+constexpr int wide_dkv_lds(int HD) { return 2 * 2 * ((HD + 63) / 64) * TILE_B + 2 * 4 * 64 * 4; }
+static_assert(wide_dkv_lds(256) <= 160 * 1024, "LDS budget");
+__host__ inline bool wide_dh(int Dh) { return Dh == 160 || Dh == 192 || Dh == 256; }
+__host__ inline bool native_dh(int Dh) { return Dh == 64 || Dh == 96 || Dh == 128 || wide_dh(Dh); }
+
+// dK/dV column split: head dim 256 only (see attn_bwd_dkv_kernel)
+template <int HD> constexpr int dkv_split() { return HD == 256 ? 2 : 1; }
+
+template <int HD>
+int attn_fwd_wide(const FwdArgs& a, int H, int64_t G, int causal, hipStream_t stream) {
+  MEANT_RAISE_LDS(attn_fwd_kernel<HD>, wide_fwd_lds(HD));
+  hipLaunchKernelGGL(attn_fwd_kernel<HD>, dim3(attn_grid(causal ? (a.nqb + 1) / 2 : a.nqb, H, G)), dim3(256), wide_fwd_lds(HD), stream, a);
+  MEANT_LAUNCH_CHECK("attn_fwd");
+  return MEANT_OK;
+}
+
+template <int HD>
+int attn_bwd_wide(const BwdArgs& a, int H, int64_t G, int causal, hipStream_t stream) {
+  constexpr int NSPLIT = dkv_split<HD>();
+  MEANT_RAISE_LDS(attn_bwd_dq_kernel<HD>, wide_fwd_lds(HD));
+  MEANT_RAISE_LDS((attn_bwd_dkv_kernel<HD, NSPLIT>), wide_dkv_lds(HD));
+  const int64_t npair = causal ? (a.nblk + 1) / 2 : a.nblk;
+  hipLaunchKernelGGL(attn_bwd_dq_kernel<HD>, dim3(attn_grid(npair, H, G)), dim3(256), wide_fwd_lds(HD), stream, a);
+  MEANT_LAUNCH_CHECK("attn_bwd_dq");
+  hipLaunchKernelGGL((attn_bwd_dkv_kernel<HD, NSPLIT>), dim3(attn_grid(npair, H * NSPLIT, G)), dim3(256), wide_dkv_lds(HD), stream, a);
+  MEANT_LAUNCH_CHECK("attn_bwd_dkv");
+  return MEANT_OK;
+}
 
 }  // namespace
 
@@ -862,9 +916,9 @@ extern "C" int meant_lab_stamps(void* dst, size_t bytes) {
 }
 #endif
 
-// Head dims 64 and 128 run on the MFMA kernels above (128 as two 64-column halves of every tile).  The host side pads
-// other head dims below 128 up to 128 with zero columns (meant_amd/ops.py: the reference's default 8 heads -> Dh = 96),
-// so this is what they run on too.  Anything else handed to the C ABI directly takes a widening detour: bf16 -> f32
+// Head dims 64, 96, 128, 160, 192 and 256 run on the MFMA kernels above (the wider ones as two to four 64-column sub-tiles of
+// every tile, 96 and 160 with a 32-column last one).  The host side pads other head dims below 256 that are multiples of 8
+// up to the next of these with zero columns (meant_amd/ops.py), so this is what they run on too.  Anything else handed to the C ABI directly takes a widening detour: bf16 -> f32
 // copies in the workspace, the fp32 attention core, f32 -> bf16.  Correct for any Dh, not fast.
 // workspace of the Dh=64 path: [delta: G*H*S floats | bias2: G*nt*64 floats | flags: G*nt ints | masks: G * 2 u64]
 static size_t ws_delta_bytes(int64_t G, int64_t S, int H) { return align256((size_t)G * H * S * 2 * sizeof(float)); }   // two planes
@@ -953,6 +1007,11 @@ int attn_bf16_fwd(const bf16* qkv, bf16* o, float* lse, const float* key_mask, i
   }
   const int nqb = (int)ceil_div(S, 128);
   FwdArgs a{qkv, o, lse, bias2, flags, masks, (int)S, H, scale, causal, (int)G, nqb};
+  if (wide_dh(Dh)) {                                   // 160 / 192 / 256: three or four 64-column sub-tiles per operand tile
+    meant_route_hit(Dh == 160 ? ROUTE_ATTN_FWD_D160 : Dh == 192 ? ROUTE_ATTN_FWD_D192 : ROUTE_ATTN_FWD_D256);
+    return Dh == 160 ? attn_fwd_wide<160>(a, H, G, causal, stream) : Dh == 192 ? attn_fwd_wide<192>(a, H, G, causal, stream)
+                                                                   : attn_fwd_wide<256>(a, H, G, causal, stream);
+  }
   MEANT_RAISE_LDS(attn_fwd_kernel<64>, FWD_LDS);
   MEANT_RAISE_LDS(attn_fwd_kernel<96>, FWD_LDS2);
   MEANT_RAISE_LDS(attn_fwd_kernel<128>, FWD_LDS2);
@@ -1021,6 +1080,13 @@ int attn_bf16_bwd(const bf16* qkv, const bf16* o, const bf16* dout, const float*
   const int64_t nblk = ceil_div(S, 128);
   const dim3 grid(attn_grid(causal ? (nblk + 1) / 2 : nblk, H, G));   // causal: one workgroup per pair of 128-row blocks
   meant_route_hit(ROUTE_ATTN_BWD);
+  if (wide_dh(Dh)) {
+    MEANT_REQUIRE(Dh != 256 || ceil_div(S, 128) * 2 * H * G < (1LL << 31) - 8, MEANT_ERR_UNSUPPORTED,
+                  "attn_bwd: G=%lld / H=%d / S=%lld exceed the grid limits", (long long)G, H, (long long)S);
+    meant_route_hit(Dh == 160 ? ROUTE_ATTN_BWD_D160 : Dh == 192 ? ROUTE_ATTN_BWD_D192 : ROUTE_ATTN_BWD_D256);
+    return Dh == 160 ? attn_bwd_wide<160>(a, H, G, causal, stream) : Dh == 192 ? attn_bwd_wide<192>(a, H, G, causal, stream)
+                                                                   : attn_bwd_wide<256>(a, H, G, causal, stream);
+  }
   if (Dh == 96) {
     meant_route_hit(ROUTE_ATTN_BWD_D96);
     hipLaunchKernelGGL(attn_bwd_dq_kernel<96>, grid, dim3(256), FWD_LDS2, stream, a);

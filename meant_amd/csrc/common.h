@@ -57,7 +57,8 @@ int meant_opt(int id);
 enum meant_route_id {
   ROUTE_NT128 = 0, ROUTE_NT256, ROUTE_NT256S, ROUTE_NT256S_ROT, ROUTE_NT_SPLIT, ROUTE_TN128, ROUTE_TN256, ROUTE_TN256_DET, ROUTE_TN_TAIL,
   ROUTE_GEMM_F32, ROUTE_ATTN_FWD, ROUTE_ATTN_FWD_D128, ROUTE_ATTN_FWD_D96, ROUTE_ATTN_BWD,
-  ROUTE_ATTN_BWD_D128, ROUTE_ATTN_BWD_D96, ROUTE_ATTN_GENERIC, ROUTE_ATTN_CLS, ROUTE_ATTN_SHORT, ROUTE_NT_OVERLAP, ROUTE_ATTN_BWD1, MEANT_ROUTE_COUNT
+  ROUTE_ATTN_BWD_D128, ROUTE_ATTN_BWD_D96, ROUTE_ATTN_GENERIC, ROUTE_ATTN_CLS, ROUTE_ATTN_SHORT, ROUTE_NT_OVERLAP, ROUTE_ATTN_BWD1,
+  ROUTE_ATTN_FWD_D160, ROUTE_ATTN_FWD_D192, ROUTE_ATTN_FWD_D256, ROUTE_ATTN_BWD_D160, ROUTE_ATTN_BWD_D192, ROUTE_ATTN_BWD_D256, MEANT_ROUTE_COUNT
 };
 void meant_route_hit(int route);
 

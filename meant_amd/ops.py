@@ -942,14 +942,22 @@ class _QKVAttention(torch.autograd.Function):
         return (dx.view(G, S, d) if dx is not None else None), dw, db, None, None, None, None, None
 
 
-NATIVE_HEAD_DIMS = (64, 96, 128)   # what the bf16 MFMA attention kernels take (csrc/attn_bf16.hip); 96 = the reference's default 8 heads
+NATIVE_HEAD_DIMS = (64, 96, 128, 160, 192, 256)   # what the bf16 MFMA attention kernels take (csrc/attn_bf16.hip); 96 = the reference's default 8 heads
+
+
+def _padded_head_dim(Dh):
+    """the native head dim a bf16 head of Dh columns is zero-padded to, or None (native already, Dh % 8 != 0, Dh > 256)"""
+    if Dh in NATIVE_HEAD_DIMS or Dh % 8 or Dh > 256:
+        return None
+    return 128 if Dh < 128 else next(n for n in NATIVE_HEAD_DIMS if n > Dh)
 
 
 def qkv_attention(x, wq, bq, wk, bk, wv, bv, tables, key_mask, causal, num_heads, pre=None):
     """pre = (W1, b1) of a Linear applied to x immediately before the projections (composed into them).
 
-    bf16 tier, head dims other than 64 / 96 / 128 (96 = the reference classes' default of 8 heads at d = 768, served
-    natively): every head is widened to 128 columns by zero rows in the projection weights, so q, k, v come out of the GEMM already padded, the
+    bf16 tier, head dims that are multiples of 8 up to 256 but not native (64 / 96 / 128 / 160 / 192 / 256; 96 = the
+    reference classes' default of 8 heads at d = 768, 160 / 192 / 256 = 8 heads at d = 1280 / 1536 / 2048): every head is
+    widened to the next native dim (128 below 128) by zero rows in the projection weights, so q, k, v come out of the GEMM already padded, the
     scores are unchanged (zeros add nothing to q.k, the scale stays 1/sqrt(dim)), and the zero columns of v give zero
     columns of the output, which are dropped again.  The padding is built from the parameters with differentiable ops,
     so their gradients need no special handling."""
@@ -959,8 +967,9 @@ def qkv_attention(x, wq, bq, wk, bk, wv, bv, tables, key_mask, causal, num_heads
         wqkv, bqkv = compose_linear(pre[0], pre[1], wqkv, bqkv)
     D = wqkv.shape[0] // 3
     Dh = D // num_heads
-    if x.dtype == torch.bfloat16 and Dh not in NATIVE_HEAD_DIMS and Dh < 128 and Dh % 8 == 0:
-        Dp, d = 128, wqkv.shape[1]
+    Dp = _padded_head_dim(Dh) if x.dtype == torch.bfloat16 else None
+    if Dp is not None:
+        d = wqkv.shape[1]
         wp = torch.nn.functional.pad(wqkv.view(3 * num_heads, Dh, d), (0, 0, 0, Dp - Dh)).reshape(3 * num_heads * Dp, d)
         bp = torch.nn.functional.pad(bqkv.view(3 * num_heads, Dh), (0, Dp - Dh)).reshape(3 * num_heads * Dp)
         o = _QKVAttention.apply(x, wp, bp, tables, key_mask, causal, num_heads, 1.0 / math.sqrt(D))
