@@ -17,7 +17,9 @@ backward to every parameter gradient (incl. the 64001x768 embedding), and for N>
 gradient all-reduce overlapped with backward.  No optimizer step (the metric is fwd+bwd).
 Weak scaling: 128 samples per GPU (global batch 1024 at 8 GPUs, BASELINE.json configs[3]).
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+Prints ONE JSON line (rank 0): the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step), the median step
+time and the run's config.  A plain run does only what that line needs: set up, warm up, time the steps, dump (--dump-outputs),
+print.  `--full` adds what takes work of its own beyond the timed steps:
   roofline     -- the dominant kernel (gemm_bf16_nt256p_kernel, MFMA-bound): algorithmic FLOPs of its launches / their
                   HIP-event durations.  The timed steps run the two encoder stacks on two HIP streams, where a launch
                   shares the CUs with the other stream's kernels and has no duration of its own; the events are
@@ -26,7 +28,8 @@ Prints ONE JSON line (rank 0) with the contract fields plus
                   other hot kernels: dW GEMM and attention against the MFMA peak, RMSNorm / attention against HBM;
   cpu_baseline -- the CPU oracle (a port: the reference is Python and cannot travel) timed on the host cores on a bounded
                   sample of the same workload (rank 0, N=1 only): batch 1 and batch 8 on all the box's threads, batch 1
-                  on one thread.
+                  on one thread (~30 s; --no-cpu-baseline leaves it out).
+The secondary figures (--with-optimizer, --forward-only, --fp32-batch, --from-host) run when their own option asks for them.
 
 `--dump-outputs DIR` writes what the last timed step handed its caller (class probabilities, loss, every parameter gradient) as
 float32 .npy files under DIR, at most 64 MB in all (dump_outputs); inputs, weights and dropout seeds are fixed by the arguments,
@@ -415,7 +418,10 @@ def main():
     ap.add_argument("--batch-per-gpu", type=int, default=0, help="samples per GPU (default: 128; meant_vision: 256)")
     ap.add_argument("--encoders", type=int, default=1)
     ap.add_argument("--heads", type=int, default=12, help="attention heads (12 = BASELINE.json; 8 = the reference classes' default, head dim 96)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: `roofline` (extra single-stream steps, PMC tables) and, "
+                         "on one GPU, `cpu_baseline` (the CPU oracle, ~30 s)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out `cpu_baseline`")
     ap.add_argument("--eval-mode", action="store_true", help="disable dropout (parity-mode numerics)")
     ap.add_argument("--two-streams", type=int, default=-1, help="override meant_amd.modules.TWO_STREAMS (0/1)")
     ap.add_argument("--with-optimizer", action="store_true", help="also time the step with clip + fused AdamW (extra field)")
@@ -542,6 +548,7 @@ def main():
         step()
     barrier()
     import meant_amd.modules as _mm
+    # the GEMM event timers run in the timed steps of every run, --full or not, so that both time the same steps
     timer.enabled = True
     timer.others_enabled = not _mm.TWO_STREAMS           # one stream: the timed steps themselves serve for every kernel
     ev0 = torch.cuda.Event(enable_timing=True)
@@ -561,10 +568,10 @@ def main():
         dump_outputs(args.dump_outputs, model, last_outs, loss)
     # The timed region runs the two encoder stacks on two HIP streams, so a launch of the dominant kernel shares the
     # CUs with whatever the other stream is running and its event-to-event time is not the kernel's own.  For the
-    # roofline the same step is therefore run a few more times on ONE stream with the same event timers.
+    # roofline the same step is therefore run a few more times on ONE stream with the same event timers (--full only).
     import meant_amd.modules as _mm
     overlapped_recs, iso_steps = timer.recs, 0
-    if _mm.TWO_STREAMS:                             # every rank: the step holds the gradient collective
+    if args.full and _mm.TWO_STREAMS:               # every rank: the step holds the gradient collective
         timer.recs, timer.other, iso_steps = [], [], min(args.steps, 4)
         iso = True
         _mm.TWO_STREAMS = False
@@ -681,26 +688,28 @@ def main():
     if rank == 0:
         ms = elapsed / args.steps * 1e3
         sps = world * B * args.steps / elapsed
-        n, gf, gt = timer.summary()
-        achieved = gf / gt / 1e12 if gt > 0 else 0.0
-        traffic = timer.traffic_per_launch() if (B == 128 and MODEL == "meant") else None   # the PMC table holds the headline's shapes
-        roofline = {"kernel": _dominant_kernel(), "bound": "mfma", "achieved": round(achieved, 1), "peak": PEAK_BF16_TFLOPS,
-                    "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
-                    "traffic": None if traffic is None else round(traffic),
-                    "traffic_source": f"{getattr(timer, 'traffic_path', None)} (rocprofv3 PMC passes; lookup by launched shape)",
-                    "traffic_table_older_than_kernel_source": getattr(timer, "traffic_stale", None),
-                    "launches_timed": n, "avg_launch_ms": round(gt / max(n, 1) * 1e3, 4),
-                    "avg_launch_gflop": round(gf / max(n, 1) / 1e9, 2),
-                    "whole_step_mfma_frac": round(sps / world * flops_per_sample_executed(E) / (PEAK_BF16_TFLOPS * 1e12), 4),
-                    # the same step priced at the reference graph's FLOPs (what a literal evaluation of the module list would
-                    # execute; the pooled last Linear of each stack skips part of it, see DESIGN.md section 6 "Pooled tail")
-                    "whole_step_mfma_frac_reference_graph": round(sps / world * flops_per_sample(E) / (PEAK_BF16_TFLOPS * 1e12), 4)}
-        if iso_steps:
-            n2, gf2, gt2 = timer.summary(overlapped_recs)
-            roofline["timed_in"] = f"{iso_steps} extra single-stream steps after the timed region"
-            roofline["achieved_while_sharing_cus_with_second_stream"] = round(gf2 / gt2 / 1e12, 1) if gt2 > 0 else None
-        roofline["others"] = timer.others_summary()
-        roofline["others_pmc"] = timer.pmc_ratios()
+        roofline = None
+        if args.full:
+            n, gf, gt = timer.summary()
+            achieved = gf / gt / 1e12 if gt > 0 else 0.0
+            traffic = timer.traffic_per_launch() if (B == 128 and MODEL == "meant") else None   # the PMC table holds the headline's shapes
+            roofline = {"kernel": _dominant_kernel(), "bound": "mfma", "achieved": round(achieved, 1), "peak": PEAK_BF16_TFLOPS,
+                        "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
+                        "traffic": None if traffic is None else round(traffic),
+                        "traffic_source": f"{getattr(timer, 'traffic_path', None)} (rocprofv3 PMC passes; lookup by launched shape)",
+                        "traffic_table_older_than_kernel_source": getattr(timer, "traffic_stale", None),
+                        "launches_timed": n, "avg_launch_ms": round(gt / max(n, 1) * 1e3, 4),
+                        "avg_launch_gflop": round(gf / max(n, 1) / 1e9, 2),
+                        "whole_step_mfma_frac": round(sps / world * flops_per_sample_executed(E) / (PEAK_BF16_TFLOPS * 1e12), 4),
+                        # the same step priced at the reference graph's FLOPs (what a literal evaluation of the module list would
+                        # execute; the pooled last Linear of each stack skips part of it, see DESIGN.md section 6 "Pooled tail")
+                        "whole_step_mfma_frac_reference_graph": round(sps / world * flops_per_sample(E) / (PEAK_BF16_TFLOPS * 1e12), 4)}
+            if iso_steps:
+                n2, gf2, gt2 = timer.summary(overlapped_recs)
+                roofline["timed_in"] = f"{iso_steps} extra single-stream steps after the timed region"
+                roofline["achieved_while_sharing_cus_with_second_stream"] = round(gf2 / gt2 / 1e12, 1) if gt2 > 0 else None
+            roofline["others"] = timer.others_summary()
+            roofline["others_pmc"] = timer.pmc_ratios()
         lag_, s_, n_, ncls_, _ = _shape()
         metric = {"meant": "samples/sec fwd+bwd, MEANT lag=12 d=768", "meant_vqa": "samples/sec fwd+bwd, meant_vqa d=768 seq=512",
                   "meant_vision": "samples/sec fwd+bwd, meant_vision lag=1 d=768"}[MODEL]
@@ -719,8 +728,9 @@ def main():
                           "train_mode_dropout": not args.eval_mode, "activation_checkpointing": True if args.checkpoint else (int(args.checkpoint_layers) or False),
                           "norm_linear_fold": _fold_state(), "grad_allreduce": reducer.active,
                           "gflop_per_sample": round(flops_per_sample(E) / 1e9, 1),
-                          "gflop_per_sample_executed": round(flops_per_sample_executed(E) / 1e9, 1)},
-               "roofline": roofline}
+                          "gflop_per_sample_executed": round(flops_per_sample_executed(E) / 1e9, 1)}}
+        if roofline is not None:
+            res["roofline"] = roofline
         if fwd_ms is not None:
             res["forward_only"] = {"ms_per_step": round(fwd_ms, 3), "samples_per_s": round(world * B / fwd_ms * 1e3, 2),
                                    "what": "eval-mode forward under no_grad, same batch"}
@@ -741,7 +751,7 @@ def main():
                                 "h2d_GB_per_s_per_gpu": round(B * bytes_per_sample / host_ms / 1e6, 2),
                                 "what": "same step, batches gathered from host numpy arrays into pinned staging, H2D on a side "
                                         "stream (double-buffered), pixel conversion + patchify on the device"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(E)
         print(json.dumps(res), flush=True)
     if dist.is_initialized():

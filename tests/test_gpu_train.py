@@ -334,11 +334,22 @@ def _run_bench(argv, env_extra, nproc=1, port="29561", timeout=900):
     return json.loads(lines[0])
 
 
+def test_bench_plain_run_prints_only_the_contract_line(dev):
+    """`bench.py --gpus 1 --steps N --warmup W` without --full: the contract line, and neither `roofline` nor `cpu_baseline`
+    (their extra single-stream steps and CPU oracle run under --full only)"""
+    res = _run_bench(["--gpus", "1", "--batch-per-gpu", "2", "--steps", "2", "--warmup", "1"], {})
+    assert res["n_gpus"] == 1 and res["steps"] == 2 and res["warmup"] == 1
+    assert res["unit"] == "samples/s" and res["higher_is_better"] is True and res["dtype"] == "bf16"
+    assert np.isfinite(res["value"]) and res["value"] > 0 and res["ms_per_step_median"] > 0
+    assert abs(res["value"] - 2 / res["ms_per_step"] * 1e3) <= 0.01 * res["value"]
+    assert "roofline" not in res and "cpu_baseline" not in res
+
+
 def test_bench_two_ranks_on_one_gpu_prints_one_contract_line(dev):
     """`python -m torch.distributed.run --nproc-per-node 2 bench.py --gpus 2 ...` exactly as the driver launches it, both
     ranks on GPU 0 over gloo (a one-GPU box cannot give RCCL two devices): one JSON line from rank 0 with the contract's
     fields, the whole-job batch, the gradient collective live"""
-    res = _run_bench(["--batch-per-gpu", "2", "--steps", "2", "--warmup", "1"],
+    res = _run_bench(["--batch-per-gpu", "2", "--steps", "2", "--warmup", "1", "--full"],
                      {"MEANT_DIST_BACKEND": "gloo", "MEANT_ALL_RANKS_ON_GPU0": "1"}, nproc=2)
     assert res["n_gpus"] == 2 and res["steps"] == 2 and res["warmup"] == 1
     assert res["config"]["grad_allreduce"] is True and res["config"]["global_batch"] == 4 and res["config"]["parallelism"] == "dp2"
@@ -351,7 +362,7 @@ def test_bench_two_ranks_on_one_gpu_prints_one_contract_line(dev):
 @pytest.mark.parametrize("model,batch", [("meant_vqa", 4), ("meant_vision", 8)])
 def test_bench_other_configs_print_the_contract_line(dev, model, batch):
     """BASELINE.json configs[4] (meant_vqa) and configs[1] (meant_vision) through bench.py --model: same contract"""
-    res = _run_bench(["--model", model, "--batch-per-gpu", str(batch), "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], {})
+    res = _run_bench(["--model", model, "--batch-per-gpu", str(batch), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"], {})
     assert res["n_gpus"] == 1 and model in res["metric"] and model in res["config"]["workload"]
     assert res["config"]["batch_per_gpu"] == batch and np.isfinite(res["value"]) and res["value"] > 0
     assert res["ms_per_step_median"] > 0 and {"bound", "achieved", "peak", "unit", "frac", "traffic"} <= set(res["roofline"])

@@ -1,8 +1,10 @@
 # per-kernel profile of the bench step (single stream, so that kernel times add up): rocprofv3 --kernel-trace --stats
-# usage (GPU box): bash tools/profile_step.sh TAG [bench args]   -> gpurun_out/prof_TAG/{stats.csv,bench.log}
+# usage (GPU box): bash tools/profile_step.sh TAG [bench args]   -> $MEANT_PROFILE_OUT/prof_TAG/{stats.csv,bench.log}
+# (MEANT_PROFILE_OUT: the output directory, default profile_out/ in the repository)
+R=$(cd "$(dirname "$0")/.." && pwd); TAG=$1; shift
+D=${MEANT_PROFILE_OUT:-$R/profile_out}/prof_$TAG
 cd /tmp && export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT; TAG=$1; shift
-mkdir -p $R/gpurun_out/prof_$TAG
-MEANT_TWO_STREAMS=0 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof_$TAG -o x -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline "$@" > $R/gpurun_out/prof_$TAG/bench.log 2>&1
-python3 $R/tools/rocprof_stats.py $R/gpurun_out/prof_$TAG/x_results.db $R/gpurun_out/prof_$TAG/stats.csv | head -40
-tail -1 $R/gpurun_out/prof_$TAG/bench.log | cut -c1-200
+mkdir -p $D
+MEANT_TWO_STREAMS=0 rocprofv3 --kernel-trace --stats -d $D -o x -- python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline "$@" > $D/bench.log 2>&1
+python3 $R/tools/rocprof_stats.py $D/x_results.db $D/stats.csv | head -40
+tail -1 $D/bench.log | cut -c1-200
