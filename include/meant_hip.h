@@ -64,18 +64,17 @@ int meant_num_cus(void);
  *   "deterministic"    0|1   parameter gradients (dW, dbias) by ordered reductions instead of float atomics: two runs
  *                            on the same inputs are bit-identical; meant_linear_bwd_dw then needs its workspace
  *   "nt_stream"        1|0   streaming 256x256 NT GEMM / one tile per workgroup           (A/B measurements)
- *   "nt_dynamic"       1|0|3|4 streaming GEMM draws tiles from per-XCD counters / fixed walk (A/B measurements) /
- *                            only XCD 0 uses its own counter, all other tiles go through the steal path (tests) /
- *                            fixed walk in runs of one A row panel (lab: measured slower)
+ *   "nt_dynamic"       1|0|3 streaming GEMM draws tiles from per-XCD counters / fixed walk (A/B measurements) /
+ *                            only XCD 0 uses its own counter, all other tiles go through the steal path (tests)
  *   "nt_grid_cap"      0|n   cap the streaming GEMM's grid at n workgroups (tests: many tiles per workgroup, steals)
  *   "nt_ragged"        1|0   M not a multiple of 256: the streaming GEMM's last row tile is moved up to end at row M (it
  *                            recomputes rows of its neighbour bit-identically) / streaming head + 128 x 128 tail launch
  *                            (also what operands that alias the output fall back to)
  *   "attn_short"       1|0   sequences of <= 16 tokens run on the one-wave-per-(group, head) kernels / on the tiled ones
- *   "nt_split"         0|1   streaming GEMM: all operand DMA issued by waves 0-3 at the top of a K-step / B tiles by waves 0-3 at
- *                            the top, A tiles by waves 4-7 after their MFMAs
  *   "attn_bwd1"        1|0   attention backward, head dim 64, S <= 256 or causal S <= 512: one pass (scores and dP computed once,
  *                            dS through LDS into the dQ product; persistent workgroups) / the dQ pass followed by the dK, dV pass
+ *   "nt_pp"            1     read-only: the streaming GEMM runs in its ping-pong form (setting any other value fails with
+ *                            MEANT_ERR_UNSUPPORTED: the lock-step kernel was removed); not read from the environment
  */
 int meant_set_option(const char* name, int value);
 int meant_get_option(const char* name, int* value);
@@ -83,7 +82,9 @@ int meant_get_option(const char* name, int* value);
  * "nt_split", "nt_overlap", "tn128", "tn256", "tn256_det", "tn_tail", "gemm_f32", "attn_fwd", "attn_fwd_d128",
  * "attn_fwd_d96", "attn_bwd" (the two-pass form), "attn_bwd1" (the single-pass form), "attn_bwd_d128", "attn_bwd_d96",
  * "attn_generic", "attn_cls", "attn_short");
- * -1 for an unknown name.  Tests use it to prove that a shape reaches the kernel it is meant to exercise. */
+ * -1 for an unknown name.  The names label routes, not kernels: "nt256s" / "nt256s_rot" count launches of the streaming
+ * GEMM (whichever kernel implements it), "nt_split" the ragged head + tail split.  Tests use it to prove that a shape
+ * reaches the kernel it is meant to exercise. */
 int64_t meant_route_count(const char* route);
 void meant_route_reset(void);
 /* tiles the streaming GEMM's workgroups took from another XCD's counter, summed over all launches on the current

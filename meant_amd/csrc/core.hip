@@ -75,16 +75,15 @@ struct OptionDef { const char* name; const char* env; int dflt; };
 // order == enum meant_option_id (common.h)
 const OptionDef k_options[MEANT_OPT_COUNT] = {
     {"nt_stream", "MEANT_NT_STREAM", 1},           // 0: one-tile-per-workgroup 256x256 NT kernel instead of the streaming one
-    {"nt_dynamic", "MEANT_NT_DYNAMIC", 1},         // 0: fixed persistent tile walk; 1: per-XCD counters; 2: draw but ignore (lab); 3: steal-only (tests); 4: fixed walk in runs of one A row panel (lab)
+    {"nt_dynamic", "MEANT_NT_DYNAMIC", 1},         // 0: fixed persistent tile walk; 1: per-XCD counters; 3: steal-only (tests)
     {"deterministic", "MEANT_DETERMINISTIC", 0},   // 1: dW / dbias, the embedding gradient (d % 8 == 0, d <= 1024) and the norm gains are bit-reproducible (ordered reductions, no float atomics)
     {"nt_grid_cap", "MEANT_NT_GRID_CAP", 0},       // tests: cap the streaming GEMM's grid (0 = one workgroup per CU)
     {"attn_short", "MEANT_ATTN_SHORT", 1},         // 0: sequences of <= 16 tokens take the tiled flash kernels instead of attn_short.hip
     {"nt_ragged", "MEANT_NT_RAGGED", 1},           // 0: ragged M as streaming head + 128 x 128 tail launch instead of the overlapped last row tile
-    {"nt_split", "MEANT_NT_SPLIT", 0},             // 1: streaming GEMM: waves 0-3 issue the B tiles at the top of a K-step, waves 4-7 the A tiles after their MFMAs
     {"attn_bwd1", "MEANT_ATTN_BWD1", 1},           // 0: attention backward always as two passes (dQ, then dK / dV) instead of the single-pass kernel where it applies
-    {"nt_pp", "MEANT_NT_PP", 1},                   // 0: streaming GEMM in its lock-step form (gemm_bf16_nt256s_kernel) instead of the ping-pong kernel; bit 3 (lab): staggered start
-    {"tn_pp", "MEANT_TN_PP", 1},                   // 0: 256 x 256 dW kernel in its lock-step form (gemm_bf16_tn256_kernel) instead of the ping-pong kernel
 };
+// "nt_pp" (the streaming GEMM in its ping-pong form) is no longer a choice: it reads 1 and cannot be set to anything else
+bool is_nt_pp(const char* name) { return name && !strcmp(name, "nt_pp"); }
 std::atomic<int> g_opt[MEANT_OPT_COUNT];
 std::once_flag g_opt_once;
 void options_init() {
@@ -110,6 +109,10 @@ int meant_opt(int id) {
 
 extern "C" int meant_set_option(const char* name, int value) {
   options_init();
+  if (is_nt_pp(name)) {
+    MEANT_REQUIRE(value == 1, MEANT_ERR_UNSUPPORTED, "meant_set_option: nt_pp is always 1 (the lock-step kernel was removed)");
+    return MEANT_OK;
+  }
   const int i = option_index(name);
   MEANT_REQUIRE(i >= 0, MEANT_ERR_ARG, "meant_set_option: unknown option '%s'", name ? name : "(null)");
   g_opt[i].store(value, std::memory_order_relaxed);
@@ -118,6 +121,7 @@ extern "C" int meant_set_option(const char* name, int value) {
 
 extern "C" int meant_get_option(const char* name, int* value) {
   options_init();
+  if (is_nt_pp(name) && value) { *value = 1; return MEANT_OK; }
   const int i = option_index(name);
   MEANT_REQUIRE(i >= 0 && value, MEANT_ERR_ARG, "meant_get_option: unknown option '%s'", name ? name : "(null)");
   *value = g_opt[i].load(std::memory_order_relaxed);

@@ -66,31 +66,6 @@ __device__ __forceinline__ void nt_stage(const bf16* __restrict__ g, int64_t ld,
   }
 }
 
-// one output row segment of 8 columns: v = acc + bias already; applies (optional) rotary, activation, residual,
-// rounds once and stores 16 bytes.  Rotary epilogue (fused QKV projection): columns are [q | k | v] blocks of
-// rot_D = H*Dh columns, a head is Dh columns, lanes c < R of every q/k head are rotated with the tables of the
-// token's position m mod S:  out[c] = t[c]*A[pos,c] + rot(t)[c]*B[pos,c]  (meant/rotary_embedding_torch.py:31-44).
-// the tail of nt_store_row8's vector path without the store: activation, residual, one rounding
-__device__ __forceinline__ bf16x8 nt_finish_row8(const GemmBf16Args& a, int64_t m, int64_t n, float (&v)[8]) {
-  if (a.epilogue & MEANT_EPI_GELU) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = gelu_erf_fast(v[e]);
-  }
-  if (a.epilogue & MEANT_EPI_SIGMOID) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = 1.f / (1.f + __expf(-v[e]));
-  }
-  if (a.residual) {
-    const bf16x8 rr = *reinterpret_cast<const bf16x8*>(a.residual + m * a.ldr + n);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] += (float)rr[e];
-  }
-  bf16x8 o;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = (bf16)v[e];
-  return o;
-}
-
 // rotate 8 consecutive columns (4 pairs) with table rows A[0..7], B[0..7]
 __device__ __forceinline__ void rot_apply8(float (&v)[8], const f32x4& a0, const f32x4& a1, const f32x4& b0, const f32x4& b1) {
 #pragma unroll
@@ -103,10 +78,11 @@ __device__ __forceinline__ void rot_apply8(float (&v)[8], const f32x4& a0, const
   }
 }
 
-// pre_res: the 8 residual values of this row segment when the caller has requested them ahead of time (streaming kernel)
-template <bool STREAM_OUT = false>
-__device__ __forceinline__ void nt_store_row8(const GemmBf16Args& a, int64_t m, int64_t n, float (&v)[8], bool vec_ok,
-                                              const bf16x8* pre_res = nullptr) {
+// one output row segment of 8 columns: v = acc + bias already; applies (optional) rotary, activation, residual,
+// rounds once and stores 16 bytes.  Rotary epilogue (fused QKV projection): columns are [q | k | v] blocks of
+// rot_D = H*Dh columns, a head is Dh columns, lanes c < R of every q/k head are rotated with the tables of the
+// token's position m mod S:  out[c] = t[c]*A[pos,c] + rot(t)[c]*B[pos,c]  (meant/rotary_embedding_torch.py:31-44).
+__device__ __forceinline__ void nt_store_row8(const GemmBf16Args& a, int64_t m, int64_t n, float (&v)[8], bool vec_ok) {
   if (vec_ok) {
     if (a.preact) {
       bf16x8 p;
@@ -134,7 +110,7 @@ __device__ __forceinline__ void nt_store_row8(const GemmBf16Args& a, int64_t m, 
       for (int e = 0; e < 8; ++e) v[e] = 1.f / (1.f + __expf(-v[e]));
     }
     if (a.residual) {
-      const bf16x8 rr = pre_res ? *pre_res : *reinterpret_cast<const bf16x8*>(a.residual + m * a.ldr + n);
+      const bf16x8 rr = *reinterpret_cast<const bf16x8*>(a.residual + m * a.ldr + n);
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] += (float)rr[e];
     }
@@ -153,8 +129,7 @@ __device__ __forceinline__ void nt_store_row8(const GemmBf16Args& a, int64_t m, 
     bf16x8 o;
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = (bf16)v[e];
-    if (STREAM_OUT) __builtin_nontemporal_store(o, reinterpret_cast<bf16x8*>(a.C + m * a.ldc + n));
-    else *reinterpret_cast<bf16x8*>(a.C + m * a.ldc + n) = o;
+    *reinterpret_cast<bf16x8*>(a.C + m * a.ldc + n) = o;
   } else {
     for (int e = 0; e < 8 && n + e < a.N; ++e) {
       float x = v[e];
@@ -396,18 +371,18 @@ constexpr int RING = 5;
 //     K-loop.  In the one-tile-per-workgroup kernels all 256 CUs finish together and write 32 MiB in one burst while
 //     the matrix pipes wait for the stores (measured: 4 us of a 24 us tile for the stores, 5 us for the rest of the
 //     prologue/epilogue).
-// Requirements (the launcher falls back to the kernels above otherwise): M % 256 == 0, N % 256 == 0, K % 64 == 0,
-// K >= 128, ldc % 8 == 0.
+// Requirements (the launcher falls back to the kernels above otherwise): M % 256 == 0 (or the ragged last tile, see the
+// launcher), N % 256 == 0, K % 64 == 0, K >= 256, ldc % 8 == 0.
 // Tile hand-out of the streaming kernel.  A fixed walk (tile += grid) is fragile: when another kernel -- the other HIP stream's,
 // or a collective's -- holds a few CUs at launch, the workgroups that start late still own a full share of the tiles and the
 // launch takes ~1.5x as long (measured with 8 of 256 CUs pinned: 1.07 -> 1.66 ms).  So only the FIRST tile of a workgroup is
 // fixed; every further tile is drawn from a counter.  There is one counter per XCD so that the tiles an XCD works on stay
 // neighbours (shared A panels / weights in its L2); an XCD that runs dry steals from the next one.  Tile k of XCD x is
 // id(x, k) = (k / CH) * G + x * CH + k % CH with CH = G / 8 workgroups per XCD -- the same order as the fixed walk.
-// The draw costs no stall: lane 0 of wave 4 (a wave that issues no DMA) sends the atomic at the top of K-step 3 and picks the
-// answer up behind the wait that ends the step anyway; it publishes the tile id to a per-workgroup mailbox in global memory
-// (LDS is full) with a fire-and-forget store, acknowledged by the end of step 4; every wave requests the mailbox at the top of
-// step 5 and has it at the end of that step.  (Blocking versions of the same protocol cost 5-7 %: memory latency under this
+// The draw costs no stall: lane 0 of wave 4 sends the atomic at the top of K-step 2 and picks the answer up behind the wait
+// that ends the step anyway; it publishes the tile id to a per-workgroup mailbox in global memory (LDS is full) with a
+// fire-and-forget store, acknowledged by the end of step 3; every wave requests the mailbox at the top of step 4 and has it at
+// the end of that step.  (Blocking versions of the same protocol cost 5-7 %: memory latency under this
 // kernel's own load is ~4 us, two K-steps.)  The last workgroup to leave zeroes the counters for the next launch.
 struct alignas(64) TileSched {
   unsigned next[8];
@@ -419,480 +394,30 @@ struct alignas(64) TileSched {
 constexpr int N_SCHED_SLOTS = 256;
 __device__ TileSched g_tile_sched[N_SCHED_SLOTS];
 
-// EXT: the extended epilogue (GemmBf16Args::row_scale / sub / sub_coef) -- an instantiation of its own so that the plain
-// kernel's register budget (236 of 256) is not touched
-template <int DBG, bool ROT, bool EXT = false>
-__global__ __launch_bounds__(512, 2) void gemm_bf16_nt256s_kernel(GemmBf16Args a, int ntm, int ntn, TileSched* __restrict__ sched, int mode) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 2, wn = wave & 3;
-  const int nk = (int)(a.K / BK);
-  const int ntiles = ntm * ntn, G = gridDim.x;
-  // workgroup b runs on XCD b % 8 (round-robin dispatch): in every round each XCD takes G/8 consecutive tile ids,
-  // i.e. a few rows of tiles that share their A panels and all of W through that XCD's L2
-  const int CH = G >> 3, xcd = blockIdx.x & 7;
-  // mode 4 (lab, fixed walk only): a workgroup walks RUNS of ntn consecutive tiles -- all column tiles of one A row panel -- before it
-  // moves G panels on, so that an A panel is requested by one CU nine times in a row rather than by nine CUs at about the same time
-  const int run = mode == 4 ? ntn : 1;
-  auto fixed_next = [&](int t) { return (t + 1) % run != 0 ? t + 1 : t + 1 + (G - 1) * run; };
-  int tile = (xcd * CH + (blockIdx.x >> 3)) * run;
-  const bool dynamic = sched != nullptr && nk >= 8;  // the draw travels during K-steps 3..5 and is needed at step nk - 2
-  auto leave = [&]() {                                 // last workgroup out resets the counters
-    if (sched && threadIdx.x == 0) {
-      if (atomicAdd(&sched->done, 1u) == (unsigned)G - 1u) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) sched->next[i] = 0;
-        sched->done = 0;
-      }
-    }
-  };
-  if (tile >= ntiles) { leave(); return; }
-  auto tile_of = [&](int x, unsigned k) { return (int)((k / (unsigned)CH) * (unsigned)G + (unsigned)(x * CH) + k % (unsigned)CH); };
-
-  // waves 0-3 issue all DMA; wave w owns pieces 4w..4w+3 and 4(w+4)..4(w+4)+3 (1 KiB = 8 rows of 128 B) of every tile.
-  // Piece p of a wave starts 8 * pp rows below its first one (pp = p, or p + 12 for the second group), which is a
-  // uniform offset; the swizzled 16-byte column of a lane only alternates between two values (c0, c0 ^ 4) with the
-  // parity of p.  So a lane keeps two 32-bit offsets per operand and everything else lives in scalar registers.
-  // SPLIT (DBG bit 7): the DMA issue is shared out in TIME as well: waves 0-3 issue the next step's B tile at the top of a K-step and
-  // then compute; their SIMD partners, waves 4-7, compute first and issue the A tile of the step after next when their MFMAs are
-  // done -- the part of the step they used to spend waiting at the barrier.  A `global_load_lds` costs the issuing wave 100-185
-  // cycles in a phase that is also reading fragments (MI355X_MICROARCH.md, LDS-DMA piece issue cost): sixteen of them in front of a
-  // wave's 64 MFMAs were longer than the MFMAs themselves.
-  constexpr bool SPLIT = (DBG & 128) != 0;
-  const bool issuer = wave < 4;
-  const int lw = wave & 3;
-  const int r0 = lw * 32 + (lane >> 3);
-  const int c0 = (lane & 7) ^ ((r0 >> 1) & 7);
-  const unsigned oA[2] = {(unsigned)(r0 * a.lda + c0 * 8), (unsigned)(r0 * a.lda + (c0 ^ 4) * 8)};
-  const unsigned oB[2] = {(unsigned)(r0 * a.ldb + c0 * 8), (unsigned)(r0 * a.ldb + (c0 ^ 4) * 8)};
-  auto stage = [&](const bf16* base, const unsigned (&off)[2], int64_t ld, int slot) {
-    char* dst = smem + slot * T2_BYTES;
-#pragma unroll
-    for (int p = 0; p < 8; ++p) {
-      const int pp = p < 4 ? p : p + 12;
-      glds16(base + (int64_t)(8 * pp) * ld + off[p & 1], dst + (lw * 4 + pp) * 1024);
-    }
-  };
-  auto origin = [&](int t, const bf16*& pa, const bf16*& pb, int64_t& m0, int64_t& n0) {
-    const int tm = t / ntn, tn = t - tm * ntn;
-    m0 = (int64_t)tm * B2;
-    m0 = m0 + B2 <= a.M ? m0 : a.M - B2;               // ragged M: the last row tile is moved up to END at row M (see the launcher)
-    n0 = (int64_t)tn * B2;
-    pa = a.A + m0 * a.lda;
-    pb = a.B + n0 * a.ldb;
-  };
-
-  const bf16 *pA, *pB, *pAn = nullptr, *pBn = nullptr;      // operand origins of this tile and of the next one
-  int64_t m0, n0, m0n = 0, n0n = 0;
-  origin(tile, pA, pB, m0, n0);
-  int next = dynamic ? -1 : fixed_next(tile);          // dynamic: unknown until the draw of this tile has come back
-  bool has_next = !dynamic && next < ntiles;
-  if (has_next) origin(next, pAn, pBn, m0n, n0n);
-  unsigned* mailbox = sched ? &sched->mailbox[blockIdx.x] : nullptr;
-
-  if (SPLIT) {
-    if (issuer) {
-      stage(pB, oB, a.ldb, 1);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
-      stage(pA, oA, a.lda, 0);
-      stage(pA + BK, oA, a.lda, 2);
-      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    }
-  } else if (issuer) {
-    stage(pA, oA, a.lda, 0);
-    stage(pB, oB, a.ldb, 1);
-    stage(pA + BK, oA, a.lda, 2);
-    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  }
-  bool first_tile = true;
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-
-  const int frow = lane & 15, fkg = lane >> 4;
-  int sA = 0;                                          // ring slot of the current step's A tile; B sits in the next one
-  for (;;) {
-    f32x4 acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    for (int kt = 0; kt < nk; ++kt) {
-      const int sB = sA + 1 == RING ? 0 : sA + 1;
-      const int s3 = sA + 3 >= RING ? sA + 3 - RING : sA + 3, s4 = sA + 4 >= RING ? sA + 4 - RING : sA + 4;
-      const bool in1 = kt + 1 < nk, in2 = kt + 2 < nk;
-      // tile draw, part 1 (see TileSched): requests only, nothing is waited for here -- they are older than this step's DMA,
-      // so the wait at the end of the step covers them.  The registers the answers land in are defined and consumed inside
-      // one iteration; hipcc does not know they are in flight, and tools/isa_inflight.py (run by tests/test_isa_guards.py)
-      // checks in the ISA that nothing touches them in between.
-      unsigned mail = 0, ticket = 0;
-      const bool reading = dynamic && kt == 5;
-      if (reading) asm volatile("global_load_dword %0, %1, off sc1" : "=v"(mail) : "v"(mailbox) : "memory");
-      const bool drawer = dynamic && kt == 3 && wave == 4 && lane == 0;
-      // mode 3 (tests): only XCD 0 draws from its own counter; everybody else behaves as if theirs had run dry, so that every
-      // tile of the other seven counters is handed out by the steal path below
-      const bool own = !(mode == 3 && xcd != 0);
-      if (drawer && own) asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=v"(ticket) : "v"(&sched->next[xcd]), "v"(1u) : "memory");
-      const bool more2 = in2 || has_next;
-      if (issuer && !(DBG & 1)) {
-        if (in1) stage(pB + (int64_t)(kt + 1) * BK, oB, a.ldb, s3);
-        else if (has_next) stage(pBn, oB, a.ldb, s3);
-        if (!SPLIT) {
-          if (in2) stage(pA + (int64_t)(kt + 2) * BK, oA, a.lda, s4);
-          else if (has_next) stage(pAn + (int64_t)(kt + 2 - nk) * BK, oA, a.lda, s4);
-        }
-      }
-      const char* At = smem + sA * T2_BYTES + (wm * 128) * 128;
-      const char* Bt = smem + sB * T2_BYTES + (wn * 64) * 128;
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        bf16x8 af[8], bfr[4];
-        const int c = ks * 4 + fkg;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const int r = i * 16 + frow;
-          af[i] = *reinterpret_cast<const bf16x8*>(At + r * 128 + ((c ^ ((r >> 1) & 7)) << 4));
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          // DIRECT: MFMA block j is fed the W rows 32 (j / 2) + 8 (frow / 4) + 4 (j % 2) + frow % 4, so that a lane's results of
-          // blocks 2 jp and 2 jp + 1 are EIGHT CONSECUTIVE output columns (32 jp + 8 fkg ..) and can be stored without a transpose
-          const int r = (DBG & 32) ? 32 * (j >> 1) + 8 * (frow >> 2) + 4 * (j & 1) + (frow & 3) : j * 16 + frow;
-          bfr[j] = *reinterpret_cast<const bf16x8*>(Bt + r * 128 + ((c ^ ((r >> 1) & 7)) << 4));
-        }
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);   // swapped: acc = C^T tile
-        __builtin_amdgcn_s_setprio(0);
-      }
-      // the next step needs its A tile (issued a step ago) and its B tile (issued above); the A tile after that may
-      // stay in flight.  The output stores of the previous tile are older than all of these and retire first.
-      asm volatile("" ::: "memory");
-      // Waves 4-7 issue no DMA: all they can have in flight are old output stores and the requests above.  In the three
-      // steps of the draw they wait for everything (the stores are long gone by then).
-      const bool sched_step = dynamic && !issuer && kt >= 3 && kt <= 5;
-      if (SPLIT) {
-        // waves 0-3: the B tile issued above (and, older, the previous tile's output stores) must have landed.  Waves 4-7: the A tile
-        // they issued at the end of the PREVIOUS step must have; in a tile's first step that request is older than the sixteen (or
-        // more) output stores of the tile before, which may stay in flight
-        if (!issuer && kt == 0 && !first_tile) asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      } else if ((DBG & 8) && !issuer && !sched_step) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // lab: stores of waves 4-7 drain freely
-      else if (more2 && !sched_step && !(DBG & 1)) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      asm volatile("" : "+v"(mail), "+v"(ticket) : : "memory");
-      // tile draw, part 2: the answers are here
-      if (drawer) {                                    // K-step 3: resolve and publish (acknowledged by the end of step 4)
-        int id = own ? tile_of(xcd, (unsigned)CH + ticket) : ntiles;
-        if (id >= ntiles) {                            // this XCD is dry: look at the others' counters, take from one with work left
-          unsigned seen[8];
-#pragma unroll
-          for (int x = 0; x < 8; ++x) seen[x] = __hip_atomic_load(&sched->next[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          for (int att = 1; id >= ntiles && att < 8; ++att) {
-            const int x2 = (xcd + att) & 7;
-            if (tile_of(x2, (unsigned)CH + seen[x2]) >= ntiles) continue;
-            id = tile_of(x2, (unsigned)CH + atomicAdd(&sched->next[x2], 1u));
-            if (id < ntiles) atomicAdd(&sched->steals, 1u);
-          }
-        }
-        const unsigned pub = id < ntiles ? (unsigned)id : 0xffffffffu;
-        asm volatile("global_store_dword %0, %1, off sc1" ::"v"(mailbox), "v"(pub) : "memory");
-      }
-      if (reading) {                                   // K-step 5: every wave has read what was published
-        const unsigned got = (unsigned)__builtin_amdgcn_readfirstlane((int)mail);
-        next = mode == 2 ? (tile + G < ntiles ? tile + G : -1) : (int)got;
-        has_next = next >= 0;
-        if (has_next) origin(next, pAn, pBn, m0n, n0n);
-      }
-      if (SPLIT && !issuer && !(DBG & 1)) {             // waves 4-7: their MFMAs are done, the A tile of the step after next goes out now
-        if (in2) stage(pA + (int64_t)(kt + 2) * BK, oA, a.lda, s4);
-        else if (has_next) stage(pAn + (int64_t)(kt + 2 - nk) * BK, oA, a.lda, s4);
-      }
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      sA = sA + 2 >= RING ? sA + 2 - RING : sA + 2;
-    }
-
-    // ---- epilogue: accumulators -> per-wave LDS patch (fp32, XOR-swizzled) -> 128-byte row segments -------------
-    // The two ring slots of the step that just finished are free until the next step issues its DMA, and every wave
-    // only talks to its own 4 KiB patch in each of them, so there is no workgroup barrier in here.  Lane layout in:
-    // acc[i][j] = C[i*16 + frow][j*16 + 4*fkg .. +3]; out: lane l owns 8 consecutive columns (l & 7) * 8 of row
-    // (l >> 3) + 8h, i.e. one store instruction writes 8 complete 128-byte lines.
-    if ((DBG & 32) && !ROT) {
-      // lab: direct epilogue -- no LDS transpose; a store instruction writes 16 rows x 64 contiguous bytes
-#pragma unroll
-      for (int jp = 0; jp < 2; ++jp) {
-        const int64_t n = n0 + wn * 64 + 32 * jp + 8 * fkg;
-        float bias[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) bias[e] = a.bias ? a.bias[n + e] : 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          float v[8];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { v[e] = acc[i][2 * jp][e] + bias[e]; v[4 + e] = acc[i][2 * jp + 1][e] + bias[4 + e]; }
-          nt_store_row8(a, m0 + wm * 128 + i * 16 + frow, n, v, true);
-        }
-      }
-    } else if (!(DBG & 4)) {
-      const int f3 = sA + 3 >= RING ? sA + 3 - RING : sA + 3, f4 = sA + 4 >= RING ? sA + 4 - RING : sA + 4;
-      float* patch[2] = {reinterpret_cast<float*>(smem + f3 * T2_BYTES + wave * 4096),
-                         reinterpret_cast<float*>(smem + f4 * T2_BYTES + wave * 4096)};
-      const int orow = lane >> 3, oc = lane & 7;
-      const int64_t n = n0 + wn * 64 + oc * 8;
-      float bias[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) bias[e] = a.bias ? a.bias[n + e] : 0.f;
-      // patch I/O goes through inline asm: hipcc does not know the DMA ring is quiescent here and would put a
-      // vmcnt(0) -- i.e. a full drain of the output stores -- in front of every plain LDS store
-      const unsigned pw[2] = {lds_addr(patch[0]) + frow * 256, lds_addr(patch[1]) + frow * 256};
-      // rotary epilogue (fused q|k|v projection): the lane's 8 columns sit at a fixed place c of a q or k head for the
-      // whole tile, only the position m mod S changes.  vmcnt retires in order, so a table load issued after a
-      // round's output stores would wait for those stores to be acknowledged: the tables of round r+1 are therefore
-      // requested BEFORE the stores of round r go out.
-      bool rot_on = false;
-      const float *tabA = nullptr, *tabB = nullptr;
-      if (ROT) {
-        const int sec = (int)(n / a.rot_D);
-        const int c = (int)((n - (int64_t)sec * a.rot_D) % a.rot_Dh);
-        rot_on = sec < 2 && c < a.rot_R;
-        tabA = (sec ? a.rot_ka : a.rot_qa) + c;
-        tabB = (sec ? a.rot_kb : a.rot_qb) + c;
-      }
-      f32x4 ta[2][2], tb[2][2];                        // [h][half]
-      auto load_tabs = [&](int i) {
-        if (ROT && rot_on) {
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const int64_t m = m0 + wm * 128 + i * 16 + orow + 8 * h;
-            const int64_t o = (int64_t)(m % a.rot_S) * a.rot_R;
-            ta[h][0] = *reinterpret_cast<const f32x4*>(tabA + o);
-            ta[h][1] = *reinterpret_cast<const f32x4*>(tabA + o + 4);
-            tb[h][0] = *reinterpret_cast<const f32x4*>(tabB + o);
-            tb[h][1] = *reinterpret_cast<const f32x4*>(tabB + o + 4);
-          }
-        }
-      };
-      load_tabs(0);
-      // residual epilogue: a round's 2 x 16 bytes per lane are requested one round ahead, BEFORE the previous round's stores go out
-      // (a load issued behind stores waits for their acknowledgement: vmcnt retires in order) -- fetched inline they cost a full
-      // memory round trip per round, +25 % (text) / +38 % (vision) on the residual GEMMs of the step
-      bf16x8 res_cur[2] = {}, res_nxt[2] = {};
-      auto load_res = [&](int i, bf16x8 (&r)[2]) {
-        if (!ROT && !EXT && a.residual) {
-#pragma unroll
-          for (int h = 0; h < 2; ++h)
-            r[h] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(a.residual + (m0 + wm * 128 + i * 16 + orow + 8 * h) * a.ldr + n));
-        }
-      };
-      load_res(0, res_cur);
-      // extended epilogue: per-row factor, residual, and a second tile operand with a per-row coefficient.  One register
-      // set: a round's operands are consumed (both rows finished into `outv`), THEN the next round's are requested into
-      // the same registers, THEN the round's stores go out -- loads never queue behind stores (vmcnt retires in order)
-      bf16x8 xres[2] = {}, xsub[2] = {};
-      float xrs[2] = {1.f, 1.f}, xkc[2] = {0.f, 0.f};
-      f32x4 xbr[2][2] = {};                            // the broadcast residual's 8 columns: reloaded only when the group changes
-      auto load_ext = [&](int i) {
-        if (EXT) {
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const int64_t m = m0 + wm * 128 + i * 16 + orow + 8 * h;
-            if (a.row_scale) xrs[h] = a.row_scale[m];
-            if (a.residual) xres[h] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(a.residual + m * a.ldr + n));
-            if (a.sub) {
-              xsub[h] = *reinterpret_cast<const bf16x8*>(a.sub + m * a.ldsub + n);
-              xkc[h] = a.sub_coef[m];
-            }
-            if (a.bres) {
-              const float* bp = a.bres + (m / a.bres_rows) * a.N + n;
-              xbr[h][0] = *reinterpret_cast<const f32x4*>(bp);
-              xbr[h][1] = *reinterpret_cast<const f32x4*>(bp + 4);
-            }
-          }
-        }
-      };
-      load_ext(0);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int u = i & 1;                           // alternate between the two free slots
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          asm volatile("ds_write_b128 %0, %1" ::"v"(pw[u] + (((j * 4 + fkg) ^ frow) << 4)), "v"(acc[i][j]) : "memory");
-        if (EXT && !ROT) {
-          bf16x8 outv[2];
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const int r = orow + 8 * h;
-            const int64_t m = m0 + wm * 128 + i * 16 + r;
-            const unsigned base = lds_addr(patch[u]) + r * 256;
-            f32x4 lo, hi;
-            asm volatile("ds_read_b128 %0, %1" : "=v"(lo) : "v"(base + (((2 * oc) ^ r) << 4)) : "memory");
-            asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(hi) : "v"(base + (((2 * oc + 1) ^ r) << 4)) : "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            float v[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = fmaf(e < 4 ? lo[e] : hi[e - 4], xrs[h], bias[e]);
-            if (a.preact) {
-              bf16x8 pz;
-#pragma unroll
-              for (int e = 0; e < 8; ++e) pz[e] = (bf16)v[e];
-              *reinterpret_cast<bf16x8*>(a.preact + m * a.ldc + n) = pz;
-            }
-            if (a.epilogue & MEANT_EPI_GELU) {
-#pragma unroll
-              for (int e = 0; e < 8; ++e) v[e] = gelu_erf_fast(v[e]);
-            }
-            if (a.residual) {
-#pragma unroll
-              for (int e = 0; e < 8; ++e) v[e] += (float)xres[h][e];
-            }
-            if (a.sub) {
-#pragma unroll
-              for (int e = 0; e < 8; ++e) v[e] = fmaf(-xkc[h], (float)xsub[h][e], v[e]);
-            }
-            if (a.bres) {
-#pragma unroll
-              for (int e = 0; e < 8; ++e) v[e] = fmaf(a.bres_scale, e < 4 ? xbr[h][0][e] : xbr[h][1][e - 4], v[e]);
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) outv[h][e] = (bf16)v[e];
-          }
-          __builtin_amdgcn_sched_barrier(0);
-          if (i + 1 < 8) load_ext(i + 1);
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int h = 0; h < 2; ++h)
-            *reinterpret_cast<bf16x8*>(a.C + (m0 + wm * 128 + i * 16 + orow + 8 * h) * a.ldc + n) = outv[h];
-        } else if (!ROT) {
-          f32x4 lo[2], hi[2];
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const int r = orow + 8 * h;
-            const unsigned base = lds_addr(patch[u]) + r * 256;
-            asm volatile("ds_read_b128 %0, %1" : "=v"(lo[h]) : "v"(base + (((2 * oc) ^ r) << 4)) : "memory");
-            asm volatile("ds_read_b128 %0, %1" : "=v"(hi[h]) : "v"(base + (((2 * oc + 1) ^ r) << 4)) : "memory");
-          }
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          __builtin_amdgcn_sched_barrier(0);
-          if (i + 1 < 8) load_res(i + 1, res_nxt);
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const int r = orow + 8 * h;
-            float v[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = (e < 4 ? lo[h][e] : hi[h][e - 4]) + bias[e];
-            if (DBG & 16) { asm volatile("" ::"v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7])); }   // lab: everything but the global store
-            else nt_store_row8<(DBG & 64) != 0>(a, m0 + wm * 128 + i * 16 + r, n, v, true, a.residual ? &res_cur[h] : nullptr);
-          }
-          res_cur[0] = res_nxt[0];
-          res_cur[1] = res_nxt[1];
-        } else {
-          // finish both rows, THEN ask for the next round's tables (into the same registers), THEN store
-          bf16x8 outv[2];
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const int r = orow + 8 * h;
-            const int64_t m = m0 + wm * 128 + i * 16 + r;
-            const unsigned base = lds_addr(patch[u]) + r * 256;
-            f32x4 lo, hi;
-            asm volatile("ds_read_b128 %0, %1" : "=v"(lo) : "v"(base + (((2 * oc) ^ r) << 4)) : "memory");
-            asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(hi) : "v"(base + (((2 * oc + 1) ^ r) << 4)) : "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            float v[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = (e < 4 ? lo[e] : hi[e - 4]) + bias[e];
-            if (a.preact) {
-              bf16x8 pz;
-#pragma unroll
-              for (int e = 0; e < 8; ++e) pz[e] = (bf16)v[e];
-              *reinterpret_cast<bf16x8*>(a.preact + m * a.ldc + n) = pz;
-            }
-            if (rot_on) rot_apply8(v, ta[h][0], ta[h][1], tb[h][0], tb[h][1]);
-            outv[h] = nt_finish_row8(a, m, n, v);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-          if (i + 1 < 8) load_tabs(i + 1);
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int h = 0; h < 2; ++h)
-            *reinterpret_cast<bf16x8*>(a.C + (m0 + wm * 128 + i * 16 + orow + 8 * h) * a.ldc + n) = outv[h];
-        }
-      }
-    }
-    first_tile = false;
-    if (!has_next) break;
-    // the patches live in the ring slots the next step's DMA is about to fill: every wave must be out of them first
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    tile = next; pA = pAn; pB = pBn; m0 = m0n; n0 = n0n;
-    if (dynamic) { next = -1; has_next = false; }
-    else {
-      next = fixed_next(next);
-      has_next = next < ntiles;
-      if (has_next) origin(next, pAn, pBn, m0n, n0n);
-    }
-  }
-  leave();
-}
-
 // ------------------------------------------------------------------------------------------------
-// Epilogue of one wave's 128 x 64 accumulator block of a 256 x 256 tile (the streaming kernels' per-wave patch epilogue as a
-// function): accumulators -> the wave's two private 4 KiB LDS patches (fp32, XOR-swizzled, alternating per 16-row round) ->
-// 128-byte row segments.  No workgroup barrier inside; the caller guarantees that nobody else touches the patches.
+// Epilogue of one wave's 128 x 64 accumulator block of a 256 x 256 tile (the streaming kernel's per-wave patch epilogue):
+// accumulators -> the wave's two private 4 KiB LDS patches (fp32, XOR-swizzled, alternating per 16-row round) -> 128-byte
+// row segments.  No workgroup barrier inside; the caller guarantees that nobody else touches the patches.
 // Lane layout in: acc[i][j] = C[i*16 + frow][j*16 + 4*fkg .. +3]; out: lane l owns 8 consecutive columns (l & 7) * 8 of row
 // (l >> 3) + 8h, i.e. one store instruction writes 8 complete 128-byte lines.  Patch I/O goes through inline asm: hipcc does
 // not know the DMA ring is quiescent there and would put a vmcnt(0) -- a full drain of the output stores and of the prefetch in
 // flight -- in front of every plain LDS store.
-#ifdef PP_LAB_STAMP
-// lab build only (tools/lab/stamp_pp.py): s_memtime sums of waves 0 (leader) and 4 (follower) per workgroup:
-// 0 steps kt > 0 (without the wait) | 1 steps kt == 0 | 2 end-of-step vmcnt wait | 3 epilogue until the bias is there | 4 epilogue rounds |
-// 5 barriers behind the epilogue | 6 steps | 7 tiles | 8 total ticks | 9 total s_memrealtime ticks (100 MHz)
-constexpr int PP_LAB_MAX_WG = 256;
-__device__ unsigned long long g_pp_stamp[PP_LAB_MAX_WG * 2 * 16];
-__device__ __forceinline__ unsigned long long pp_now() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-#define PPSTAMP(i) { const unsigned long long n__ = pp_now(); lab_acc[i] += n__ - lab_t; lab_t = n__; }
-#define PPSTAMP_ARGS , unsigned long long (&lab_acc)[10], unsigned long long& lab_t
-#define PPSTAMP_PASS , lab_acc, lab_t
-#else
-#define PPSTAMP(i)
-#define PPSTAMP_ARGS
-#define PPSTAMP_PASS
-#endif
 // Epilogue modes: what the launcher knows about a launch is a TEMPLATE parameter, so that the eight rounds are straight-line code.
 // With the options as run-time flags every `if (a.residual)` / `if (a.preact)` ... is a branch with loads on one side, and at each
 // join hipcc waits for vmcnt(0): every round then waited for the previous round's output stores to be ACKNOWLEDGED by memory
-// (2.5 k cycles per round, 20 k of a 64 k-cycle tile at K = 768: round 4, tools/lab/stamp_pp.py) -- a store is fire-and-forget
+// (2.5 k cycles per round, 20 k of a 64 k-cycle tile at K = 768: round 4, per-phase timestamps) -- a store is fire-and-forget
 // only while nothing behind it asks for the counter.
 enum { NTE_PLAIN = 0, NTE_RES, NTE_GELU_PRE, NTE_ROT, NTE_EXT, NTE_GENERIC };
 // Output stores as write-through (sc1) stores: a plain store leaves its line in the XCD's 4 MiB L2 (MI355X_MICROARCH.md, "stores of
 // each flavour"), and a tile's 128 KiB of output per CU push the A panels the neighbouring CUs are about to re-read out of it.
 // Measured (profiles/r04_nt256p_hbm_traffic*.json): HBM traffic 1.175x -> 1.08x of the algorithmic bytes at N = K = 768, 1.72x ->
-// 1.65x at N = 2304; +1-2 % throughput.  PP_STORE_SC1=0 builds the plain stores.
-#ifndef PP_STORE_SC1
-#define PP_STORE_SC1 1
-#endif
-#ifndef PP_ROT_WALK
-#define PP_ROT_WALK 1
-#endif
+// 1.65x at N = 2304; +1-2 % throughput.
 #define GAS __attribute__((address_space(1)))
 template <typename T> __device__ __forceinline__ const GAS T* gp(const T* p) { return (const GAS T*)p; }
-template <typename T> __device__ __forceinline__ GAS T* gpw(T* p) { return (GAS T*)p; }
 
 template <int MODE>
 __device__ __forceinline__ void nt256_wave_epilogue(const GemmBf16Args& a, f32x4 (&acc)[8][4], float* patch0, float* patch1, int64_t m0,
-                                                    int64_t n0, int wm, int wn, int lane PPSTAMP_ARGS) {
+                                                    int64_t n0, int wm, int wn, int lane) {
   constexpr bool ROT = MODE == NTE_ROT, EXT = MODE == NTE_EXT, GEN = MODE == NTE_GENERIC || EXT;
   // compile-time constants in the specialised modes, run-time flags in the two generic ones
   const bool f_res = MODE == NTE_RES || (GEN && a.residual != nullptr);
@@ -931,13 +456,8 @@ __device__ __forceinline__ void nt256_wave_epilogue(const GemmBf16Args& a, f32x4
     const int c = (int)((n - (int64_t)sec * a.rot_D) % a.rot_Dh);
     tile_rot = sec < 2;
     rot_on = tile_rot && c < a.rot_R;
-#ifdef PP_LAB_ROT_BCAST
-    tabA = (sec ? a.rot_ka : a.rot_qa);
-    tabB = (sec ? a.rot_kb : a.rot_qb);
-#else
     tabA = (sec ? a.rot_ka : a.rot_qa) + (rot_on ? c : 0);
     tabB = (sec ? a.rot_kb : a.rot_qb) + (rot_on ? c : 0);
-#endif
     posb = (unsigned)(mrow % (int64_t)rS);
   }
   auto pos_of = [&](int i, int h) {
@@ -960,11 +480,7 @@ __device__ __forceinline__ void nt256_wave_epilogue(const GemmBf16Args& a, f32x4
       const int64_t m = mrow + i * 16 + 8 * h;
       if (ROT) {
         if (tile_rot) {
-#ifdef PP_LAB_ROT_BCAST
-          const unsigned o = (unsigned)__builtin_amdgcn_readfirstlane((int)(pos_of(i, h) * (unsigned)a.rot_R));   // lab: one address per wave (wrong values)
-#else
           const unsigned o = pos_of(i, h) * (unsigned)a.rot_R;
-#endif
           ta[st][h][0] = *gp(reinterpret_cast<const f32x4*>(tabA + o));
           ta[st][h][1] = *gp(reinterpret_cast<const f32x4*>(tabA + o + 4));
           tb[st][h][0] = *gp(reinterpret_cast<const f32x4*>(tabB + o));
@@ -989,10 +505,6 @@ __device__ __forceinline__ void nt256_wave_epilogue(const GemmBf16Args& a, f32x4
   };
 #pragma unroll
   for (int i = 0; i < NS; ++i) load_ops(i, i);
-#ifdef PP_LAB_STAMP
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  PPSTAMP(3)
-#endif
   // output rows by running pointers (rows 8 apart: cstep8 elements): no 64-bit multiply per row
   const int64_t cstep8 = 8 * a.ldc;
   bf16* cp = a.C + mrow * a.ldc + n;
@@ -1084,19 +596,10 @@ __device__ __forceinline__ void nt256_wave_epilogue(const GemmBf16Args& a, f32x4
     for (int h = 0; h < 2; ++h) {
       bf16* const cq = cp + (h ? cstep8 : 0);
       bf16* const pq = f_pre ? pp + (h ? cstep8 : 0) : nullptr;
-#ifndef PP_LAB_NOSTORE
-#if PP_STORE_SC1
-      // write-through stores (see PP_STORE_SC1).  The s_nop: the data registers of a 16-byte store may be rewritten right behind it
+      // write-through stores (see above).  The s_nop: the data registers of a 16-byte store may be rewritten right behind it
       // only after a wait state, which hipcc inserts for its own stores and cannot know about here
       if (f_pre) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(pq), "v"(prev[h]) : "memory");
       asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(cq), "v"(outv[h]) : "memory");
-#else
-      if (f_pre) *gpw(reinterpret_cast<bf16x8*>(pq)) = prev[h];
-      *gpw(reinterpret_cast<bf16x8*>(cq)) = outv[h];
-#endif
-#else
-      asm volatile("" ::"v"(outv[h]), "v"(prev[h]), "v"(cq), "v"(pq));
-#endif
     }
     cp += 2 * cstep8;
     if (f_pre) pp += 2 * cstep8;
@@ -1107,34 +610,30 @@ __device__ __forceinline__ void nt256_wave_epilogue(const GemmBf16Args& a, f32x4
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         bf16* const cq = cp + (h ? cstep8 : 0);
-#if PP_STORE_SC1
         asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(cq), "v"(held[i][h]) : "memory");
-#else
-        *gpw(reinterpret_cast<bf16x8*>(cq)) = held[i][h];
-#endif
       }
       cp += 2 * cstep8;
     }
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // the wave is out of its patches
-  PPSTAMP(4)
 }
 
 // ------------------------------------------------------------------------------------------------
-// Streaming NT kernel, PING-PONG form (round 4).  Same tile (256 x 256 x 64), same 8 waves (2 along M x 4 along N, 128 x 64 per
-// wave), same five-slot ring, tile walk and per-wave patch epilogue as gemm_bf16_nt256s_kernel -- what changes is WHEN the two
-// waves of a SIMD do what.  In the kernel above all eight waves run in lock step: both waves of a SIMD read fragments at the same
-// time (matrix pipe idle) and then both queue MFMAs (LDS and the address unit idle); a K-step measures 1.65 us against 1.08 us
-// of MFMA time.  Here the workgroup is two GROUPS of four waves, one wave per SIMD each: the LEADER (waves 0-3, rows 0..127 of the
-// tile) and the FOLLOWER (waves 4-7, rows 128..255), which runs the same program ONE BARRIER INTERVAL behind.  A K-step is TWO
-// phases (one 64-row half of the wave's block x all of K = 64: 32 MFMAs; four phases of 16 and one of 64 both measured slower); a phase is a
-// LOAD half (the phase's fragment reads and its share of the prefetch stream's LDS-DMA pieces) and an MFMA half, with a workgroup
-// barrier after each.  The one-interval lag puts every MFMA half of one group beside a LOAD half of the other: a SIMD's matrix
-// pipe always has exactly one wave feeding it, and fragment reads, DMA issue and address arithmetic of its partner run underneath
-// (cdna_hip_programming.md "The 256^2 8-phase template"; MI355X_MICROARCH.md "Two waves per SIMD", items 1, 5, 9).
-// A wave issues one instruction every ~4-5 cycles, so a LOAD half hides only while it stays well under (MFMAs per phase) x 16 / 4.5
-// instructions: the prefetch cursors are branch-free scalar selects, DMA pieces use the SGPR-base form (no per-piece VALU), and
-// everything the epilogue needs is re-read from the kernarg segment per tile instead of living in SGPRs across the K-loop.
+// Streaming NT kernel, PING-PONG form (round 4).  Tile 256 x 256 x 64, 8 waves (2 along M x 4 along N, 128 x 64 per wave), the
+// five-slot ring, tile walk and per-wave patch epilogue described above -- and a schedule for WHEN the two waves of a SIMD do
+// what.  In the lock-step form this replaced (retired) all eight waves ran in step: both waves of a SIMD read
+// fragments at the same time (matrix pipe idle) and then both queued MFMAs (LDS and the address unit idle); a K-step measured
+// 1.65 us against 1.08 us of MFMA time.  Here the workgroup is two GROUPS of four waves, one wave per SIMD each: the LEADER (waves
+// 0-3, rows 0..127 of the tile) and the FOLLOWER (waves 4-7, rows 128..255), which runs the same program ONE BARRIER INTERVAL
+// behind.  A K-step is TWO phases (one 64-row half of the wave's block x all of K = 64: 32 MFMAs; four phases of 16 and one of 64
+// both measured slower); a phase is a LOAD half (the phase's fragment reads and its share of the prefetch stream's LDS-DMA
+// pieces) and an MFMA half, with a workgroup barrier after each.  The one-interval lag puts every MFMA half of one group beside a
+// LOAD half of the other: a SIMD's matrix pipe always has exactly one wave feeding it, and fragment reads, DMA issue and address
+// arithmetic of its partner run underneath (cdna_hip_programming.md "The 256^2 8-phase template"; MI355X_MICROARCH.md "Two waves
+// per SIMD", items 1, 5, 9).  A wave issues one instruction every ~4-5 cycles, so a LOAD half hides only while it stays well under
+// (MFMAs per phase) x 16 / 4.5 instructions: the prefetch cursors are branch-free scalar selects, DMA pieces use the SGPR-base
+// form (no per-piece VALU), and everything the epilogue needs is re-read from the kernarg segment per tile instead of living in
+// SGPRs across the K-loop.
 //
 // Barrier intervals of K-step n, P = 2 (I = 4n + ...), L/M = load / MFMA half of phase p:
 //     leader:    L0 M0 L1 M1          follower:  -- L0 M0 L1 | M1
@@ -1151,48 +650,17 @@ __device__ __forceinline__ void nt256_wave_epilogue(const GemmBf16Args& a, f32x4
 // live in the two slots of the tile's last step, each wave inside rows only its own group read; the DMA into those slots starts
 // behind that barrier.  After the last tile the cursors keep prefetching (valid rows of the last tile, never read): no branch
 // in the K-loop distinguishes it.
-__device__ __forceinline__ void glds16_s(const void* sbase, unsigned voff, unsigned lds) {   // sbase, lds: wave-uniform
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds) : "memory");
-}
-// the four pieces (1 KiB each, consecutive in LDS) a wave owns of one tile.  PP_DMA_IMM: ONE M0 write for the group; the
-// instruction's immediate offset moves source and destination alike, so piece p's lane offset is built as v[p] - 1024 p (the
-// launch code adds 3072 to every v[] and subtracts it from the base: the 32-bit lane offset is unsigned)
-#ifndef PP_DMA_IMM
-#define PP_DMA_IMM 1
-#endif
+// the four pieces (1 KiB each, consecutive in LDS) a wave owns of one tile (sbase, lds: wave-uniform).  ONE M0 write for the
+// group; the instruction's immediate offset moves source and destination alike, so piece p's lane offset is built as
+// v[p] - 1024 p (the launch code adds 3072 to every v[] and subtracts it from the base: the 32-bit lane offset is unsigned)
 __device__ __forceinline__ void glds16_x4(const void* sbase, const unsigned (&v)[4], unsigned lds) {
-#if PP_DMA_IMM
   asm volatile("s_mov_b32 m0, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %4\n\tglobal_load_lds_dwordx4 %1, %4 offset:1024\n\t"
                "global_load_lds_dwordx4 %2, %4 offset:2048\n\tglobal_load_lds_dwordx4 %3, %4 offset:3072"
                ::"v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "s"((const char*)sbase - 3072), "s"(lds) : "memory");
-#else
-#pragma unroll
-  for (int p = 0; p < 4; ++p) glds16_s(sbase, v[p], lds + p * 1024);
-#endif
 }
 typedef const __attribute__((address_space(4))) unsigned* kernarg_words_t;
 static_assert(sizeof(GemmBf16Args) % 4 == 0, "kernarg copy by words");
 
-#ifdef PP_LAB_STAMP2
-// second lab build (tools/lab/stamp_pp.py with PROBE_FINE=1), P = 2 only: s_memtime sums per half phase of waves 0 and 4:
-// 0 L0 | 1 barrier behind L0 | 2 M0 | 3 barrier behind M0 | 4 L1 (+ follower's wait) | 5 barrier behind L1 | 6 M1 | 7 rest of the step up
-// to the next L0 (leader's wait, cursors, barrier) | 8 steps.  Stamps taken while LDS reads are in flight are not waited for on the
-// spot (the wait would serialise behind the reads): they are read behind the next lgkmcnt(0) the code has anyway.
-__device__ unsigned long long g_pp_stamp2[256 * 2 * 16];
-#define PP2_NOW(v) asm volatile("s_memtime %0" : "=s"(v)::"memory")
-#define PP2_SYNC() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#define PP2_BEGIN() { PP2_NOW(f_a); PP2_SYNC(); f_acc[7] += f_a - f_e; }
-#define PP2_BEGIN2(i) { PP2_NOW(f_a); PP2_SYNC(); f_acc[i] += f_a - f_e; }
-#define PP2_L_END() { PP2_NOW(f_b); }
-#define PP2_M_BEGIN(i) { PP2_NOW(f_c); PP2_SYNC(); f_acc[i] += f_b - f_a; f_acc[i + 1] += f_c - f_b; }
-#define PP2_M_END(i) { PP2_NOW(f_e); PP2_SYNC(); f_acc[i] += f_e - f_c; }
-#else
-#define PP2_BEGIN()
-#define PP2_BEGIN2(i)
-#define PP2_L_END()
-#define PP2_M_BEGIN(i)
-#define PP2_M_END(i)
-#endif
 template <int MODE>
 __global__ __launch_bounds__(512, 2) void gemm_bf16_nt256p_kernel(GemmBf16Args a, int ntm, int ntn, TileSched* __restrict__ sched, int mode) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1223,8 +691,8 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt256p_kernel(GemmBf16Args a
   unsigned vA[4], vB[4];                               // byte offsets of this lane's 16 bytes of piece p from the tile's origin
 #pragma unroll
   for (int p = 0; p < 4; ++p) {
-    vA[p] = (unsigned)(((32 * wave + 8 * p + rl) * a.lda + (c0 ^ ((p & 1) << 2)) * 8) * 2) + (PP_DMA_IMM ? 3072 - 1024 * p : 0);
-    vB[p] = (unsigned)(((32 * wave + 8 * p + rl) * a.ldb + (c0 ^ ((p & 1) << 2)) * 8) * 2) + (PP_DMA_IMM ? 3072 - 1024 * p : 0);
+    vA[p] = (unsigned)(((32 * wave + 8 * p + rl) * a.lda + (c0 ^ ((p & 1) << 2)) * 8) * 2) + (3072 - 1024 * p);
+    vB[p] = (unsigned)(((32 * wave + 8 * p + rl) * a.ldb + (c0 ^ ((p & 1) << 2)) * 8) * 2) + (3072 - 1024 * p);
   }
   const unsigned lds0 = lds_addr(smem) + wave * 4096;  // this wave's first piece inside slot 0
   // Rotary mode, sequences of P = S / 256 > 1 row panels (mode bits 16..: P; the launcher checks that P divides the panel count):
@@ -1256,17 +724,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt256p_kernel(GemmBf16Args a
   if (has_next) origin(next, pAn, pBn, m0n, n0n);
   unsigned* mailbox = sched ? &sched->mailbox[blockIdx.x] : nullptr;
 
-  // Start stagger (mode bit 8).  All workgroups start together and a tile takes every CU the same time, so all 256 CUs reach their
-  // epilogues -- 32 MiB of output stores -- in the same few microseconds and then sit in the store queue (measured: 20 k of a tile's
-  // 64 k cycles at K = 768) while HBM writes idle for the rest of the tile.  Workgroup j of the G / 8 on its XCD therefore starts
-  // j / (G / 8) of a tile time late: the bursts of different CUs fall beside other CUs' K-loops.  The tiles are handed out by counters,
-  // so a late starter simply ends up with fewer of them.
-  if (mode & 0x100) {
-    const int j = blockIdx.x >> 3;                     // position inside the XCD's group of CH workgroups
-    // a K-step is ~1.5 us ~ 3000 cycles, an epilogue ~ 4 of them; s_sleep 127 ~ 8128 cycles
-    const int naps = (int)(((int64_t)(nk + 4) * 3000 * j / CH) >> 13);
-    for (int i = 0; i < naps; ++i) __builtin_amdgcn_s_sleep(127);
-  }
   // prologue: A_0, B_0, A_1 (four pieces per wave and tile); the first two must have landed
   glds16_x4(pA, vA, lds0);
   glds16_x4(pB, vB, lds0 + T2_BYTES);
@@ -1289,16 +746,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt256p_kernel(GemmBf16Args a
     __builtin_amdgcn_sched_barrier(0);    \
   } while (0)
 
-#ifdef PP_LAB_STAMP
-  unsigned long long lab_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long lab_t = pp_now();
-  const unsigned long long lab_t0 = lab_t, lab_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
-#ifdef PP_LAB_STAMP2
-  unsigned long long f_acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long f_a = 0, f_b = 0, f_c = 0, f_e = 0;
-  PP2_NOW(f_e); PP2_SYNC();
-#endif
   const int frow = lane & 15, fkg = lane >> 4;
   // fragment read offsets inside a slot: row i*16 + frow, chunk (ks*4 + fkg) ^ ((row >> 1) & 7); i adds 2048 bytes, ks flips bit 6
   const unsigned fo0 = (unsigned)(frow * 128 + ((fkg ^ (frow >> 1)) << 4));
@@ -1359,20 +806,15 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt256p_kernel(GemmBf16Args a
       };
       auto wait_step = [&]() { asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); };
       // ---- phase 0: rows 0..63 of the wave's block, both k-halves ------------------------------------------------------
-      PP2_BEGIN()
       glds16_x4(qB, vB, dB);
       ldB(0, bq[0]); ldB(1, bq[1]);
       ldA(0, 0, aq[0]); ldA(0, 1, aq[1]);
-      PP2_L_END()
       PP_BAR();
-      PP2_M_BEGIN(0)
       __builtin_amdgcn_s_setprio(1);
       mm(0, aq[0], bq[0]); mm(0, aq[1], bq[1]);
       __builtin_amdgcn_s_setprio(0);
-      PP2_M_END(2)
       PP_BAR();
       // ---- phase 1: rows 64..127 --------------------------------------------------------------------------------------
-      PP2_BEGIN2(3)
       glds16_x4(qA, vA, dA);
       ldA(1, 0, aq[0]); ldA(1, 1, aq[1]);
       // the next step's scalars (see above).  Cursors: one K-block on, or into the next tile when the step they feed is one (B: step
@@ -1386,33 +828,14 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt256p_kernel(GemmBf16Args a
       const bf16* n_qB = kt + 2 == nk ? pBn : qB + BK;
       const bf16* n_qA = kt + 3 == nk ? pAn : qA + BK;
       asm volatile("" : "+s"(n_sA), "+s"(n_aoff), "+s"(n_boff), "+s"(n_dB), "+s"(n_dA), "+s"(n_qB), "+s"(n_qA));
-      PP2_L_END()
       __builtin_amdgcn_sched_barrier(0);
-#ifdef PP_LAB_STAMP
-      if (!leader) { if (kt) PPSTAMP(0) else PPSTAMP(1) }
-#endif
       if (!leader) wait_step();                        // follower: its pieces of the next step must be in before the leader's L0
-#ifdef PP_LAB_STAMP
-      if (!leader) PPSTAMP(2)
-#endif
       PP_BAR();
-      PP2_M_BEGIN(4)
       __builtin_amdgcn_s_setprio(1);
       mm(1, aq[0], bq[0]); mm(1, aq[1], bq[1]);
       __builtin_amdgcn_s_setprio(0);
-      PP2_M_END(6)
       __builtin_amdgcn_sched_barrier(0);
-#ifdef PP_LAB_STAMP
-      if (leader) { if (kt) PPSTAMP(0) else PPSTAMP(1) }
-#endif
       if (leader) wait_step();
-#ifdef PP_LAB_STAMP
-      if (leader) PPSTAMP(2)
-      lab_acc[6] += 1;
-#endif
-#ifdef PP_LAB_STAMP2
-      f_acc[8] += 1;
-#endif
       // the follower's last MFMAs of a tile and its epilogue share one interval (see the header)
       if (leader || kt + 1 < nk) PP_BAR();
       sA = n_sA; aoff = n_aoff; boff = n_boff; dB = n_dB; dA = n_dA; qB = n_qB; qA = n_qA;
@@ -1437,7 +860,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt256p_kernel(GemmBf16Args a
         }
         if (kt == 4) {
           const unsigned got = (unsigned)__builtin_amdgcn_readfirstlane((int)req);
-          next = (mode & 0xff) == 2 ? (tile + G < ntiles ? tile + G : -1) : (int)got;
+          next = (int)got;
           has_next = next >= 0;
           if (has_next) origin(next, pAn, pBn, m0n, n0n);
         }
@@ -1459,15 +882,11 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt256p_kernel(GemmBf16Args a
       GemmBf16Args ea;
       __builtin_memcpy(&ea, kw, sizeof(GemmBf16Args));
       nt256_wave_epilogue<MODE>(ea, acc, reinterpret_cast<float*>(smem + f3 * T2_BYTES + wave * 4096),
-                                    reinterpret_cast<float*>(smem + f4 * T2_BYTES + wave * 4096), m0, n0, wm, wn, lane PPSTAMP_PASS);
+                                    reinterpret_cast<float*>(smem + f4 * T2_BYTES + wave * 4096), m0, n0, wm, wn, lane);
     }
     PP_BAR();
-#ifdef PP_LAB_STAMP
-    lab_acc[7] += 1;
-#endif
     if (!has_next) break;
     if (!leader) PP_BAR();                             // the follower idles through the leader's first L0
-    PPSTAMP(5)
     tile = next; pA = pAn; pB = pBn; m0 = m0n; n0 = n0n;
     if (dynamic) { next = -1; has_next = false; }
     else {
@@ -1478,16 +897,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt256p_kernel(GemmBf16Args a
   }
 #undef PP_BAR
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the cursors' last (unused) pieces
-#ifdef PP_LAB_STAMP2
-  if ((wave == 0 || wave == 4) && lane == 0 && blockIdx.x < 256)
-    for (int i = 0; i < 9; ++i) g_pp_stamp2[(blockIdx.x * 2 + wm) * 16 + i] = f_acc[i];
-#endif
-#ifdef PP_LAB_STAMP
-  lab_acc[8] = pp_now() - lab_t0;
-  lab_acc[9] = __builtin_amdgcn_s_memrealtime() - lab_r0;
-  if ((wave == 0 || wave == 4) && lane == 0 && blockIdx.x < PP_LAB_MAX_WG)
-    for (int i = 0; i < 10; ++i) g_pp_stamp[(blockIdx.x * 2 + wm) * 16 + i] = lab_acc[i];
-#endif
   leave();
 }
 
@@ -1598,27 +1007,9 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_tn_kernel(const bf16* __rest
     }
 }
 
-
 // ------------------------------------------------------------------------------------------------
-// TN kernel, 256 x 256 output tile, 8 waves (2 along n x 4 along k), 128 x 64 per wave, 64 token rows per
-// stage ([64 m][256] tiles, 512-byte rows, 32 KiB each, 2 stages = 128 KiB).  Same load-path argument as
-// the 256 x 256 NT kernel.  The bias gradient (column sums of dY) is accumulated from the dY fragments
-// the k-tile-0 blocks already hold -- no separate pass over dY.
-constexpr int TN2_TILE = TN_BKM * 256 * 2;         // 32 KiB
-
-__device__ __forceinline__ void tn256_stage(const bf16* __restrict__ g, int64_t ld, int64_t m0, int64_t mend, int64_t col0,
-                                             char* lds_tile, int wave, int lane) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int piece = wave * 4 + i;                // 1 KiB = 2 rows of 512 B
-    const int r = piece * 2 + (lane >> 5);
-    const int slot = lane & 31;
-    const int c = slot ^ ((r & 3) << 2);
-    const int64_t gm = m0 + r;                     // always < mend (whole 64-row tiles only)
-    glds16(g + gm * ld + col0 + c * 8, lds_tile + piece * 1024);
-  }
-}
-
+// dW kernel, 256 x 256 output tile: same load-path argument as the 256 x 256 NT kernel.  The bias gradient (column sums of dY)
+// is accumulated from the dY fragments the workgroups already hold -- no separate pass over dY.
 // per-lane byte offset (inside a [64][256] tile) of the transposed-read address for the 32-column block at col0:
 // row 8h + q of the first k-step, this lane's 4 columns; k-step ks / half t add (16 ks + 4 t) * 512 as an immediate.
 __device__ __forceinline__ unsigned tn256_lane_off(int col0, int lane) {
@@ -1633,139 +1024,16 @@ __device__ __forceinline__ void tn256_frag_issue(unsigned addr, u32x2& lo, u32x2
   hi = lds_read_tr16<KS * 8192 + 2048>(addr);
 }
 
+// ------------------------------------------------------------------------------------------------
 // DET: instead of float atomics on dW / dbias (whose order differs from run to run) every workgroup stores its 256 x 256 partial
 // tile to `part` [split][tile][256][256] and its bias partials to `pbias` [split][tk][wk][N]; tn256_reduce_kernel then adds them
 // up in a fixed order.  Same MFMA stream, so the partial sums themselves are bit-identical between runs.
-template <bool DET>
-__global__ __launch_bounds__(512, 2) void gemm_bf16_tn256_kernel(const bf16* __restrict__ dY, int64_t lddy, const bf16* __restrict__ X,
-                                                                  int64_t ldx, float* __restrict__ dW, float* __restrict__ dbias,
-                                                                  int64_t M, int64_t N, int64_t K, int ntn, int ntk,
-                                                                  int64_t rows_per_split, float* __restrict__ part,
-                                                                  float* __restrict__ pbias) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wn = wave >> 2, wk = wave & 3;
-  const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int tile = bid % (ntn * ntk);
-  const int split = bid / (ntn * ntk);
-  const int tn = tile / ntk, tk = tile - tn * ntk;
-  const int64_t n0 = (int64_t)tn * 256, k0 = (int64_t)tk * 256;
-  const int64_t mbeg = (int64_t)split * rows_per_split;
-  const int64_t mend = (mbeg + rows_per_split < M) ? mbeg + rows_per_split : M;
-  if (mbeg >= mend) return;
-  const int nt = (int)((mend - mbeg + TN_BKM - 1) / TN_BKM);
-  // fused dbias: column sums of dY from the A fragments.  The conversions and adds are VALU work the MFMA stream has
-  // to wait for, so they are dealt out evenly: of the ntk workgroups that read the same dY tile, the one with
-  // tk == t mod ntk takes step t, and inside it wave wk takes k-sub-step ks == wk (everybody ends with atomics).
-  const bool do_bias = dbias != nullptr;
-
-  f32x16 acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-  float csum[4] = {0.f, 0.f, 0.f, 0.f};
-  unsigned aoff[4], boff[2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) aoff[i] = tn256_lane_off(wn * 128 + i * 32, lane);
-#pragma unroll
-  for (int j = 0; j < 2; ++j) boff[j] = tn256_lane_off(wk * 64 + j * 32, lane);
-
-  tn256_stage(dY, lddy, mbeg, mend, n0, smem, wave, lane);
-  tn256_stage(X, ldx, mbeg, mend, k0, smem + TN2_TILE, wave, lane);
-  __syncthreads();
-  for (int t = 0; t < nt; ++t) {
-    char* cur = smem + (t & 1) * 2 * TN2_TILE;
-    char* nxt = smem + ((t + 1) & 1) * 2 * TN2_TILE;
-    // as in the NT kernel: waves 0-3 issue all DMA pieces, their SIMD partners (waves 4-7) go straight to the MFMAs
-    if (t + 1 < nt && __builtin_amdgcn_readfirstlane(threadIdx.x) < 256) {
-      tn256_stage(dY, lddy, mbeg + (int64_t)(t + 1) * TN_BKM, mend, n0, nxt, wave, lane);
-      tn256_stage(X, ldx, mbeg + (int64_t)(t + 1) * TN_BKM, mend, k0, nxt + TN2_TILE, wave, lane);
-      tn256_stage(dY, lddy, mbeg + (int64_t)(t + 1) * TN_BKM, mend, n0, nxt, wave + 4, lane);
-      tn256_stage(X, ldx, mbeg + (int64_t)(t + 1) * TN_BKM, mend, k0, nxt + TN2_TILE, wave + 4, lane);
-    }
-    const unsigned cbase = lds_addr(cur);
-    const bool bias_step = (t % ntk) == tk;
-    // fragment reads are software-pipelined one k-step ahead: while the MFMAs of k-step ks run, the 12 transposed
-    // reads of k-step ks+1 are in flight; the wait before the MFMAs is a counted lgkmcnt(12)
-    u32x2 alo[2][4], ahi[2][4], blo[2][2], bhi[2][2];
-    auto issue = [&](auto KS) {
-      constexpr int ks = decltype(KS)::value;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) tn256_frag_issue<ks>(cbase + aoff[i], alo[ks & 1][i], ahi[ks & 1][i]);
-#pragma unroll
-      for (int j = 0; j < 2; ++j) tn256_frag_issue<ks>(cbase + TN2_TILE + boff[j], blo[ks & 1][j], bhi[ks & 1][j]);
-    };
-    auto compute = [&](auto KS) {
-      constexpr int ks = decltype(KS)::value;
-      bf16x8 af[4], bfr[2];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) af[i] = pack_tr(alo[ks & 1][i], ahi[ks & 1][i]);
-#pragma unroll
-      for (int j = 0; j < 2; ++j) bfr[j] = pack_tr(blo[ks & 1][j], bhi[ks & 1][j]);
-      if (do_bias && ks == wk && bias_step) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int e = 0; e < 8; ++e) csum[i] += (float)af[i][e];
-      }
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-    };
-    issue(std::integral_constant<int, 0>{});
-    issue(std::integral_constant<int, 1>{});
-    lds_wait_upto<12>();
-    compute(std::integral_constant<int, 0>{});
-    issue(std::integral_constant<int, 2>{});
-    lds_wait_upto<12>();
-    compute(std::integral_constant<int, 1>{});
-    issue(std::integral_constant<int, 3>{});
-    lds_wait_upto<12>();
-    compute(std::integral_constant<int, 2>{});
-    lds_wait_upto<0>();
-    compute(std::integral_constant<int, 3>{});
-    __syncthreads();
-  }
-  float* ptile = DET ? part + ((int64_t)split * (ntn * ntk) + tile) * 65536 : nullptr;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int kl = wk * 64 + j * 32 + (lane & 31);
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int nl = wn * 128 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-        if (DET) ptile[nl * 256 + kl] = acc[i][j][e];
-        else atomicAdd(dW + (n0 + nl) * K + k0 + kl, acc[i][j][e]);
-      }
-    }
-  if (do_bias) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float s2 = csum[i] + __shfl_xor(csum[i], 32, 64);
-      if (lane < 32) {
-        const int64_t n = n0 + wn * 128 + i * 32 + lane;
-        if (DET) pbias[(((int64_t)split * ntk + tk) * 4 + wk) * N + n] = s2;
-        else atomicAdd(dbias + n, s2);
-      }
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// dW kernel, PING-PONG form (round 4): the structure of gemm_bf16_nt256p_kernel on the tiles, fragments and epilogue of
-// gemm_bf16_tn256_kernel.  Output tile 256 (n) x 256 (k), waves 2 (n) x 4 (k), 128 x 64 per wave in 4 x 2 accumulators of
-// v_mfma_f32_32x32x16_bf16; a STEP is 64 token rows ([64 m][256] tiles of dY and X, 512-byte rows, transposed fragment reads), a
-// phase is one half of them (k-steps 0-1: token rows 0..31; k-steps 2-3: rows 32..63): 24 ds_read_b64_tr_b16 + 4 LDS-DMA pieces in
-// its LOAD half, 16 MFMAs (512 cycles) in its MFMA half.  The leader (waves 0-3: n rows 0..127) and the follower (waves 4-7) run one
-// barrier interval apart, so one wave of every SIMD is always in an MFMA half.
+// dW kernel, PING-PONG form (round 4): the structure of gemm_bf16_nt256p_kernel on the tiles and fragments above.  Output tile 256
+// (n) x 256 (k), waves 2 (n) x 4 (k), 128 x 64 per wave in 4 x 2 accumulators of v_mfma_f32_32x32x16_bf16; a STEP is 64 token
+// rows ([64 m][256] tiles of dY and X, 512-byte rows, transposed fragment reads), a phase is one half of them (k-steps 0-1: token
+// rows 0..31; k-steps 2-3: rows 32..63): 24 ds_read_b64_tr_b16 + 4 LDS-DMA pieces in its LOAD half, 16 MFMAs (512 cycles) in its
+// MFMA half.  The leader (waves 0-3: n rows 0..127) and the follower (waves 4-7) run one barrier interval apart, so one wave of
+// every SIMD is always in an MFMA half.
 // Ring of five 32 KiB slots: dY_t, X_t, dY_t+1, X_t+1 (landing during step t), dY_t+2 (landing).  Every wave reads all 64 token rows of
 // both tiles (its own columns), so a slot of step t-1 is refilled by halves: token rows 0..31 were last read in the follower's first
 // load half of step t-1 and are refilled by waves 0-3 (pieces 4w + p = rows 8w + 2p ..) from the leader's L0 of step t on; rows
@@ -1815,8 +1083,8 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn256p_kernel(const bf16* __
   for (int p = 0; p < 4; ++p) {
     const int r = 8 * wave + 2 * p + (lane >> 5);
     const int c = (lane & 31) ^ ((r & 3) << 2);
-    vY[p] = (unsigned)((r * lddy + c * 8) * 2) + (PP_DMA_IMM ? 3072 - 1024 * p : 0);
-    vX[p] = (unsigned)((r * ldx + c * 8) * 2) + (PP_DMA_IMM ? 3072 - 1024 * p : 0);
+    vY[p] = (unsigned)((r * lddy + c * 8) * 2) + (3072 - 1024 * p);
+    vX[p] = (unsigned)((r * ldx + c * 8) * 2) + (3072 - 1024 * p);
   }
   const unsigned lds0 = lds_addr(smem) + wave * 4096;
   const bf16* pY = dY + mbeg * lddy + n0;
@@ -1982,17 +1250,6 @@ __global__ __launch_bounds__(256) void tn256_reduce_kernel(const float* __restri
 
 }  // namespace
 
-#ifdef PP_LAB_STAMP2
-extern "C" int meant_lab_pp_stamps2(void* dst, size_t bytes) {
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_pp_stamp2), bytes < sizeof(g_pp_stamp2) ? bytes : sizeof(g_pp_stamp2));
-}
-#endif
-#ifdef PP_LAB_STAMP
-extern "C" int meant_lab_pp_stamps(void* dst, size_t bytes) {
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_pp_stamp), bytes < sizeof(g_pp_stamp) ? bytes : sizeof(g_pp_stamp));
-}
-#endif
-
 // Scheduler slot of (current device, stream); nullptr when the table is full or the symbol cannot be resolved.
 // g_tile_sched is a __device__ array: every device has its own copy at its own address.
 static TileSched* tile_sched_for(hipStream_t stream) {
@@ -2036,21 +1293,17 @@ int gemm_bf16_nt_launch(const GemmBf16Args& a, hipStream_t stream) {
   MEANT_REQUIRE((a.lda % 8) == 0 && (a.ldb % 8) == 0 && meant_aligned16(a.A) && meant_aligned16(a.B), MEANT_ERR_ARG,
                 "gemm_bf16_nt: operands must be 16-byte aligned with row strides that are multiples of 8");
   MEANT_RAISE_LDS(gemm_bf16_nt256_kernel, 4 * T2_BYTES);
-  MEANT_RAISE_LDS((gemm_bf16_nt256s_kernel<0, false>), RING * T2_BYTES);
-  MEANT_RAISE_LDS((gemm_bf16_nt256s_kernel<0, true>), RING * T2_BYTES);
-  MEANT_RAISE_LDS((gemm_bf16_nt256s_kernel<0, false, true>), RING * T2_BYTES);
   MEANT_RAISE_LDS((gemm_bf16_nt256p_kernel<NTE_PLAIN>), RING * T2_BYTES);
   MEANT_RAISE_LDS((gemm_bf16_nt256p_kernel<NTE_RES>), RING * T2_BYTES);
   MEANT_RAISE_LDS((gemm_bf16_nt256p_kernel<NTE_GELU_PRE>), RING * T2_BYTES);
   MEANT_RAISE_LDS((gemm_bf16_nt256p_kernel<NTE_ROT>), RING * T2_BYTES);
   MEANT_RAISE_LDS((gemm_bf16_nt256p_kernel<NTE_EXT>), RING * T2_BYTES);
   MEANT_RAISE_LDS((gemm_bf16_nt256p_kernel<NTE_GENERIC>), RING * T2_BYTES);
-  MEANT_RAISE_LDS((gemm_bf16_nt256s_kernel<128, false, false>), RING * T2_BYTES);
-  MEANT_RAISE_LDS((gemm_bf16_nt256s_kernel<128, true, false>), RING * T2_BYTES);
-  MEANT_RAISE_LDS((gemm_bf16_nt256s_kernel<128, false, true>), RING * T2_BYTES);
   const bool ext = a.row_scale || a.sub || a.bres;
+  const bool act = (a.epilogue & (MEANT_EPI_GELU | MEANT_EPI_SIGMOID)) != 0;
   MEANT_REQUIRE(!a.bres || (a.bres_rows > 0 && (a.N & 7) == 0 && meant_aligned16(a.bres)), MEANT_ERR_ARG, "gemm_bf16_nt: bad broadcast residual");
   MEANT_REQUIRE(!ext || (!a.rot_qa && !(a.epilogue & MEANT_EPI_SIGMOID)), MEANT_ERR_UNSUPPORTED, "gemm_bf16_nt: extended epilogue with rotary / sigmoid");
+  MEANT_REQUIRE(!a.rot_qa || (!a.residual && !a.preact && !act), MEANT_ERR_UNSUPPORTED, "gemm_bf16_nt: rotary epilogue with residual / activation / preact");
   MEANT_REQUIRE(!a.sub || (a.sub_coef && (a.ldsub & 7) == 0 && meant_aligned16(a.sub)), MEANT_ERR_ARG, "gemm_bf16_nt: bad sub operand");
   // big tall problems: 256 x 256 tiles (half the operand bytes per FLOP) -- once there are enough of them to occupy at least
   // half the CUs (the temporal encoder's 1536^2 Linears make 36: four times as many 128 x 128 tiles finish in a third of the time)
@@ -2068,7 +1321,7 @@ int gemm_bf16_nt_launch(const GemmBf16Args& a, hipStream_t stream) {
       const char *p0 = (const char*)p, *q0 = (const char*)q;
       return p && q && p0 < q0 + rows * ldq * 2 && q0 < p0 + rows * ld * 2;
     };
-    const bool ragged_overlap = stream_ok && meant_opt(MEANT_OPT_NT_RAGGED) != 0 && a.M % B2 != 0 && a.K >= 2 * BK && (a.ldc & 7) == 0 &&
+    const bool ragged_overlap = stream_ok && meant_opt(MEANT_OPT_NT_RAGGED) != 0 && a.M % B2 != 0 && a.K >= 4 * BK && (a.ldc & 7) == 0 &&
                                 (!a.residual || (a.ldr & 7) == 0) && !overlaps(a.C, a.ldc, a.residual, a.ldr, a.M) &&
                                 !overlaps(a.C, a.ldc, a.sub, a.ldsub, a.M) &&
                                 !overlaps(a.C, a.ldc, a.A, a.lda, a.M) && (!a.preact || !overlaps(a.preact, a.ldc, a.A, a.lda, a.M));
@@ -2076,7 +1329,7 @@ int gemm_bf16_nt_launch(const GemmBf16Args& a, hipStream_t stream) {
     // to the 128 x 128 kernel as a second launch (row-local epilogues only: the rotary epilogue indexes its tables by the
     // absolute row, so it splits only where the boundary is a multiple of the sequence length).
     const int64_t m_full = (a.M / B2) * B2;
-    if (!ragged_overlap && stream_ok && m_full >= 1024 && m_full != a.M && a.K >= 2 * BK && (a.ldc & 7) == 0 && (!a.residual || (a.ldr & 7) == 0) &&
+    if (!ragged_overlap && stream_ok && m_full >= 1024 && m_full != a.M && a.K >= 4 * BK && (a.ldc & 7) == 0 && (!a.residual || (a.ldr & 7) == 0) &&
         (!a.rot_qa || m_full % a.rot_S == 0)) {
       GemmBf16Args head = a, tail = a;
       head.M = m_full;
@@ -2093,7 +1346,9 @@ int gemm_bf16_nt_launch(const GemmBf16Args& a, hipStream_t stream) {
       const int rc = gemm_bf16_nt_launch(head, stream);
       return rc ? rc : gemm_bf16_nt_launch(tail, stream);
     }
-    if (stream_ok && (a.M % B2 == 0 || ragged_overlap) && a.K >= 2 * BK && (a.ldc & 7) == 0 && (!a.residual || (a.ldr & 7) == 0)) {
+    // the streaming kernel (ping-pong form: the two waves of a SIMD alternate between MFMA and load halves) needs four K-steps;
+    // shorter K goes to the one-tile kernel below
+    if (stream_ok && (a.M % B2 == 0 || ragged_overlap) && a.K >= 4 * BK && (a.ldc & 7) == 0 && (!a.residual || (a.ldr & 7) == 0)) {
       if (ragged_overlap) meant_route_hit(ROUTE_NT_OVERLAP);
       int ncu = meant_num_cus() & ~7;
       const int cap = meant_opt(MEANT_OPT_NT_GRID_CAP) & ~7;     // tests: fewer workgroups => more tiles each, dry XCDs steal
@@ -2102,44 +1357,31 @@ int gemm_bf16_nt_launch(const GemmBf16Args& a, hipStream_t stream) {
       // Tile counters: one slot per (device, stream).  Launches on one stream execute in order and a launch leaves its
       // slot zeroed (last workgroup out), so a slot is never shared by two launches in flight -- by construction, not by
       // distance.  A stream beyond the table's capacity gets the fixed walk (sched = nullptr).  Option nt_dynamic = 0 forces it.
-      const int dynmode0 = meant_opt(MEANT_OPT_NT_DYNAMIC);
-      const int dynmode = dynmode0;
-      TileSched* sched = (dynmode != 0 && dynmode != 4 && grid <= 512) ? tile_sched_for(stream) : nullptr;
+      const int dynmode = meant_opt(MEANT_OPT_NT_DYNAMIC);
+      TileSched* sched = (dynmode != 0 && grid <= 512) ? tile_sched_for(stream) : nullptr;
       meant_route_hit(a.rot_qa ? ROUTE_NT256S_ROT : ROUTE_NT256S);
       const dim3 g3((unsigned)grid), b3(512);
-      if (meant_opt(MEANT_OPT_NT_PP) != 0 && a.K >= 4 * BK) {   // ping-pong form: the two waves of a SIMD alternate between MFMA and load halves
-        const int ppopt = meant_opt(MEANT_OPT_NT_PP);
-        const int dynmode = dynmode0 | ((ppopt & 8) ? 0x100 : 0);   // lab, bit 3: staggered start
-        // rotary mode: panels of one position range after the other (see the kernel's `origin`); PP_ROT_WALK=0 builds without it
-        int rotP = 0;
-        if (a.rot_qa && PP_ROT_WALK && a.rot_S % B2 == 0 && a.rot_S / B2 > 1 && a.rot_S / B2 < 256 && a.M % B2 == 0 && ntm2 % (a.rot_S / B2) == 0) rotP = (int)(a.rot_S / B2);
-        // the epilogue's options as a template parameter (see nt256_wave_epilogue): the combinations the models run get straight-line
-        // code, anything else the generic instantiation with run-time flags
-        const bool act = (a.epilogue & (MEANT_EPI_GELU | MEANT_EPI_SIGMOID)) != 0;
-        int emode = NTE_GENERIC;
-        if (a.rot_qa) emode = (!a.residual && !a.preact && !act) ? NTE_ROT : -1;
-        else if (ext) emode = NTE_EXT;
-        else if (!a.residual && !a.preact && !act) emode = NTE_PLAIN;
-        else if (a.residual && !a.preact && !act) emode = NTE_RES;
-        else if (!a.residual && a.preact && (a.epilogue & MEANT_EPI_GELU) && !(a.epilogue & MEANT_EPI_SIGMOID)) emode = NTE_GELU_PRE;
-        MEANT_REQUIRE(emode >= 0, MEANT_ERR_UNSUPPORTED, "gemm_bf16_nt: rotary epilogue with residual / activation / preact");
+      // rotary mode: panels of one position range after the other (see the kernel's `origin`)
+      int rotP = 0;
+      if (a.rot_qa && a.rot_S % B2 == 0 && a.rot_S / B2 > 1 && a.rot_S / B2 < 256 && a.M % B2 == 0 && ntm2 % (a.rot_S / B2) == 0) rotP = (int)(a.rot_S / B2);
+      // the epilogue's options as a template parameter (see nt256_wave_epilogue): the combinations the models run get straight-line
+      // code, anything else the generic instantiation with run-time flags
+      int emode = NTE_GENERIC;
+      if (a.rot_qa) emode = NTE_ROT;
+      else if (ext) emode = NTE_EXT;
+      else if (!a.residual && !a.preact && !act) emode = NTE_PLAIN;
+      else if (a.residual && !a.preact && !act) emode = NTE_RES;
+      else if (!a.residual && a.preact && (a.epilogue & MEANT_EPI_GELU) && !(a.epilogue & MEANT_EPI_SIGMOID)) emode = NTE_GELU_PRE;
 #define PP_LAUNCH(MODE_) hipLaunchKernelGGL((gemm_bf16_nt256p_kernel<MODE_>), g3, b3, RING * T2_BYTES, stream, a, (int)ntm2, (int)ntn2, sched, dynmode | (rotP << 16))
-        switch (emode) {
-          case NTE_PLAIN: PP_LAUNCH(NTE_PLAIN); break;
-          case NTE_RES: PP_LAUNCH(NTE_RES); break;
-          case NTE_GELU_PRE: PP_LAUNCH(NTE_GELU_PRE); break;
-          case NTE_ROT: PP_LAUNCH(NTE_ROT); break;
-          case NTE_EXT: PP_LAUNCH(NTE_EXT); break;
-          default: PP_LAUNCH(NTE_GENERIC); break;
-        }
+      switch (emode) {
+        case NTE_PLAIN: PP_LAUNCH(NTE_PLAIN); break;
+        case NTE_RES: PP_LAUNCH(NTE_RES); break;
+        case NTE_GELU_PRE: PP_LAUNCH(NTE_GELU_PRE); break;
+        case NTE_ROT: PP_LAUNCH(NTE_ROT); break;
+        case NTE_EXT: PP_LAUNCH(NTE_EXT); break;
+        default: PP_LAUNCH(NTE_GENERIC); break;
+      }
 #undef PP_LAUNCH
-      } else if (meant_opt(MEANT_OPT_NT_SPLIT) != 0) {   // DMA issue split in time between the two waves of a SIMD (see the kernel)
-        if (a.rot_qa) hipLaunchKernelGGL((gemm_bf16_nt256s_kernel<128, true>), g3, b3, RING * T2_BYTES, stream, a, (int)ntm2, (int)ntn2, sched, dynmode);
-        else if (ext) hipLaunchKernelGGL((gemm_bf16_nt256s_kernel<128, false, true>), g3, b3, RING * T2_BYTES, stream, a, (int)ntm2, (int)ntn2, sched, dynmode);
-        else hipLaunchKernelGGL((gemm_bf16_nt256s_kernel<128, false>), g3, b3, RING * T2_BYTES, stream, a, (int)ntm2, (int)ntn2, sched, dynmode);
-      } else if (a.rot_qa) hipLaunchKernelGGL((gemm_bf16_nt256s_kernel<0, true>), g3, b3, RING * T2_BYTES, stream, a, (int)ntm2, (int)ntn2, sched, dynmode);
-      else if (ext) hipLaunchKernelGGL((gemm_bf16_nt256s_kernel<0, false, true>), g3, b3, RING * T2_BYTES, stream, a, (int)ntm2, (int)ntn2, sched, dynmode);
-      else hipLaunchKernelGGL((gemm_bf16_nt256s_kernel<0, false>), g3, b3, RING * T2_BYTES, stream, a, (int)ntm2, (int)ntn2, sched, dynmode);
     } else {
       meant_route_hit(ROUTE_NT256);
       hipLaunchKernelGGL(gemm_bf16_nt256_kernel, dim3((unsigned)(ntm2 * ntn2)), dim3(512), 4 * T2_BYTES, stream, a, (int)ntm2, (int)ntn2);
@@ -2216,7 +1458,6 @@ int gemm_bf16_tn_launch(const bf16* dY, int64_t lddy, const bf16* X, int64_t ldx
     int64_t splits2, rows2;
     tn256_geometry(M, N, K, splits2, rows2);
     const dim3 grid((unsigned)(ntn2 * ntk2 * splits2));
-    const bool pp = meant_opt(MEANT_OPT_TN_PP) != 0;     // ping-pong form of the 256 x 256 dW kernel
     if (det) {
       const size_t need = (size_t)(splits2 * N * K + splits2 * ntk2 * 4 * N) * sizeof(float);
       MEANT_REQUIRE(ws && ws_bytes >= need && meant_aligned16(ws), MEANT_ERR_WORKSPACE,
@@ -2224,15 +1465,9 @@ int gemm_bf16_tn_launch(const bf16* dY, int64_t lddy, const bf16* X, int64_t ldx
       float* part = (float*)ws;
       float* pbias = part + splits2 * N * K;
       meant_route_hit(ROUTE_TN256_DET);
-      if (pp) {
-        MEANT_RAISE_LDS(gemm_bf16_tn256p_kernel<true>, RING * T2_BYTES);
-        hipLaunchKernelGGL(gemm_bf16_tn256p_kernel<true>, grid, dim3(512), RING * T2_BYTES, stream, dY, lddy, X, ldx, dW, dbias, M, N, K, (int)ntn2,
-                           (int)ntk2, rows2, part, pbias);
-      } else {
-        MEANT_RAISE_LDS(gemm_bf16_tn256_kernel<true>, 4 * TN2_TILE);
-        hipLaunchKernelGGL(gemm_bf16_tn256_kernel<true>, grid, dim3(512), 4 * TN2_TILE, stream, dY, lddy, X, ldx, dW, dbias, M, N, K, (int)ntn2,
-                           (int)ntk2, rows2, part, pbias);
-      }
+      MEANT_RAISE_LDS(gemm_bf16_tn256p_kernel<true>, RING * T2_BYTES);
+      hipLaunchKernelGGL(gemm_bf16_tn256p_kernel<true>, grid, dim3(512), RING * T2_BYTES, stream, dY, lddy, X, ldx, dW, dbias, M, N, K, (int)ntn2,
+                         (int)ntk2, rows2, part, pbias);
       MEANT_LAUNCH_CHECK("gemm_bf16_tn256<det>");
       hipLaunchKernelGGL(tn256_reduce_kernel, dim3((unsigned)ceil_div(N * K / 4, 256)), dim3(256), 0, stream, part, dbias ? pbias : nullptr, dW, dbias,
                          N, K, (int)ntk2, (int)(ntn2 * ntk2), (int)splits2);
@@ -2240,15 +1475,9 @@ int gemm_bf16_tn_launch(const bf16* dY, int64_t lddy, const bf16* X, int64_t ldx
       return MEANT_OK;
     }
     meant_route_hit(ROUTE_TN256);
-    if (pp) {
-      MEANT_RAISE_LDS(gemm_bf16_tn256p_kernel<false>, RING * T2_BYTES);
-      hipLaunchKernelGGL(gemm_bf16_tn256p_kernel<false>, grid, dim3(512), RING * T2_BYTES, stream, dY, lddy, X, ldx, dW, dbias, M, N, K, (int)ntn2,
-                         (int)ntk2, rows2, (float*)nullptr, (float*)nullptr);
-    } else {
-      MEANT_RAISE_LDS(gemm_bf16_tn256_kernel<false>, 4 * TN2_TILE);
-      hipLaunchKernelGGL(gemm_bf16_tn256_kernel<false>, grid, dim3(512), 4 * TN2_TILE, stream, dY, lddy, X, ldx, dW, dbias, M, N, K, (int)ntn2,
-                         (int)ntk2, rows2, (float*)nullptr, (float*)nullptr);
-    }
+    MEANT_RAISE_LDS(gemm_bf16_tn256p_kernel<false>, RING * T2_BYTES);
+    hipLaunchKernelGGL(gemm_bf16_tn256p_kernel<false>, grid, dim3(512), RING * T2_BYTES, stream, dY, lddy, X, ldx, dW, dbias, M, N, K, (int)ntn2,
+                       (int)ntk2, rows2, (float*)nullptr, (float*)nullptr);
     MEANT_LAUNCH_CHECK("gemm_bf16_tn256");
     return MEANT_OK;
   }

@@ -1,6 +1,6 @@
-"""Element-level parity of the STREAMING 256x256 NT GEMM (`gemm_bf16_nt256s_kernel`, the kernel that carries the headline
-number) and of the 256x256 dW kernel, at shapes that provably route to them with more than one tile per workgroup, the
-dynamic tile draw live, XCD stealing, the ragged head + tail split, every epilogue, the rotary instantiation of the fused
+"""Element-level parity of the STREAMING 256x256 NT GEMM (`gemm_bf16_nt256p_kernel`, route counter "nt256s", the kernel that
+carries the headline number) and of the 256x256 dW kernel, at shapes that provably route to them with more than one tile per
+workgroup, the dynamic tile draw live, XCD stealing, the ragged head + tail split, every epilogue, the rotary instantiation of the fused
 q|k|v projection and the vocabulary GEMM of the MLM head.  Reference: fp32 on the CPU on the bf16-rounded inputs
 (the arithmetic of meant/meant.py:59-64,101-107 nn.Linear call sites, meant/attention.py:36-40, pretrain_mlm.py:74-89,160).
 
@@ -88,6 +88,15 @@ def test_streaming_linear(L, dev, M_, N, K, epi, dynamic):
     assert r["nt256s"] == 1 and r["nt128"] == 0 and r["nt256"] == 0, r      # forward took the streaming kernel
     assert L.route_count("nt256s") == 2                                       # ... and so did dX
     assert L.route_count("tn256") == 1                                        # dW on the 256 x 256 TN kernel
+
+
+@pytest.mark.parametrize("K", [128, 192])
+@pytest.mark.parametrize("epi", ["residual", "gelu"])
+def test_short_k_linear_takes_the_one_tile_kernel(L, dev, epi, K):
+    """2 or 3 K-steps: too few for the streaming kernel (it needs K >= 256), so the forward runs on the one-tile-per-workgroup
+    256 x 256 kernel, whose epilogue handles every mode"""
+    r = _linear_case(L, dev, 36864, 768, K, epi, 1, 0)
+    assert r["nt256"] == 1 and r["nt256s"] == 0, r
 
 
 @pytest.mark.parametrize("epi", ["none", "residual", "gelu"])

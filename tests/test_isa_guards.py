@@ -18,7 +18,7 @@ def _tool():
 
 def test_checker_flags_a_touched_register():
     tool = _tool()
-    good = """_Z23gemm_bf16_nt256s_kernelv:
+    good = """_Z23gemm_bf16_nt256p_kernelv:
 	global_load_dword v9, v[2:3], off sc1
 	v_add_u32_e32 v4, v5, v6
 	s_waitcnt vmcnt(8)
@@ -30,18 +30,6 @@ def test_checker_flags_a_touched_register():
     assert [r[4] for r in tool.check(good)] == [None]
     assert tool.check(bad)[0][4] is not None
     assert tool.check(ranged)[0][4] is not None
-
-
-@pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
-def test_tile_draw_registers_stay_untouched_in_flight():
-    tool = _tool()
-    res = tool.check(tool.compile_to_isa())
-    # six kernel instantiations (plain / rotary / extended epilogue, each with the DMA issue at the top of the K-step or split in time
-    # between the two waves of a SIMD), each with the mailbox read and the counter draw
-    assert len(res) == 12, res
-    for kernel, req, reg, n, bad in res:
-        assert bad is None, f"{kernel}: `{req}`: v{reg} touched while in flight by `{bad}`"
-        assert n > 100, f"{kernel}: `{req}` is no longer issued ahead of the K-step body ({n} instructions)"
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")

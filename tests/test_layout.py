@@ -34,6 +34,18 @@ def test_library_builds_loads_and_exports_header_symbols():
     assert meant_amd.lib.meant_version() >= 100          # pure host call, no GPU needed
 
 
+def test_retired_gemm_options():
+    """the lock-step GEMM kernels are gone: "nt_pp" reads 1 and takes no other value (bench.py --full names the dominant kernel
+    by it); "nt_split" and "tn_pp" are unknown names"""
+    from meant_amd import _lib
+    assert _lib.get_option("nt_pp") == 1
+    _lib.set_option("nt_pp", 1)
+    for name, value in (("nt_pp", 0), ("nt_split", 1), ("tn_pp", 0)):
+        with pytest.raises(_lib.MeantHipError):
+            _lib.set_option(name, value)
+    assert _lib.get_option("nt_pp") == 1
+
+
 def test_attention_forward_workspace_leaves_out_the_backward_scratch():
     """the single-pass backward's partial-dQ scratch (G*H*64 KiB for 256 < S <= 512) and the backward's row statistics
     are not part of what a forward call allocates (pure host arithmetic, no GPU needed)"""

@@ -1,11 +1,11 @@
 """ISA guard for registers that are "in flight" behind hipcc's back.
 
-The streaming NT GEMMs (meant_amd/csrc/gemm_bf16.hip, gemm_bf16_nt256s_kernel and its ping-pong form gemm_bf16_nt256p_kernel) request their next tile with inline-asm memory
+The streaming NT GEMM (meant_amd/csrc/gemm_bf16.hip, gemm_bf16_nt256p_kernel) requests its next tile with inline-asm memory
 operations whose results arrive during the K-step and are picked up behind the wait that ends the step.  hipcc believes the
 destination registers are defined the moment the asm statement ends, so nothing stops it from copying or reusing them while
-the load is still outstanding.  This script compiles the file to ISA and checks, for every such request (marked by its cache
-scope bits: `global_load_dword ... sc1`, `global_atomic_add ... sc0` with an `off` address), that no instruction between the
-request and the next `s_waitcnt vmcnt(...)` touches the destination register.
+the load is still outstanding.  This script compiles the file to ISA and checks, for every such request in any kernel (marked
+by its cache scope bits: `global_load_dword ... sc1`, `global_atomic_add ... sc0` with an `off` address), that no instruction
+between the request and the next `s_waitcnt vmcnt(...)` touches the destination register.
 
     python tools/isa_inflight.py            # prints one line per request, exit code 1 on a violation
 """
@@ -38,8 +38,9 @@ def masked(lines, j):
     return any(l.startswith("s_mov_b32 exec_lo") for l in up) and down.startswith("s_mov_b64 exec,")
 
 
-def check(asm_text, kernel_substr="gemm_bf16_nt256s_kernel"):
-    """-> list of (kernel, request line, register, n instructions in flight, offending line or None)"""
+def check(asm_text, kernel_substr=""):
+    """-> list of (kernel, request line, register, n instructions in flight, offending line or None), over every kernel of the
+    listing whose mangled name contains kernel_substr (all of them by default)"""
     results = []
     kernel = None
     lines = asm_text.splitlines()
@@ -90,7 +91,7 @@ def compile_to_isa():
 
 if __name__ == "__main__":
     text = open(sys.argv[1]).read() if len(sys.argv) > 1 else compile_to_isa()
-    res = check(text) + check(text, "gemm_bf16_nt256p_kernel")
+    res = check(text)
     rc = 0
     for kernel, req, reg, n, bad in res:
         print(f"{kernel[:60]}: `{req}` v{reg} in flight over {n} instructions: {'OK' if bad is None else 'TOUCHED BY ' + bad}")

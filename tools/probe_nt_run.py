@@ -1,6 +1,6 @@
-"""lab: the streaming NT GEMM at the step's big shapes under MEANT_NT_DYNAMIC = 1 (per-XCD counters, the default), 0 (fixed walk) and
-4 (fixed walk in runs of one A row panel: the nine column tiles of a panel by ONE workgroup, back to back) -- time per launch.
-usage: MEANT_NT_DYNAMIC=4 python3 tools/probe_nt_run.py"""
+"""lab: the streaming NT GEMM at the step's big shapes under MEANT_NT_DYNAMIC = 1 (per-XCD counters, the default) or 0 (fixed walk)
+-- time per launch.
+usage: MEANT_NT_DYNAMIC=0 python3 tools/probe_nt_run.py"""
 import math, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
