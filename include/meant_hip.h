@@ -73,6 +73,8 @@ int meant_num_cus(void);
  *   "attn_short"       1|0   sequences of <= 16 tokens run on the one-wave-per-(group, head) kernels / on the tiled ones
  *   "attn_bwd1"        1|0   attention backward, head dim 64, S <= 256 or causal S <= 512: one pass (scores and dP computed once,
  *                            dS through LDS into the dQ product; persistent workgroups) / the dQ pass followed by the dK, dV pass
+ *   "temporal_long"    0|1   the temporal attention core runs its long-lag kernels for L > 64 only / at every lag (a measuring
+ *                            switch: tools/probe_temporal_lag.py times both kernel families at L <= 64 with it)
  *   "nt_pp"            1     read-only: the streaming GEMM runs in its ping-pong form (setting any other value fails with
  *                            MEANT_ERR_UNSUPPORTED: the lock-step kernel was removed); not read from the environment
  */
@@ -81,7 +83,8 @@ int meant_get_option(const char* name, int* value);
 /* how many launches took a given kernel route since the last reset ("nt128", "nt256", "nt256s", "nt256s_rot",
  * "nt_split", "nt_overlap", "tn128", "tn256", "tn256_det", "tn_tail", "gemm_f32", "attn_fwd", "attn_fwd_d128",
  * "attn_fwd_d96", "attn_bwd" (the two-pass form), "attn_bwd1" (the single-pass form), "attn_bwd_d128", "attn_bwd_d96",
- * "attn_generic", "attn_cls", "attn_short");
+ * "attn_generic", "attn_cls", "attn_short", "attn_fwd_d160" ... "attn_bwd_d256", "temporal_long" (the temporal attention
+ * core's long-lag kernels, forward and backward each count one));
  * -1 for an unknown name.  The names label routes, not kernels: "nt256s" / "nt256s_rot" count launches of the streaming
  * GEMM (whichever kernel implements it), "nt_split" the ragged head + tail split.  Tests use it to prove that a shape
  * reaches the kernel it is meant to exercise. */
@@ -316,7 +319,13 @@ int meant_dropout(const void* x, void* y, int64_t n, float p, uint64_t seed, int
 
 /* ---- temporal attention core ----------------------------- meant/temporal.py:44-56
  * q: act [B, H*Dh] (last lag step), kv: act [B*L, 2*H*Dh] packed (k | v); o: act [B, H*Dh];
- * p: float [B, H, L] softmax weights (saved). */
+ * p: float [B, H, L] softmax weights (saved; the forward may hold raw scores in it while it runs).
+ * Any lag L >= 1 and any head dim: L <= 64 on the one-wave-per-(b, h) kernels, L > 64 on the long-lag kernels (route
+ * "temporal_long"; temporal_long.hip): one workgroup per (b, h) whose waves split L, several key rows per 16-byte load
+ * instruction, online softmax merged through LDS; head dims that are no multiple of 8 or above 512, and operands that are
+ * not 16-byte aligned, on scalar-access kernels.  The backward recomputes nothing from o: its row term sum_l p_l dp_l comes
+ * from a first pass over V, whose dp_l stay in LDS up to L = 2048 (beyond, V is read a second time).  No atomics: two runs
+ * give the same bits.  L <= 0 fails with MEANT_ERR_UNSUPPORTED. */
 int meant_temporal_attn_fwd(const void* q, const void* kv, void* o, float* p, int64_t B, int L, int H, int Dh,
                             float scale, int dtype, void* stream);
 int meant_temporal_attn_bwd(const void* q, const void* kv, const float* p, const void* do_, void* dq, void* dkv,

@@ -81,6 +81,7 @@ const OptionDef k_options[MEANT_OPT_COUNT] = {
     {"attn_short", "MEANT_ATTN_SHORT", 1},         // 0: sequences of <= 16 tokens take the tiled flash kernels instead of attn_short.hip
     {"nt_ragged", "MEANT_NT_RAGGED", 1},           // 0: ragged M as streaming head + 128 x 128 tail launch instead of the overlapped last row tile
     {"attn_bwd1", "MEANT_ATTN_BWD1", 1},           // 0: attention backward always as two passes (dQ, then dK / dV) instead of the single-pass kernel where it applies
+    {"temporal_long", "MEANT_TEMPORAL_LONG", 0},   // 1: the temporal core runs the long-lag kernels at every lag (tools/probe_temporal_lag.py's like-for-like row); 0: only for L > 64
 };
 // "nt_pp" (the streaming GEMM in its ping-pong form) is no longer a choice: it reads 1 and cannot be set to anything else
 bool is_nt_pp(const char* name) { return name && !strcmp(name, "nt_pp"); }
@@ -135,6 +136,7 @@ const char* const k_routes[MEANT_ROUTE_COUNT] = {
     "attn_fwd", "attn_fwd_d128", "attn_fwd_d96", "attn_bwd", "attn_bwd_d128", "attn_bwd_d96",
     "attn_generic", "attn_cls", "attn_short", "nt_overlap", "attn_bwd1",
     "attn_fwd_d160", "attn_fwd_d192", "attn_fwd_d256", "attn_bwd_d160", "attn_bwd_d192", "attn_bwd_d256",
+    "temporal_long",
 };
 std::atomic<long long> g_route[MEANT_ROUTE_COUNT];
 }  // namespace

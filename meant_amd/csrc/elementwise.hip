@@ -1,10 +1,10 @@
 // Streaming / elementwise kernels of the MEANT path (all HBM-bound; fp32 math, T storage):
 //   K6 rotary / xPos (in place on the packed q|k|v projection), K7a patchify, K8 sequence mean-pool,
-//   K9 temporal (lag-axis) attention core, embedding gather / scatter-add, and small glue
+//   K9 temporal (lag-axis) attention core (lags up to 64; longer ones: temporal_long.hip), embedding gather / scatter-add, and small glue
 //   (broadcast add, GELU / sigmoid backward, casts, weight transposes).
 // Each thread moves 16 bytes (8 bf16) or 2x16 bytes (8 f32) per access; grids are capped and
 // grid-strided so that launches stay at a few thousand workgroups.
-#include "common.h"
+#include "internal.h"
 
 namespace {
 
@@ -304,7 +304,7 @@ __global__ __launch_bounds__(EW_THREADS) void meanpool_bwd_kernel(const TO* __re
 }
 
 // ------------------------------------------------------------------------------------------------
-// K9 temporal attention core: one wave per (b, h); L <= 64 keys, any Dh.
+// K9 temporal attention core: one wave per (b, h); L <= 64 keys, any Dh.  (L > 64: temporal_long.hip)
 template <typename T>
 __global__ __launch_bounds__(256) void temporal_fwd_kernel(const T* __restrict__ q, const T* __restrict__ kv, T* __restrict__ o,
                                                             float* __restrict__ p, int64_t B, int L, int H, int Dh, float scale) {
@@ -739,7 +739,8 @@ extern "C" int meant_meanpool_bwd(const void* dout, int64_t ld_out, int64_t col_
 
 extern "C" int meant_temporal_attn_fwd(const void* q, const void* kv, void* o, float* p, int64_t B, int L, int H, int Dh, float scale, int dtype, void* stream) {
   EW_REQ(q && kv && o && p && B > 0 && H > 0 && Dh > 0, "temporal_attn_fwd: bad argument");
-  MEANT_REQUIRE(L > 0 && L <= 64, MEANT_ERR_UNSUPPORTED, "temporal_attn_fwd: lag %d not in 1..64", L);
+  MEANT_REQUIRE(L > 0, MEANT_ERR_UNSUPPORTED, "temporal_attn_fwd: lag %d is not positive", L);
+  if (L > 64 || meant_opt(MEANT_OPT_TEMPORAL_LONG)) return temporal_long_fwd(q, kv, o, p, B, L, H, Dh, scale, dtype, (hipStream_t)stream);
   DISPATCH_DTYPE(dtype, T,
                  hipLaunchKernelGGL(temporal_fwd_kernel<T>, dim3((unsigned)ceil_div(B * H, 4)), dim3(256), 0, (hipStream_t)stream,
                                     (const T*)q, (const T*)kv, (T*)o, p, B, L, H, Dh, scale));
@@ -748,7 +749,8 @@ extern "C" int meant_temporal_attn_fwd(const void* q, const void* kv, void* o, f
 }
 extern "C" int meant_temporal_attn_bwd(const void* q, const void* kv, const float* p, const void* do_, void* dq, void* dkv, int64_t B, int L, int H, int Dh, float scale, int dtype, void* stream) {
   EW_REQ(q && kv && p && do_ && dq && dkv && B > 0 && H > 0 && Dh > 0, "temporal_attn_bwd: bad argument");
-  MEANT_REQUIRE(L > 0 && L <= 64, MEANT_ERR_UNSUPPORTED, "temporal_attn_bwd: lag %d not in 1..64", L);
+  MEANT_REQUIRE(L > 0, MEANT_ERR_UNSUPPORTED, "temporal_attn_bwd: lag %d is not positive", L);
+  if (L > 64 || meant_opt(MEANT_OPT_TEMPORAL_LONG)) return temporal_long_bwd(q, kv, p, do_, dq, dkv, B, L, H, Dh, scale, dtype, (hipStream_t)stream);
   DISPATCH_DTYPE(dtype, T,
                  hipLaunchKernelGGL(temporal_bwd_kernel<T>, dim3((unsigned)ceil_div(B * H, 4)), dim3(256), 0, (hipStream_t)stream,
                                     (const T*)q, (const T*)kv, p, (const T*)do_, (T*)dq, (T*)dkv, B, L, H, Dh, scale));
