@@ -61,8 +61,9 @@ int meant_num_cus(void);
  * process (the reference's nn.DataParallel, pretrain_mlm.py:329): every call acts on the calling thread's current
  * device, whose memory all pointer arguments must belong to.
  * Options (initial value from the environment variable MEANT_<NAME IN CAPITALS>):
- *   "deterministic"    0|1   parameter gradients (dW, dbias) by ordered reductions instead of float atomics: two runs
- *                            on the same inputs are bit-identical; meant_linear_bwd_dw then needs its workspace
+ *   "deterministic"    0|1   parameter gradients (dW, dbias, the norm gains, the embedding table at any d % 8 == 0) by ordered
+ *                            reductions instead of float atomics: two runs on the same inputs are bit-identical;
+ *                            meant_linear_bwd_dw then needs its workspace
  *   "nt_stream"        1|0   streaming 256x256 NT GEMM / one tile per workgroup           (A/B measurements)
  *   "nt_dynamic"       1|0|3 streaming GEMM draws tiles from per-XCD counters / fixed walk (A/B measurements) /
  *                            only XCD 0 uses its own counter, all other tiles go through the steal path (tests)
@@ -84,7 +85,7 @@ int meant_get_option(const char* name, int* value);
  * "nt_split", "nt_overlap", "tn128", "tn256", "tn256_det", "tn_tail", "gemm_f32", "attn_fwd", "attn_fwd_d128",
  * "attn_fwd_d96", "attn_bwd" (the two-pass form), "attn_bwd1" (the single-pass form), "attn_bwd_d128", "attn_bwd_d96",
  * "attn_generic", "attn_cls", "attn_short", "attn_fwd_d160" ... "attn_bwd_d256", "temporal_long" (the temporal attention
- * core's long-lag kernels, forward and backward each count one));
+ * core's long-lag kernels, forward and backward each count one), "emb_seg" (meant_embedding_bwd_seg), "sort_ids" (meant_sort_ids));
  * -1 for an unknown name.  The names label routes, not kernels: "nt256s" / "nt256s_rot" count launches of the streaming
  * GEMM (whichever kernel implements it), "nt_split" the ragged head + tail split.  Tests use it to prove that a shape
  * reaches the kernel it is meant to exercise. */
@@ -387,6 +388,22 @@ int meant_embedding_bwd_sorted(const void* dout, const int64_t* sorted_ids, cons
  * final only with the last kernel of backward).  The union over a partition of [0, V) equals meant_embedding_bwd_sorted. */
 int meant_embedding_bwd_sorted_range(const void* dout, const int64_t* sorted_ids, const int64_t* order, float* dtable,
                                      int64_t n, int64_t d, int64_t V, int64_t id_lo, int64_t id_hi, int dtype, void* stream);
+/* stable device sort of the ids, clamped into [0, V) as meant_embedding_fwd clamps them: sorted_ids[j] ascending (int64 [n]),
+ * order[j] = original row of the j-th smallest id, equal ids in ascending row order -- the layout the two *_sorted calls above
+ * and meant_embedding_bwd_seg read.  An LSD radix sort over 8-bit digits, ceil(bits(V - 1) / 8) passes; the result does not
+ * depend on timing.  ids, sorted_ids and order must not overlap (MEANT_ERR_ARG).  n, V < 2^31 (beyond: MEANT_ERR_UNSUPPORTED).  workspace: meant_sort_ids_ws(n, V) bytes (host arithmetic). */
+size_t meant_sort_ids_ws(int64_t n, int64_t V);
+int meant_sort_ids(const int64_t* ids, int64_t n, int64_t V, int64_t* sorted_ids, int64_t* order, void* workspace,
+                   size_t workspace_bytes, void* stream);
+/* the scatter-add over sorted ids at any d % 8 == 0 (otherwise MEANT_ERR_UNSUPPORTED), rows of ids in [id_lo, id_hi) only, added
+ * into dtable; no float atomics with or without the "deterministic" option: runs of equal ids that cross the 256-entry stretch of
+ * a wave leave partial sums in the workspace, which two small kernels add in a fixed order that depends on the sorted ids alone.
+ * Bit-reproducible for a given (sorted_ids, order, dout); the union over a partition of [0, V) equals one call over [0, V) bit
+ * for bit.  workspace: meant_embedding_bwd_seg_ws(n, d) bytes (host arithmetic), 16-byte aligned. */
+size_t meant_embedding_bwd_seg_ws(int64_t n, int64_t d);
+int meant_embedding_bwd_seg(const void* dout, const int64_t* sorted_ids, const int64_t* order, float* dtable, int64_t n,
+                            int64_t d, int64_t V, int64_t id_lo, int64_t id_hi, int dtype, void* workspace,
+                            size_t workspace_bytes, void* stream);
 
 /* ---- train-step tail ------------------------------------------- in_loop_train.py:232-238,547-548
  * CrossEntropyLoss (mean) applied to the model's probabilities [B, C] as the reference does: loss_accum[0] +=

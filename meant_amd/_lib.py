@@ -86,6 +86,10 @@ SIGNATURES = {
     "meant_adamw_f32": (_i, [_p, _p, _p, _p, _i64, _f, _f, _f, _f, _f, _i64, _p, _f, _f, _p]),
     "meant_embedding_bwd_sorted": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i, _p]),
     "meant_embedding_bwd_sorted_range": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i, _p]),
+    "meant_sort_ids_ws": (_sz, [_i64, _i64]),
+    "meant_sort_ids": (_i, [_p, _i64, _i64, _p, _p, _p, _sz, _p]),
+    "meant_embedding_bwd_seg_ws": (_sz, [_i64, _i64]),
+    "meant_embedding_bwd_seg": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i, _p, _sz, _p]),
     "meant_rmsnorm_partial_fwd": (_i, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _f, _i, _p]),
     "meant_rmsnorm_partial_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _f, _i, _p, _sz, _p]),
     "meant_rmsnorm_stats": (_i, [_p, _p, _i64, _i64, _f, _i, _p]),

@@ -1,0 +1,465 @@
+// Embedding gradient at any width: a stable device sort of the token ids and a segmented reduction over the sorted ids that needs
+// no float atomics ("Embedding gradient at any width").
+//   meant_sort_ids            LSD radix sort over 8-bit digits of the ids clamped into [0, V); equal ids keep their row order
+//   meant_embedding_bwd_seg   dtable[id, :] += sum of the rows of dout that carry id, any d % 8 == 0, bit-reproducible
+#include "common.h"
+
+#define EMB_REQ(c, ...) MEANT_REQUIRE(c, MEANT_ERR_ARG, __VA_ARGS__)
+
+namespace {
+
+// ------------------------------------------------------------------------------------------------
+// The sort.  A tile is 2048 consecutive entries of a pass's input, owned by one workgroup; wave w of it owns entries
+// [512 w, 512 w + 512) and takes them in eight rounds of 64, lane l the l-th of a round, so (tile, wave, round, lane) is the input
+// order.  Per pass:  tile counts [digit][tile]  ->  exclusive scan in (digit, tile) order  ->  stable scatter.  The digit totals of
+// EVERY pass do not depend on the order of the entries: one kernel over the ids counts them all (integer atomics on 4 x 256
+// counters, the only atomics here), together with the tile counts of pass 0.  The tile counts of a later pass are those of the
+// previous pass's output and are counted from it.  Nothing waits on another workgroup and no position comes from an atomic, so the
+// result does not depend on timing.
+constexpr int SORT_TILE = 2048, SORT_WAVE_SPAN = 512, SORT_ROUNDS = 8;
+
+__device__ __forceinline__ uint32_t sort_key(int64_t id, int64_t V) {     // clamped as meant_embedding_fwd clamps
+  return (uint32_t)(id < 0 ? 0 : (id >= V ? V - 1 : id));
+}
+
+// ghist[p][digit] += occurrences of digit p of every key (all passes); tile_hist[digit][tile] = pass 0's tile counts
+__global__ __launch_bounds__(256) void sort_hist_kernel(const int64_t* __restrict__ ids, int64_t n, int64_t V, int passes,
+                                                         uint32_t* __restrict__ ghist, uint32_t* __restrict__ tile_hist, int64_t ntiles) {
+  __shared__ uint32_t h[4][256];
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int p = 0; p < 4; ++p) h[p][tid] = 0;
+  __syncthreads();
+  const int64_t base = (int64_t)blockIdx.x * SORT_TILE;
+  for (int i = 0; i < SORT_TILE / 256; ++i) {
+    const int64_t j = base + i * 256 + tid;
+    if (j < n) {
+      const uint32_t key = sort_key(ids[j], V);
+      for (int p = 0; p < passes; ++p) atomicAdd(&h[p][(key >> (8 * p)) & 255u], 1u);
+    }
+  }
+  __syncthreads();
+  tile_hist[(int64_t)tid * ntiles + blockIdx.x] = h[0][tid];
+  for (int p = 0; p < passes; ++p)
+    if (h[p][tid]) atomicAdd(&ghist[p * 256 + tid], h[p][tid]);
+}
+
+// tile counts of a later pass, from the keys as the previous pass left them
+__global__ __launch_bounds__(256) void sort_count_kernel(const uint32_t* __restrict__ keys, int64_t n, int shift,
+                                                          uint32_t* __restrict__ tile_hist, int64_t ntiles) {
+  __shared__ uint32_t h[256];
+  const int tid = threadIdx.x;
+  h[tid] = 0;
+  __syncthreads();
+  const int64_t base = (int64_t)blockIdx.x * SORT_TILE;
+  for (int i = 0; i < SORT_TILE / 256; ++i) {
+    const int64_t j = base + i * 256 + tid;
+    if (j < n) atomicAdd(&h[(keys[j] >> shift) & 255u], 1u);
+  }
+  __syncthreads();
+  tile_hist[(int64_t)tid * ntiles + blockIdx.x] = h[tid];
+}
+
+// inclusive sum over the 256 threads of a workgroup; *total = the workgroup's sum.  `wsum` is 4 words of LDS; two barriers.
+__device__ __forceinline__ uint32_t block_scan_incl(uint32_t x, uint32_t* wsum, uint32_t* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t y = __shfl_up(x, o, 64);
+    if (lane >= o) x += y;
+  }
+  __syncthreads();                                    // the previous call's readers are done with wsum
+  if (lane == 63) wsum[wave] = x;
+  __syncthreads();
+  uint32_t pre = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const uint32_t s = wsum[w];
+    if (w < wave) pre += s;
+    tot += s;
+  }
+  *total = tot;
+  return x + pre;
+}
+
+// tile_hist[digit][tile] -> first output position of that tile's entries with that digit.  One workgroup per digit: its base is
+// the total of the smaller digits (ghist), then an exclusive scan along the tiles.
+__global__ __launch_bounds__(256) void sort_scan_kernel(const uint32_t* __restrict__ ghist, uint32_t* __restrict__ tile_hist, int64_t ntiles) {
+  __shared__ uint32_t wsum[4];
+  const int tid = threadIdx.x, digit = blockIdx.x;
+  uint32_t carry;
+  block_scan_incl(tid < digit ? ghist[tid] : 0u, wsum, &carry);
+  uint32_t* row = tile_hist + (int64_t)digit * ntiles;
+  for (int64_t t0 = 0; t0 < ntiles; t0 += 256) {
+    const int64_t t = t0 + tid;
+    const uint32_t x = t < ntiles ? row[t] : 0u;
+    uint32_t total;
+    const uint32_t incl = block_scan_incl(x, wsum, &total);
+    if (t < ntiles) row[t] = carry + incl - x;
+    carry += total;
+  }
+}
+
+// stable scatter of one pass.  Rank of an entry among the equal digits of its round: a match mask from eight wave ballots and a
+// population count below the lane; among the earlier rounds of its wave: a running per-wave count in LDS, advanced by the lowest
+// lane of each match group; among the earlier waves and tiles: the scanned counts.
+// FIRST: keys are the clamped ids and the values the row numbers; LAST: the outputs are the caller's int64 arrays.
+template <bool FIRST, bool LAST>
+__global__ __launch_bounds__(256) void sort_scatter_kernel(const int64_t* __restrict__ ids, const uint32_t* __restrict__ kin,
+                                                            const uint32_t* __restrict__ vin, int64_t n, int64_t V, int shift,
+                                                            const uint32_t* __restrict__ tile_off, int64_t ntiles,
+                                                            uint32_t* __restrict__ kout, uint32_t* __restrict__ vout,
+                                                            int64_t* __restrict__ sorted_ids, int64_t* __restrict__ order) {
+  __shared__ uint32_t cnt[4][256];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) cnt[w][tid] = 0;
+  __syncthreads();
+  const int64_t base = (int64_t)blockIdx.x * SORT_TILE + wave * SORT_WAVE_SPAN;
+  uint32_t key[SORT_ROUNDS], val[SORT_ROUNDS], rk[SORT_ROUNDS];
+#pragma unroll
+  for (int r = 0; r < SORT_ROUNDS; ++r) {
+    const int64_t j = base + r * 64 + lane;
+    const bool valid = j < n;
+    key[r] = valid ? (FIRST ? sort_key(ids[j], V) : kin[j]) : 0u;
+    val[r] = valid ? (FIRST ? (uint32_t)j : vin[j]) : 0u;
+    const uint32_t dig = (key[r] >> shift) & 255u;
+    unsigned long long m = __ballot(valid);
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+      const bool bit = (dig >> b) & 1u;
+      const unsigned long long bal = __ballot(valid && bit);
+      m &= bit ? bal : ~bal;
+    }
+    const unsigned long long below = m & ((1ull << lane) - 1ull);
+    rk[r] = valid ? cnt[wave][dig] + (uint32_t)__popcll(below) : 0u;
+    __syncthreads();
+    if (valid && below == 0) cnt[wave][dig] += (uint32_t)__popcll(m);
+    __syncthreads();
+  }
+  {                                                    // per-wave counts of digit `tid` -> first output position of each wave's share
+    uint32_t o = tile_off[(int64_t)tid * ntiles + blockIdx.x];
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const uint32_t c = cnt[w][tid];
+      cnt[w][tid] = o;
+      o += c;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < SORT_ROUNDS; ++r) {
+    const int64_t j = base + r * 64 + lane;
+    if (j >= n) continue;
+    const int64_t pos = (int64_t)cnt[wave][(key[r] >> shift) & 255u] + rk[r];
+    if (pos >= n) continue;                            // cannot happen with consistent counts; never write outside the arrays
+    if (LAST) {
+      sorted_ids[pos] = (int64_t)key[r];
+      order[pos] = (int64_t)val[r];
+    } else {
+      kout[pos] = key[r];
+      vout[pos] = val[r];
+    }
+  }
+}
+
+int sort_passes(int64_t V) {
+  int bits = 0;
+  for (uint64_t m = (uint64_t)(V - 1); m; m >>= 1) ++bits;
+  const int p = (bits + 7) / 8;
+  return p < 1 ? 1 : p;
+}
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+struct SortWs { size_t ghist, tile_hist, buf[2], total; int nbuf; };
+SortWs sort_ws_layout(int64_t n, int64_t V) {
+  SortWs w;
+  const int64_t ntiles = ceil_div(n, SORT_TILE);
+  const int passes = sort_passes(V);
+  w.nbuf = passes - 1 < 2 ? passes - 1 : 2;            // the last pass writes the caller's arrays
+  size_t off = 0;
+  w.ghist = off; off += align256(4 * 256 * sizeof(uint32_t));
+  w.tile_hist = off; off += align256((size_t)ntiles * 256 * sizeof(uint32_t));
+  for (int i = 0; i < 2; ++i) {
+    w.buf[i] = off;
+    if (i < w.nbuf) off += 2 * align256((size_t)n * sizeof(uint32_t));
+  }
+  w.total = off;
+  return w;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The reduction.  As embedding_bwd_sorted_kernel (elementwise.hip): a wave walks a stretch of 256 sorted entries, four rows
+// requested before the first is consumed, and sums a run of equal ids in registers; a run inside the stretch is a plain
+// read-modify-write of its table row.  Two differences.  The width: grid.y cuts the row into column blocks of at most 128 8-column
+// chunks, so a lane still owns two chunks.  The runs that cross the stretch's ends: their partial sums go to the workspace slot
+// [stretch][0] (the run came in from the left) or [stretch][1] (it starts here and leaves to the right), and
+// emb_seg_cross_kernel / emb_seg_long_kernel add each such run's slots in an order that depends on the sorted ids alone.
+constexpr int SEG = 256;
+template <typename T>
+__global__ __launch_bounds__(256) void emb_seg_kernel(const T* __restrict__ dout, const int64_t* __restrict__ sorted_ids,
+                                                       const int64_t* __restrict__ order, float* __restrict__ dtable,
+                                                       float* __restrict__ part, int64_t n, int64_t d, int64_t V, int64_t id_lo,
+                                                       int64_t id_hi, int cb_chunks) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t s = (int64_t)blockIdx.x * 4 + wave;
+  const int64_t j0 = s * SEG;
+  if (j0 >= n) return;
+  const int64_t j1 = j0 + SEG < n ? j0 + SEG : n;
+  if (sorted_ids[j1 - 1] < id_lo || sorted_ids[j0] >= id_hi) return;     // the ids are sorted: a stretch outside the range leaves at once
+  const int c0 = blockIdx.y * cb_chunks;                                   // this column block: chunks [c0, c0 + nch)
+  const int left = (int)(d >> 3) - c0;
+  const int nch = left < cb_chunks ? left : cb_chunks;
+  const bool has0 = lane < nch, has1 = lane + 64 < nch;
+  const int64_t col0 = (int64_t)(c0 + lane) * 8, col1 = (int64_t)(c0 + lane + 64) * 8;
+  float acc0[8], acc1[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) acc0[e] = acc1[e] = 0.f;
+  int64_t cur = sorted_ids[j0];
+  bool open_left = j0 > 0 && sorted_ids[j0 - 1] == cur;                  // the first run started in an earlier stretch
+
+  // slot < 0: the run is this wave's alone
+  auto flush = [&](int64_t id, int slot) {
+    if (id < 0 || id >= V || id < id_lo || id >= id_hi) return;
+    if (slot >= 0) {
+      float* row = part + (s * 2 + slot) * d;
+      Vec8<float> v;
+      if (has0) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v.set(e, acc0[e]);
+        store8<float>(row + col0, v);
+      }
+      if (has1) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v.set(e, acc1[e]);
+        store8<float>(row + col1, v);
+      }
+      return;
+    }
+    float* row = dtable + id * d;
+    if (has0) {
+      Vec8<float> v = load8<float>(row + col0);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v.set(e, v.get(e) + acc0[e]);
+      store8<float>(row + col0, v);
+    }
+    if (has1) {
+      Vec8<float> v = load8<float>(row + col1);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v.set(e, v.get(e) + acc1[e]);
+      store8<float>(row + col1, v);
+    }
+  };
+
+  for (int64_t jb = j0; jb < j1; jb += 64) {
+    const int64_t jl = jb + lane < j1 ? jb + lane : j1 - 1;
+    const long long my_id = sorted_ids[jl], my_ord = order[jl];
+    const int cnt = (int)(j1 - jb < 64 ? j1 - jb : 64);
+    for (int t0 = 0; t0 < cnt; t0 += 4) {
+      Vec8<T> r0[4], r1[4];
+      long long ids4[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int t = t0 + u < cnt ? t0 + u : cnt - 1;
+        ids4[u] = __shfl(my_id, t, 64);
+        const long long ord = __shfl(my_ord, t, 64);
+        const bool row_ok = ord >= 0 && ord < n;        // an order that is no permutation must not become an address
+        const T* src = dout + (row_ok ? ord : 0) * d;
+        r0[u] = Vec8<T>{};
+        r1[u] = Vec8<T>{};
+        if (has0 && row_ok) r0[u] = load8s<T>(src + col0);
+        if (has1 && row_ok) r1[u] = load8s<T>(src + col1);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (t0 + u >= cnt) break;
+        const int64_t id = ids4[u];
+        if (id != cur) {
+          flush(cur, open_left ? 0 : -1);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) acc0[e] = acc1[e] = 0.f;
+          cur = id;
+          open_left = false;
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          if (has0) acc0[e] += r0[u].get(e);
+          if (has1) acc1[e] += r1[u].get(e);
+        }
+      }
+    }
+  }
+  const bool open_right = j1 < n && sorted_ids[j1] == cur;
+  flush(cur, open_left ? 0 : (open_right ? 1 : -1));
+}
+
+// The runs that cross stretch ends.  A run belongs to the stretch it STARTS in: its partial sums are slot 1 of that stretch and
+// slot 0 of every following stretch that begins with the same id (sorted ids: a contiguous range).
+// Short lists (at most SEG_SHORT partials; two for a typical id): one wave per (stretch, 256 columns) adds them in stretch order and
+// adds the sum to the table row.  It also leaves the list's length in longk[stretch] where the list is longer (0 otherwise), for
+// the kernel below.
+constexpr int SEG_SHORT = 16;
+__global__ __launch_bounds__(256) void emb_seg_cross_kernel(const int64_t* __restrict__ sorted_ids, const float* __restrict__ part,
+                                                             int* __restrict__ longk, float* __restrict__ dtable, int64_t n, int64_t d,
+                                                             int64_t V, int64_t id_lo, int64_t id_hi) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t s = (int64_t)blockIdx.x * 4 + wave, j0 = s * SEG, j1 = j0 + SEG;
+  if (j1 >= n) return;                                                    // the last stretch has nothing to its right (and no longk slot)
+  const int64_t id = sorted_ids[j1 - 1];
+  const bool owner = sorted_ids[j1] == id && !(j0 > 0 && sorted_ids[j0 - 1] == id)      // leaves to the right, did not come in from the left
+                     && id >= 0 && id < V && id >= id_lo && id < id_hi;
+  int64_t K = 0;
+  if (owner) {                                                            // wave-uniform
+    const int64_t nst = (n + SEG - 1) / SEG;
+    int64_t follow = 0;
+    for (int64_t t0 = s + 1;; t0 += 64) {
+      const int64_t t = t0 + lane;
+      const int k = __popcll(__ballot(t < nst && sorted_ids[t * SEG] == id));
+      follow += k;
+      if (k < 64) break;
+    }
+    K = follow + 1;
+  }
+  if (blockIdx.y == 0 && lane == 0) longk[s] = K > SEG_SHORT ? (int)K : 0;
+  if (K == 0 || K > SEG_SHORT) return;
+  const int64_t col = (int64_t)blockIdx.y * 256 + lane * 4;
+  if (col >= d) return;
+  f32x4 acc = *reinterpret_cast<const f32x4*>(part + (s * 2 + 1) * d + col);
+  for (int64_t k = 1; k < K; ++k) acc += *reinterpret_cast<const f32x4*>(part + (s + k) * 2 * d + col);
+  f32x4* dst = reinterpret_cast<f32x4*>(dtable + id * d + col);
+  *dst = *dst + acc;
+}
+
+// Long lists (a padding id: one partial per stretch it covers).  One workgroup per (stretch, 64 columns), at work only where
+// longk says so.  The list is cut into 16 equal pieces (a cut that depends on its length alone), 16 threads with 4 columns each sum
+// a piece in order, and the 16 pieces are added as a fixed binary tree: the sum depends on the sorted ids and the rows, on nothing else.
+__global__ __launch_bounds__(256) void emb_seg_long_kernel(const int64_t* __restrict__ sorted_ids, const float* __restrict__ part,
+                                                            const int* __restrict__ longk, float* __restrict__ dtable, int64_t d) {
+  __shared__ f32x4 red[16][16];
+  const int tid = threadIdx.x;
+  const int64_t s = blockIdx.x;
+  const int64_t K = longk[s];
+  if (K == 0) return;                                                     // uniform over the workgroup
+  const int64_t id = sorted_ids[s * SEG + SEG - 1];                       // in range: emb_seg_cross_kernel checked it
+  const int p = tid >> 4;
+  const int64_t col = (int64_t)blockIdx.y * 64 + (tid & 15) * 4;
+  const bool active = col < d;
+  const int64_t piece = (K + 15) / 16, k0 = p * piece, k1 = k0 + piece < K ? k0 + piece : K;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  if (active) {
+#pragma unroll 4
+    for (int64_t k = k0; k < k1; ++k) {
+      const float* row = k == 0 ? part + (s * 2 + 1) * d : part + (s + k) * 2 * d;
+      acc += *reinterpret_cast<const f32x4*>(row + col);
+    }
+  }
+  red[p][tid & 15] = acc;
+  __syncthreads();
+#pragma unroll
+  for (int h = 8; h > 0; h >>= 1) {
+    if (p < h) red[p][tid & 15] += red[p + h][tid & 15];
+    __syncthreads();
+  }
+  if (p == 0 && active) {
+    f32x4* dst = reinterpret_cast<f32x4*>(dtable + id * d + col);
+    *dst = *dst + red[0][tid & 15];
+  }
+}
+
+size_t seg_part_bytes(int64_t n, int64_t d) { return (size_t)ceil_div(n, SEG) * 2 * (size_t)d * sizeof(float); }
+
+}  // namespace
+
+extern "C" size_t meant_sort_ids_ws(int64_t n, int64_t V) {
+  if (n <= 0 || V <= 0 || n >= (1ll << 31) || V >= (1ll << 31)) return 0;
+  return sort_ws_layout(n, V).total;
+}
+
+extern "C" int meant_sort_ids(const int64_t* ids, int64_t n, int64_t V, int64_t* sorted_ids, int64_t* order, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+  EMB_REQ(ids && sorted_ids && order && n > 0 && V > 0, "sort_ids: bad argument");
+  MEANT_REQUIRE(n < (1ll << 31) && V < (1ll << 31), MEANT_ERR_UNSUPPORTED, "sort_ids: n=%lld and V=%lld must be below 2^31", (long long)n,
+                (long long)V);
+  // not in place: the first pass still reads ids while the last may already write the outputs (one pass: the same kernel)
+  {
+    const char *a = (const char*)ids, *o1 = (const char*)sorted_ids, *o2 = (const char*)order;
+    const size_t len = (size_t)n * sizeof(int64_t);
+    const auto overlap = [len](const char* x, const char* y) { return x < y + len && y < x + len; };
+    EMB_REQ(!overlap(a, o1) && !overlap(a, o2) && !overlap(o1, o2), "sort_ids: ids, sorted_ids and order must not overlap");
+  }
+  const SortWs w = sort_ws_layout(n, V);
+  MEANT_REQUIRE(workspace && workspace_bytes >= w.total, MEANT_ERR_WORKSPACE, "sort_ids: workspace of %zu bytes needed, %zu given", w.total, workspace_bytes);
+  EMB_REQ((reinterpret_cast<uintptr_t>(workspace) & 3) == 0, "sort_ids: 4-byte workspace alignment");
+  hipStream_t st = (hipStream_t)stream;
+  char* base = (char*)workspace;
+  uint32_t* ghist = (uint32_t*)(base + w.ghist);
+  uint32_t* tile_hist = (uint32_t*)(base + w.tile_hist);
+  uint32_t* bk[2] = {nullptr, nullptr};
+  uint32_t* bv[2] = {nullptr, nullptr};
+  for (int i = 0; i < w.nbuf; ++i) {
+    bk[i] = (uint32_t*)(base + w.buf[i]);
+    bv[i] = (uint32_t*)(base + w.buf[i] + align256((size_t)n * sizeof(uint32_t)));
+  }
+  const int64_t ntiles = ceil_div(n, SORT_TILE);
+  const int passes = sort_passes(V);
+  const dim3 grid((unsigned)ntiles), block(256);
+  const hipError_t e = hipMemsetAsync(ghist, 0, 4 * 256 * sizeof(uint32_t), st);
+  MEANT_REQUIRE(e == hipSuccess, MEANT_ERR_LAUNCH, "sort_ids: clearing the digit counters failed: %s", hipGetErrorString(e));
+  hipLaunchKernelGGL(sort_hist_kernel, grid, block, 0, st, ids, n, V, passes, ghist, tile_hist, ntiles);
+  for (int p = 0; p < passes; ++p) {
+    const bool first = p == 0, last = p == passes - 1;
+    const uint32_t* kin = first ? nullptr : bk[(p - 1) & 1];
+    const uint32_t* vin = first ? nullptr : bv[(p - 1) & 1];
+    uint32_t* kout = last ? nullptr : bk[p & 1];
+    uint32_t* vout = last ? nullptr : bv[p & 1];
+    const int shift = 8 * p;
+    if (!first) hipLaunchKernelGGL(sort_count_kernel, grid, block, 0, st, kin, n, shift, tile_hist, ntiles);
+    hipLaunchKernelGGL(sort_scan_kernel, dim3(256), block, 0, st, (const uint32_t*)(ghist + p * 256), tile_hist, ntiles);
+#define SORT_SCATTER(F, L)                                                                                                     \
+  hipLaunchKernelGGL((sort_scatter_kernel<F, L>), grid, block, 0, st, ids, kin, vin, n, V, shift, (const uint32_t*)tile_hist, \
+                     ntiles, kout, vout, sorted_ids, order)
+    if (first && last) SORT_SCATTER(true, true);
+    else if (first) SORT_SCATTER(true, false);
+    else if (last) SORT_SCATTER(false, true);
+    else SORT_SCATTER(false, false);
+#undef SORT_SCATTER
+  }
+  MEANT_LAUNCH_CHECK("sort_ids");
+  meant_route_hit(ROUTE_SORT_IDS);
+  return MEANT_OK;
+}
+
+extern "C" size_t meant_embedding_bwd_seg_ws(int64_t n, int64_t d) {
+  if (n <= 0 || d <= 0) return 0;
+  return seg_part_bytes(n, d) + align256((size_t)ceil_div(n, SEG) * sizeof(int));      // partial sums [stretch][2][d], then longk [stretch]
+}
+
+extern "C" int meant_embedding_bwd_seg(const void* dout, const int64_t* sorted_ids, const int64_t* order, float* dtable, int64_t n,
+                                       int64_t d, int64_t V, int64_t id_lo, int64_t id_hi, int dtype, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+  EMB_REQ(dout && sorted_ids && order && dtable && n > 0 && d > 0 && V > 0 && 0 <= id_lo && id_lo <= id_hi && id_hi <= V,
+          "embedding_bwd_seg: bad argument");
+  MEANT_REQUIRE(d % 8 == 0, MEANT_ERR_UNSUPPORTED, "embedding_bwd_seg: d=%lld must be a multiple of 8", (long long)d);
+  MEANT_REQUIRE(d < (1ll << 22), MEANT_ERR_UNSUPPORTED, "embedding_bwd_seg: d=%lld is beyond the launch grid (d < 2^22)", (long long)d);
+  const size_t need = meant_embedding_bwd_seg_ws(n, d);
+  MEANT_REQUIRE(workspace && workspace_bytes >= need, MEANT_ERR_WORKSPACE, "embedding_bwd_seg: workspace of %zu bytes needed, %zu given", need, workspace_bytes);
+  EMB_REQ(meant_aligned16(dout) && meant_aligned16(dtable) && meant_aligned16(workspace), "embedding_bwd_seg: 16-byte alignment");
+  if (id_lo == id_hi) return MEANT_OK;
+  const int64_t nst = ceil_div(n, SEG);
+  const int chunks = (int)(d >> 3);
+  const int ncb = (int)ceil_div(chunks, 128);
+  const int cb_chunks = (int)ceil_div(chunks, ncb);
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH_DTYPE(dtype, T,
+                 hipLaunchKernelGGL(emb_seg_kernel<T>, dim3((unsigned)ceil_div(nst, 4), (unsigned)ncb), dim3(256), 0, st, (const T*)dout,
+                                    sorted_ids, order, dtable, (float*)workspace, n, d, V, id_lo, id_hi, cb_chunks));
+  if (nst > 1) {
+    int* longk = (int*)((char*)workspace + seg_part_bytes(n, d));
+    hipLaunchKernelGGL(emb_seg_cross_kernel, dim3((unsigned)ceil_div(nst - 1, 4), (unsigned)ceil_div(d, 256)), dim3(256), 0, st, sorted_ids,
+                       (const float*)workspace, longk, dtable, n, d, V, id_lo, id_hi);
+    hipLaunchKernelGGL(emb_seg_long_kernel, dim3((unsigned)(nst - 1), (unsigned)ceil_div(d, 64)), dim3(256), 0, st, sorted_ids,
+                       (const float*)workspace, (const int*)longk, dtable, d);
+  }
+  MEANT_LAUNCH_CHECK("embedding_bwd_seg");
+  meant_route_hit(ROUTE_EMB_SEG);
+  return MEANT_OK;
+}

@@ -1291,6 +1291,33 @@ def _emb_sorted_bwd_ok(n: int, d: int) -> bool:
     return d <= 1024 and d % 8 == 0 and (n >= 4096 or bool(_lib_option("deterministic")))
 
 
+def _emb_seg_bwd_ok(n: int, d: int) -> bool:
+    """shapes meant_embedding_bwd_seg takes: any width that is a multiple of 8 (enough tokens for a sort to pay, or the promise of
+    option "deterministic" to keep)"""
+    return d % 8 == 0 and (n >= 4096 or bool(_lib_option("deterministic")))
+
+
+def _emb_bwd_route(n: int, d: int) -> str:
+    """which kernel sums the embedding gradient: "seg" (meant_embedding_bwd_seg: every width above the sorted kernel's 1024, with or
+    without option "deterministic" -- no float atomics, a hot id spread over the chip), "sorted" (meant_embedding_bwd_sorted:
+    d <= 1024; under "deterministic" its follow-the-run branch, which the segmented reduction did not beat on uniform ids --
+    DESIGN section 6, "Embedding gradient at any width") or "atomic" (meant_embedding_bwd: few tokens, or d % 8 != 0)"""
+    if _emb_seg_bwd_ok(n, d) and d > 1024:
+        return "seg"
+    return "sorted" if _emb_sorted_bwd_ok(n, d) else "atomic"
+
+
+def _sort_ids(ids_flat: torch.Tensor, V: int):
+    """(sorted ids, order) on the current stream: meant_sort_ids, the library's stable radix sort of the clamped ids (equal ids keep
+    their row order, so the order of every sum is the library's own; 7 launches and 0.06 ms at 786 k ids against torch.sort's 23 and 0.2)"""
+    n = ids_flat.numel()
+    sorted_ids, order = torch.empty_like(ids_flat), torch.empty_like(ids_flat)
+    wsb = lib.meant_sort_ids_ws(n, V)
+    ws = torch.empty(wsb, device=ids_flat.device, dtype=torch.uint8)
+    check(lib.meant_sort_ids(_p(ids_flat), n, V, _p(sorted_ids), _p(order), _p(ws), wsb, _stream()), "sort_ids")
+    return sorted_ids, order
+
+
 class _Embedding(torch.autograd.Function):
     """nn.Embedding lookup (meant/meant.py:211) emitting the compute dtype directly."""
 
@@ -1312,16 +1339,17 @@ class _Embedding(torch.autograd.Function):
             tf = _c(table.detach().float())
             check(lib.meant_embedding_fwd(_p(tf), _p(ids_c), _p(out), n, d, V, F32 if dtype == torch.float32 else BF16, _stream()),
                   "embedding_fwd")
-        # The backward sums rows in the order of the sorted ids.  The sort (a radix block sort + ~20 merge launches, 0.2 ms of
-        # kernels that do not fill the chip) used to run in backward, where the embedding's gradient is the very last thing
+        # The backward sums rows in the order of the sorted ids.  The sort (meant_sort_ids: 7 small launches, kernels that do not
+        # fill the chip) used to run in backward, where the embedding's gradient is the very last thing
         # of the step; the ids are known now, so it runs here on a side stream, beside the forward's big kernels.
         presort = None
-        if EMB_PRESORT and ctx.needs_input_grad[1] and _emb_sorted_bwd_ok(n, d):
+        route = _emb_bwd_route(n, d)
+        if EMB_PRESORT and ctx.needs_input_grad[1] and route != "atomic":
             main = torch.cuda.current_stream(ids_c.device)
             side = _aux_stream(ids_c.device)
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                sorted_ids, order = torch.sort(ids_c.view(-1))
+                sorted_ids, order = _sort_ids(ids_c.view(-1), V)
                 ev = torch.cuda.Event()
                 ev.record(side)
             presort = (sorted_ids, order, ev)
@@ -1345,7 +1373,8 @@ class _Embedding(torch.autograd.Function):
             sink = None
         dtab = sink.view if sink is not None else torch.zeros((V, d), device=dout.device, dtype=torch.float32)
         n = ids_c.numel()
-        if _emb_sorted_bwd_ok(n, d):                     # the other kernel is float atomics per token
+        route = _emb_bwd_route(n, d)
+        if route != "atomic":                            # the other kernel is float atomics per token
             # index preparation (a sort of the token ids) is host-side plumbing; the reduction itself is the HIP kernel
             if ctx.presort is not None:
                 sorted_ids, order, ev = ctx.presort
@@ -1354,9 +1383,20 @@ class _Embedding(torch.autograd.Function):
                 sorted_ids.record_stream(cur)            # allocated on the side stream, read on this one
                 order.record_stream(cur)
             else:
-                sorted_ids, order = torch.sort(ids_c.view(-1))
+                sorted_ids, order = _sort_ids(ids_c.view(-1), V)
             nsl = sink.row_slices(ctx.table) if sink is not None else 1
-            if nsl > 1:
+            if route == "seg":
+                wsb = lib.meant_embedding_bwd_seg_ws(n, d)
+                ws = torch.empty(wsb, device=dout.device, dtype=torch.uint8)
+                for c in range(nsl):                     # row slices as below; one slice is the whole table
+                    lo, hi = V * c // nsl, V * (c + 1) // nsl
+                    check(lib.meant_embedding_bwd_seg(_p(dout), _p(sorted_ids), _p(order), _p(dtab), n, d, V, lo, hi, _dt(dout), _p(ws), wsb,
+                                                      _stream()), "embedding_bwd_seg")
+                    if nsl > 1:
+                        sink.report_rows(ctx.table, lo, hi, c == nsl - 1)
+                if nsl > 1:
+                    return None, None, None
+            elif nsl > 1:
                 # data parallel: the table's gradient is the last thing backward produces and two thirds of the bytes to reduce.
                 # It is summed in row slices; each slice's all-reduce starts while the next slice is being summed
                 for c in range(nsl):
@@ -1365,8 +1405,9 @@ class _Embedding(torch.autograd.Function):
                                                                _stream()), "embedding_bwd_sorted_range")
                     sink.report_rows(ctx.table, lo, hi, c == nsl - 1)
                 return None, None, None
-            check(lib.meant_embedding_bwd_sorted(_p(dout), _p(sorted_ids), _p(order), _p(dtab), n, d, V, _dt(dout), _stream()),
-                  "embedding_bwd_sorted")
+            else:
+                check(lib.meant_embedding_bwd_sorted(_p(dout), _p(sorted_ids), _p(order), _p(dtab), n, d, V, _dt(dout), _stream()),
+                      "embedding_bwd_sorted")
         else:
             check(lib.meant_embedding_bwd(_p(dout), _p(ids_c), _p(dtab), n, d, V, _dt(dout), _stream()), "embedding_bwd")
         if sink is not None:
