@@ -2,10 +2,24 @@
 #include "internal.h"
 
 // preconditions of the MFMA bf16 NT kernel (global_load_lds moves 16-byte pieces; vector epilogue stores)
-static bool bf16_nt_ok(const void* a, int64_t lda, const void* b, int64_t ldb, const void* c, int64_t ldc, const void* r,
-                       int64_t ldr, int64_t K) {
-  (void)c; (void)ldc; (void)r; (void)ldr;
+static bool bf16_nt_ok(const void* a, int64_t lda, const void* b, int64_t ldb, int64_t K) {
   return (K % 64) == 0 && (lda % 8) == 0 && (ldb % 8) == 0 && meant_aligned16(a) && meant_aligned16(b);
+}
+
+// the exact-f32 GEMM on row-major operands, C[M,N] = A B^T with A [M,K] and B [N,K] ("NT": Linear forward and input gradient), or
+// C[M,N] += A^T B with A [K,M] and B [K,N] ("TN": the weight gradient).  `storage`: dtype of A and B; C takes it too in the NT form
+// and is float in the TN form.  The caller adds bias / residual / epilogue.
+static GemmF32Args f32_rowmajor(bool tn, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int64_t M, int64_t N,
+                                int64_t K, int storage) {
+  GemmF32Args a{};
+  a.in_dtype = storage; a.out_dtype = tn ? MEANT_F32 : storage;
+  a.A = A; a.B = B; a.C = C;
+  a.M = M; a.N = N; a.K = K; a.nb1 = 1; a.nb2 = 1;
+  a.sA[2] = tn ? 1 : lda; a.sA[3] = tn ? lda : 1;
+  a.sB[2] = tn ? ldb : 1; a.sB[3] = tn ? 1 : ldb;
+  a.sC[2] = ldc; a.sC[3] = 1;
+  a.alpha = 1.f; a.accumulate = tn ? 1 : 0;
+  return a;
 }
 
 extern "C" int meant_linear_fwd(const void* x, int64_t ldx, const void* w, const float* bias, const void* residual, int64_t ldr,
@@ -15,24 +29,12 @@ extern "C" int meant_linear_fwd(const void* x, int64_t ldx, const void* w, const
   MEANT_REQUIRE(M > 0 && N > 0 && K > 0 && ldx >= K && ldy >= N, MEANT_ERR_ARG, "linear_fwd: bad shape M=%lld N=%lld K=%lld", (long long)M, (long long)N, (long long)K);
   MEANT_REQUIRE(!(epilogue & MEANT_EPI_RESIDUAL) || residual, MEANT_ERR_ARG, "linear_fwd: residual epilogue without residual pointer");
   if (!(epilogue & MEANT_EPI_RESIDUAL)) residual = nullptr;
-  if (dtype == MEANT_F32) {
-    MEANT_REQUIRE(!residual || ldr == ldy, MEANT_ERR_UNSUPPORTED, "linear_fwd(f32): residual stride must equal output stride");
-    GemmF32Args a{};
-    a.A = x; a.B = w; a.C = y;
-    a.M = M; a.N = N; a.K = K; a.nb1 = 1; a.nb2 = 1;
-    a.sA[2] = ldx; a.sA[3] = 1; a.sB[2] = 1; a.sB[3] = K; a.sC[2] = ldy; a.sC[3] = 1;
-    a.alpha = 1.f; a.bias = bias; a.residual = residual; a.preact = preact; a.epilogue = epilogue;
-    return gemm_f32_launch(a, (hipStream_t)stream);
-  }
-  if (dtype == MEANT_BF16 && !bf16_nt_ok(x, ldx, w, K, y, ldy, residual, ldr, K)) {
-    // odd shapes (K not a multiple of 64, unaligned rows: e.g. the class head): exact-f32 generic path on bf16 storage
-    MEANT_REQUIRE(!residual || ldr == ldy, MEANT_ERR_UNSUPPORTED, "linear_fwd(bf16 generic): residual stride must equal output stride");
-    GemmF32Args a{};
-    a.in_dtype = MEANT_BF16; a.out_dtype = MEANT_BF16;
-    a.A = x; a.B = w; a.C = y;
-    a.M = M; a.N = N; a.K = K; a.nb1 = 1; a.nb2 = 1;
-    a.sA[2] = ldx; a.sA[3] = 1; a.sB[2] = 1; a.sB[3] = K; a.sC[2] = ldy; a.sC[3] = 1;
-    a.alpha = 1.f; a.bias = bias; a.residual = residual; a.preact = preact; a.epilogue = epilogue;
+  // bf16 at odd shapes (K not a multiple of 64, unaligned rows: e.g. the class head): the exact-f32 path on bf16 storage
+  if (dtype == MEANT_F32 || (dtype == MEANT_BF16 && !bf16_nt_ok(x, ldx, w, K, K))) {
+    MEANT_REQUIRE(!residual || ldr == ldy, MEANT_ERR_UNSUPPORTED, "linear_fwd(%s): residual stride must equal output stride",
+                  dtype == MEANT_F32 ? "f32" : "bf16 generic");
+    GemmF32Args a = f32_rowmajor(false, x, ldx, w, K, y, ldy, M, N, K, dtype);
+    a.bias = bias; a.residual = residual; a.preact = preact; a.epilogue = epilogue;
     return gemm_f32_launch(a, (hipStream_t)stream);
   }
   if (dtype == MEANT_BF16) {
@@ -55,7 +57,7 @@ extern "C" int meant_qkv_proj_fwd(const void* x, int64_t ldx, const void* w, con
   const bool rot = qa != nullptr;
   MEANT_REQUIRE(!rot || (qb && ka && kb && R > 0 && R % 2 == 0 && R <= Dh), MEANT_ERR_ARG, "qkv_proj_fwd: bad rotary tables");
   const int64_t D = (int64_t)H * Dh, N = 3 * D;
-  const bool fused = rot && dtype == MEANT_BF16 && bf16_nt_ok(x, ldx, w, K, qkv, N, nullptr, 0, K) && Dh % 8 == 0 && R % 8 == 0;
+  const bool fused = rot && dtype == MEANT_BF16 && bf16_nt_ok(x, ldx, w, K, K) && Dh % 8 == 0 && R % 8 == 0;
   if (fused) {
     GemmBf16Args a{};
     a.A = (const bf16*)x; a.lda = ldx; a.B = (const bf16*)w; a.ldb = K; a.C = (bf16*)qkv; a.ldc = N;
@@ -73,23 +75,8 @@ extern "C" int meant_linear_bwd_dx(const void* dy, int64_t lddy, const void* wT,
                                    int64_t K, int dtype, void* stream) {
   MEANT_REQUIRE(dy && wT && dx, MEANT_ERR_ARG, "linear_bwd_dx: null pointer");
   MEANT_REQUIRE(M > 0 && N > 0 && K > 0 && lddy >= N && lddx >= K, MEANT_ERR_ARG, "linear_bwd_dx: bad shape");
-  if (dtype == MEANT_F32) {
-    GemmF32Args a{};
-    a.A = dy; a.B = wT; a.C = dx;
-    a.M = M; a.N = K; a.K = N; a.nb1 = 1; a.nb2 = 1;
-    a.sA[2] = lddy; a.sA[3] = 1; a.sB[2] = 1; a.sB[3] = N; a.sC[2] = lddx; a.sC[3] = 1;
-    a.alpha = 1.f;
-    return gemm_f32_launch(a, (hipStream_t)stream);
-  }
-  if (dtype == MEANT_BF16 && !bf16_nt_ok(dy, lddy, wT, N, dx, lddx, nullptr, 0, N)) {
-    GemmF32Args a{};
-    a.in_dtype = MEANT_BF16; a.out_dtype = MEANT_BF16;
-    a.A = dy; a.B = wT; a.C = dx;
-    a.M = M; a.N = K; a.K = N; a.nb1 = 1; a.nb2 = 1;
-    a.sA[2] = lddy; a.sA[3] = 1; a.sB[2] = 1; a.sB[3] = N; a.sC[2] = lddx; a.sC[3] = 1;
-    a.alpha = 1.f;
-    return gemm_f32_launch(a, (hipStream_t)stream);
-  }
+  if (dtype == MEANT_F32 || (dtype == MEANT_BF16 && !bf16_nt_ok(dy, lddy, wT, N, N)))
+    return gemm_f32_launch(f32_rowmajor(false, dy, lddy, wT, N, dx, lddx, M, K, N, dtype), (hipStream_t)stream);
   if (dtype == MEANT_BF16) {
     GemmBf16Args a{};
     a.A = (const bf16*)dy; a.lda = lddy; a.B = (const bf16*)wT; a.ldb = N; a.C = (bf16*)dx; a.ldc = lddx;
@@ -109,7 +96,7 @@ extern "C" int meant_linear_fwd_rowscale(const void* x, int64_t ldx, const void*
                                          int64_t K, int epilogue, int dtype, void* stream) {
   MEANT_REQUIRE(x && w && y && row_scale, MEANT_ERR_ARG, "linear_fwd_rowscale: null pointer");
   MEANT_REQUIRE(M > 0 && N > 0 && K > 0 && ldx >= K && ldy >= N, MEANT_ERR_ARG, "linear_fwd_rowscale: bad shape");
-  MEANT_REQUIRE(dtype == MEANT_BF16 && bf16_nt_ok(x, ldx, w, K, y, ldy, residual, ldr, K) && (ldy & 7) == 0 && !(epilogue & MEANT_EPI_SIGMOID),
+  MEANT_REQUIRE(dtype == MEANT_BF16 && bf16_nt_ok(x, ldx, w, K, K) && (ldy & 7) == 0 && !(epilogue & MEANT_EPI_SIGMOID),
                 MEANT_ERR_UNSUPPORTED, "linear_fwd_rowscale: bf16 tier, K %% 64 == 0, 16-byte aligned rows only");
   MEANT_REQUIRE(!(epilogue & MEANT_EPI_RESIDUAL) || residual, MEANT_ERR_ARG, "linear_fwd_rowscale: residual epilogue without residual pointer");
   GemmBf16Args a{};
@@ -126,7 +113,7 @@ extern "C" int meant_linear_bwd_dx_norm(const void* dy_scaled, int64_t lddy, con
                                         int64_t M, int64_t N, int64_t K, int dtype, void* stream) {
   MEANT_REQUIRE(dy_scaled && wT && x && coef && dx, MEANT_ERR_ARG, "linear_bwd_dx_norm: null pointer");
   MEANT_REQUIRE(M > 0 && N > 0 && K > 0 && lddy >= N && lddx >= K && ldx >= K, MEANT_ERR_ARG, "linear_bwd_dx_norm: bad shape");
-  MEANT_REQUIRE(dtype == MEANT_BF16 && bf16_nt_ok(dy_scaled, lddy, wT, N, dx, lddx, nullptr, 0, N) && (lddx & 7) == 0 && (ldx & 7) == 0 &&
+  MEANT_REQUIRE(dtype == MEANT_BF16 && bf16_nt_ok(dy_scaled, lddy, wT, N, N) && (lddx & 7) == 0 && (ldx & 7) == 0 &&
                 meant_aligned16(x) && (!dres || ((lddres & 7) == 0 && meant_aligned16(dres))),
                 MEANT_ERR_UNSUPPORTED, "linear_bwd_dx_norm: bf16 tier, N %% 64 == 0, 16-byte aligned rows only");
   GemmBf16Args a{};
@@ -149,27 +136,10 @@ extern "C" int meant_linear_bwd_dw(const void* dy, int64_t lddy, const void* x, 
                                    int64_t N, int64_t K, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
   MEANT_REQUIRE(dy && x && dw, MEANT_ERR_ARG, "linear_bwd_dw: null pointer");
   MEANT_REQUIRE(M > 0 && N > 0 && K > 0 && lddy >= N && ldx >= K, MEANT_ERR_ARG, "linear_bwd_dw: bad shape");
-  if (dtype == MEANT_F32) {
-    GemmF32Args a{};
-    a.A = dy; a.B = x; a.C = dw;
-    a.M = N; a.N = K; a.K = M; a.nb1 = 1; a.nb2 = 1;
-    a.sA[2] = 1; a.sA[3] = lddy; a.sB[2] = ldx; a.sB[3] = 1; a.sC[2] = K; a.sC[3] = 1;
-    a.alpha = 1.f; a.accumulate = 1;
-    int rc = gemm_f32_launch(a, (hipStream_t)stream);
+  if (dtype == MEANT_F32 || (dtype == MEANT_BF16 && (N < 8 || K < 8 || (lddy & 7) || (ldx & 7) || !meant_aligned16(dy) || !meant_aligned16(x)))) {
+    int rc = gemm_f32_launch(f32_rowmajor(true, dy, lddy, x, ldx, dw, K, N, K, M, dtype), (hipStream_t)stream);
     if (rc) return rc;
-    if (dbias) return colsum_launch(dy, lddy, dbias, M, N, MEANT_F32, 1, (hipStream_t)stream);
-    return MEANT_OK;
-  }
-  if (dtype == MEANT_BF16 && (N < 8 || K < 8 || (lddy & 7) || (ldx & 7) || !meant_aligned16(dy) || !meant_aligned16(x))) {
-    GemmF32Args a{};
-    a.in_dtype = MEANT_BF16; a.out_dtype = MEANT_F32;
-    a.A = dy; a.B = x; a.C = dw;
-    a.M = N; a.N = K; a.K = M; a.nb1 = 1; a.nb2 = 1;
-    a.sA[2] = 1; a.sA[3] = lddy; a.sB[2] = ldx; a.sB[3] = 1; a.sC[2] = K; a.sC[3] = 1;
-    a.alpha = 1.f; a.accumulate = 1;
-    int rc = gemm_f32_launch(a, (hipStream_t)stream);
-    if (rc) return rc;
-    if (dbias) return colsum_launch(dy, lddy, dbias, M, N, MEANT_BF16, 1, (hipStream_t)stream);
+    if (dbias) return colsum_launch(dy, lddy, dbias, M, N, dtype, 1, (hipStream_t)stream);
     return MEANT_OK;
   }
   if (dtype == MEANT_BF16)

@@ -871,40 +871,96 @@ __global__ __launch_bounds__(256, HD_ <= 96 ? 2 : 1) void attn_bwd_dkv_kernel(Bw
   ATTN_PAIR_LOOP_H(a.nblk, false, H * NSPLIT)
 }
 
-constexpr int BWD_DKV_LDS = 4 * TILE_B + 2 * 4 * 64 * 4 + 4 * 32 * 144;
-constexpr int FWD_LDS = 4 * TILE_B + 2 * 64 * 4 + 4 * 32 * 144;
-// head dim 128 (NH = 2): twice the tile space, the output patches live in it (2 workgroups per CU by LDS)
-constexpr int BWD_DKV_LDS2 = 8 * TILE_B + 2 * 4 * 64 * 4;
-constexpr int FWD_LDS2 = 8 * TILE_B + 2 * 64 * 4;
-// head dims 160, 192, 256 (NH = 3, 3, 4 sub-tiles): double-buffered K|V (Q|dO) tiles of 96 / 128 KiB plus the bias (stats)
-// rows, the output patches in the tile space; one workgroup per CU
-constexpr int wide_fwd_lds(int HD) { return 2 * 2 * ((HD + 63) / 64) * TILE_B + 2 * 64 * 4; }
-constexpr int wide_dkv_lds(int HD) { return 2 * 2 * ((HD + 63) / 64) * TILE_B + 2 * 4 * 64 * 4; }
-static_assert(wide_dkv_lds(256) <= 160 * 1024, "LDS budget");
-__host__ inline bool wide_dh(int Dh) { return Dh == 160 || Dh == 192 || Dh == 256; }
-__host__ inline bool native_dh(int Dh) { return Dh == 64 || Dh == 96 || Dh == 128 || wide_dh(Dh); }
+// ---- host side ----------------------------------------------------------------------------------------------------------------
+// Head dims 64, 96, 128, 160, 192 and 256 run on the MFMA kernels above (the wider ones as two to four 64-column sub-tiles of
+// every tile, 96 and 160 with a 32-column last one).  The host side pads other head dims below 256 that are multiples of 8
+// up to the next of these with zero columns (meant_amd/ops.py), so this is what they run on too.  Anything else handed to the C ABI directly takes a widening detour: bf16 -> f32
+// copies in the workspace, the fp32 attention core, f32 -> bf16.  Correct for any Dh, not fast.
+__host__ inline bool native_dh(int Dh) { return Dh == 64 || Dh == 96 || Dh == 128 || Dh == 160 || Dh == 192 || Dh == 256; }
 
-// dK/dV column split: head dim 256 only (see attn_bwd_dkv_kernel)
-template <int HD> constexpr int dkv_split() { return HD == 256 ? 2 : 1; }
+// What the launches need to know of a head dim.  Dynamic LDS: NH = ceil(HD / 64) sub-tiles per operand tile, double-buffered K|V
+// (Q|dO) tiles plus the bias (stats) rows; the output patches live in the tile space except at 64, which has room for its own
+// beside 3 (2) workgroups per CU.  96 / 128 hold two workgroups per CU by LDS, 160 / 192 / 256 (96 / 128 KiB of tiles) one.
+template <int HD> struct AttnDim {
+  static constexpr int NH = (HD + 63) / 64, PATCH = HD == 64 ? 4 * 32 * 144 : 0;
+  static constexpr int fwd_lds = 2 * 2 * NH * TILE_B + 2 * 64 * 4 + PATCH;       // the forward and the dQ kernel
+  static constexpr int dkv_lds = 2 * 2 * NH * TILE_B + 2 * 4 * 64 * 4 + PATCH;
+  static constexpr int dkv_split = HD == 256 ? 2 : 1;                            // dK/dV column split (see attn_bwd_dkv_kernel)
+  // route counters: the forward hits exactly one; the two-pass backward hits attn_bwd at every head dim and bwd_route on top (-1: none)
+  static constexpr int fwd_route = HD == 64 ? ROUTE_ATTN_FWD : HD == 96 ? ROUTE_ATTN_FWD_D96 : HD == 128 ? ROUTE_ATTN_FWD_D128
+                                 : HD == 160 ? ROUTE_ATTN_FWD_D160 : HD == 192 ? ROUTE_ATTN_FWD_D192 : ROUTE_ATTN_FWD_D256;
+  static constexpr int bwd_route = HD == 64 ? -1 : HD == 96 ? ROUTE_ATTN_BWD_D96 : HD == 128 ? ROUTE_ATTN_BWD_D128
+                                 : HD == 160 ? ROUTE_ATTN_BWD_D160 : HD == 192 ? ROUTE_ATTN_BWD_D192 : ROUTE_ATTN_BWD_D256;
+};
+static_assert(AttnDim<256>::dkv_lds <= 160 * 1024, "LDS budget");
+
+// f(std::integral_constant<int, HD>{}) for a native runtime Dh
+template <typename F> int switch_hd(int Dh, F&& f) {
+  switch (Dh) {
+    case 64: return f(std::integral_constant<int, 64>{});
+    case 96: return f(std::integral_constant<int, 96>{});
+    case 128: return f(std::integral_constant<int, 128>{});
+    case 160: return f(std::integral_constant<int, 160>{});
+    case 192: return f(std::integral_constant<int, 192>{});
+    default: return f(std::integral_constant<int, 256>{});
+  }
+}
 
 template <int HD>
-int attn_fwd_wide(const FwdArgs& a, int H, int64_t G, int causal, hipStream_t stream) {
-  MEANT_RAISE_LDS(attn_fwd_kernel<HD>, wide_fwd_lds(HD));
-  hipLaunchKernelGGL(attn_fwd_kernel<HD>, dim3(attn_grid(causal ? (a.nqb + 1) / 2 : a.nqb, H, G)), dim3(256), wide_fwd_lds(HD), stream, a);
+int launch_fwd(const FwdArgs& a, int H, int64_t G, int causal, hipStream_t stream) {
+  using D = AttnDim<HD>;
+  MEANT_RAISE_LDS(attn_fwd_kernel<HD>, D::fwd_lds);
+  meant_route_hit(D::fwd_route);
+  hipLaunchKernelGGL(attn_fwd_kernel<HD>, dim3(attn_grid(causal ? (a.nqb + 1) / 2 : a.nqb, H, G)), dim3(256), D::fwd_lds, stream, a);
   MEANT_LAUNCH_CHECK("attn_fwd");
   return MEANT_OK;
 }
 
 template <int HD>
-int attn_bwd_wide(const BwdArgs& a, int H, int64_t G, int causal, hipStream_t stream) {
-  constexpr int NSPLIT = dkv_split<HD>();
-  MEANT_RAISE_LDS(attn_bwd_dq_kernel<HD>, wide_fwd_lds(HD));
-  MEANT_RAISE_LDS((attn_bwd_dkv_kernel<HD, NSPLIT>), wide_dkv_lds(HD));
-  const int64_t npair = causal ? (a.nblk + 1) / 2 : a.nblk;
-  hipLaunchKernelGGL(attn_bwd_dq_kernel<HD>, dim3(attn_grid(npair, H, G)), dim3(256), wide_fwd_lds(HD), stream, a);
+int launch_bwd(const BwdArgs& a, int H, int64_t G, int causal, hipStream_t stream) {
+  using D = AttnDim<HD>;
+  meant_route_hit(ROUTE_ATTN_BWD);
+  MEANT_REQUIRE(D::dkv_split == 1 || (int64_t)a.nblk * D::dkv_split * H * G < (1LL << 31) - 8, MEANT_ERR_UNSUPPORTED,
+                "attn_bwd: G=%lld / H=%d / S=%d exceed the grid limits", (long long)G, H, a.S);
+  if (D::bwd_route >= 0) meant_route_hit(D::bwd_route);
+  MEANT_RAISE_LDS(attn_bwd_dq_kernel<HD>, D::fwd_lds);
+  MEANT_RAISE_LDS((attn_bwd_dkv_kernel<HD, D::dkv_split>), D::dkv_lds);
+  const int64_t npair = causal ? (a.nblk + 1) / 2 : a.nblk;   // causal: one workgroup per pair of 128-row blocks
+  hipLaunchKernelGGL(attn_bwd_dq_kernel<HD>, dim3(attn_grid(npair, H, G)), dim3(256), D::fwd_lds, stream, a);
   MEANT_LAUNCH_CHECK("attn_bwd_dq");
-  hipLaunchKernelGGL((attn_bwd_dkv_kernel<HD, NSPLIT>), dim3(attn_grid(npair, H * NSPLIT, G)), dim3(256), wide_dkv_lds(HD), stream, a);
+  hipLaunchKernelGGL((attn_bwd_dkv_kernel<HD, D::dkv_split>), dim3(attn_grid(npair, H * D::dkv_split, G)), dim3(256), D::dkv_lds, stream, a);
   MEANT_LAUNCH_CHECK("attn_bwd_dkv");
+  return MEANT_OK;
+}
+
+// Workspace of the MFMA path: [delta: two planes of G*H*S floats | bias2: G*nt*64 floats | flags: G*nt ints | masks: G * 2 u64 |
+// the single-pass backward's item counters and partial dQ blocks].  The forward's own is [bias2 | flags | masks] alone: neither the
+// delta planes nor the single-pass scratch (1.2 GB at the text shape) belong to it.
+struct AttnWs {
+  int nt;                                   // key tiles
+  size_t delta, bias, flags, masks, bwd1;   // bytes of each part
+  AttnWs(int64_t G, int64_t S, int H, int Dh)
+      : nt((int)ceil_div(S, KV_TILE)), delta(align256((size_t)G * H * S * 2 * sizeof(float))), bias(align256((size_t)G * nt * KV_TILE * sizeof(float))),
+        flags(align256((size_t)G * nt * sizeof(int))), masks(align256((size_t)G * 2 * sizeof(uint64_t))), bwd1(attn_bwd1_ws(G, S, H, Dh)) {}
+  size_t fwd_bytes() const { return bias + flags + masks; }
+  size_t bytes() const { return delta + fwd_bytes() + bwd1; }
+};
+struct AttnMasks { float* bias2; int* flags; uint64_t* masks; void* ws1; };
+
+// bias and tile flags from the key mask into the [bias2 | flags | masks] block at `base`, the flags packed to one word per group when
+// they fit (masks = null otherwise); `zero_counters`: the mask kernel also clears the single-pass backward's item counters at ws1
+int prep_masks(const AttnWs& L, void* base, const float* key_mask, int64_t G, int64_t S, int causal, bool zero_counters, hipStream_t stream,
+               AttnMasks& m) {
+  m.bias2 = (float*)base;
+  m.flags = (int*)((char*)base + L.bias);
+  m.masks = L.nt <= 64 ? (uint64_t*)((char*)m.flags + L.flags) : nullptr;
+  m.ws1 = (char*)m.flags + L.flags + L.masks;
+  hipLaunchKernelGGL(attn_prep_mask_kernel, dim3((unsigned)L.nt, (unsigned)G), dim3(64), 0, stream, key_mask, m.bias2, m.flags, (int)S, L.nt, causal,
+                     zero_counters ? (unsigned*)m.ws1 : (unsigned*)nullptr);
+  MEANT_LAUNCH_CHECK("attn_prep_mask");
+  if (!m.masks) return MEANT_OK;
+  hipLaunchKernelGGL(attn_pack_flags_kernel, dim3((unsigned)G), dim3(64), 0, stream, m.flags, m.masks, L.nt);
+  MEANT_LAUNCH_CHECK("attn_pack_flags");
   return MEANT_OK;
 }
 
@@ -916,34 +972,16 @@ extern "C" int meant_lab_stamps(void* dst, size_t bytes) {
 }
 #endif
 
-// Head dims 64, 96, 128, 160, 192 and 256 run on the MFMA kernels above (the wider ones as two to four 64-column sub-tiles of
-// every tile, 96 and 160 with a 32-column last one).  The host side pads other head dims below 256 that are multiples of 8
-// up to the next of these with zero columns (meant_amd/ops.py), so this is what they run on too.  Anything else handed to the C ABI directly takes a widening detour: bf16 -> f32
-// copies in the workspace, the fp32 attention core, f32 -> bf16.  Correct for any Dh, not fast.
-// workspace of the Dh=64 path: [delta: G*H*S floats | bias2: G*nt*64 floats | flags: G*nt ints | masks: G * 2 u64]
-static size_t ws_delta_bytes(int64_t G, int64_t S, int H) { return align256((size_t)G * H * S * 2 * sizeof(float)); }   // two planes
-static size_t ws_bias_bytes(int64_t G, int64_t S) { return align256((size_t)G * ceil_div(S, KV_TILE) * KV_TILE * sizeof(float)); }
-static size_t ws_flag_bytes(int64_t G, int64_t S) { return align256((size_t)G * ceil_div(S, KV_TILE) * sizeof(int)); }
-static size_t ws_mask_bytes(int64_t G) { return align256((size_t)G * 2 * sizeof(uint64_t)); }
-
-size_t attn_bf16_ws(int64_t G, int64_t S, int H, int Dh) {
-  if (native_dh(Dh)) return ws_delta_bytes(G, S, H) + ws_bias_bytes(G, S) + ws_flag_bytes(G, S) + ws_mask_bytes(G) + attn_bwd1_ws(G, S, H, Dh);
-  return 2 * align256((size_t)G * S * 3 * H * Dh * 4) + 2 * align256((size_t)G * S * H * Dh * 4) + attn_f32_ws(G, S, H, Dh);
-}
-
-// the forward's own workspace: [bias2 | flags | masks] -- neither the backward's delta planes nor the single-pass backward's
-// partial-dQ scratch (1.2 GB at the text shape) belong to it
-size_t attn_bf16_fwd_ws(int64_t G, int64_t S, int H, int Dh) {
-  if (native_dh(Dh)) return ws_bias_bytes(G, S) + ws_flag_bytes(G, S) + ws_mask_bytes(G);
-  return attn_bf16_ws(G, S, H, Dh);
-}
-
-static int cast_async(const void* src, int sd, void* dst, int dd, int64_t n, hipStream_t st) { return meant_cast(src, sd, dst, dd, n, st); }
-
+// the widening detour's workspace: f32 copies of qkv, dqkv, o and dout, then the fp32 core's own
 static size_t generic_ws(int64_t G, int64_t S, int H, int Dh) {
   const size_t T = (size_t)G * S, D = (size_t)H * Dh;
   return 2 * align256(T * 3 * D * 4) + 2 * align256(T * D * 4) + attn_f32_ws(G, S, H, Dh);
 }
+
+size_t attn_bf16_ws(int64_t G, int64_t S, int H, int Dh) { return native_dh(Dh) ? AttnWs(G, S, H, Dh).bytes() : generic_ws(G, S, H, Dh); }
+size_t attn_bf16_fwd_ws(int64_t G, int64_t S, int H, int Dh) { return native_dh(Dh) ? AttnWs(G, S, H, Dh).fwd_bytes() : generic_ws(G, S, H, Dh); }
+
+static int cast_async(const void* src, int sd, void* dst, int dd, int64_t n, hipStream_t st) { return meant_cast(src, sd, dst, dd, n, st); }
 
 static int attn_bf16_generic(bool backward, const bf16* qkv, const bf16* o, const bf16* dout, bf16* o_out, float* lse, const float* key_mask,
                              bf16* dqkv, int64_t G, int64_t S, int H, int Dh, float scale, int causal, void* ws, size_t ws_bytes,
@@ -992,45 +1030,13 @@ int attn_bf16_fwd(const bf16* qkv, bf16* o, float* lse, const float* key_mask, i
   if (attn_short_ok(S, Dh)) return attn_short_fwd(qkv, o, lse, key_mask, G, S, H, Dh, scale, causal, stream);
   int rc = attn_bf16_check("attn_fwd", G, S, H, Dh);
   if (rc) return rc;
+  const AttnWs L(G, S, H, Dh);
   MEANT_REQUIRE(meant_aligned16(qkv) && meant_aligned16(o), MEANT_ERR_ARG, "attn_fwd: 16-byte alignment");
-  MEANT_REQUIRE(ws && ws_bytes >= attn_bf16_fwd_ws(G, S, H, Dh), MEANT_ERR_WORKSPACE, "attn_fwd: workspace too small");
-  const int nt = (int)ceil_div(S, KV_TILE);
-  float* bias2 = (float*)ws;
-  int* flags = (int*)((char*)bias2 + ws_bias_bytes(G, S));
-  hipLaunchKernelGGL(attn_prep_mask_kernel, dim3((unsigned)nt, (unsigned)G), dim3(64), 0, stream, key_mask, bias2, flags, (int)S, nt, causal, (unsigned*)nullptr);
-  MEANT_LAUNCH_CHECK("attn_prep_mask");
-  uint64_t* masks = nullptr;
-  if (nt <= 64) {
-    masks = (uint64_t*)((char*)flags + ws_flag_bytes(G, S));
-    hipLaunchKernelGGL(attn_pack_flags_kernel, dim3((unsigned)G), dim3(64), 0, stream, flags, masks, nt);
-    MEANT_LAUNCH_CHECK("attn_pack_flags");
-  }
-  const int nqb = (int)ceil_div(S, 128);
-  FwdArgs a{qkv, o, lse, bias2, flags, masks, (int)S, H, scale, causal, (int)G, nqb};
-  if (wide_dh(Dh)) {                                   // 160 / 192 / 256: three or four 64-column sub-tiles per operand tile
-    meant_route_hit(Dh == 160 ? ROUTE_ATTN_FWD_D160 : Dh == 192 ? ROUTE_ATTN_FWD_D192 : ROUTE_ATTN_FWD_D256);
-    return Dh == 160 ? attn_fwd_wide<160>(a, H, G, causal, stream) : Dh == 192 ? attn_fwd_wide<192>(a, H, G, causal, stream)
-                                                                   : attn_fwd_wide<256>(a, H, G, causal, stream);
-  }
-  MEANT_RAISE_LDS(attn_fwd_kernel<64>, FWD_LDS);
-  MEANT_RAISE_LDS(attn_fwd_kernel<96>, FWD_LDS2);
-  MEANT_RAISE_LDS(attn_fwd_kernel<128>, FWD_LDS2);
-  if (Dh != DH) {                                      // 96 and 128: two 64-column sub-tiles per operand tile
-    const dim3 grid2(attn_grid(causal ? (nqb + 1) / 2 : nqb, H, G));
-    if (Dh == 96) {
-      meant_route_hit(ROUTE_ATTN_FWD_D96);
-      hipLaunchKernelGGL(attn_fwd_kernel<96>, grid2, dim3(256), FWD_LDS2, stream, a);
-    } else {
-      meant_route_hit(ROUTE_ATTN_FWD_D128);
-      hipLaunchKernelGGL(attn_fwd_kernel<128>, grid2, dim3(256), FWD_LDS2, stream, a);
-    }
-    MEANT_LAUNCH_CHECK("attn_fwd");
-    return MEANT_OK;
-  }
-  meant_route_hit(ROUTE_ATTN_FWD);
-  hipLaunchKernelGGL(attn_fwd_kernel<64>, dim3(attn_grid(causal ? (nqb + 1) / 2 : nqb, H, G)), dim3(256), FWD_LDS, stream, a);
-  MEANT_LAUNCH_CHECK("attn_fwd");
-  return MEANT_OK;
+  MEANT_REQUIRE(ws && ws_bytes >= L.fwd_bytes(), MEANT_ERR_WORKSPACE, "attn_fwd: workspace too small");
+  AttnMasks m;
+  if ((rc = prep_masks(L, ws, key_mask, G, S, causal, false, stream, m))) return rc;
+  const FwdArgs a{qkv, o, lse, m.bias2, m.flags, m.masks, (int)S, H, scale, causal, (int)G, (int)ceil_div(S, 128)};
+  return switch_hd(Dh, [&](auto hd) { return launch_fwd<decltype(hd)::value>(a, H, G, causal, stream); });
 }
 
 int attn_bf16_bwd(const bf16* qkv, const bf16* o, const bf16* dout, const float* lse, const float* key_mask, bf16* dqkv, int64_t G,
@@ -1052,60 +1058,14 @@ int attn_bf16_bwd(const bf16* qkv, const bf16* o, const bf16* dout, const float*
   MEANT_REQUIRE(!rot.qa || (rot.R % 8 == 0 && rot.R <= DH), MEANT_ERR_UNSUPPORTED, "attn_bwd: rotary dim must be a multiple of 8 and <= 64");
   int rc = attn_bf16_check("attn_bwd", G, S, H, Dh);
   if (rc) return rc;
-  MEANT_REQUIRE(ws && ws_bytes >= attn_bf16_ws(G, S, H, Dh), MEANT_ERR_WORKSPACE, "attn_bwd: workspace too small");
+  const AttnWs L(G, S, H, Dh);
+  MEANT_REQUIRE(ws && ws_bytes >= L.bytes(), MEANT_ERR_WORKSPACE, "attn_bwd: workspace too small");
   MEANT_REQUIRE(meant_aligned16(qkv) && meant_aligned16(o) && meant_aligned16(dout) && meant_aligned16(dqkv), MEANT_ERR_ARG,
                 "attn_bwd: 16-byte alignment");
-  const int nt = (int)ceil_div(S, KV_TILE);
-  float* bias2 = (float*)((char*)ws + ws_delta_bytes(G, S, H));
-  int* flags = (int*)((char*)bias2 + ws_bias_bytes(G, S));
-  const bool one_pass = nt <= 64 && attn_bwd1_ok(S, Dh, causal);   // S and dP computed once, dQ through LDS (attn_bwd1.hip)
-  void* ws1 = (char*)flags + ws_flag_bytes(G, S) + ws_mask_bytes(G);   // its item counters (zeroed by the mask kernel) and partial dQ blocks
-  hipLaunchKernelGGL(attn_prep_mask_kernel, dim3((unsigned)nt, (unsigned)G), dim3(64), 0, stream, key_mask, bias2, flags, (int)S, nt, causal,
-                     one_pass ? (unsigned*)ws1 : (unsigned*)nullptr);
-  MEANT_LAUNCH_CHECK("attn_prep_mask");
-  uint64_t* masks = nullptr;
-  if (nt <= 64) {
-    masks = (uint64_t*)((char*)flags + ws_flag_bytes(G, S));
-    hipLaunchKernelGGL(attn_pack_flags_kernel, dim3((unsigned)G), dim3(64), 0, stream, flags, masks, nt);
-    MEANT_LAUNCH_CHECK("attn_pack_flags");
-  }
-  if (one_pass) return attn_bwd1_launch(qkv, o, dout, lse, bias2, flags, masks, dqkv, ws1, G, S, H, scale, causal, rot, stream);
-  BwdArgs a{qkv, o, dout, lse, bias2, flags, dqkv, (float*)ws, masks, G * (int64_t)H * S, (int)S, H, scale, causal, (int)G, (int)ceil_div(S, 128), rot};
-  MEANT_RAISE_LDS(attn_bwd_dq_kernel<64>, FWD_LDS);
-  MEANT_RAISE_LDS(attn_bwd_dkv_kernel<64>, BWD_DKV_LDS);
-  MEANT_RAISE_LDS(attn_bwd_dq_kernel<96>, FWD_LDS2);
-  MEANT_RAISE_LDS(attn_bwd_dkv_kernel<96>, BWD_DKV_LDS2);
-  MEANT_RAISE_LDS(attn_bwd_dq_kernel<128>, FWD_LDS2);
-  MEANT_RAISE_LDS(attn_bwd_dkv_kernel<128>, BWD_DKV_LDS2);
-  const int64_t nblk = ceil_div(S, 128);
-  const dim3 grid(attn_grid(causal ? (nblk + 1) / 2 : nblk, H, G));   // causal: one workgroup per pair of 128-row blocks
-  meant_route_hit(ROUTE_ATTN_BWD);
-  if (wide_dh(Dh)) {
-    MEANT_REQUIRE(Dh != 256 || ceil_div(S, 128) * 2 * H * G < (1LL << 31) - 8, MEANT_ERR_UNSUPPORTED,
-                  "attn_bwd: G=%lld / H=%d / S=%lld exceed the grid limits", (long long)G, H, (long long)S);
-    meant_route_hit(Dh == 160 ? ROUTE_ATTN_BWD_D160 : Dh == 192 ? ROUTE_ATTN_BWD_D192 : ROUTE_ATTN_BWD_D256);
-    return Dh == 160 ? attn_bwd_wide<160>(a, H, G, causal, stream) : Dh == 192 ? attn_bwd_wide<192>(a, H, G, causal, stream)
-                                                                   : attn_bwd_wide<256>(a, H, G, causal, stream);
-  }
-  if (Dh == 96) {
-    meant_route_hit(ROUTE_ATTN_BWD_D96);
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<96>, grid, dim3(256), FWD_LDS2, stream, a);
-    MEANT_LAUNCH_CHECK("attn_bwd_dq");
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel<96>, grid, dim3(256), BWD_DKV_LDS2, stream, a);
-    MEANT_LAUNCH_CHECK("attn_bwd_dkv");
-    return MEANT_OK;
-  }
-  if (Dh == 128) {
-    meant_route_hit(ROUTE_ATTN_BWD_D128);
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<128>, grid, dim3(256), FWD_LDS2, stream, a);
-    MEANT_LAUNCH_CHECK("attn_bwd_dq");
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel<128>, grid, dim3(256), BWD_DKV_LDS2, stream, a);
-    MEANT_LAUNCH_CHECK("attn_bwd_dkv");
-    return MEANT_OK;
-  }
-  hipLaunchKernelGGL(attn_bwd_dq_kernel<64>, grid, dim3(256), FWD_LDS, stream, a);
-  MEANT_LAUNCH_CHECK("attn_bwd_dq");
-  hipLaunchKernelGGL(attn_bwd_dkv_kernel<64>, grid, dim3(256), BWD_DKV_LDS, stream, a);
-  MEANT_LAUNCH_CHECK("attn_bwd_dkv");
-  return MEANT_OK;
+  const bool one_pass = L.nt <= 64 && attn_bwd1_ok(S, Dh, causal);   // S and dP computed once, dQ through LDS (attn_bwd1.hip)
+  AttnMasks m;                                                       // only then does the mask kernel clear its item counters
+  if ((rc = prep_masks(L, (char*)ws + L.delta, key_mask, G, S, causal, one_pass, stream, m))) return rc;
+  if (one_pass) return attn_bwd1_launch(qkv, o, dout, lse, m.bias2, m.flags, m.masks, dqkv, m.ws1, G, S, H, scale, causal, rot, stream);
+  const BwdArgs a{qkv, o, dout, lse, m.bias2, m.flags, dqkv, (float*)ws, m.masks, G * (int64_t)H * S, (int)S, H, scale, causal, (int)G, (int)ceil_div(S, 128), rot};
+  return switch_hd(Dh, [&](auto hd) { return launch_bwd<decltype(hd)::value>(a, H, G, causal, stream); });
 }

@@ -1,7 +1,7 @@
 // Streaming / elementwise kernels of the MEANT path (all HBM-bound; fp32 math, T storage):
-//   K6 rotary / xPos (in place on the packed q|k|v projection), K7a patchify, K8 sequence mean-pool,
-//   K9 temporal (lag-axis) attention core (lags up to 64; longer ones: temporal_long.hip), embedding gather / scatter-add, and small glue
+//   K6 rotary / xPos (in place on the packed q|k|v projection), K7a patchify, K8 sequence mean-pool, and small glue
 //   (broadcast add, GELU / sigmoid backward, casts, weight transposes).
+//   (K9, the temporal attention core, is temporal.hip; the embedding gather and its gradients are embedding.hip.)
 // Each thread moves 16 bytes (8 bf16) or 2x16 bytes (8 f32) per access; grids are capped and
 // grid-strided so that launches stay at a few thousand workgroups.
 #include "internal.h"
@@ -303,217 +303,6 @@ __global__ __launch_bounds__(EW_THREADS) void meanpool_bwd_kernel(const TO* __re
   }
 }
 
-// ------------------------------------------------------------------------------------------------
-// K9 temporal attention core: one wave per (b, h); L <= 64 keys, any Dh.  (L > 64: temporal_long.hip)
-template <typename T>
-__global__ __launch_bounds__(256) void temporal_fwd_kernel(const T* __restrict__ q, const T* __restrict__ kv, T* __restrict__ o,
-                                                            float* __restrict__ p, int64_t B, int L, int H, int Dh, float scale) {
-  __shared__ float sc[4][64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t bh = (int64_t)blockIdx.x * 4 + wave;
-  if (bh >= B * H) return;
-  const int64_t b = bh / H;
-  const int h = (int)(bh - b * H);
-  const int D = H * Dh;
-  const T* qp = q + b * D + h * Dh;
-  for (int l = 0; l < L; ++l) {
-    const T* kp = kv + (b * L + l) * (int64_t)(2 * D) + h * Dh;
-    float s = 0.f;
-    for (int e = lane; e < Dh; e += 64) s += to_f(qp[e]) * to_f(kp[e]);
-    s = wave_sum(s) * scale;
-    if (lane == 0) sc[wave][l] = s;
-  }
-  __builtin_amdgcn_wave_barrier();
-  float m = -INFINITY;
-  for (int l = 0; l < L; ++l) m = fmaxf(m, sc[wave][l]);
-  float sum = 0.f;
-  for (int l = 0; l < L; ++l) sum += __expf(sc[wave][l] - m);
-  const float inv = 1.f / sum;
-  __builtin_amdgcn_wave_barrier();
-  if (lane < L) {
-    const float w = __expf(sc[wave][lane] - m) * inv;
-    p[bh * L + lane] = w;
-    sc[wave][lane] = w;
-  }
-  __builtin_amdgcn_wave_barrier();
-  for (int e = lane; e < Dh; e += 64) {
-    float acc = 0.f;
-    for (int l = 0; l < L; ++l) acc += sc[wave][l] * to_f(kv[(b * L + l) * (int64_t)(2 * D) + D + h * Dh + e]);
-    o[b * D + h * Dh + e] = from_f<T>(acc);
-  }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void temporal_bwd_kernel(const T* __restrict__ q, const T* __restrict__ kv,
-                                                            const float* __restrict__ p, const T* __restrict__ dout,
-                                                            T* __restrict__ dq, T* __restrict__ dkv, int64_t B, int L, int H,
-                                                            int Dh, float scale) {
-  __shared__ float ds[4][64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t bh = (int64_t)blockIdx.x * 4 + wave;
-  if (bh >= B * H) return;
-  const int64_t b = bh / H;
-  const int h = (int)(bh - b * H);
-  const int D = H * Dh;
-  const T* dop = dout + b * D + h * Dh;
-  float dot = 0.f;                                   // sum_l p_l dp_l
-  for (int l = 0; l < L; ++l) {
-    const T* vp = kv + (b * L + l) * (int64_t)(2 * D) + D + h * Dh;
-    float s = 0.f;
-    for (int e = lane; e < Dh; e += 64) s += to_f(dop[e]) * to_f(vp[e]);
-    s = wave_sum(s);                                 // dp_l
-    if (lane == 0) ds[wave][l] = s;
-    dot += p[bh * L + l] * s;
-  }
-  __builtin_amdgcn_wave_barrier();
-  if (lane < L) ds[wave][lane] = p[bh * L + lane] * (ds[wave][lane] - dot) * scale;
-  __builtin_amdgcn_wave_barrier();
-  for (int e = lane; e < Dh; e += 64) {
-    const float qe = to_f(q[b * D + h * Dh + e]);
-    const float doe = to_f(dop[e]);
-    float dqe = 0.f;
-    for (int l = 0; l < L; ++l) {
-      const int64_t row = (b * L + l) * (int64_t)(2 * D);
-      dqe += ds[wave][l] * to_f(kv[row + h * Dh + e]);
-      dkv[row + h * Dh + e] = from_f<T>(ds[wave][l] * qe);
-      dkv[row + D + h * Dh + e] = from_f<T>(p[bh * L + l] * doe);
-    }
-    dq[b * D + h * Dh + e] = from_f<T>(dqe);
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// embedding gather (one wave per token row) and scatter-add of its gradient (f32 atomics)
-template <typename T>
-__global__ __launch_bounds__(256) void embedding_fwd_kernel(const float* __restrict__ table, const int64_t* __restrict__ ids,
-                                                             T* __restrict__ out, int64_t n, int d, int64_t V) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int nch = d >> 3;
-  for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < n; r += (int64_t)gridDim.x * 4) {
-    int64_t id = ids[r];
-    id = id < 0 ? 0 : (id >= V ? V - 1 : id);
-    const float* src = table + id * d;
-    for (int ch = lane; ch < nch; ch += 64) {
-      const Vec8<float> v = load8<float>(src + ch * 8);
-      Vec8<T> o;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) o.set(k, v.get(k));
-      store8s<T>(out + r * d + ch * 8, o);
-    }
-  }
-}
-template <typename T>
-__global__ __launch_bounds__(256) void embedding_bwd_kernel(const T* __restrict__ dout, const int64_t* __restrict__ ids,
-                                                             float* __restrict__ dtable, int64_t n, int d, int64_t V) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < n; r += (int64_t)gridDim.x * 4) {
-    int64_t id = ids[r];
-    id = id < 0 ? 0 : (id >= V ? V - 1 : id);
-    float* dst = dtable + id * d;
-    for (int e = lane; e < d; e += 64) atomicAdd(dst + e, to_f(dout[r * d + e]));   // 256 contiguous bytes per wave-instruction
-  }
-}
-
-// scatter-add of the embedding gradient over ids SORTED by the caller (order[j] = original row of the j-th smallest id).
-// A wave walks SEG consecutive sorted entries; a lane owns 8-column chunks `lane` and `lane + 64` of the row (16-byte loads, four
-// rows requested before the first is consumed) and sums the rows of a run of equal ids in registers.  A run that lies entirely
-// inside the wave's stretch belongs to nobody else: its sum is added with a plain read-modify-write.  Only the (at most two) runs
-// that cross the stretch's ends use float atomics -- at 12 tokens per id that is one row in eleven (the atomic rate, 1.3 TB/s of added
-// bytes, was a third of this kernel's time when every run went that way, and 2-byte loads most of the rest).
-constexpr int EMB_SEG = 256;
-template <typename T>
-__global__ __launch_bounds__(256) void embedding_bwd_sorted_kernel(const T* __restrict__ dout, const int64_t* __restrict__ sorted_ids,
-                                                                    const int64_t* __restrict__ order, float* __restrict__ dtable,
-                                                                    int64_t n, int d, int64_t V, int det, int64_t id_lo, int64_t id_hi) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int64_t j0 = ((int64_t)blockIdx.x * 4 + wave) * EMB_SEG;
-  if (j0 >= n) return;
-  int64_t j1 = j0 + EMB_SEG < n ? j0 + EMB_SEG : n;
-  // [id_lo, id_hi): only the rows of this id range are produced (meant_embedding_bwd_sorted_range: the table's gradient in row
-  // slices, each handed to its collective as soon as it is final).  The ids are sorted: a stretch outside the range leaves at once.
-  if (sorted_ids[j1 - 1] < id_lo || sorted_ids[j0] >= id_hi) return;
-  if (det) {
-    // option "deterministic": no atomics.  A run belongs to the wave in whose stretch it STARTS: that wave follows it to its end
-    // (however far), the others skip the part of their stretch that continues an earlier run.  Slow for a hot id; a debugging mode.
-    if (j0 > 0) {
-      const int64_t prev = sorted_ids[j0 - 1];
-      while (j0 < j1 && sorted_ids[j0] == prev) ++j0;
-      if (j0 == j1) return;
-    }
-    const int64_t last = sorted_ids[j1 - 1];
-    while (j1 < n && sorted_ids[j1] == last) ++j1;
-  }
-  const int nch = d >> 3;                              // d % 8 == 0, d <= 1024
-  const bool has1 = lane + 64 < nch, has0 = lane < nch;
-  float acc0[8], acc1[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) acc0[e] = acc1[e] = 0.f;
-  int64_t cur = sorted_ids[j0];
-  bool shared = !det && j0 > 0 && sorted_ids[j0 - 1] == cur;   // the first run started in the previous stretch
-
-  auto flush = [&](int64_t id, bool atomic) {
-    if (id < 0 || id >= V || id < id_lo || id >= id_hi) return;
-    float* row = dtable + id * d;
-    if (atomic) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        if (has0) atomicAdd(row + lane * 8 + e, acc0[e]);
-        if (has1) atomicAdd(row + (lane + 64) * 8 + e, acc1[e]);
-      }
-    } else {
-      if (has0) {
-        Vec8<float> v = load8<float>(row + lane * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v.set(e, v.get(e) + acc0[e]);
-        store8<float>(row + lane * 8, v);
-      }
-      if (has1) {
-        Vec8<float> v = load8<float>(row + (lane + 64) * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v.set(e, v.get(e) + acc1[e]);
-        store8<float>(row + (lane + 64) * 8, v);
-      }
-    }
-  };
-
-  for (int64_t jb = j0; jb < j1; jb += 64) {
-    const int64_t jl = jb + lane < j1 ? jb + lane : j1 - 1;
-    const long long my_id = sorted_ids[jl], my_ord = order[jl];
-    const int cnt = (int)(j1 - jb < 64 ? j1 - jb : 64);
-    for (int t0 = 0; t0 < cnt; t0 += 4) {
-      Vec8<T> r0[4], r1[4];
-      long long ids4[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int t = t0 + u < cnt ? t0 + u : cnt - 1;
-        ids4[u] = __shfl(my_id, t, 64);
-        const long long ord = __shfl(my_ord, t, 64);
-        const T* src = dout + ord * d;
-        if (has0) r0[u] = load8s<T>(src + lane * 8);
-        if (has1) r1[u] = load8s<T>(src + (lane + 64) * 8);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        if (t0 + u >= cnt) break;
-        const int64_t id = ids4[u];
-        if (id != cur) {
-          flush(cur, shared);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) acc0[e] = acc1[e] = 0.f;
-          cur = id;
-          shared = false;
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          if (has0) acc0[e] += r0[u].get(e);
-          if (has1) acc1[e] += r1[u].get(e);
-        }
-      }
-    }
-  }
-  flush(cur, !det && (shared || (j1 < n && sorted_ids[j1] == cur)));   // ... or continues into the next stretch
-}
-
 }  // namespace
 
 #define EW_REQ(c, ...) MEANT_REQUIRE(c, MEANT_ERR_ARG, __VA_ARGS__)
@@ -734,71 +523,5 @@ extern "C" int meant_meanpool_bwd(const void* dout, int64_t ld_out, int64_t col_
   else if (dtype == MEANT_BF16 && out_dtype == MEANT_BF16) hipLaunchKernelGGL((meanpool_bwd_kernel<bf16, bf16>), grid, block, 0, st, (const bf16*)dout, ld_out, col_off, (bf16*)dx, G, (int)S, (int)d);
   else { meant_set_error("meanpool_bwd: unsupported dtype combination"); return MEANT_ERR_UNSUPPORTED; }
   MEANT_LAUNCH_CHECK("meanpool_bwd");
-  return MEANT_OK;
-}
-
-extern "C" int meant_temporal_attn_fwd(const void* q, const void* kv, void* o, float* p, int64_t B, int L, int H, int Dh, float scale, int dtype, void* stream) {
-  EW_REQ(q && kv && o && p && B > 0 && H > 0 && Dh > 0, "temporal_attn_fwd: bad argument");
-  MEANT_REQUIRE(L > 0, MEANT_ERR_UNSUPPORTED, "temporal_attn_fwd: lag %d is not positive", L);
-  if (L > 64 || meant_opt(MEANT_OPT_TEMPORAL_LONG)) return temporal_long_fwd(q, kv, o, p, B, L, H, Dh, scale, dtype, (hipStream_t)stream);
-  DISPATCH_DTYPE(dtype, T,
-                 hipLaunchKernelGGL(temporal_fwd_kernel<T>, dim3((unsigned)ceil_div(B * H, 4)), dim3(256), 0, (hipStream_t)stream,
-                                    (const T*)q, (const T*)kv, (T*)o, p, B, L, H, Dh, scale));
-  MEANT_LAUNCH_CHECK("temporal_attn_fwd");
-  return MEANT_OK;
-}
-extern "C" int meant_temporal_attn_bwd(const void* q, const void* kv, const float* p, const void* do_, void* dq, void* dkv, int64_t B, int L, int H, int Dh, float scale, int dtype, void* stream) {
-  EW_REQ(q && kv && p && do_ && dq && dkv && B > 0 && H > 0 && Dh > 0, "temporal_attn_bwd: bad argument");
-  MEANT_REQUIRE(L > 0, MEANT_ERR_UNSUPPORTED, "temporal_attn_bwd: lag %d is not positive", L);
-  if (L > 64 || meant_opt(MEANT_OPT_TEMPORAL_LONG)) return temporal_long_bwd(q, kv, p, do_, dq, dkv, B, L, H, Dh, scale, dtype, (hipStream_t)stream);
-  DISPATCH_DTYPE(dtype, T,
-                 hipLaunchKernelGGL(temporal_bwd_kernel<T>, dim3((unsigned)ceil_div(B * H, 4)), dim3(256), 0, (hipStream_t)stream,
-                                    (const T*)q, (const T*)kv, p, (const T*)do_, (T*)dq, (T*)dkv, B, L, H, Dh, scale));
-  MEANT_LAUNCH_CHECK("temporal_attn_bwd");
-  return MEANT_OK;
-}
-
-extern "C" int meant_embedding_fwd(const float* table, const int64_t* ids, void* out, int64_t n, int64_t d, int64_t V, int dtype, void* stream) {
-  EW_REQ(table && ids && out && n > 0 && d > 0 && d % 8 == 0 && V > 0, "embedding_fwd: bad argument");
-  int64_t nb = ceil_div(n, 4); if (nb > 8192) nb = 8192;
-  DISPATCH_DTYPE(dtype, T,
-                 hipLaunchKernelGGL(embedding_fwd_kernel<T>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, table, ids, (T*)out, n, (int)d, V));
-  MEANT_LAUNCH_CHECK("embedding_fwd");
-  return MEANT_OK;
-}
-extern "C" int meant_embedding_bwd_sorted(const void* dout, const int64_t* sorted_ids, const int64_t* order, float* dtable, int64_t n,
-                                          int64_t d, int64_t V, int dtype, void* stream) {
-  EW_REQ(dout && sorted_ids && order && dtable && n > 0 && d > 0 && V > 0, "embedding_bwd_sorted: bad argument");
-  MEANT_REQUIRE(d <= 1024 && d % 8 == 0, MEANT_ERR_UNSUPPORTED, "embedding_bwd_sorted: d=%lld must be a multiple of 8 and <= 1024", (long long)d);
-  EW_REQ(meant_aligned16(dout) && meant_aligned16(dtable), "embedding_bwd_sorted: 16-byte alignment");
-  const int64_t nb = ceil_div(n, 4 * EMB_SEG);
-  DISPATCH_DTYPE(dtype, T,
-                 hipLaunchKernelGGL(embedding_bwd_sorted_kernel<T>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (const T*)dout,
-                                    sorted_ids, order, dtable, n, (int)d, V, meant_opt(MEANT_OPT_DETERMINISTIC) != 0, (int64_t)0, V));
-  MEANT_LAUNCH_CHECK("embedding_bwd_sorted");
-  return MEANT_OK;
-}
-
-extern "C" int meant_embedding_bwd_sorted_range(const void* dout, const int64_t* sorted_ids, const int64_t* order, float* dtable, int64_t n,
-                                                int64_t d, int64_t V, int64_t id_lo, int64_t id_hi, int dtype, void* stream) {
-  EW_REQ(dout && sorted_ids && order && dtable && n > 0 && d > 0 && V > 0 && 0 <= id_lo && id_lo <= id_hi && id_hi <= V,
-         "embedding_bwd_sorted_range: bad argument");
-  MEANT_REQUIRE(d <= 1024 && d % 8 == 0, MEANT_ERR_UNSUPPORTED, "embedding_bwd_sorted_range: d=%lld must be a multiple of 8 and <= 1024", (long long)d);
-  EW_REQ(meant_aligned16(dout) && meant_aligned16(dtable), "embedding_bwd_sorted_range: 16-byte alignment");
-  if (id_lo == id_hi) return MEANT_OK;
-  const int64_t nb = ceil_div(n, 4 * EMB_SEG);
-  DISPATCH_DTYPE(dtype, T,
-                 hipLaunchKernelGGL(embedding_bwd_sorted_kernel<T>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (const T*)dout,
-                                    sorted_ids, order, dtable, n, (int)d, V, meant_opt(MEANT_OPT_DETERMINISTIC) != 0, id_lo, id_hi));
-  MEANT_LAUNCH_CHECK("embedding_bwd_sorted_range");
-  return MEANT_OK;
-}
-
-extern "C" int meant_embedding_bwd(const void* dout, const int64_t* ids, float* dtable, int64_t n, int64_t d, int64_t V, int dtype, void* stream) {
-  EW_REQ(dout && ids && dtable && n > 0 && d > 0 && V > 0, "embedding_bwd: bad argument");
-  int64_t nb = ceil_div(n, 4); if (nb > 8192) nb = 8192;
-  DISPATCH_DTYPE(dtype, T,
-                 hipLaunchKernelGGL(embedding_bwd_kernel<T>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (const T*)dout, ids, dtable, n, (int)d, V));
-  MEANT_LAUNCH_CHECK("embedding_bwd");
   return MEANT_OK;
 }

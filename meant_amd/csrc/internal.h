@@ -80,11 +80,6 @@ int attn_short_fwd(const bf16* qkv, bf16* o, float* lse, const float* key_mask, 
                    int causal, hipStream_t stream);
 int attn_short_bwd(const bf16* qkv, const bf16* dout, const float* lse, const float* key_mask, bf16* dqkv, int64_t G, int64_t S, int H,
                    int Dh, float scale, int causal, RotTables rot, hipStream_t stream);
-// temporal (lag-axis) attention core at long lags (temporal_long.hip): any L >= 1, any Dh; the entry points send L > 64 here
-int temporal_long_fwd(const void* q, const void* kv, void* o, float* p, int64_t B, int L, int H, int Dh, float scale, int dtype,
-                      hipStream_t stream);
-int temporal_long_bwd(const void* q, const void* kv, const float* p, const void* do_, void* dq, void* dkv, int64_t B, int L, int H,
-                      int Dh, float scale, int dtype, hipStream_t stream);
 // single-pass backward (attn_bwd1.hip): Dh = 64, S <= 256 or causal S <= 512; bias2 / flags / masks as prepared by attn_bf16_bwd
 bool attn_bwd1_ok(int64_t S, int Dh, int causal);
 size_t attn_bwd1_ws(int64_t G, int64_t S, int H, int Dh);

@@ -6,6 +6,7 @@
 //   the add of the gradient that arrives through the residual branch sharing x, and the GELU derivative
 //   when x = gelu(pre) (meant/meant.py:64,107).
 // Reference semantics: utils/rms_norm.py:40-57 (eps added to the RMS, outside the sqrt).
+#include <type_traits>
 #include "internal.h"
 
 namespace {
@@ -598,15 +599,6 @@ __global__ __launch_bounds__(NORM_THREADS, 2) void rmsnorm_bwd_packed_kernel(con
   }
 }
 
-// rows per wave R and chunks per lane C of the packed kernels, or R = 0 if the shape does not pack
-inline void norm_packing(int64_t rows, int64_t d, int& R, int& C) {
-  const int nchunk = (int)(d >> 3);
-  for (R = 1; R <= 4; R *= 2) {
-    if ((R * nchunk) % 64 == 0 && R * nchunk / 64 <= 3 && rows % R == 0) { C = R * nchunk / 64; return; }
-  }
-  R = 0; C = 0;
-}
-
 // out[j] = sum_p partial[p, j]   (and optionally a second array at partial + np*d)
 __global__ void colreduce_kernel(const float* __restrict__ partial, float* __restrict__ out, int np, int d) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1110,217 +1102,254 @@ __global__ __launch_bounds__(NORM_THREADS) void layernorm_bwd_wide_kernel(const 
   }
 }
 
-inline int packed_blocks(int64_t groups) {
-  int64_t b = ceil_div(groups, 4);
-  return (int)(b < 1 ? 1 : (b > NORM_PACKED_BLOCKS ? NORM_PACKED_BLOCKS : b));
-}
+// ---- host side: one classifier, one launcher per kernel template, the entry points ------------------------------------------
+inline int clamp_blocks(int64_t b, int64_t cap) { return (int)(b < 1 ? 1 : (b > cap ? cap : b)); }
+inline int packed_blocks(int64_t groups) { return clamp_blocks(ceil_div(groups, 4), NORM_PACKED_BLOCKS); }
 // the packed backward kernels hold two workgroups per CU (205 VGPRs): more than 512 workgroups run in rounds, each paying the
 // prologue (gain loads) and the epilogue (LDS reduction of the gain gradient, partial row) again -- at the MLM step's 32 k rows
 // the 2048-block launch spent two thirds of its 98 us there
-inline int packed_blocks_bwd(int64_t groups) {
-  int64_t b = ceil_div(groups, 4);
-  const int64_t cap = 2 * (int64_t)meant_num_cus();
-  return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-inline int norm_blocks(int64_t rows) {
-  int64_t b = ceil_div(rows, 4);
-  return (int)(b < 1 ? 1 : (b > NORM_MAX_BLOCKS ? NORM_MAX_BLOCKS : b));
-}
-// the widths of the one-wave-per-row and packed kernels; every other d > 0 goes to the *_wide_kernel family
-inline bool norm_narrow(int64_t d) { return d % 8 == 0 && d <= MAXC * 512; }
-// alignment a wide-route kernel needs: 16 bytes for the 8-element loads (d % 8 == 0), the element's own otherwise
-inline bool wide_aligned(const void* p, int64_t d, size_t elt) {
-  return d % 8 == 0 ? meant_aligned16(p) : (reinterpret_cast<uintptr_t>(p) % elt) == 0;
-}
+inline int packed_blocks_bwd(int64_t groups) { return clamp_blocks(ceil_div(groups, 4), 2 * (int64_t)meant_num_cus()); }
+inline int norm_blocks(int64_t rows) { return clamp_blocks(ceil_div(rows, 4), NORM_MAX_BLOCKS); }
 inline size_t dtype_bytes(int dtype) { return dtype == MEANT_BF16 ? 2 : 4; }
 
-int rmsnorm_fwd_wide(const void* x, const float* scale, void* y, float* rinv, int64_t rows, int64_t d, float eps, float drop_p, uint64_t seed,
-                     int64_t d_part, const float* offset, int dtype, void* stream, const char* name) {
-#define LAUNCH_FW(VV)                                                                                                         \
-  DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((rmsnorm_fwd_wide_kernel<T, VV>), dim3(norm_blocks(rows)), dim3(NORM_THREADS), 0,        \
-                                              (hipStream_t)stream, (const T*)x, scale, (T*)y, rinv, rows, (int)d, eps, drop_p, seed,   \
-                                              (int)d_part, offset))
-  if (d % 8 == 0) LAUNCH_FW(8); else LAUNCH_FW(1);
-#undef LAUNCH_FW
-  MEANT_LAUNCH_CHECK(name);
-  return MEANT_OK;
+// Which kernel family a shape runs on; the only place that knows the widths.
+//   NORM_WIDE:   d % 8 != 0 or d > MAXC * 512 = 2048: the *_wide_kernel family, V = 8 elements per load if d % 8 == 0, else V = 1;
+//   NORM_PACKED: R = 1, 2 or 4 rows per wave with R * d / 8 = C * 64 chunks, C <= 3 per lane (so d <= 1536), and rows % R == 0;
+//   NORM_ROW:    every other d <= 2048, one wave per row (also what a packing shape gets from a caller that cannot pack).
+enum NormKind { NORM_PACKED, NORM_ROW, NORM_WIDE };
+struct NormRoute { NormKind kind; int R, C, V; };
+inline NormRoute norm_route(int64_t rows, int64_t d, bool may_pack = true) {
+  if (d % 8 != 0 || d > MAXC * 512) return {NORM_WIDE, 0, 0, d % 8 == 0 ? 8 : 1};
+  const int nchunk = (int)(d >> 3);
+  for (int R = 1; may_pack && rows > 0 && d > 0 && R <= 4; R *= 2)
+    if ((R * nchunk) % 64 == 0 && R * nchunk / 64 <= 3 && rows % R == 0) return {NORM_PACKED, R, R * nchunk / 64, 8};
+  return {NORM_ROW, 0, 0, 8};
+}
+// alignment a route's kernels need of a row pointer: 16 bytes for the 8-element loads, the element's own at V = 1
+inline bool norm_aligned(const NormRoute& nr, const void* p, size_t elt) {
+  return nr.V == 8 ? meant_aligned16(p) : (reinterpret_cast<uintptr_t>(p) % elt) == 0;
+}
+
+// compile-time switches over the chunks per lane C and the vector width V: f(Int<N>{}) for the runtime value
+template <int N> using Int = std::integral_constant<int, N>;
+template <typename F> inline int switch_c(int C, F&& f) { return C == 1 ? f(Int<1>{}) : C == 2 ? f(Int<2>{}) : f(Int<3>{}); }
+template <typename F> inline int switch_v(int V, F&& f) { return V == 8 ? f(Int<8>{}) : f(Int<1>{}); }
+
+// the reductions of per-block partial rows every backward ends with: out1 from `partial`, out2 (if not null) from the plane after it
+inline int norm_colsums(const float* partial, int nb, int64_t d, float* out1, float* out2, int accumulate2, void* stream) {
+  int rc = colsum_launch(partial, d, out1, nb, d, MEANT_F32, 0, (hipStream_t)stream);
+  if (rc || !out2) return rc;
+  return colsum_launch(partial + (size_t)nb * d, d, out2, nb, d, MEANT_F32, accumulate2, (hipStream_t)stream);
+}
+
+// ---- launchers: each kernel template is named here and nowhere else ----
+inline int launched(const char* name) { MEANT_LAUNCH_CHECK(name); return MEANT_OK; }
+// the one-wave-per-row and the wide forward
+int launch_fwd_unpacked(const char* name, const NormRoute& nr, const void* x, const float* scale, void* y, float* rinv, int64_t rows, int64_t d,
+                        float eps, float drop_p, uint64_t seed, int64_t d_part, const float* offset, int dtype, void* stream) {
+  if (nr.kind == NORM_ROW) {
+    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(rmsnorm_fwd_kernel<T>, dim3(norm_blocks(rows)), dim3(NORM_THREADS), 0, (hipStream_t)stream,
+                                                (const T*)x, scale, (T*)y, rinv, rows, (int)d, eps, drop_p, seed, (int)d_part, offset));
+    return launched(name);
+  }
+  return switch_v(nr.V, [&](auto v) -> int {
+    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((rmsnorm_fwd_wide_kernel<T, v.value>), dim3(norm_blocks(rows)), dim3(NORM_THREADS), 0,
+                                                (hipStream_t)stream, (const T*)x, scale, (T*)y, rinv, rows, (int)d, eps, drop_p, seed,
+                                                (int)d_part, offset));
+    return launched(name);
+  });
+}
+
+int launch_fwd_packed(const char* name, const NormRoute& nr, const void* x, const float* scale, void* y, float* rinv, int64_t rows, int64_t d,
+                      float eps, float drop_p, uint64_t seed, int dtype, void* stream) {
+  return switch_c(nr.C, [&](auto c) -> int {
+    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((rmsnorm_fwd_packed_kernel<T, c.value>), dim3(packed_blocks(rows / nr.R)), dim3(NORM_THREADS), 0,
+                                                (hipStream_t)stream, (const T*)x, scale, (T*)y, rinv, rows, (int)d, nr.R, eps, drop_p, seed));
+    return launched(name);
+  });
+}
+
+int launch_stats_packed(const char* name, const NormRoute& nr, const void* x, float* rinv, int64_t rows, int64_t d, float eps, int dtype,
+                        void* stream) {
+  return switch_c(nr.C, [&](auto c) -> int {
+    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((rmsnorm_stats_packed_kernel<T, c.value>), dim3(packed_blocks(rows / nr.R)), dim3(NORM_THREADS), 0,
+                                                (hipStream_t)stream, (const T*)x, rinv, rows, (int)d, nr.R, eps));
+    return launched(name);
+  });
+}
+
+template <int POOL, bool GELU_IN>
+int launch_fwd_pooled(const char* name, const NormRoute& nr, const void* x, const float* scale, void* y, float* rinv, float* pooled,
+                      int64_t ngroups, int64_t d, int64_t group_rows, float eps, float drop_p, uint64_t seed, int dtype, void* stream) {
+  const int nb = (int)(ngroups < NORM_PACKED_BLOCKS ? ngroups : NORM_PACKED_BLOCKS);
+  return switch_c(nr.C, [&](auto c) -> int {
+    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((rmsnorm_fwd_pooled_kernel<T, c.value, POOL, GELU_IN>), dim3(nb), dim3(NORM_THREADS), 0,
+                                                (hipStream_t)stream, (const T*)x, scale, (T*)y, rinv, ngroups, (int)d, nr.R, eps, drop_p, seed,
+                                                pooled, (int)group_rows));
+    return launched(name);
+  });
+}
+
+// the plain (BC = 0), pooled (BC = 1, 2, 3, 5) and chained (CHAIN with BC = 0 or 5) packed backward on rows / R groups; the callers'
+// explicit <BC, CHAIN> are the only instantiations
+template <int BC, bool CHAIN>
+int launch_bwd_packed(const char* name, const NormRoute& nr, int nbp, const void* dy, const void* x, const float* scale, const float* rinv,
+                      void* dx, float* partial, int64_t rows, int64_t d, float eps, float drop_p, uint64_t seed, const void* dres,
+                      const void* gelu_pre, int64_t group_rows, const NormChain& ch, int dtype, void* stream) {
+  return switch_c(nr.C, [&](auto c) -> int {
+    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((rmsnorm_bwd_packed_kernel<T, c.value, BC, CHAIN>), dim3(nbp), dim3(NORM_THREADS), 0,
+                                                (hipStream_t)stream, (const T*)dy, (const T*)x, scale, rinv, (T*)dx, partial, rows, (int)d, nr.R,
+                                                eps, drop_p, seed, (const T*)dres, (const T*)gelu_pre, (int)group_rows, ch));
+    return launched(name);
+  });
+}
+
+// the one-wave-per-row and the wide backward; partial_off (may be null): the plane of the offset gradient's partial rows
+int launch_bwd_unpacked(const char* name, const NormRoute& nr, int nb, const void* dy, const void* x, const float* scale, const float* rinv,
+                        void* dx, float* partial, int64_t rows, int64_t d, float eps, float drop_p, uint64_t seed, const void* dres,
+                        const void* gelu_pre, int64_t d_part, float* partial_off, int dtype, void* stream) {
+  if (nr.kind == NORM_ROW) {
+    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(rmsnorm_bwd_kernel<T>, dim3(nb), dim3(NORM_THREADS), 0, (hipStream_t)stream, (const T*)dy,
+                                                (const T*)x, scale, rinv, (T*)dx, partial, rows, (int)d, eps, drop_p, seed, (const T*)dres,
+                                                (const T*)gelu_pre, (int)d_part, partial_off));
+    return launched(name);
+  }
+  auto wide = [&](auto v, auto off) -> int {
+    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((rmsnorm_bwd_wide_kernel<T, v.value, off.value>), dim3(nb), dim3(NORM_THREADS), 0,
+                                                (hipStream_t)stream, (const T*)dy, (const T*)x, scale, rinv, (T*)dx, partial, rows, (int)d, eps,
+                                                drop_p, seed, (const T*)dres, (const T*)gelu_pre, (int)d_part, partial_off));
+    return launched(name);
+  };
+  return switch_v(nr.V, [&](auto v) -> int { return partial_off ? wide(v, std::true_type{}) : wide(v, std::false_type{}); });
+}
+
+int launch_ln_fwd(const char* name, const NormRoute& nr, const void* x, const float* gamma, const float* beta, void* y, float* stats,
+                  int64_t rows, int64_t d, float eps, int dtype, void* stream) {
+  if (nr.kind == NORM_ROW) {
+    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(layernorm_fwd_kernel<T>, dim3(norm_blocks(rows)), dim3(NORM_THREADS), 0, (hipStream_t)stream,
+                                                (const T*)x, gamma, beta, (T*)y, stats, rows, (int)d, eps));
+    return launched(name);
+  }
+  return switch_v(nr.V, [&](auto v) -> int {
+    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((layernorm_fwd_wide_kernel<T, v.value>), dim3(norm_blocks(rows)), dim3(NORM_THREADS), 0,
+                                                (hipStream_t)stream, (const T*)x, gamma, beta, (T*)y, stats, rows, (int)d, eps));
+    return launched(name);
+  });
+}
+
+int launch_ln_bwd(const char* name, const NormRoute& nr, int nb, const void* dy, const void* x, const float* gamma, const float* stats, void* dx,
+                  float* partial, int64_t rows, int64_t d, int dtype, void* stream) {
+  if (nr.kind == NORM_ROW) {
+    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(layernorm_bwd_kernel<T>, dim3(nb), dim3(NORM_THREADS), 0, (hipStream_t)stream, (const T*)dy,
+                                                (const T*)x, gamma, stats, (T*)dx, partial, rows, (int)d));
+    return launched(name);
+  }
+  return switch_v(nr.V, [&](auto v) -> int {
+    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((layernorm_bwd_wide_kernel<T, v.value>), dim3(nb), dim3(NORM_THREADS), 0, (hipStream_t)stream,
+                                                (const T*)dy, (const T*)x, gamma, stats, (T*)dx, partial, rows, (int)d));
+    return launched(name);
+  });
+}
+
+// ---- RMSNorm forward / backward, full and partial form.  The full form (d_part = d, no offset) may pack; the partial one never does. ----
+int rmsnorm_fwd_any(const char* name, bool may_pack, const void* x, const float* scale, const float* offset, void* y, float* rinv, int64_t rows,
+                    int64_t d, int64_t d_part, float eps, float drop_p, uint64_t seed, int dtype, void* stream) {
+  MEANT_REQUIRE(x && scale && y && rinv, MEANT_ERR_ARG, "%s: null pointer", name);
+  MEANT_REQUIRE(rows >= 0 && d > 0 && d <= NORM_MAX_D && d_part >= 1 && d_part <= d, MEANT_ERR_UNSUPPORTED,
+                "%s: unsupported d=%lld, d_part=%lld: need 1 <= d_part <= d", name, (long long)d, (long long)d_part);
+  MEANT_REQUIRE(drop_p >= 0.f && drop_p < 1.f, MEANT_ERR_ARG, "%s: drop_p out of range", name);
+  const NormRoute nr = norm_route(rows, d, may_pack);
+  const size_t eb = dtype_bytes(dtype);
+  MEANT_REQUIRE(norm_aligned(nr, x, eb) && norm_aligned(nr, y, eb) && norm_aligned(nr, scale, 4), MEANT_ERR_ARG, "%s: alignment", name);
+  if (rows == 0) return MEANT_OK;
+  if (nr.kind == NORM_PACKED) return launch_fwd_packed(name, nr, x, scale, y, rinv, rows, d, eps, drop_p, seed, dtype, stream);
+  return launch_fwd_unpacked(name, nr, x, scale, y, rinv, rows, d, eps, drop_p, seed, d_part, offset, dtype, stream);
 }
 
 // dscale (and doffset, if not null) from the per-block partial rows in `workspace` (meant_rmsnorm_bwd_ws bytes)
-int rmsnorm_bwd_wide(const void* dy, const void* x, const float* scale, const float* rinv, void* dx, float* dscale, float* doffset,
-                     int64_t rows, int64_t d, int64_t d_part, float eps, float drop_p, uint64_t seed, const void* dres, const void* gelu_pre,
-                     int dtype, void* workspace, void* stream, const char* name) {
-  const int nb = norm_blocks(rows);
+int rmsnorm_bwd_any(const char* name, bool may_pack, const void* dy, const void* x, const float* scale, const float* rinv, void* dx, float* dscale,
+                    float* doffset, int64_t rows, int64_t d, int64_t d_part, float eps, float drop_p, uint64_t seed, const void* dres,
+                    const void* gelu_pre, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  MEANT_REQUIRE(dy && x && scale && rinv && dx && dscale && workspace, MEANT_ERR_ARG, "%s: null pointer", name);
+  MEANT_REQUIRE(rows > 0 && d > 0 && d <= NORM_MAX_D && d_part >= 1 && d_part <= d, MEANT_ERR_UNSUPPORTED,
+                "%s: unsupported d=%lld, d_part=%lld: need 1 <= d_part <= d", name, (long long)d, (long long)d_part);
+  MEANT_REQUIRE(workspace_bytes >= meant_rmsnorm_bwd_ws(rows, d), MEANT_ERR_WORKSPACE, "%s: workspace too small", name);
+  const NormRoute nr = norm_route(rows, d, may_pack);
   float* part1 = (float*)workspace;
-  float* part2 = doffset ? part1 + (size_t)nb * d : nullptr;
-#define LAUNCH_BW(VV, OO)                                                                                                     \
-  DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((rmsnorm_bwd_wide_kernel<T, VV, OO>), dim3(nb), dim3(NORM_THREADS), 0, (hipStream_t)stream, \
-                                              (const T*)dy, (const T*)x, scale, rinv, (T*)dx, part1, rows, (int)d, eps, drop_p, seed,  \
-                                              (const T*)dres, (const T*)gelu_pre, (int)d_part, part2))
-  if (d % 8 == 0) { if (doffset) LAUNCH_BW(8, true); else LAUNCH_BW(8, false); }
-  else { if (doffset) LAUNCH_BW(1, true); else LAUNCH_BW(1, false); }
-#undef LAUNCH_BW
-  MEANT_LAUNCH_CHECK(name);
-  int rc = colsum_launch(part1, d, dscale, nb, d, MEANT_F32, 0, (hipStream_t)stream);
-  if (rc || !doffset) return rc;
-  return colsum_launch(part2, d, doffset, nb, d, MEANT_F32, 0, (hipStream_t)stream);
+  if (nr.kind == NORM_PACKED) {
+    const int nbp = packed_blocks_bwd(rows / nr.R);
+    const int rc = launch_bwd_packed<0, false>(name, nr, nbp, dy, x, scale, rinv, dx, part1, rows, d, eps, drop_p, seed, dres, gelu_pre, 1,
+                                                NormChain{}, dtype, stream);
+    return rc ? rc : norm_colsums(part1, nbp, d, dscale, nullptr, 0, stream);
+  }
+  const size_t eb = dtype_bytes(dtype);
+  MEANT_REQUIRE(nr.kind != NORM_WIDE || (norm_aligned(nr, dy, eb) && norm_aligned(nr, x, eb) && norm_aligned(nr, dx, eb) && norm_aligned(nr, scale, 4) &&
+                                         (!dres || norm_aligned(nr, dres, eb)) && (!gelu_pre || norm_aligned(nr, gelu_pre, eb))),
+                MEANT_ERR_ARG, "%s: alignment", name);
+  const int nb = norm_blocks(rows);
+  const int rc = launch_bwd_unpacked(name, nr, nb, dy, x, scale, rinv, dx, part1, rows, d, eps, drop_p, seed, dres, gelu_pre, d_part,
+                                     doffset ? part1 + (size_t)nb * d : nullptr, dtype, stream);
+  return rc ? rc : norm_colsums(part1, nb, d, dscale, doffset, 0, stream);
 }
 
 }  // namespace
-
-extern "C" int meant_rmsnorm_fwd(const void* x, const float* scale, void* y, float* rinv, int64_t rows, int64_t d,
-                                 float eps, float drop_p, uint64_t seed, int dtype, void* stream) {
-  MEANT_REQUIRE(x && scale && y && rinv, MEANT_ERR_ARG, "rmsnorm_fwd: null pointer");
-  MEANT_REQUIRE(rows >= 0 && d > 0 && d <= NORM_MAX_D, MEANT_ERR_UNSUPPORTED, "rmsnorm_fwd: unsupported d=%lld", (long long)d);
-  MEANT_REQUIRE(drop_p >= 0.f && drop_p < 1.f, MEANT_ERR_ARG, "rmsnorm_fwd: drop_p out of range");
-  if (!norm_narrow(d)) {
-    const size_t eb = dtype_bytes(dtype);
-    MEANT_REQUIRE(wide_aligned(x, d, eb) && wide_aligned(y, d, eb) && wide_aligned(scale, d, 4), MEANT_ERR_ARG, "rmsnorm_fwd: alignment");
-    if (rows == 0) return MEANT_OK;
-    return rmsnorm_fwd_wide(x, scale, y, rinv, rows, d, eps, drop_p, seed, d, nullptr, dtype, stream, "rmsnorm_fwd");
-  }
-  MEANT_REQUIRE(meant_aligned16(x) && meant_aligned16(y) && meant_aligned16(scale), MEANT_ERR_ARG, "rmsnorm_fwd: 16-byte alignment");
-  if (rows == 0) return MEANT_OK;
-  int R, C;
-  norm_packing(rows, d, R, C);
-  if (R) {
-    const int nb = packed_blocks(rows / R);
-#define LAUNCH_FWD(CC)                                                                                                        \
-    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((rmsnorm_fwd_packed_kernel<T, CC>), dim3(nb), dim3(NORM_THREADS), 0, (hipStream_t)stream, \
-                                                (const T*)x, scale, (T*)y, rinv, rows, (int)d, R, eps, drop_p, seed))
-    if (C == 1) LAUNCH_FWD(1); else if (C == 2) LAUNCH_FWD(2); else LAUNCH_FWD(3);
-#undef LAUNCH_FWD
-    MEANT_LAUNCH_CHECK("rmsnorm_fwd");
-    return MEANT_OK;
-  }
-  DISPATCH_DTYPE(dtype, T,
-                 hipLaunchKernelGGL(rmsnorm_fwd_kernel<T>, dim3(norm_blocks(rows)), dim3(NORM_THREADS), 0, (hipStream_t)stream,
-                                    (const T*)x, scale, (T*)y, rinv, rows, (int)d, eps, drop_p, seed));
-  MEANT_LAUNCH_CHECK("rmsnorm_fwd");
-  return MEANT_OK;
-}
 
 extern "C" size_t meant_rmsnorm_bwd_ws(int64_t rows, int64_t d) {
   const int64_t nb = norm_blocks(rows) > packed_blocks(rows) ? norm_blocks(rows) : packed_blocks(rows);
   return (size_t)nb * d * sizeof(float) * 2;
 }
 
+extern "C" int meant_rmsnorm_fwd(const void* x, const float* scale, void* y, float* rinv, int64_t rows, int64_t d,
+                                 float eps, float drop_p, uint64_t seed, int dtype, void* stream) {
+  return rmsnorm_fwd_any("rmsnorm_fwd", true, x, scale, nullptr, y, rinv, rows, d, d, eps, drop_p, seed, dtype, stream);
+}
+
 extern "C" int meant_rmsnorm_bwd(const void* dy, const void* x, const float* scale, const float* rinv, void* dx,
                                  float* dscale, int64_t rows, int64_t d, float eps, float drop_p, uint64_t seed,
                                  const void* dres, const void* gelu_pre, int dtype, void* workspace, size_t workspace_bytes,
                                  void* stream) {
-  MEANT_REQUIRE(dy && x && scale && rinv && dx && dscale && workspace, MEANT_ERR_ARG, "rmsnorm_bwd: null pointer");
-  MEANT_REQUIRE(rows > 0 && d > 0 && d <= NORM_MAX_D, MEANT_ERR_UNSUPPORTED, "rmsnorm_bwd: unsupported d=%lld", (long long)d);
-  MEANT_REQUIRE(workspace_bytes >= meant_rmsnorm_bwd_ws(rows, d), MEANT_ERR_WORKSPACE, "rmsnorm_bwd: workspace too small");
-  if (!norm_narrow(d)) {
-    const size_t eb = dtype_bytes(dtype);
-    MEANT_REQUIRE(wide_aligned(dy, d, eb) && wide_aligned(x, d, eb) && wide_aligned(dx, d, eb) && wide_aligned(scale, d, 4) &&
-                  (!dres || wide_aligned(dres, d, eb)) && (!gelu_pre || wide_aligned(gelu_pre, d, eb)), MEANT_ERR_ARG, "rmsnorm_bwd: alignment");
-    return rmsnorm_bwd_wide(dy, x, scale, rinv, dx, dscale, nullptr, rows, d, d, eps, drop_p, seed, dres, gelu_pre, dtype, workspace, stream,
-                            "rmsnorm_bwd");
-  }
-  int R, C;
-  norm_packing(rows, d, R, C);
-  if (R) {
-    const int nbp = packed_blocks_bwd(rows / R);
-#define LAUNCH_BWD(CC)                                                                                                        \
-    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((rmsnorm_bwd_packed_kernel<T, CC, 0>), dim3(nbp), dim3(NORM_THREADS), 0, (hipStream_t)stream, \
-                                                (const T*)dy, (const T*)x, scale, rinv, (T*)dx, (float*)workspace, rows, (int)d, R, eps,    \
-                                                drop_p, seed, (const T*)dres, (const T*)gelu_pre, 1))
-    if (C == 1) LAUNCH_BWD(1); else if (C == 2) LAUNCH_BWD(2); else LAUNCH_BWD(3);
-#undef LAUNCH_BWD
-    MEANT_LAUNCH_CHECK("rmsnorm_bwd");
-    return colsum_launch(workspace, d, dscale, nbp, d, MEANT_F32, 0, (hipStream_t)stream);
-  }
-  const int nb = norm_blocks(rows);
-  DISPATCH_DTYPE(dtype, T,
-                 hipLaunchKernelGGL(rmsnorm_bwd_kernel<T>, dim3(nb), dim3(NORM_THREADS), 0, (hipStream_t)stream, (const T*)dy,
-                                    (const T*)x, scale, rinv, (T*)dx, (float*)workspace, rows, (int)d, eps, drop_p, seed,
-                                    (const T*)dres, (const T*)gelu_pre));
-  MEANT_LAUNCH_CHECK("rmsnorm_bwd");
-  return colsum_launch(workspace, d, dscale, nb, d, MEANT_F32, 0, (hipStream_t)stream);
+  return rmsnorm_bwd_any("rmsnorm_bwd", true, dy, x, scale, rinv, dx, dscale, nullptr, rows, d, d, eps, drop_p, seed, dres, gelu_pre, dtype,
+                         workspace, workspace_bytes, stream);
 }
 
 // ---- partial / bias forms of the reference class (utils/rms_norm.py:44-57); not used by any MEANT model, generic kernels ----
 extern "C" int meant_rmsnorm_partial_fwd(const void* x, const float* scale, const float* offset, void* y, float* rinv, int64_t rows,
                                          int64_t d, int64_t d_part, float eps, int dtype, void* stream) {
-  MEANT_REQUIRE(x && scale && y && rinv, MEANT_ERR_ARG, "rmsnorm_partial_fwd: null pointer");
-  MEANT_REQUIRE(rows >= 0 && d > 0 && d <= NORM_MAX_D && d_part >= 1 && d_part <= d, MEANT_ERR_UNSUPPORTED,
-                "rmsnorm_partial_fwd: d=%lld, d_part=%lld: need 1 <= d_part <= d", (long long)d, (long long)d_part);
-  if (!norm_narrow(d)) {
-    const size_t eb = dtype_bytes(dtype);
-    MEANT_REQUIRE(wide_aligned(x, d, eb) && wide_aligned(y, d, eb) && wide_aligned(scale, d, 4), MEANT_ERR_ARG, "rmsnorm_partial_fwd: alignment");
-    if (rows == 0) return MEANT_OK;
-    return rmsnorm_fwd_wide(x, scale, y, rinv, rows, d, eps, 0.f, 0, d_part, offset, dtype, stream, "rmsnorm_partial_fwd");
-  }
-  MEANT_REQUIRE(meant_aligned16(x) && meant_aligned16(y) && meant_aligned16(scale), MEANT_ERR_ARG, "rmsnorm_partial_fwd: 16-byte alignment");
-  if (rows == 0) return MEANT_OK;
-  DISPATCH_DTYPE(dtype, T,
-                 hipLaunchKernelGGL(rmsnorm_fwd_kernel<T>, dim3(norm_blocks(rows)), dim3(NORM_THREADS), 0, (hipStream_t)stream,
-                                    (const T*)x, scale, (T*)y, rinv, rows, (int)d, eps, 0.f, (uint64_t)0, (int)d_part, offset));
-  MEANT_LAUNCH_CHECK("rmsnorm_partial_fwd");
-  return MEANT_OK;
+  return rmsnorm_fwd_any("rmsnorm_partial_fwd", false, x, scale, offset, y, rinv, rows, d, d_part, eps, 0.f, 0, dtype, stream);
 }
 
 extern "C" int meant_rmsnorm_partial_bwd(const void* dy, const void* x, const float* scale, const float* rinv, void* dx, float* dscale,
                                          float* doffset, int64_t rows, int64_t d, int64_t d_part, float eps, int dtype, void* workspace,
                                          size_t workspace_bytes, void* stream) {
-  MEANT_REQUIRE(dy && x && scale && rinv && dx && dscale && workspace, MEANT_ERR_ARG, "rmsnorm_partial_bwd: null pointer");
-  MEANT_REQUIRE(rows > 0 && d > 0 && d <= NORM_MAX_D && d_part >= 1 && d_part <= d, MEANT_ERR_UNSUPPORTED, "rmsnorm_partial_bwd: unsupported shape");
-  MEANT_REQUIRE(workspace_bytes >= meant_rmsnorm_bwd_ws(rows, d), MEANT_ERR_WORKSPACE, "rmsnorm_partial_bwd: workspace too small");
-  if (!norm_narrow(d)) {
-    const size_t eb = dtype_bytes(dtype);
-    MEANT_REQUIRE(wide_aligned(dy, d, eb) && wide_aligned(x, d, eb) && wide_aligned(dx, d, eb) && wide_aligned(scale, d, 4), MEANT_ERR_ARG,
-                  "rmsnorm_partial_bwd: alignment");
-    return rmsnorm_bwd_wide(dy, x, scale, rinv, dx, dscale, doffset, rows, d, d_part, eps, 0.f, 0, nullptr, nullptr, dtype, workspace, stream,
-                            "rmsnorm_partial_bwd");
-  }
-  const int nb = norm_blocks(rows);
-  float* part1 = (float*)workspace;
-  float* part2 = doffset ? part1 + (size_t)nb * d : nullptr;
-  DISPATCH_DTYPE(dtype, T,
-                 hipLaunchKernelGGL(rmsnorm_bwd_kernel<T>, dim3(nb), dim3(NORM_THREADS), 0, (hipStream_t)stream, (const T*)dy,
-                                    (const T*)x, scale, rinv, (T*)dx, part1, rows, (int)d, eps, 0.f, (uint64_t)0,
-                                    (const T*)nullptr, (const T*)nullptr, (int)d_part, part2));
-  MEANT_LAUNCH_CHECK("rmsnorm_partial_bwd");
-  int rc = colsum_launch(part1, d, dscale, nb, d, MEANT_F32, 0, (hipStream_t)stream);
-  if (rc || !doffset) return rc;
-  return colsum_launch(part2, d, doffset, nb, d, MEANT_F32, 0, (hipStream_t)stream);
+  return rmsnorm_bwd_any("rmsnorm_partial_bwd", false, dy, x, scale, rinv, dx, dscale, doffset, rows, d, d_part, eps, 0.f, 0, nullptr, nullptr,
+                         dtype, workspace, workspace_bytes, stream);
 }
 
 // ---- pooled forms (the norms whose output or input feeds the sequence mean-pool only) ----
 extern "C" int meant_rmsnorm_pooled_ok(int64_t rows, int64_t d, int64_t group_rows) {
-  if (rows <= 0 || d <= 0 || d % 8 || d > MAXC * 512 || group_rows <= 0 || rows % group_rows) return 0;
-  int R, C;
-  norm_packing(rows, d, R, C);
-  return R != 0 && group_rows % R == 0;
+  if (group_rows <= 0 || rows % group_rows) return 0;
+  const NormRoute nr = norm_route(rows, d);
+  return nr.kind == NORM_PACKED && group_rows % nr.R == 0;
 }
 
 extern "C" int meant_rmsnorm_fwd_pooled(const void* x, const float* scale, void* y, float* rinv, float* pooled, int64_t rows, int64_t d,
                                         int64_t group_rows, int pool_input, int gelu_input, float eps, float drop_p, uint64_t seed,
                                         int dtype, void* stream) {
+  const char* name = "rmsnorm_fwd_pooled";
   MEANT_REQUIRE(x && scale && rinv && pooled, MEANT_ERR_ARG, "rmsnorm_fwd_pooled: null pointer");   // y == NULL with pool_input: statistics + means of x only
   MEANT_REQUIRE(!(pool_input && gelu_input), MEANT_ERR_UNSUPPORTED, "rmsnorm_fwd_pooled: gelu_input goes with pool_input == 0");
   MEANT_REQUIRE(meant_rmsnorm_pooled_ok(rows, d, group_rows), MEANT_ERR_UNSUPPORTED,
                 "rmsnorm_fwd_pooled: rows=%lld d=%lld group_rows=%lld is not a packed shape (see meant_rmsnorm_pooled_ok)", (long long)rows,
                 (long long)d, (long long)group_rows);
-  MEANT_REQUIRE(meant_aligned16(x) && meant_aligned16(scale) && (!y || meant_aligned16(y)), MEANT_ERR_ARG, "rmsnorm_fwd_pooled: 16-byte alignment");
+  const NormRoute nr = norm_route(rows, d);
+  const size_t eb = dtype_bytes(dtype);
+  MEANT_REQUIRE(norm_aligned(nr, x, eb) && norm_aligned(nr, scale, 4) && (!y || norm_aligned(nr, y, eb)), MEANT_ERR_ARG,
+                "rmsnorm_fwd_pooled: 16-byte alignment");
   MEANT_REQUIRE(drop_p >= 0.f && drop_p < 1.f, MEANT_ERR_ARG, "rmsnorm_fwd_pooled: drop_p out of range");
-  int R, C;
-  norm_packing(rows, d, R, C);
   const int64_t ngroups = rows / group_rows;
-  const int nb = (int)(ngroups < NORM_PACKED_BLOCKS ? ngroups : NORM_PACKED_BLOCKS);
-#define LAUNCH_FWDP(CC, PP, GG)                                                                                               \
-    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((rmsnorm_fwd_pooled_kernel<T, CC, PP, GG>), dim3(nb), dim3(NORM_THREADS), 0, (hipStream_t)stream, \
-                                                (const T*)x, scale, (T*)y, rinv, ngroups, (int)d, R, eps, drop_p, seed, pooled, (int)group_rows))
-#define LAUNCH_FWDP_C(PP, GG) { if (C == 1) LAUNCH_FWDP(1, PP, GG); else if (C == 2) LAUNCH_FWDP(2, PP, GG); else LAUNCH_FWDP(3, PP, GG); }
-  if (pool_input) LAUNCH_FWDP_C(2, false)
-  else if (gelu_input) LAUNCH_FWDP_C(1, true)
-  else LAUNCH_FWDP_C(1, false)
-#undef LAUNCH_FWDP_C
-#undef LAUNCH_FWDP
-  MEANT_LAUNCH_CHECK("rmsnorm_fwd_pooled");
-  return MEANT_OK;
+  if (pool_input) return launch_fwd_pooled<2, false>(name, nr, x, scale, y, rinv, pooled, ngroups, d, group_rows, eps, drop_p, seed, dtype, stream);
+  if (gelu_input) return launch_fwd_pooled<1, true>(name, nr, x, scale, y, rinv, pooled, ngroups, d, group_rows, eps, drop_p, seed, dtype, stream);
+  return launch_fwd_pooled<1, false>(name, nr, x, scale, y, rinv, pooled, ngroups, d, group_rows, eps, drop_p, seed, dtype, stream);
 }
 
 extern "C" int meant_rmsnorm_bwd_pooled(const void* dy, int dy_pooled, const void* x, const float* scale, const float* rinv, void* dx,
@@ -1331,94 +1360,62 @@ extern "C" int meant_rmsnorm_bwd_pooled(const void* dy, int dy_pooled, const voi
   MEANT_REQUIRE((dy_pooled || dres_pooled) && (!dres_pooled || dres), MEANT_ERR_ARG, "rmsnorm_bwd_pooled: nothing pooled (use meant_rmsnorm_bwd)");
   MEANT_REQUIRE(meant_rmsnorm_pooled_ok(rows, d, group_rows) && rows < 2147483647LL, MEANT_ERR_UNSUPPORTED, "rmsnorm_bwd_pooled: not a packed shape");
   MEANT_REQUIRE(workspace_bytes >= meant_rmsnorm_bwd_ws(rows, d), MEANT_ERR_WORKSPACE, "rmsnorm_bwd_pooled: workspace too small");
-  int R, C;
-  norm_packing(rows, d, R, C);
-  const int nbp = packed_blocks_bwd(rows / R);
+  const NormRoute nr = norm_route(rows, d);
+  const int nbp = packed_blocks_bwd(rows / nr.R);
   const int bc = (dy_pooled ? 1 : 0) | (dres_pooled ? 2 : 0) | (x ? 0 : 4);
   MEANT_REQUIRE(bc == 1 || bc == 2 || bc == 3 || bc == 5, MEANT_ERR_UNSUPPORTED, "rmsnorm_bwd_pooled: unsupported combination");
-#define LAUNCH_BWDP(CC, BB)                                                                                                   \
-    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((rmsnorm_bwd_packed_kernel<T, CC, BB>), dim3(nbp), dim3(NORM_THREADS), 0, (hipStream_t)stream, \
-                                                (const T*)dy, (const T*)x, scale, rinv, (T*)dx, (float*)workspace, rows, (int)d, R, eps,    \
-                                                drop_p, seed, (const T*)dres, (const T*)gelu_pre, (int)group_rows))
-#define LAUNCH_BWDP_C(BB) { if (C == 1) LAUNCH_BWDP(1, BB); else if (C == 2) LAUNCH_BWDP(2, BB); else LAUNCH_BWDP(3, BB); }
-  if (bc == 1) LAUNCH_BWDP_C(1) else if (bc == 2) LAUNCH_BWDP_C(2) else if (bc == 3) LAUNCH_BWDP_C(3) else LAUNCH_BWDP_C(5)
-#undef LAUNCH_BWDP_C
-#undef LAUNCH_BWDP
-  MEANT_LAUNCH_CHECK("rmsnorm_bwd_pooled");
-  return colsum_launch(workspace, d, dscale, nbp, d, MEANT_F32, 0, (hipStream_t)stream);
+  auto launch = [&](auto b) -> int {
+    return launch_bwd_packed<decltype(b)::value, false>("rmsnorm_bwd_pooled", nr, nbp, dy, x, scale, rinv, dx, (float*)workspace, rows, d, eps,
+                                                        drop_p, seed, dres, gelu_pre, group_rows, NormChain{}, dtype, stream);
+  };
+  const int rc = bc == 1 ? launch(Int<1>{}) : bc == 2 ? launch(Int<2>{}) : bc == 3 ? launch(Int<3>{}) : launch(Int<5>{});
+  return rc ? rc : norm_colsums((const float*)workspace, nbp, d, dscale, nullptr, 0, stream);
 }
 
 // ---- RMSNorm folded into the consumer Linear (meant_linear_fwd_rowscale): statistics pass and chained backward ----
 extern "C" int meant_rmsnorm_stats(const void* x, float* rinv, int64_t rows, int64_t d, float eps, int dtype, void* stream) {
   MEANT_REQUIRE(x && rinv, MEANT_ERR_ARG, "rmsnorm_stats: null pointer");
-  MEANT_REQUIRE(meant_aligned16(x), MEANT_ERR_ARG, "rmsnorm_stats: 16-byte alignment");
-  int R, C;
-  norm_packing(rows, d, R, C);
-  MEANT_REQUIRE(rows > 0 && d > 0 && d % 8 == 0 && d <= MAXC * 512 && R != 0, MEANT_ERR_UNSUPPORTED,
+  const NormRoute nr = norm_route(rows, d);
+  MEANT_REQUIRE(nr.kind == NORM_PACKED, MEANT_ERR_UNSUPPORTED,
                 "rmsnorm_stats: rows=%lld d=%lld is not a packed shape (see meant_rmsnorm_pooled_ok)", (long long)rows, (long long)d);
-  const int nb = packed_blocks(rows / R);
-#define LAUNCH_STATS(CC)                                                                                                      \
-    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((rmsnorm_stats_packed_kernel<T, CC>), dim3(nb), dim3(NORM_THREADS), 0, (hipStream_t)stream, \
-                                                (const T*)x, rinv, rows, (int)d, R, eps))
-  if (C == 1) LAUNCH_STATS(1); else if (C == 2) LAUNCH_STATS(2); else LAUNCH_STATS(3);
-#undef LAUNCH_STATS
-  MEANT_LAUNCH_CHECK("rmsnorm_stats");
-  return MEANT_OK;
+  MEANT_REQUIRE(norm_aligned(nr, x, dtype_bytes(dtype)), MEANT_ERR_ARG, "rmsnorm_stats: 16-byte alignment");
+  return launch_stats_packed("rmsnorm_stats", nr, x, rinv, rows, d, eps, dtype, stream);
 }
 
 extern "C" int meant_rmsnorm_bwd_chain(const void* dy, int dy_pooled, const void* x, const float* scale, const float* rinv, void* dx_scaled,
                                        float* dscale, int64_t rows, int64_t d, int64_t group_rows, float eps, float drop_p, uint64_t seed,
                                        const void* gelu_pre, const float* up_rinv, const float* up_bias, float up_eps, int64_t up_d,
                                        float* kcoef, float* dbias_up, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* name = "rmsnorm_bwd_chain";
   MEANT_REQUIRE(dy && gelu_pre && scale && rinv && dx_scaled && dscale && up_rinv && up_bias && kcoef && dbias_up && workspace, MEANT_ERR_ARG,
                 "rmsnorm_bwd_chain: null pointer");
   MEANT_REQUIRE((x != nullptr) != (dy_pooled != 0), MEANT_ERR_UNSUPPORTED,
                 "rmsnorm_bwd_chain: either token-level dy with the stored activation x, or pooled dy with x formed from gelu_pre");
-  int R, C;
-  norm_packing(rows, d, R, C);
-  MEANT_REQUIRE(rows > 0 && rows < 2147483647LL && R != 0 && (!dy_pooled || (group_rows > 0 && rows % group_rows == 0 && group_rows % R == 0)),
-                MEANT_ERR_UNSUPPORTED, "rmsnorm_bwd_chain: not a packed shape");
+  const NormRoute nr = norm_route(rows, d);
+  MEANT_REQUIRE(nr.kind == NORM_PACKED && rows < 2147483647LL && (!dy_pooled || meant_rmsnorm_pooled_ok(rows, d, group_rows)),
+                MEANT_ERR_UNSUPPORTED, "rmsnorm_bwd_chain: rows=%lld d=%lld is not a packed shape (see meant_rmsnorm_pooled_ok)", (long long)rows,
+                (long long)d);
   MEANT_REQUIRE(workspace_bytes >= meant_rmsnorm_bwd_ws(rows, d), MEANT_ERR_WORKSPACE, "rmsnorm_bwd_chain: workspace too small");
-  const int nbp = packed_blocks_bwd(rows / R);
+  const int nbp = packed_blocks_bwd(rows / nr.R);
   float* part1 = (float*)workspace;
-  float* part2 = part1 + (size_t)nbp * d;
   MEANT_REQUIRE(up_d > 0 && up_d < (1LL << 30), MEANT_ERR_ARG, "rmsnorm_bwd_chain: bad up_d");
-  const NormChain ch{up_rinv, up_bias, kcoef, part2, up_eps, (int)up_d};
-#define LAUNCH_CH(CC, BB)                                                                                                     \
-    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((rmsnorm_bwd_packed_kernel<T, CC, BB, true>), dim3(nbp), dim3(NORM_THREADS), 0, (hipStream_t)stream, \
-                                                (const T*)dy, (const T*)x, scale, rinv, (T*)dx_scaled, part1, rows, (int)d, R, eps, drop_p, seed,  \
-                                                (const T*)nullptr, (const T*)gelu_pre, (int)(dy_pooled ? group_rows : 1), ch))
-#define LAUNCH_CH_C(BB) { if (C == 1) LAUNCH_CH(1, BB); else if (C == 2) LAUNCH_CH(2, BB); else LAUNCH_CH(3, BB); }
-  if (dy_pooled) LAUNCH_CH_C(5) else LAUNCH_CH_C(0)
-#undef LAUNCH_CH_C
-#undef LAUNCH_CH
-  MEANT_LAUNCH_CHECK("rmsnorm_bwd_chain");
-  int rc = colsum_launch(part1, d, dscale, nbp, d, MEANT_F32, 0, (hipStream_t)stream);
-  if (rc) return rc;
-  return colsum_launch(part2, d, dbias_up, nbp, d, MEANT_F32, 1, (hipStream_t)stream);      // += : a gradient sink may be handed in
+  const NormChain ch{up_rinv, up_bias, kcoef, part1 + (size_t)nbp * d, up_eps, (int)up_d};
+  const int rc = dy_pooled ? launch_bwd_packed<5, true>(name, nr, nbp, dy, x, scale, rinv, dx_scaled, part1, rows, d, eps, drop_p, seed, nullptr,
+                                                        gelu_pre, group_rows, ch, dtype, stream)
+                           : launch_bwd_packed<0, true>(name, nr, nbp, dy, x, scale, rinv, dx_scaled, part1, rows, d, eps, drop_p, seed, nullptr,
+                                                        gelu_pre, 1, ch, dtype, stream);
+  return rc ? rc : norm_colsums(part1, nbp, d, dscale, dbias_up, 1, stream);      // dbias_up +=: a gradient sink may be handed in
 }
 
 extern "C" int meant_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* stats,
                                    int64_t rows, int64_t d, float eps, int dtype, void* stream) {
   MEANT_REQUIRE(x && gamma && beta && y && stats, MEANT_ERR_ARG, "layernorm_fwd: null pointer");
   MEANT_REQUIRE(rows > 0 && d > 0 && d <= NORM_MAX_D, MEANT_ERR_UNSUPPORTED, "layernorm_fwd: unsupported d=%lld", (long long)d);
-  if (!norm_narrow(d)) {
-    const size_t eb = dtype_bytes(dtype);
-    MEANT_REQUIRE(wide_aligned(x, d, eb) && wide_aligned(y, d, eb) && wide_aligned(gamma, d, 4) && wide_aligned(beta, d, 4), MEANT_ERR_ARG,
-                  "layernorm_fwd: alignment");
-#define LAUNCH_LNW(VV)                                                                                                        \
-    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((layernorm_fwd_wide_kernel<T, VV>), dim3(norm_blocks(rows)), dim3(NORM_THREADS), 0,      \
-                                                (hipStream_t)stream, (const T*)x, gamma, beta, (T*)y, stats, rows, (int)d, eps))
-    if (d % 8 == 0) LAUNCH_LNW(8); else LAUNCH_LNW(1);
-#undef LAUNCH_LNW
-    MEANT_LAUNCH_CHECK("layernorm_fwd");
-    return MEANT_OK;
-  }
-  DISPATCH_DTYPE(dtype, T,
-                 hipLaunchKernelGGL(layernorm_fwd_kernel<T>, dim3(norm_blocks(rows)), dim3(NORM_THREADS), 0, (hipStream_t)stream,
-                                    (const T*)x, gamma, beta, (T*)y, stats, rows, (int)d, eps));
-  MEANT_LAUNCH_CHECK("layernorm_fwd");
-  return MEANT_OK;
+  const NormRoute nr = norm_route(rows, d, false);
+  const size_t eb = dtype_bytes(dtype);
+  MEANT_REQUIRE(nr.kind != NORM_WIDE || (norm_aligned(nr, x, eb) && norm_aligned(nr, y, eb) && norm_aligned(nr, gamma, 4) && norm_aligned(nr, beta, 4)),
+                MEANT_ERR_ARG, "layernorm_fwd: alignment");
+  return launch_ln_fwd("layernorm_fwd", nr, x, gamma, beta, y, stats, rows, d, eps, dtype, stream);
 }
 
 extern "C" int meant_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* stats, void* dx,
@@ -1427,23 +1424,11 @@ extern "C" int meant_layernorm_bwd(const void* dy, const void* x, const float* g
   MEANT_REQUIRE(dy && x && gamma && stats && dx && dgamma && dbeta && workspace, MEANT_ERR_ARG, "layernorm_bwd: null pointer");
   MEANT_REQUIRE(rows > 0 && d > 0 && d <= NORM_MAX_D, MEANT_ERR_UNSUPPORTED, "layernorm_bwd: unsupported d=%lld", (long long)d);
   MEANT_REQUIRE(workspace_bytes >= meant_rmsnorm_bwd_ws(rows, d), MEANT_ERR_WORKSPACE, "layernorm_bwd: workspace too small");
+  const NormRoute nr = norm_route(rows, d, false);
+  const size_t eb = dtype_bytes(dtype);
+  MEANT_REQUIRE(nr.kind != NORM_WIDE || (norm_aligned(nr, dy, eb) && norm_aligned(nr, x, eb) && norm_aligned(nr, dx, eb) && norm_aligned(nr, gamma, 4)),
+                MEANT_ERR_ARG, "layernorm_bwd: alignment");
   const int nb = norm_blocks(rows);
-  if (!norm_narrow(d)) {
-    const size_t eb = dtype_bytes(dtype);
-    MEANT_REQUIRE(wide_aligned(dy, d, eb) && wide_aligned(x, d, eb) && wide_aligned(dx, d, eb) && wide_aligned(gamma, d, 4), MEANT_ERR_ARG,
-                  "layernorm_bwd: alignment");
-#define LAUNCH_LNBW(VV)                                                                                                       \
-    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((layernorm_bwd_wide_kernel<T, VV>), dim3(nb), dim3(NORM_THREADS), 0, (hipStream_t)stream, \
-                                                (const T*)dy, (const T*)x, gamma, stats, (T*)dx, (float*)workspace, rows, (int)d))
-    if (d % 8 == 0) LAUNCH_LNBW(8); else LAUNCH_LNBW(1);
-#undef LAUNCH_LNBW
-  } else {
-    DISPATCH_DTYPE(dtype, T,
-                   hipLaunchKernelGGL(layernorm_bwd_kernel<T>, dim3(nb), dim3(NORM_THREADS), 0, (hipStream_t)stream, (const T*)dy,
-                                      (const T*)x, gamma, stats, (T*)dx, (float*)workspace, rows, (int)d));
-  }
-  MEANT_LAUNCH_CHECK("layernorm_bwd");
-  int rc = colsum_launch(workspace, d, dgamma, nb, d, MEANT_F32, 0, (hipStream_t)stream);
-  if (rc) return rc;
-  return colsum_launch((const float*)workspace + (size_t)nb * d, d, dbeta, nb, d, MEANT_F32, 0, (hipStream_t)stream);
+  const int rc = launch_ln_bwd("layernorm_bwd", nr, nb, dy, x, gamma, stats, dx, (float*)workspace, rows, d, dtype, stream);
+  return rc ? rc : norm_colsums((const float*)workspace, nb, d, dgamma, dbeta, 0, stream);
 }

@@ -1,4 +1,5 @@
-// K9 temporal (lag-axis) attention core at long lags (L > 64; elementwise.hip keeps the one-wave kernels for 1 <= L <= 64).
+// K9 temporal (lag-axis) attention core: meant_temporal_attn_fwd / _bwd.  One-wave kernels for 1 <= L <= 64 (at the end of the
+// kernel section), and the long-lag kernels described here for L > 64 (or any L under the option `temporal_long`).
 //   q [B, D] (last lag step), kv [B*L, 2D] (K | V), p [B, H, L] fp32: raw scores while a kernel runs, softmax weights after it.
 //
 // Row-sweep kernels (Dh % 8 == 0, Dh <= 512, 16-byte aligned operands): one workgroup of four waves per (b, h).  A lane owns
@@ -324,10 +325,89 @@ int tl_lpr_log2(int Dh, const void* a, const void* b, const void* c, const void*
   return lg;
 }
 
+// ------------------------------------------------------------------------------------------------
+// short lags: one wave per (b, h); L <= 64 keys, any Dh
+template <typename T>
+__global__ __launch_bounds__(256) void temporal_fwd_kernel(const T* __restrict__ q, const T* __restrict__ kv, T* __restrict__ o,
+                                                            float* __restrict__ p, int64_t B, int L, int H, int Dh, float scale) {
+  __shared__ float sc[4][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t bh = (int64_t)blockIdx.x * 4 + wave;
+  if (bh >= B * H) return;
+  const int64_t b = bh / H;
+  const int h = (int)(bh - b * H);
+  const int D = H * Dh;
+  const T* qp = q + b * D + h * Dh;
+  for (int l = 0; l < L; ++l) {
+    const T* kp = kv + (b * L + l) * (int64_t)(2 * D) + h * Dh;
+    float s = 0.f;
+    for (int e = lane; e < Dh; e += 64) s += to_f(qp[e]) * to_f(kp[e]);
+    s = wave_sum(s) * scale;
+    if (lane == 0) sc[wave][l] = s;
+  }
+  __builtin_amdgcn_wave_barrier();
+  float m = -INFINITY;
+  for (int l = 0; l < L; ++l) m = fmaxf(m, sc[wave][l]);
+  float sum = 0.f;
+  for (int l = 0; l < L; ++l) sum += __expf(sc[wave][l] - m);
+  const float inv = 1.f / sum;
+  __builtin_amdgcn_wave_barrier();
+  if (lane < L) {
+    const float w = __expf(sc[wave][lane] - m) * inv;
+    p[bh * L + lane] = w;
+    sc[wave][lane] = w;
+  }
+  __builtin_amdgcn_wave_barrier();
+  for (int e = lane; e < Dh; e += 64) {
+    float acc = 0.f;
+    for (int l = 0; l < L; ++l) acc += sc[wave][l] * to_f(kv[(b * L + l) * (int64_t)(2 * D) + D + h * Dh + e]);
+    o[b * D + h * Dh + e] = from_f<T>(acc);
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void temporal_bwd_kernel(const T* __restrict__ q, const T* __restrict__ kv,
+                                                            const float* __restrict__ p, const T* __restrict__ dout,
+                                                            T* __restrict__ dq, T* __restrict__ dkv, int64_t B, int L, int H,
+                                                            int Dh, float scale) {
+  __shared__ float ds[4][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t bh = (int64_t)blockIdx.x * 4 + wave;
+  if (bh >= B * H) return;
+  const int64_t b = bh / H;
+  const int h = (int)(bh - b * H);
+  const int D = H * Dh;
+  const T* dop = dout + b * D + h * Dh;
+  float dot = 0.f;                                   // sum_l p_l dp_l
+  for (int l = 0; l < L; ++l) {
+    const T* vp = kv + (b * L + l) * (int64_t)(2 * D) + D + h * Dh;
+    float s = 0.f;
+    for (int e = lane; e < Dh; e += 64) s += to_f(dop[e]) * to_f(vp[e]);
+    s = wave_sum(s);                                 // dp_l
+    if (lane == 0) ds[wave][l] = s;
+    dot += p[bh * L + l] * s;
+  }
+  __builtin_amdgcn_wave_barrier();
+  if (lane < L) ds[wave][lane] = p[bh * L + lane] * (ds[wave][lane] - dot) * scale;
+  __builtin_amdgcn_wave_barrier();
+  for (int e = lane; e < Dh; e += 64) {
+    const float qe = to_f(q[b * D + h * Dh + e]);
+    const float doe = to_f(dop[e]);
+    float dqe = 0.f;
+    for (int l = 0; l < L; ++l) {
+      const int64_t row = (b * L + l) * (int64_t)(2 * D);
+      dqe += ds[wave][l] * to_f(kv[row + h * Dh + e]);
+      dkv[row + h * Dh + e] = from_f<T>(ds[wave][l] * qe);
+      dkv[row + D + h * Dh + e] = from_f<T>(p[bh * L + l] * doe);
+    }
+    dq[b * D + h * Dh + e] = from_f<T>(dqe);
+  }
+}
+
 }  // namespace
 
-int temporal_long_fwd(const void* q, const void* kv, void* o, float* p, int64_t B, int L, int H, int Dh, float scale, int dtype,
-                      hipStream_t stream) {
+static int temporal_long_fwd(const void* q, const void* kv, void* o, float* p, int64_t B, int L, int H, int Dh, float scale, int dtype,
+                             hipStream_t stream) {
   const int64_t BH = B * H;
   MEANT_REQUIRE(BH <= 2147483647LL, MEANT_ERR_UNSUPPORTED, "temporal_attn_fwd: B * H = %lld exceeds the grid limit", (long long)BH);
   const int lg = tl_lpr_log2(Dh, q, kv, o, nullptr, nullptr);
@@ -345,8 +425,8 @@ int temporal_long_fwd(const void* q, const void* kv, void* o, float* p, int64_t 
   return MEANT_OK;
 }
 
-int temporal_long_bwd(const void* q, const void* kv, const float* p, const void* do_, void* dq, void* dkv, int64_t B, int L, int H,
-                      int Dh, float scale, int dtype, hipStream_t stream) {
+static int temporal_long_bwd(const void* q, const void* kv, const float* p, const void* do_, void* dq, void* dkv, int64_t B, int L, int H,
+                             int Dh, float scale, int dtype, hipStream_t stream) {
   const int64_t BH = B * H;
   MEANT_REQUIRE(BH <= 2147483647LL, MEANT_ERR_UNSUPPORTED, "temporal_attn_bwd: B * H = %lld exceeds the grid limit", (long long)BH);
   const int lg = tl_lpr_log2(Dh, q, kv, do_, dq, dkv);
@@ -361,5 +441,26 @@ int temporal_long_bwd(const void* q, const void* kv, const float* p, const void*
   }
   MEANT_LAUNCH_CHECK("temporal_attn_bwd (long lag)");
   meant_route_hit(ROUTE_TEMPORAL_LONG);
+  return MEANT_OK;
+}
+
+extern "C" int meant_temporal_attn_fwd(const void* q, const void* kv, void* o, float* p, int64_t B, int L, int H, int Dh, float scale, int dtype, void* stream) {
+  MEANT_REQUIRE(q && kv && o && p && B > 0 && H > 0 && Dh > 0, MEANT_ERR_ARG, "temporal_attn_fwd: bad argument");
+  MEANT_REQUIRE(L > 0, MEANT_ERR_UNSUPPORTED, "temporal_attn_fwd: lag %d is not positive", L);
+  if (L > 64 || meant_opt(MEANT_OPT_TEMPORAL_LONG)) return temporal_long_fwd(q, kv, o, p, B, L, H, Dh, scale, dtype, (hipStream_t)stream);
+  DISPATCH_DTYPE(dtype, T,
+                 hipLaunchKernelGGL(temporal_fwd_kernel<T>, dim3((unsigned)ceil_div(B * H, 4)), dim3(256), 0, (hipStream_t)stream,
+                                    (const T*)q, (const T*)kv, (T*)o, p, B, L, H, Dh, scale));
+  MEANT_LAUNCH_CHECK("temporal_attn_fwd");
+  return MEANT_OK;
+}
+extern "C" int meant_temporal_attn_bwd(const void* q, const void* kv, const float* p, const void* do_, void* dq, void* dkv, int64_t B, int L, int H, int Dh, float scale, int dtype, void* stream) {
+  MEANT_REQUIRE(q && kv && p && do_ && dq && dkv && B > 0 && H > 0 && Dh > 0, MEANT_ERR_ARG, "temporal_attn_bwd: bad argument");
+  MEANT_REQUIRE(L > 0, MEANT_ERR_UNSUPPORTED, "temporal_attn_bwd: lag %d is not positive", L);
+  if (L > 64 || meant_opt(MEANT_OPT_TEMPORAL_LONG)) return temporal_long_bwd(q, kv, p, do_, dq, dkv, B, L, H, Dh, scale, dtype, (hipStream_t)stream);
+  DISPATCH_DTYPE(dtype, T,
+                 hipLaunchKernelGGL(temporal_bwd_kernel<T>, dim3((unsigned)ceil_div(B * H, 4)), dim3(256), 0, (hipStream_t)stream,
+                                    (const T*)q, (const T*)kv, p, (const T*)do_, (T*)dq, (T*)dkv, B, L, H, Dh, scale));
+  MEANT_LAUNCH_CHECK("temporal_attn_bwd");
   return MEANT_OK;
 }

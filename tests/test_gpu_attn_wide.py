@@ -96,7 +96,7 @@ def _reference(qkv, do, mask, G, S, H, Dh, scale, causal, tables=None):
     return o.detach(), torch.stack([m, logl], dim=-1), leaf.grad.reshape(G * S, 3 * D)
 
 
-def _run(qkv, do, mask, G, S, H, Dh, scale, causal, tables=None):
+def _run(qkv, do, mask, G, S, H, Dh, scale, causal, tables=None, route_names=None):
     from meant_amd import _lib
     from meant_amd._lib import lib, check
     D, st = H * Dh, torch.cuda.current_stream().cuda_stream
@@ -115,7 +115,7 @@ def _run(qkv, do, mask, G, S, H, Dh, scale, causal, tables=None):
     check(lib.meant_attn_bwd(qkv.data_ptr(), o.data_ptr(), do.data_ptr(), lse.data_ptr(), mp, dqkv.data_ptr(), G, S, H, Dh, scale, causal,
                              pp[0], pp[1], pp[2], pp[3], R, BF16, ws.data_ptr(), wsb, st), "attn_bwd")
     torch.cuda.synchronize()
-    routes = {r: _lib.route_count(r) for r in (f"attn_fwd_d{Dh}", f"attn_bwd_d{Dh}", "attn_generic", "attn_short", "attn_bwd1")}
+    routes = {r: _lib.route_count(r) for r in route_names or (f"attn_fwd_d{Dh}", f"attn_bwd_d{Dh}", "attn_generic", "attn_short", "attn_bwd1")}
     return o, lse, dqkv, routes
 
 
@@ -352,3 +352,37 @@ def test_wide_workspace(Dh):
         detour = 32 * G * S * H * Dh                    # what the fp32 detour's four copies alone take
         assert 0 < fwd < full, (G, S, H, fwd, full)
         assert full * 8 < detour, (G, S, H, full, detour)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# 7. the route table of the bf16 entry points: which counters one forward + one backward move, at every head-dim tier
+ATTN_ROUTES = ("attn_fwd", "attn_fwd_d96", "attn_fwd_d128", "attn_fwd_d160", "attn_fwd_d192", "attn_fwd_d256", "attn_bwd", "attn_bwd_d96",
+               "attn_bwd_d128", "attn_bwd_d160", "attn_bwd_d192", "attn_bwd_d256", "attn_bwd1", "attn_generic", "attn_short", "attn_cls")
+ROUTE_TABLE = [(17, 64, None, {"attn_fwd": 1, "attn_bwd1": 1}),
+               (17, 64, ("attn_bwd1", 0), {"attn_fwd": 1, "attn_bwd": 1}),
+               (17, 72, None, {"attn_generic": 2}),
+               (16, 64, None, {"attn_short": 2})] + \
+              [(17, n, None, {f"attn_fwd_d{n}": 1, "attn_bwd": 1, f"attn_bwd_d{n}": 1}) for n in (96, 128, 160, 192, 256)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("S,Dh,option,expected", ROUTE_TABLE, ids=[f"S{s}-Dh{n}" + ("-two_pass" if o else "") for s, n, o, _ in ROUTE_TABLE])
+def test_attention_route_table(dev, S, Dh, option, expected):
+    """the forward hits attn_fwd at Dh = 64 only and attn_fwd_dN otherwise; the two-pass backward hits attn_bwd at every head dim and
+    attn_bwd_dN on top at N != 64; every other attn_* counter stays 0.  No mask, not causal; results against float64 as above."""
+    from meant_amd import _lib
+    G, H = 2, 2
+    qkv, do = _inputs(G, S, H, Dh, 31 * Dh + S, dev)
+    scale = 0.7 / math.sqrt(Dh)
+    old = _lib.get_option(option[0]) if option else None
+    try:
+        if option:
+            _lib.set_option(*option)
+        o, lse, dqkv, counts = _run(qkv, do, None, G, S, H, Dh, scale, 0, route_names=ATTN_ROUTES)   # counters reset, one forward, one backward
+    finally:
+        if option:
+            _lib.set_option(option[0], old)
+    assert counts == {r: expected.get(r, 0) for r in ATTN_ROUTES}, f"S={S} Dh={Dh} {option}: {counts}"
+    if expected.get("attn_generic"):                 # the detour is the f32 tier's core: its (m, log l) are in natural-log units
+        lse = lse * LOG2E                            # (include/meant_hip.h, "attention core"); _check compares in log2 units
+    _check(o, lse, dqkv, _reference(qkv, do, None, G, S, H, Dh, scale, 0), H, Dh, f"route table S={S} Dh={Dh} {option}")

@@ -216,3 +216,30 @@ def test_checkpointed_layers_repeat_their_stacks_fold_decision(dev, monkeypatch)
         assert torch.equal(res[0][0], other[0])
         for k, g0 in res[0][1].items():
             assert (g0 - other[1][k]).abs().max().item() <= 1e-5 * max(1.0, g0.abs().max().item()), k
+
+
+@pytest.mark.parametrize("fn,rows,d,ok", [("chain", 4, 512, True), ("stats", 4, 512, True), ("chain", 4, 516, False), ("stats", 4, 516, False),
+                                          ("stats", 4, 0, False), ("chain", 4, 2048, False)])
+def test_chain_and_stats_refuse_what_does_not_pack(dev, fn, rows, d, ok):
+    """meant_rmsnorm_stats and meant_rmsnorm_bwd_chain have packed kernels only: any other shape is MEANT_ERR_UNSUPPORTED before a
+    launch (d = 516 is no multiple of 8 and used to pass the chained backward's own test as R = 1, C = 1; 2048 is one wave per row)"""
+    from meant_amd._lib import lib
+    st, w = torch.cuda.current_stream().cuda_stream, max(d, 8)
+    gen = torch.Generator().manual_seed(d + rows)
+    x, dy, pre = (torch.randn(rows, w, generator=gen).bfloat16().to(dev) for _ in range(3))
+    rinv, up_rinv, kcoef = (torch.ones(rows, device=dev) for _ in range(3))
+    if fn == "stats":
+        rc = lib.meant_rmsnorm_stats(x.data_ptr(), rinv.data_ptr(), rows, d, 1e-8, 1, st)
+    else:
+        scale, dscale, up_bias, dbias = (torch.ones(w, device=dev) for _ in range(4))
+        dx = torch.empty_like(x)
+        wsb = lib.meant_rmsnorm_bwd_ws(rows, d)
+        ws = torch.empty(max(wsb, 16), device=dev, dtype=torch.uint8)
+        rc = lib.meant_rmsnorm_bwd_chain(dy.data_ptr(), 0, x.data_ptr(), scale.data_ptr(), rinv.data_ptr(), dx.data_ptr(), dscale.data_ptr(), rows, d, 1,
+                                         1e-8, 0.0, 0, pre.data_ptr(), up_rinv.data_ptr(), up_bias.data_ptr(), 1e-8, 64, kcoef.data_ptr(),
+                                         dbias.data_ptr(), 1, ws.data_ptr(), wsb, st)
+    torch.cuda.synchronize()
+    assert rc == (0 if ok else -2), f"{fn} rows={rows} d={d}: rc {rc}"                 # -2: MEANT_ERR_UNSUPPORTED
+    if ok and fn == "stats":
+        ref = 1.0 / (x.float().norm(dim=-1) / d ** 0.5 + 1e-8)
+        assert torch.allclose(rinv, ref, rtol=1e-5, atol=0), (rinv, ref)

@@ -1,4 +1,4 @@
-"""Temporal (lag-axis) attention at lags past 64: the long-lag kernels of temporal_long.hip behind meant_temporal_attn_fwd / _bwd,
+"""Temporal (lag-axis) attention at lags past 64: the long-lag kernels of temporal.hip behind meant_temporal_attn_fwd / _bwd,
 against fp64 on the device (core), against the CPU oracle (module and models), in both precision tiers."""
 import math
 
@@ -50,7 +50,7 @@ def _raw_bwd(q, kv, p, do, B, L, H, Dh, scale):
 
 
 # (B, L, H, Dh).  The first seven are the shapes the feature was specified with; the rest are the other places where
-# temporal_long.hip changes path: one lane per row and 64 lanes per row of the row-sweep kernels (Dh = 8, 512), the scalar
+# temporal.hip changes path: one lane per row and 64 lanes per row of the row-sweep kernels (Dh = 8, 512), the scalar
 # kernels' second sweep over the head (Dh > 512), and the backward past its LDS cache of dp_l (L > 2048).
 CORE_SHAPES = [
     (2, 65, 12, 128),       # one key past the cap and past one 64-key chunk

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """dev probe: the temporal (lag-axis) attention core, forward and backward, at B = 128, H = 12, Dh = 128 for
 L in {12, 64, 65, 128, 512} in both tiers, through meant_temporal_attn_fwd / _bwd.  L <= 64 runs the one-wave kernels of
-elementwise.hip, L > 64 the long-lag kernels of temporal_long.hip; at L <= 64 the long-lag kernels are timed as well (library
+temporal.hip, L > 64 its long-lag kernels; at L <= 64 the long-lag kernels are timed as well (library
 option "temporal_long" = 1, toggled here), interleaved with the short ones: the one like-for-like comparison there is.
 MEANT_PROBE_LONG_AT_SHORT=0 (read only here) leaves those rows out.
 
