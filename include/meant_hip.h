@@ -82,6 +82,7 @@ int meant_num_cus(void);
 int meant_set_option(const char* name, int value);
 int meant_get_option(const char* name, int* value);
 /* how many launches took a given kernel route since the last reset ("nt128", "nt256", "nt256s", "nt256s_rot",
+ * "nt128k", "nt256k" (the K-tail forms of the 128 x 128 and 256 x 256 one-tile kernels: K % 64 != 0),
  * "nt_split", "nt_overlap", "tn128", "tn256", "tn256_det", "tn_tail", "gemm_f32", "attn_fwd", "attn_fwd_d128",
  * "attn_fwd_d96", "attn_bwd" (the two-pass form), "attn_bwd1" (the single-pass form), "attn_bwd_d128", "attn_bwd_d96",
  * "attn_generic", "attn_cls", "attn_short", "attn_fwd_d160" ... "attn_bwd_d256", "temporal_long" (the temporal attention
@@ -182,13 +183,18 @@ int meant_layernorm_bwd(const void* dy, const void* x, const float* gamma, const
 /* ---- Linear ------------------- nn.Linear call sites meant/meant.py:59-64,101-107,132-136,195,204
  *                                   and q/v/k/multi_mad in meant/attention.py:31-33,57-60 etc.
  * y[M,N] = x[M,K] w[N,K]^T + bias[N]  (+ epilogue).  x,w,y,residual,preact: act dtype; bias float
- * (may be NULL).  ldx/ldy/ldr: row strides.  preact (optional, EPI_GELU) receives x W^T + b. */
+ * (may be NULL).  ldx/ldy/ldr: row strides.  preact (optional, EPI_GELU) receives x W^T + b.
+ * bf16 tier: any K that is a multiple of 8 (with ldx % 8 == 0 and 16-byte aligned x, w) runs on the MFMA kernels: K % 64 == 0 on
+ * the streaming / one-tile kernels, any other such K on the K-tail forms of the one-tile kernels (routes "nt128k" / "nt256k"),
+ * which read neither operand at or beyond column K of a row.  Everything else takes the exact-f32 engine on bf16 storage; a caller
+ * with K % 8 != 0 pads both operands to ceil8(K) with meant_pad_copy2d first. */
 int meant_linear_fwd(const void* x, int64_t ldx, const void* w, const float* bias, const void* residual,
                      int64_t ldr, void* y, int64_t ldy, void* preact, int64_t M, int64_t N, int64_t K,
                      int epilogue, int dtype, void* stream);
 /* Fused q|k|v projection + rotary:  qkv[M, 3*H*Dh] = x[M,K] w[3*H*Dh, K]^T + bias, then the rotation of
  * meant_rotary_qk on the q and k blocks (tables may be NULL: plain projection).  In the bf16 tier the rotation
- * rides the GEMM epilogue (no extra pass over qkv).   meant/attention.py:36-40, meant/xPosAttention.py:37-39 */
+ * rides the GEMM epilogue (no extra pass over qkv) at every K % 8 == 0 (Dh % 8 == 0, R % 8 == 0), K % 64 != 0 included
+ * (K-tail kernels, as meant_linear_fwd).   meant/attention.py:36-40, meant/xPosAttention.py:37-39 */
 int meant_qkv_proj_fwd(const void* x, int64_t ldx, const void* w, const float* bias, void* qkv, int64_t M,
                        int64_t K, int64_t S, int H, int Dh, int R, const float* qa, const float* qb,
                        const float* ka, const float* kb, int dtype, void* stream);
@@ -205,7 +211,9 @@ int meant_linear_bwd_dx_norm(const void* dy_scaled, int64_t lddy, const void* wT
                              const float* coef, const void* dres, int64_t lddres, const float* dres_pooled,
                              int64_t group_rows, void* dx, int64_t lddx, int64_t M, int64_t N, int64_t K, int dtype,
                              void* stream);
-/* dx[M,K] = dy[M,N] w[N,K]   (wT is w transposed, [K,N], act dtype: see meant_transpose2d) */
+/* dx[M,K] = dy[M,N] w[N,K]   (wT is w transposed, [K,N], act dtype: see meant_transpose2d).  The reduction length is N: bf16
+ * tier, any N % 8 == 0 on the MFMA kernels (N % 64 != 0: the K-tail forms, as meant_linear_fwd); K is free (K % 8 != 0 stores
+ * element by element). */
 int meant_linear_bwd_dx(const void* dy, int64_t lddy, const void* wT, void* dx, int64_t lddx, int64_t M,
                         int64_t N, int64_t K, int dtype, void* stream);
 /* dw[N,K] += dy[M,N]^T x[M,K]  and  dbias[N] += colsum(dy)  -- float accumulators the caller zeroes
@@ -373,6 +381,12 @@ int meant_cast(const void* src, int dtype_src, void* dst, int dtype_dst, int64_t
 /* dst[c, r] (dtype_dst) = src[r, c] (dtype_src); src is [rows, cols] */
 int meant_transpose2d(const void* src, int dtype_src, void* dst, int dtype_dst, int64_t rows, int64_t cols,
                       void* stream);
+/* dst[r, c] (dtype_dst, row stride ld_dst) = src[r, c] (dtype_src, row stride ld_src) for c < min(cols_src, cols_dst),
+ * 0 for cols_src <= c < cols_dst; columns of src at or beyond cols_dst are dropped.  Rows of src need element alignment
+ * only (the operands of a Linear whose K is not a multiple of 8 are padded to ceil8(K) with it, and its dW is cut
+ * back out of the padded accumulator); src is never read at or beyond column cols_src of a row. */
+int meant_pad_copy2d(const void* src, int64_t ld_src, int64_t cols_src, int dtype_src, void* dst, int64_t ld_dst,
+                     int64_t cols_dst, int dtype_dst, int64_t rows, void* stream);
 /* embedding gather: out act [n, d] = table float [V, d] rows ids[n] (int64); and its scatter-add backward
  * into dtable float [V, d] (caller zeroes).            nn.Embedding at meant/meant.py:211 */
 int meant_embedding_fwd(const float* table, const int64_t* ids, void* out, int64_t n, int64_t d, int64_t V, int dtype,

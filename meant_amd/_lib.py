@@ -77,6 +77,7 @@ SIGNATURES = {
     "meant_add": (_i, [_p, _p, _p, _i64, _i, _p]),
     "meant_cast": (_i, [_p, _i, _p, _i, _i64, _p]),
     "meant_transpose2d": (_i, [_p, _i, _p, _i, _i64, _i64, _p]),
+    "meant_pad_copy2d": (_i, [_p, _i64, _i64, _i, _p, _i64, _i64, _i, _i64, _p]),
     "meant_embedding_fwd": (_i, [_p, _p, _p, _i64, _i64, _i64, _i, _p]),
     "meant_embedding_bwd": (_i, [_p, _p, _p, _i64, _i64, _i64, _i, _p]),
     "meant_ce_probs": (_i, [_p, _p, _p, _p, _i64, _i, _p]),

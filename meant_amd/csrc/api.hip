@@ -1,9 +1,10 @@
 // extern "C" entry points for Linear and the attention core: argument checks + dtype dispatch.
 #include "internal.h"
 
-// preconditions of the MFMA bf16 NT kernel (global_load_lds moves 16-byte pieces; vector epilogue stores)
+// preconditions of the MFMA bf16 NT kernels (global_load_lds moves 16-byte pieces; vector epilogue stores).  K % 64 != 0 runs on the
+// K-tail forms of the one-tile kernels (gemm_bf16.hip); the RMSNorm-into-Linear fold entries below keep K % 64 == 0.
 static bool bf16_nt_ok(const void* a, int64_t lda, const void* b, int64_t ldb, int64_t K) {
-  return (K % 64) == 0 && (lda % 8) == 0 && (ldb % 8) == 0 && meant_aligned16(a) && meant_aligned16(b);
+  return K >= 8 && (K % 8) == 0 && (lda % 8) == 0 && (ldb % 8) == 0 && meant_aligned16(a) && meant_aligned16(b);
 }
 
 // the exact-f32 GEMM on row-major operands, C[M,N] = A B^T with A [M,K] and B [N,K] ("NT": Linear forward and input gradient), or
@@ -29,7 +30,7 @@ extern "C" int meant_linear_fwd(const void* x, int64_t ldx, const void* w, const
   MEANT_REQUIRE(M > 0 && N > 0 && K > 0 && ldx >= K && ldy >= N, MEANT_ERR_ARG, "linear_fwd: bad shape M=%lld N=%lld K=%lld", (long long)M, (long long)N, (long long)K);
   MEANT_REQUIRE(!(epilogue & MEANT_EPI_RESIDUAL) || residual, MEANT_ERR_ARG, "linear_fwd: residual epilogue without residual pointer");
   if (!(epilogue & MEANT_EPI_RESIDUAL)) residual = nullptr;
-  // bf16 at odd shapes (K not a multiple of 64, unaligned rows: e.g. the class head): the exact-f32 path on bf16 storage
+  // bf16 at odd shapes (K not a multiple of 8, unaligned rows: e.g. the class head): the exact-f32 path on bf16 storage
   if (dtype == MEANT_F32 || (dtype == MEANT_BF16 && !bf16_nt_ok(x, ldx, w, K, K))) {
     MEANT_REQUIRE(!residual || ldr == ldy, MEANT_ERR_UNSUPPORTED, "linear_fwd(%s): residual stride must equal output stride",
                   dtype == MEANT_F32 ? "f32" : "bf16 generic");
@@ -96,7 +97,7 @@ extern "C" int meant_linear_fwd_rowscale(const void* x, int64_t ldx, const void*
                                          int64_t K, int epilogue, int dtype, void* stream) {
   MEANT_REQUIRE(x && w && y && row_scale, MEANT_ERR_ARG, "linear_fwd_rowscale: null pointer");
   MEANT_REQUIRE(M > 0 && N > 0 && K > 0 && ldx >= K && ldy >= N, MEANT_ERR_ARG, "linear_fwd_rowscale: bad shape");
-  MEANT_REQUIRE(dtype == MEANT_BF16 && bf16_nt_ok(x, ldx, w, K, K) && (ldy & 7) == 0 && !(epilogue & MEANT_EPI_SIGMOID),
+  MEANT_REQUIRE(dtype == MEANT_BF16 && K % 64 == 0 && bf16_nt_ok(x, ldx, w, K, K) && (ldy & 7) == 0 && !(epilogue & MEANT_EPI_SIGMOID),
                 MEANT_ERR_UNSUPPORTED, "linear_fwd_rowscale: bf16 tier, K %% 64 == 0, 16-byte aligned rows only");
   MEANT_REQUIRE(!(epilogue & MEANT_EPI_RESIDUAL) || residual, MEANT_ERR_ARG, "linear_fwd_rowscale: residual epilogue without residual pointer");
   GemmBf16Args a{};
@@ -113,7 +114,7 @@ extern "C" int meant_linear_bwd_dx_norm(const void* dy_scaled, int64_t lddy, con
                                         int64_t M, int64_t N, int64_t K, int dtype, void* stream) {
   MEANT_REQUIRE(dy_scaled && wT && x && coef && dx, MEANT_ERR_ARG, "linear_bwd_dx_norm: null pointer");
   MEANT_REQUIRE(M > 0 && N > 0 && K > 0 && lddy >= N && lddx >= K && ldx >= K, MEANT_ERR_ARG, "linear_bwd_dx_norm: bad shape");
-  MEANT_REQUIRE(dtype == MEANT_BF16 && bf16_nt_ok(dy_scaled, lddy, wT, N, N) && (lddx & 7) == 0 && (ldx & 7) == 0 &&
+  MEANT_REQUIRE(dtype == MEANT_BF16 && N % 64 == 0 && bf16_nt_ok(dy_scaled, lddy, wT, N, N) && (lddx & 7) == 0 && (ldx & 7) == 0 &&
                 meant_aligned16(x) && (!dres || ((lddres & 7) == 0 && meant_aligned16(dres))),
                 MEANT_ERR_UNSUPPORTED, "linear_bwd_dx_norm: bf16 tier, N %% 64 == 0, 16-byte aligned rows only");
   GemmBf16Args a{};

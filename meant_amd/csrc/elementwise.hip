@@ -64,6 +64,37 @@ __global__ void transpose_kernel(const TS* __restrict__ s, TD* __restrict__ d, i
   }
 }
 
+// d[r, c] = s[r, c] for c < cols_src, 0 up to cols_dst; one thread per 8 destination columns.  Source rows are only
+// element-aligned (K % 8 != 0 is why this kernel exists), so the source is read element by element (a wave's loads of one
+// element index still cover one contiguous kilobyte); the destination takes 16-byte stores where its rows are aligned.
+// s is never read at or beyond column cols_src of a row.
+template <typename TS, typename TD>
+__global__ __launch_bounds__(EW_THREADS) void pad_copy2d_kernel(const TS* __restrict__ s, int64_t ld_src, int64_t cols_src,
+                                                                 TD* __restrict__ d, int64_t ld_dst, int64_t cols_dst, int64_t rows,
+                                                                 int vec_dst) {
+  const int64_t cpr = (cols_dst + 7) >> 3, total = rows * cpr;
+  const bool small = total < (1LL << 31);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = small ? (int64_t)((unsigned)i / (unsigned)cpr) : i / cpr;
+    const int64_t c0 = (i - r * cpr) << 3;
+    const TS* sp = s + r * ld_src + c0;
+    float v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = c0 + k < cols_src ? to_f(sp[k]) : 0.f;
+    TD* dp = d + r * ld_dst + c0;
+    if (vec_dst && c0 + 8 <= cols_dst) {
+      Vec8<TD> o;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) o.set(k, v[k]);
+      store8<TD>(dp, o);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (c0 + k < cols_dst) dp[k] = from_f<TD>(v[k]);
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // y[r,:] = x[r,:] + v[r % period, :]
 template <typename T>
@@ -418,6 +449,27 @@ extern "C" int meant_transpose2d(const void* src, int dtype_src, void* dst, int 
   else if (dtype_src == MEANT_BF16 && dtype_dst == MEANT_F32) hipLaunchKernelGGL((transpose_kernel<bf16, float>), grid, block, 0, st, (const bf16*)src, (float*)dst, rows, cols);
   else { meant_set_error("transpose2d: unknown dtype"); return MEANT_ERR_ARG; }
   MEANT_LAUNCH_CHECK("transpose2d");
+  return MEANT_OK;
+}
+
+template <typename TS, typename TD>
+static void pad_copy2d_launch(const void* src, int64_t ld_src, int64_t cols_src, void* dst, int64_t ld_dst, int64_t cols_dst, int64_t rows,
+                              hipStream_t st) {
+  const int vec_dst = meant_aligned16(dst) && (ld_dst * (int64_t)sizeof(TD)) % 16 == 0;
+  hipLaunchKernelGGL((pad_copy2d_kernel<TS, TD>), dim3(ew_blocks(rows * ceil_div(cols_dst, 8))), dim3(EW_THREADS), 0, st, (const TS*)src, ld_src,
+                     cols_src, (TD*)dst, ld_dst, cols_dst, rows, vec_dst);
+}
+
+extern "C" int meant_pad_copy2d(const void* src, int64_t ld_src, int64_t cols_src, int dtype_src, void* dst, int64_t ld_dst, int64_t cols_dst,
+                                int dtype_dst, int64_t rows, void* stream) {
+  EW_REQ(src && dst && rows > 0 && cols_src > 0 && cols_dst > 0 && ld_src >= cols_src && ld_dst >= cols_dst, "pad_copy2d: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype_src == MEANT_F32 && dtype_dst == MEANT_BF16) pad_copy2d_launch<float, bf16>(src, ld_src, cols_src, dst, ld_dst, cols_dst, rows, st);
+  else if (dtype_src == MEANT_BF16 && dtype_dst == MEANT_BF16) pad_copy2d_launch<bf16, bf16>(src, ld_src, cols_src, dst, ld_dst, cols_dst, rows, st);
+  else if (dtype_src == MEANT_F32 && dtype_dst == MEANT_F32) pad_copy2d_launch<float, float>(src, ld_src, cols_src, dst, ld_dst, cols_dst, rows, st);
+  else if (dtype_src == MEANT_BF16 && dtype_dst == MEANT_F32) pad_copy2d_launch<bf16, float>(src, ld_src, cols_src, dst, ld_dst, cols_dst, rows, st);
+  else { meant_set_error("pad_copy2d: unknown dtype"); return MEANT_ERR_ARG; }
+  MEANT_LAUNCH_CHECK("pad_copy2d");
   return MEANT_OK;
 }
 

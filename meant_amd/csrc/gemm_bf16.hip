@@ -49,11 +49,27 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// K-tail forms (KTAIL = true) of the two one-tile NT kernels: K a multiple of 8 but not of 64.  The K loop runs ceil(K / 64)
+// steps; a lane whose 8-element chunk starts at or beyond K takes its 16 bytes from this block of zeros instead of the operand,
+// so the LDS tile holds zeros there and the MFMA loop and the epilogue are those of the K % 64 == 0 kernels.  The operand is
+// never addressed at or beyond column K of a row: the next row's head belongs to another token (a NaN there would poison the
+// product even when multiplied by the other operand's zeros), and the last row's tail is past the allocation.
+__device__ __attribute__((aligned(16))) const unsigned g_nt_zero16[4] = {0u, 0u, 0u, 0u};   // read-only: nothing ever writes it
+
+// source of the 16-byte chunk at columns kc .. kc+7 of row gr in the K-tail form
+__device__ __forceinline__ const bf16* nt_tail_src(const bf16* __restrict__ g, int64_t ld, int64_t gr, int64_t kc, int64_t K) {
+  const int64_t off = kc < K ? gr * ld + kc : 0;
+  const bf16* p = g + off;
+  return kc < K ? p : reinterpret_cast<const bf16*>(g_nt_zero16);
+}
+
+// ------------------------------------------------------------------------------------------------
 // NT kernel
 // stage one 128 x 64 bf16 tile (rows row0.., columns k0..k0+63 of a K-contiguous matrix) into LDS.
 // wave w issues DMA pieces 4w..4w+3; piece i covers tile rows 8i..8i+7 (8 lanes per 128-byte row).
+template <bool KTAIL>
 __device__ __forceinline__ void nt_stage(const bf16* __restrict__ g, int64_t ld, int64_t row0, int64_t nrows, int64_t k0,
-                                          char* lds_tile, int wave, int lane) {
+                                          char* lds_tile, int wave, int lane, int64_t K) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int piece = wave * 4 + i;
@@ -62,7 +78,8 @@ __device__ __forceinline__ void nt_stage(const bf16* __restrict__ g, int64_t ld,
     const int c = slot ^ ((r >> 1) & 7);
     int64_t gr = row0 + r;
     gr = gr < nrows ? gr : nrows - 1;            // clamp: rows past the edge are computed and discarded
-    glds16(g + gr * ld + k0 + c * 8, lds_tile + piece * 1024);
+    if (KTAIL) glds16(nt_tail_src(g, ld, gr, k0 + c * 8, K), lds_tile + piece * 1024);
+    else glds16(g + gr * ld + k0 + c * 8, lds_tile + piece * 1024);
   }
 }
 
@@ -144,6 +161,7 @@ __device__ __forceinline__ void nt_store_row8(const GemmBf16Args& a, int64_t m, 
   }
 }
 
+template <bool KTAIL>
 __global__ __launch_bounds__(256, 2) void gemm_bf16_nt_kernel(GemmBf16Args a, int ntm, int ntn) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -151,7 +169,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_nt_kernel(GemmBf16Args a, in
   const int id = xcd_remap(blockIdx.x, ntm * ntn);
   const int tm = id / ntn, tn = id - tm * ntn;
   const int64_t m0 = (int64_t)tm * BM, n0 = (int64_t)tn * BN;
-  const int nk = (int)(a.K / BK);
+  const int nk = KTAIL ? (int)((a.K + BK - 1) / BK) : (int)(a.K / BK);
 
   f32x4 acc[4][4];
 #pragma unroll
@@ -159,8 +177,8 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_nt_kernel(GemmBf16Args a, in
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  nt_stage(a.A, a.lda, m0, a.M, 0, smem, wave, lane);
-  nt_stage(a.B, a.ldb, n0, a.N, 0, smem + TILE_BYTES, wave, lane);
+  nt_stage<KTAIL>(a.A, a.lda, m0, a.M, 0, smem, wave, lane, a.K);
+  nt_stage<KTAIL>(a.B, a.ldb, n0, a.N, 0, smem + TILE_BYTES, wave, lane, a.K);
   __syncthreads();                                  // (drains the DMA: vmcnt(0) + barrier)
 
   const int frow = lane & 15, fkg = lane >> 4;
@@ -168,8 +186,8 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_nt_kernel(GemmBf16Args a, in
     char* cur = smem + (kt & 1) * 2 * TILE_BYTES;
     char* nxt = smem + ((kt + 1) & 1) * 2 * TILE_BYTES;
     if (kt + 1 < nk) {
-      nt_stage(a.A, a.lda, m0, a.M, (int64_t)(kt + 1) * BK, nxt, wave, lane);
-      nt_stage(a.B, a.ldb, n0, a.N, (int64_t)(kt + 1) * BK, nxt + TILE_BYTES, wave, lane);
+      nt_stage<KTAIL>(a.A, a.lda, m0, a.M, (int64_t)(kt + 1) * BK, nxt, wave, lane, a.K);
+      nt_stage<KTAIL>(a.B, a.ldb, n0, a.N, (int64_t)(kt + 1) * BK, nxt + TILE_BYTES, wave, lane, a.K);
     }
     const char* At = cur + (wm * 64) * 128;
     const char* Bt = cur + TILE_BYTES + (wn * 64) * 128;
@@ -235,8 +253,9 @@ constexpr int B2 = 256;
 constexpr int T2_BYTES = B2 * BK * 2;              // 32 KiB per operand per stage
 
 // 32 pieces of 1 KiB (8 rows each) per tile; wave w issues pieces 4w .. 4w+3
+template <bool KTAIL>
 __device__ __forceinline__ void nt256_stage(const bf16* __restrict__ g, int64_t ld, int64_t row0, int64_t nrows, int64_t k0,
-                                             char* lds_tile, int wave, int lane) {
+                                             char* lds_tile, int wave, int lane, int64_t K) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int piece = wave * 4 + i;
@@ -244,10 +263,12 @@ __device__ __forceinline__ void nt256_stage(const bf16* __restrict__ g, int64_t 
     const int c = (lane & 7) ^ ((r >> 1) & 7);
     int64_t gr = row0 + r;
     gr = gr < nrows ? gr : nrows - 1;
-    glds16(g + gr * ld + k0 + c * 8, lds_tile + piece * 1024);
+    if (KTAIL) glds16(nt_tail_src(g, ld, gr, k0 + c * 8, K), lds_tile + piece * 1024);
+    else glds16(g + gr * ld + k0 + c * 8, lds_tile + piece * 1024);
   }
 }
 
+template <bool KTAIL>
 __global__ __launch_bounds__(512, 2) void gemm_bf16_nt256_kernel(GemmBf16Args a, int ntm, int ntn) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -255,7 +276,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt256_kernel(GemmBf16Args a,
   const int id = xcd_remap(blockIdx.x, ntm * ntn);
   const int tm = id / ntn, tn = id - tm * ntn;
   const int64_t m0 = (int64_t)tm * B2, n0 = (int64_t)tn * B2;
-  const int nk = (int)(a.K / BK);
+  const int nk = KTAIL ? (int)((a.K + BK - 1) / BK) : (int)(a.K / BK);
 
   f32x4 acc[8][4];
 #pragma unroll
@@ -263,8 +284,8 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt256_kernel(GemmBf16Args a,
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  nt256_stage(a.A, a.lda, m0, a.M, 0, smem, wave, lane);
-  nt256_stage(a.B, a.ldb, n0, a.N, 0, smem + T2_BYTES, wave, lane);
+  nt256_stage<KTAIL>(a.A, a.lda, m0, a.M, 0, smem, wave, lane, a.K);
+  nt256_stage<KTAIL>(a.B, a.ldb, n0, a.N, 0, smem + T2_BYTES, wave, lane, a.K);
   __syncthreads();
 
   const int frow = lane & 15, fkg = lane >> 4;
@@ -277,10 +298,10 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt256_kernel(GemmBf16Args a,
     // K-loop; issuing late instead -- after the MFMAs -- exposes the load latency at the barrier and measured -10 %).
     const bool late = __builtin_amdgcn_readfirstlane(threadIdx.x) >= 256;
     if (!late && kt + 1 < nk) {
-      nt256_stage(a.A, a.lda, m0, a.M, (int64_t)(kt + 1) * BK, nxt, wave, lane);
-      nt256_stage(a.B, a.ldb, n0, a.N, (int64_t)(kt + 1) * BK, nxt + T2_BYTES, wave, lane);
-      nt256_stage(a.A, a.lda, m0, a.M, (int64_t)(kt + 1) * BK, nxt, wave + 4, lane);
-      nt256_stage(a.B, a.ldb, n0, a.N, (int64_t)(kt + 1) * BK, nxt + T2_BYTES, wave + 4, lane);
+      nt256_stage<KTAIL>(a.A, a.lda, m0, a.M, (int64_t)(kt + 1) * BK, nxt, wave, lane, a.K);
+      nt256_stage<KTAIL>(a.B, a.ldb, n0, a.N, (int64_t)(kt + 1) * BK, nxt + T2_BYTES, wave, lane, a.K);
+      nt256_stage<KTAIL>(a.A, a.lda, m0, a.M, (int64_t)(kt + 1) * BK, nxt, wave + 4, lane, a.K);
+      nt256_stage<KTAIL>(a.B, a.ldb, n0, a.N, (int64_t)(kt + 1) * BK, nxt + T2_BYTES, wave + 4, lane, a.K);
     }
     const char* At = cur + (wm * 128) * 128;
     const char* Bt = cur + T2_BYTES + (wn * 64) * 128;
@@ -1289,10 +1310,11 @@ int gemm_bf16_nt_launch(const GemmBf16Args& a, hipStream_t stream) {
   MEANT_REQUIRE(a.A && a.B && a.C, MEANT_ERR_ARG, "gemm_bf16_nt: null pointer");
   MEANT_REQUIRE(!a.rot_qa || (a.N == 3 * (int64_t)a.rot_D && a.rot_Dh % 8 == 0 && a.rot_R % 8 == 0 && (a.ldc & 7) == 0 && a.rot_D % a.rot_Dh == 0),
                 MEANT_ERR_ARG, "gemm_bf16_nt: rotary epilogue needs N = 3*H*Dh, Dh %% 8 == 0, rot_dim %% 8 == 0");
-  MEANT_REQUIRE(a.K % BK == 0, MEANT_ERR_UNSUPPORTED, "gemm_bf16_nt: K=%lld must be a multiple of %d (use the fp32 tier otherwise)", (long long)a.K, BK);
+  MEANT_REQUIRE(a.K >= 8 && a.K % 8 == 0, MEANT_ERR_UNSUPPORTED, "gemm_bf16_nt: K=%lld must be a multiple of 8 (use the fp32 tier otherwise)", (long long)a.K);
   MEANT_REQUIRE((a.lda % 8) == 0 && (a.ldb % 8) == 0 && meant_aligned16(a.A) && meant_aligned16(a.B), MEANT_ERR_ARG,
                 "gemm_bf16_nt: operands must be 16-byte aligned with row strides that are multiples of 8");
-  MEANT_RAISE_LDS(gemm_bf16_nt256_kernel, 4 * T2_BYTES);
+  MEANT_RAISE_LDS(gemm_bf16_nt256_kernel<false>, 4 * T2_BYTES);
+  const bool ktail = a.K % BK != 0;                    // K-tail forms of the two one-tile kernels; never the streaming, split or overlap routes
   MEANT_RAISE_LDS((gemm_bf16_nt256p_kernel<NTE_PLAIN>), RING * T2_BYTES);
   MEANT_RAISE_LDS((gemm_bf16_nt256p_kernel<NTE_RES>), RING * T2_BYTES);
   MEANT_RAISE_LDS((gemm_bf16_nt256p_kernel<NTE_GELU_PRE>), RING * T2_BYTES);
@@ -1311,7 +1333,7 @@ int gemm_bf16_nt_launch(const GemmBf16Args& a, hipStream_t stream) {
     const int64_t ntm2 = ceil_div(a.M, B2), ntn2 = a.N / B2;
     MEANT_REQUIRE(ntm2 * ntn2 < 2147483647LL, MEANT_ERR_UNSUPPORTED, "gemm_bf16_nt: grid too large");
     // option nt_stream = 0 forces the one-tile-per-workgroup kernel (A/B measurements)
-    const bool stream_ok = meant_opt(MEANT_OPT_NT_STREAM) != 0;
+    const bool stream_ok = meant_opt(MEANT_OPT_NT_STREAM) != 0 && !ktail;
     // Ragged M, option nt_ragged = 1 (default): the streaming kernel takes all of it; its last row tile is moved up so that it
     // ENDS at row M and recomputes up to 255 rows of its neighbour.  Every element of C is a function of its own row of A
     // and column of W with a fixed K order, so both tiles store identical bits (no cost in the K-loop, no second launch:
@@ -1382,9 +1404,13 @@ int gemm_bf16_nt_launch(const GemmBf16Args& a, hipStream_t stream) {
         default: PP_LAUNCH(NTE_GENERIC); break;
       }
 #undef PP_LAUNCH
+    } else if (ktail) {
+      MEANT_RAISE_LDS(gemm_bf16_nt256_kernel<true>, 4 * T2_BYTES);
+      meant_route_hit(ROUTE_NT256K);
+      hipLaunchKernelGGL(gemm_bf16_nt256_kernel<true>, dim3((unsigned)(ntm2 * ntn2)), dim3(512), 4 * T2_BYTES, stream, a, (int)ntm2, (int)ntn2);
     } else {
       meant_route_hit(ROUTE_NT256);
-      hipLaunchKernelGGL(gemm_bf16_nt256_kernel, dim3((unsigned)(ntm2 * ntn2)), dim3(512), 4 * T2_BYTES, stream, a, (int)ntm2, (int)ntn2);
+      hipLaunchKernelGGL(gemm_bf16_nt256_kernel<false>, dim3((unsigned)(ntm2 * ntn2)), dim3(512), 4 * T2_BYTES, stream, a, (int)ntm2, (int)ntn2);
     }
     MEANT_LAUNCH_CHECK("gemm_bf16_nt256");
     return MEANT_OK;
@@ -1392,9 +1418,16 @@ int gemm_bf16_nt_launch(const GemmBf16Args& a, hipStream_t stream) {
   const int64_t ntm = ceil_div(a.M, BM), ntn = ceil_div(a.N, BN);
   MEANT_REQUIRE(ntm * ntn < 2147483647LL, MEANT_ERR_UNSUPPORTED, "gemm_bf16_nt: grid too large");
   const size_t lds = 128 * (128 + 4) * sizeof(float);   // 67584 B: covers the 64 KiB of staging buffers too
-  MEANT_RAISE_LDS(gemm_bf16_nt_kernel, lds);
+  if (ktail) {
+    MEANT_RAISE_LDS(gemm_bf16_nt_kernel<true>, lds);
+    meant_route_hit(ROUTE_NT128K);
+    hipLaunchKernelGGL(gemm_bf16_nt_kernel<true>, dim3((unsigned)(ntm * ntn)), dim3(256), lds, stream, a, (int)ntm, (int)ntn);
+    MEANT_LAUNCH_CHECK("gemm_bf16_nt_ktail");
+    return MEANT_OK;
+  }
+  MEANT_RAISE_LDS(gemm_bf16_nt_kernel<false>, lds);
   meant_route_hit(ROUTE_NT128);
-  hipLaunchKernelGGL(gemm_bf16_nt_kernel, dim3((unsigned)(ntm * ntn)), dim3(256), lds, stream, a, (int)ntm, (int)ntn);
+  hipLaunchKernelGGL(gemm_bf16_nt_kernel<false>, dim3((unsigned)(ntm * ntn)), dim3(256), lds, stream, a, (int)ntm, (int)ntn);
   MEANT_LAUNCH_CHECK("gemm_bf16_nt");
   return MEANT_OK;
 }

@@ -68,7 +68,8 @@ class _WeightCache:
     dies.  Tensors without a stable identity (results of F.pad / cat / arithmetic) are converted without being cached, so
     nothing can accumulate from per-step temporaries.  `pad_rows` appends zero rows to the (concatenated) weight before
     the conversion: the padded bf16 / transposed copies of a vocabulary matrix are built once per optimizer step instead
-    of once per call.  Thread-safe (autograd worker threads, nn.DataParallel replicas)."""
+    of once per call.  `pad_cols` appends zero columns to the (untransposed) compute-dtype copy: the K-padded weight of a
+    Linear whose K is not a multiple of 8 (see _k_pad).  Thread-safe (autograd worker threads, nn.DataParallel replicas)."""
 
     def __init__(self):
         self._store = {}
@@ -89,7 +90,7 @@ class _WeightCache:
         with self._lock:
             self._store.pop(key, None)
 
-    def _build(self, params, dtype, transposed, pad_rows):
+    def _build(self, params, dtype, transposed, pad_rows, pad_cols=0):
         with torch.no_grad():
             w = params[0].detach() if len(params) == 1 else torch.cat([p.detach() for p in params], dim=0)
             if pad_rows:
@@ -97,7 +98,11 @@ class _WeightCache:
             w = _c(w.float())
             N, K = w.shape
             dd = F32 if dtype == torch.float32 else BF16
-            if transposed:
+            if pad_cols:
+                assert not transposed
+                out = torch.empty((N, K + pad_cols), device=w.device, dtype=dtype)
+                check(lib.meant_pad_copy2d(_p(w), K, K, F32, _p(out), K + pad_cols, K + pad_cols, dd, N, _stream()), "pad_copy2d")
+            elif transposed:
                 out = torch.empty((K, N), device=w.device, dtype=dtype)
                 check(lib.meant_transpose2d(_p(w), F32, _p(out), dd, N, K, _stream()), "transpose2d")
             elif dtype == torch.float32:
@@ -107,20 +112,20 @@ class _WeightCache:
                 check(lib.meant_cast(_p(w), F32, _p(out), dd, N * K, _stream()), "cast")
         return out
 
-    def get(self, params, dtype: torch.dtype, transposed: bool, pad_rows: int = 0):
-        """params: tuple of [N_i, K] fp32 tensors, concatenated along N (+ pad_rows zero rows)."""
+    def get(self, params, dtype: torch.dtype, transposed: bool, pad_rows: int = 0, pad_cols: int = 0):
+        """params: tuple of [N_i, K] fp32 tensors, concatenated along N (+ pad_rows zero rows, + pad_cols zero columns)."""
         roots = tuple(self._root(p) for p in params)
         if any(r is None for r in roots):
-            return self._build(params, dtype, transposed, pad_rows)
+            return self._build(params, dtype, transposed, pad_rows, pad_cols)
         key = (tuple((id(r), tuple(p.shape), p.storage_offset(), p.stride()) for r, p in zip(roots, params)), dtype, transposed,
-               pad_rows, params[0].device)
+               pad_rows, pad_cols, params[0].device)
         ver = (self._epoch,) + tuple((r._version, r.data_ptr()) for r in roots)
         with self._lock:
             hit = self._store.get(key)
             # id() values are recycled once a parameter is freed: an entry is valid only for the very same objects
             if hit is not None and hit[0] == ver and all(wr() is r for wr, r in zip(hit[2], roots)):
                 return hit[1]
-        out = self._build(params, dtype, transposed, pad_rows)
+        out = self._build(params, dtype, transposed, pad_rows, pad_cols)
         with self._lock:
             fresh = key not in self._store
             self._store[key] = (ver, out, tuple(weakref.ref(r) for r in roots))
@@ -295,8 +300,7 @@ class _LinearPre(torch.autograd.Function):
     def forward(ctx, x, weight, bias):
         _need_gpu(x, weight)
         shp = x.shape
-        x2 = _c(x).view(-1, shp[-1])
-        w_c = weights.get((weight,), x.dtype, False)
+        x2, w_c = _k_pad(_c(x).view(-1, shp[-1]), weight)
         bias_f = _c(bias.detach().float()) if bias is not None else None
         y, pre = _linear_fwd_raw(x2, w_c, bias_f, None, EPI_GELU, True)
         ctx.weight, ctx.bias, ctx.has_bias, ctx.in_shape = weight, bias, bias is not None, shp
@@ -315,7 +319,7 @@ class _LinearPre(torch.autograd.Function):
         (x2,) = ctx.saved_tensors
         N = ctx.weight.shape[0]
         d2 = _c(dpre).view(-1, N)
-        dx, dw, db = _linear_bwd_raw(d2, x2, (ctx.weight,), ctx.needs_input_grad[0], ctx.has_bias, bias_param=ctx.bias)
+        dx, dw, db = _linear_bwd_raw(d2, x2, (ctx.weight,), ctx.needs_input_grad[0], ctx.has_bias, bias_param=ctx.bias, K=ctx.in_shape[-1])
         return (dx.view(ctx.in_shape) if dx is not None else None), dw, db
 
 
@@ -682,6 +686,26 @@ def _linear_fwd_raw(x2, w_c, bias_f, residual2, epilogue, want_preact):
     return y, pre
 
 
+def _pad_cols(src2, cols, dtype=None):
+    """[rows, cols] copy of the 2-D tensor src2 (unit column stride): zero columns beyond its own, its columns beyond `cols` dropped"""
+    rows, cols_src = src2.shape
+    out = torch.empty((rows, cols), device=src2.device, dtype=dtype or src2.dtype)
+    check(lib.meant_pad_copy2d(_p(src2), src2.stride(0), cols_src, _dt(src2), _p(out), cols, cols, _dt(out), rows, _stream()), "pad_copy2d")
+    return out
+
+
+def _k_pad(x2, weight):
+    """operands of x2 W^T.  bf16 tier, K not a multiple of 8 (patch_dim 588 of a 14 x 14 x 3 patch, the fork's 1540): rows of
+    such a matrix are not 16-byte aligned, which the MFMA kernels' operand DMA needs, so both operands get zero columns up to
+    ceil8(K) -- x by one copy pass (the padded copy is what backward keeps), the weight inside the weight cache -- and the
+    product runs on the K-tail kernels instead of the exact-f32 engine.  Every other case: x2 and the cached compute-dtype weight"""
+    K = x2.shape[1]
+    if x2.dtype == torch.bfloat16 and K % 8:
+        K8 = (K + 7) & ~7
+        return _pad_cols(x2, K8), weights.get((weight,), x2.dtype, False, pad_cols=K8 - K)
+    return x2, weights.get((weight,), x2.dtype, False)
+
+
 def _bwd_dw(dy2, x2, dw, db):
     """dw [N, K] += dy2^T x2, db [N] += colsum(dy2) (float accumulators)"""
     M, N = dy2.shape
@@ -759,17 +783,19 @@ def _sink_of(param, site: str):
     return ent
 
 
-def _linear_bwd_raw(dy2, x2, params, need_dx, has_bias, pad_rows=0, bias_param=None, site="linear"):
+def _linear_bwd_raw(dy2, x2, params, need_dx, has_bias, pad_rows=0, bias_param=None, site="linear", K=None):
     """returns dx2 (or None), dW [sum N_i (+ pad_rows), K] fp32, db [same] fp32 or None; dW / db are None when they went
-    straight into the parameters' gradient sinks"""
+    straight into the parameters' gradient sinks.  K: the Linear's own reduction length where x2 is the K-padded copy of
+    _k_pad (dW then goes through an [N, ceil8(K)] accumulator and is cut back; no gradient sink: its view is [N, K])"""
     M, N = dy2.shape
-    K = x2.shape[1]
+    K8 = x2.shape[1]
+    K = K8 if K is None else K
     dx = None
     if need_dx:
         wT = weights.get(params, dy2.dtype, True, pad_rows)             # [K, N]
         dx = torch.empty((M, K), device=dy2.device, dtype=dy2.dtype)
         check(lib.meant_linear_bwd_dx(_p(dy2), dy2.stride(0), _p(wT), _p(dx), K, M, N, K, _dt(dy2), _stream()), "linear_bwd_dx")
-    if len(params) == 1 and pad_rows == 0 and grad_sinks and (bias_param is not None or not has_bias):
+    if len(params) == 1 and pad_rows == 0 and K8 == K and grad_sinks and (bias_param is not None or not has_bias):
         ws_, bs_ = _sink_of(params[0], site), (_sink_of(bias_param, site) if has_bias else None)
         if ws_ is not None and (not has_bias or bs_ is not None) and ws_.view.shape == (N, K) and ws_.view.is_contiguous():
             _bwd_dw(dy2, x2, ws_.view, bs_.view if has_bias else None)
@@ -777,9 +803,11 @@ def _linear_bwd_raw(dy2, x2, params, need_dx, has_bias, pad_rows=0, bias_param=N
             if has_bias:
                 bs_.report(bias_param)
             return dx, None, None
-    dw = torch.zeros((N, K), device=dy2.device, dtype=torch.float32)
+    dw = torch.zeros((N, K8), device=dy2.device, dtype=torch.float32)
     db = torch.zeros(N, device=dy2.device, dtype=torch.float32) if has_bias else None
     _bwd_dw(dy2, x2, dw, db)
+    if K8 != K:
+        dw = _pad_cols(dw, K)
     return dx, dw, db
 
 
@@ -790,9 +818,8 @@ class _Linear(torch.autograd.Function):
     def forward(ctx, x, weight, bias, residual, epilogue):
         _need_gpu(x, weight)
         shp = x.shape
-        x2 = _c(x).view(-1, shp[-1])
+        x2, w_c = _k_pad(_c(x).view(-1, shp[-1]), weight)
         res2 = _c(residual).view(-1, weight.shape[0]) if residual is not None else None
-        w_c = weights.get((weight,), x.dtype, False)
         bias_f = _c(bias.detach().float()) if bias is not None else None
         epi = epilogue | (EPI_RESIDUAL if residual is not None else 0)
         y, pre = _linear_fwd_raw(x2, w_c, bias_f, res2, epi, bool(epilogue & EPI_GELU))
@@ -819,7 +846,7 @@ class _Linear(torch.autograd.Function):
             d2 = torch.empty_like(dy2)
             check(lib.meant_sigmoid_bwd(_p(dy2), _p(aux), _p(d2), dy2.numel(), _dt(dy2), _stream()), "sigmoid_bwd")
             dy2 = d2
-        dx, dw, db = _linear_bwd_raw(dy2, x2, (ctx.weight,), ctx.needs_input_grad[0], ctx.has_bias, bias_param=ctx.bias)
+        dx, dw, db = _linear_bwd_raw(dy2, x2, (ctx.weight,), ctx.needs_input_grad[0], ctx.has_bias, bias_param=ctx.bias, K=ctx.in_shape[-1])
         return (dx.view(ctx.in_shape) if dx is not None else None), dw, db, dres, None
 
 
