@@ -86,7 +86,7 @@ int meant_get_option(const char* name, int* value);
  * "nt_split", "nt_overlap", "tn128", "tn256", "tn256_det", "tn_tail", "gemm_f32", "attn_fwd", "attn_fwd_d128",
  * "attn_fwd_d96", "attn_bwd" (the two-pass form), "attn_bwd1" (the single-pass form), "attn_bwd_d128", "attn_bwd_d96",
  * "attn_generic", "attn_cls", "attn_short", "attn_fwd_d160" ... "attn_bwd_d256", "temporal_long" (the temporal attention
- * core's long-lag kernels, forward and backward each count one), "emb_seg" (meant_embedding_bwd_seg), "sort_ids" (meant_sort_ids));
+ * core's long-lag kernels, forward and backward each count one), "emb_seg" (meant_embedding_bwd_seg), "sort_ids" (meant_sort_ids), "select_rows" (meant_select_rows));
  * -1 for an unknown name.  The names label routes, not kernels: "nt256s" / "nt256s_rot" count launches of the streaming
  * GEMM (whichever kernel implements it), "nt_split" the ragged head + tail split.  Tests use it to prove that a shape
  * reaches the kernel it is meant to exercise. */
@@ -434,6 +434,20 @@ int meant_softmax_ce_fwd(const void* logits, int64_t ld, const int64_t* target, 
                          float* row_loss, float* lse, int dtype, void* stream);
 int meant_softmax_ce_bwd(const void* logits, int64_t ld, const int64_t* target, const float* lse, int64_t T, int64_t V,
                          int64_t ignore_index, const float* gscale, void* dlogits, int dtype, void* stream);
+/* the rows that count, as lists: row t is labelled iff target[t] != ignore_index && 0 <= target[t] < V (the predicate of the two
+ * calls above).  The reference's mlm_dataset labels 15 % of the positions and sets every other label to -100
+ * (utils/custom_datasets.py:46-54, consumed at pretrain_mlm.py:160,178); the head is row-wise from its first op to the loss, so it
+ * may run on the labelled rows alone.  count[0] = n, the number of labelled rows; idx int32 [T]: the labelled rows in ascending
+ * order, -1 from place n on; inv int32 [T]: inv[t] = place of row t in that list, or -1; target_sel int64 [T]: target[idx[j]] for
+ * j < n, ignore_index beyond.  With those tails a caller may round n up to any padded length m <= T and hand idx[0..m) to
+ * meant_gather_rows (-1: a zero row) and target_sel[0..m) to the loss (ignored rows); inv gathers a gradient of the m rows back
+ * to T rows with exact zeros elsewhere.  A stable compaction by prefix sums (wave ballots, per-workgroup counts, their scan,
+ * the scatter): no atomics, two runs give the same bits.  T <= 0, V <= 0, a null pointer or buffers that overlap: MEANT_ERR_ARG;
+ * T >= 2^31: MEANT_ERR_UNSUPPORTED before any launch.  workspace: meant_select_rows_ws(T) bytes (host arithmetic, monotone in T;
+ * 0 for a T the call rejects). */
+size_t meant_select_rows_ws(int64_t T);
+int meant_select_rows(const int64_t* target, int64_t T, int64_t V, int64_t ignore_index, int32_t* idx, int32_t* inv,
+                      int64_t* target_sel, int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
 /* out_accum[0] += sum(x^2) over a flat float buffer (global gradient norm; caller zeroes the scalar) */
 int meant_sumsq_f32(const float* x, int64_t n, float* out_accum, void* stream);
 /* One AdamW step (torch.optim.AdamW semantics, `step` >= 1 for the bias corrections) over flat float buffers.

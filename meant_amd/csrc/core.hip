@@ -136,7 +136,7 @@ const char* const k_routes[MEANT_ROUTE_COUNT] = {
     "attn_fwd", "attn_fwd_d128", "attn_fwd_d96", "attn_bwd", "attn_bwd_d128", "attn_bwd_d96",
     "attn_generic", "attn_cls", "attn_short", "nt_overlap", "attn_bwd1",
     "attn_fwd_d160", "attn_fwd_d192", "attn_fwd_d256", "attn_bwd_d160", "attn_bwd_d192", "attn_bwd_d256",
-    "temporal_long", "emb_seg", "sort_ids", "nt128k", "nt256k",
+    "temporal_long", "emb_seg", "sort_ids", "nt128k", "nt256k", "select_rows",
 };
 std::atomic<long long> g_route[MEANT_ROUTE_COUNT];
 }  // namespace

@@ -749,6 +749,10 @@ xPosAttention_flash = xPosAttention
 
 
 # ------------------------------------------------------------------------------------------
+# MEANT_MLM_LABELLED_ONLY=0: meant_language_pretrainer.loss() runs its head on every row (the initial value of the module's attribute)
+MLM_LABELLED_ONLY = _os.environ.get("MEANT_MLM_LABELLED_ONLY", "1") != "0"
+
+
 def _is_roberta_lm_head(h) -> bool:
     """HF `RobertaLMHead`: dense -> gelu -> layer_norm -> decoder (weight usually tied to the word embedding)"""
     return all(hasattr(h, a) for a in ("dense", "layer_norm", "decoder")) and isinstance(getattr(h, "decoder"), nn.Linear)
@@ -769,6 +773,8 @@ class meant_language_pretrainer(nn.Module):
         self.languageEncoders = nn.ModuleList([languageEncoder(text_dim, num_heads, flash=flash) for _ in range(num_encoders)])
         self.mlm_head = lm_head
         self.lag = lag
+        self.labelled_only = MLM_LABELLED_ONLY
+        self.last_head_rows = None                       # rows the head ran on in the last loss() call, padding included
 
     def _encode(self, words, attention_mask):
         dt = resolve_compute_dtype(self, None)
@@ -790,12 +796,31 @@ class meant_language_pretrainer(nn.Module):
             return ops.vocab_linear(self._head_features(x), h.decoder.weight, h.decoder.bias)
         return h(x)
 
-    def loss(self, words, attention_mask, labels, ignore_index: int = -100):
-        x = self._encode(words, attention_mask)
+    def loss(self, words, attention_mask, labels, ignore_index: int = -100, labelled_only=None):
+        """labelled_only (None: the attribute of that name, initially MEANT_MLM_LABELLED_ONLY, default 1): a RobertaLMHead-shaped head
+        -- row-wise from its dense layer to the loss -- runs on the rows that carry a label alone (utils/custom_datasets.py:46-54
+        labels 15 % of the positions): same loss, same gradients up to the order of fp32 sums.  The rows are selected HERE, before
+        the encoder stack is enqueued: the labels are ready, and reading the count back (labels on the device; labels on the host
+        need no read) waits only for what the stream already holds, never for this step's stack."""
         h = self.mlm_head
-        if _is_roberta_lm_head(h):
-            return ops.vocab_linear_cross_entropy(self._head_features(x), h.decoder.weight, h.decoder.bias, labels, ignore_index)
-        return ops.softmax_cross_entropy(h(x), labels, ignore_index)
+        roberta = _is_roberta_lm_head(h)
+        T = labels.numel()
+        sel, m = None, T
+        if roberta and (self.labelled_only if labelled_only is None else labelled_only):
+            sel = ops.select_rows(labels, h.decoder.weight.shape[0], ignore_index)
+            m = ops.padded_rows(sel.n)
+            if m >= T:                                   # nothing to save (causal-LM style labels): the all-rows route
+                sel, m = None, T
+        x = self._encode(words, attention_mask)
+        self.last_head_rows = m
+        if sel is None and not labels.is_cuda:           # host labels on the all-rows route: uploaded here, as select_rows would have
+            labels = labels.to(x.device)
+        if not roberta:
+            return ops.softmax_cross_entropy(h(x), labels, ignore_index)
+        if sel is not None:
+            x = ops.take_rows(x.reshape(T, x.shape[-1]), sel.idx, sel.inv, m)
+            labels = sel.target_sel[:m]
+        return ops.vocab_linear_cross_entropy(self._head_features(x), h.decoder.weight, h.decoder.bias, labels, ignore_index)
 
 
 # ------------------------------------------------------------------------------------------

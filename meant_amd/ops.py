@@ -11,7 +11,7 @@ import math
 import os
 import threading
 import weakref
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -1542,11 +1542,97 @@ def vocab_linear(x, weight, bias=None):
     return _vocab_logits_padded(x, weight, bias)[..., :weight.shape[0]]
 
 
-def vocab_linear_cross_entropy(x, weight, bias, target, ignore_index: int = -100):
+def vocab_linear_cross_entropy(x, weight, bias, target, ignore_index: int = -100, rows: str = "all"):
     """CrossEntropyLoss(vocab_linear(x).view(-1, V), target.view(-1)) without ever slicing or re-homing the logits:
-    the padded logits buffer goes straight into the fused loss and its gradient straight back into the GEMMs."""
+    the padded logits buffer goes straight into the fused loss and its gradient straight back into the GEMMs.
+    rows = "labelled": the GEMMs and the loss run on the rows that carry a label alone (select_rows / take_rows; the
+    count rounded up by padded_rows, the padding being zero rows with the ignore target) -- the same loss and gradients
+    up to the order of fp32 sums, with the rows of dx that the loss ignores exact zeros as before."""
+    if rows not in ("all", "labelled"):
+        raise ValueError(f"vocab_linear_cross_entropy: rows must be 'all' or 'labelled', got {rows!r}")
+    V = weight.shape[0]
+    if rows == "labelled":
+        sel = select_rows(target.reshape(-1), V, ignore_index)
+        m = padded_rows(sel.n)
+        if m < sel.idx.numel():                        # otherwise nothing to save (causal-LM style labels): all rows, below
+            x = take_rows(x.reshape(-1, x.shape[-1]), sel.idx, sel.inv, m)
+            target = sel.target_sel[:m]
     lp = _vocab_logits_padded(x, weight, bias)
-    return _SoftmaxCE.apply(lp.reshape(-1, lp.shape[-1]), target.reshape(-1), weight.shape[0], ignore_index)
+    return _SoftmaxCE.apply(lp.reshape(-1, lp.shape[-1]), target.reshape(-1), V, ignore_index)
+
+
+# ---- the labelled rows of an MLM batch (utils/custom_datasets.py:46-54: 15 % of the positions; the rest carry -100) ----------
+ROW_PAD_SMALL, ROW_PAD_STREAM, ROW_STREAM_MIN = 8, 256, 1024
+
+
+def padded_rows(n: int) -> int:
+    """the row count the head runs on for n labelled rows (always >= 8, so n = 0 is one block of zero rows and no special case):
+    from 1024 rows on -- where the vocabulary GEMM, its dX and the 768-wide Linears take the streaming 256 x 256 kernel -- a
+    multiple of 256, so that those launches see whole row tiles and the dW kernel whole 64-row steps (no overlapped last tile,
+    no tail launch); below, a multiple of 8."""
+    g = ROW_PAD_STREAM if n >= ROW_STREAM_MIN else ROW_PAD_SMALL
+    return max((int(n) + g - 1) // g * g, g)
+
+
+class SelectedRows(NamedTuple):
+    idx: torch.Tensor            # int32 [T]: the labelled rows, ascending; -1 behind them
+    inv: torch.Tensor            # int32 [T]: a row's place in idx, or -1
+    target_sel: torch.Tensor     # int64 [T]: target[idx[j]]; ignore_index behind them
+    count: torch.Tensor          # int32 [1] on the device
+    n: int                       # the same count on the host
+
+
+def select_rows(target, V: int, ignore_index: int = -100) -> SelectedRows:
+    """meant_select_rows on the labels `target` (any shape, read as [T]): the lists take_rows and the loss need to run on the
+    labelled rows alone.  Labels on the host (where a data loader leaves them): the count comes from the labels themselves, the
+    labels are uploaded and the kernel builds the lists -- nothing is read back.  Labels on the device: ONE read of the count
+    (it waits for what is queued on the stream at that moment, so call it before enqueueing work it need not wait for)."""
+    tgt = target.reshape(-1)
+    if tgt.dtype != torch.int64:
+        tgt = tgt.long()
+    n_host = None
+    if not tgt.is_cuda:
+        n_host = int(((tgt != ignore_index) & (tgt >= 0) & (tgt < V)).sum())
+        tgt = tgt.to(torch.device("cuda", torch.cuda.current_device()))
+    _need_gpu(tgt)
+    tgt = _c(tgt)
+    T = tgt.numel()
+    dev = tgt.device
+    idx = torch.empty(T, device=dev, dtype=torch.int32)
+    inv = torch.empty(T, device=dev, dtype=torch.int32)
+    tsel = torch.empty(T, device=dev, dtype=torch.int64)
+    count = torch.empty(1, device=dev, dtype=torch.int32)
+    wsb = lib.meant_select_rows_ws(T)
+    ws = torch.empty(max(wsb, 16), device=dev, dtype=torch.uint8)
+    check(lib.meant_select_rows(_p(tgt), T, int(V), int(ignore_index), _p(idx), _p(inv), _p(tsel), _p(count), _p(ws), wsb, _stream()),
+          "select_rows")
+    if n_host is None:
+        n_host = int(count.item())
+    return SelectedRows(idx, inv, tsel, count, n_host)
+
+
+class _TakeRows(torch.autograd.Function):
+    """y = x2d[idx[:m]] (zero rows where idx is -1); the gradient goes back through the inverse list: dx[t] = dy[inv[t]], exact zeros
+    where inv is -1 -- a gather both ways, no atomics"""
+
+    @staticmethod
+    def forward(ctx, x2d, idx, inv, m):
+        ctx.save_for_backward(inv)
+        return gather_rows(x2d, idx[:m])
+
+    @staticmethod
+    def backward(ctx, dy):
+        (inv,) = ctx.saved_tensors
+        return gather_rows(dy, inv), None, None, None
+
+
+def take_rows(x2d, idx, inv, m: int):
+    """differentiable row gather by the lists of select_rows: x2d [T, W] (W % 8 == 0, either tier) -> [m, W], m <= T"""
+    if x2d.dim() != 2 or x2d.shape[0] != idx.numel() or inv.numel() != idx.numel() or not 0 < m <= idx.numel():
+        raise ValueError(f"take_rows: x2d {tuple(x2d.shape)}, idx [{idx.numel()}], inv [{inv.numel()}], m = {m}")
+    if x2d.shape[1] % 8:
+        raise ValueError(f"take_rows: row width {x2d.shape[1]} must be a multiple of 8")
+    return _TakeRows.apply(x2d, idx, inv, int(m))
 
 
 def softmax_cross_entropy(logits, target, ignore_index: int = -100):
