@@ -86,7 +86,9 @@ int meant_get_option(const char* name, int* value);
  * "nt_split", "nt_overlap", "tn128", "tn256", "tn256_det", "tn_tail", "gemm_f32", "attn_fwd", "attn_fwd_d128",
  * "attn_fwd_d96", "attn_bwd" (the two-pass form), "attn_bwd1" (the single-pass form), "attn_bwd_d128", "attn_bwd_d96",
  * "attn_generic", "attn_cls", "attn_short", "attn_fwd_d160" ... "attn_bwd_d256", "temporal_long" (the temporal attention
- * core's long-lag kernels, forward and backward each count one), "emb_seg" (meant_embedding_bwd_seg), "sort_ids" (meant_sort_ids), "select_rows" (meant_select_rows));
+ * core's long-lag kernels, forward and backward each count one), "emb_seg" (meant_embedding_bwd_seg), "sort_ids" (meant_sort_ids), "select_rows" (meant_select_rows),
+ * "rotary_qk" (every meant_rotary_qk launch), "rotary_pairs" (those of its pair-by-pair kernel: Dh % 8 != 0 or an unaligned base)
+ * and "nt_rot" (every bf16 NT GEMM launched with the rotary epilogue, on top of the nt* route it takes));
  * -1 for an unknown name.  The names label routes, not kernels: "nt256s" / "nt256s_rot" count launches of the streaming
  * GEMM (whichever kernel implements it), "nt_split" the ragged head + tail split.  Tests use it to prove that a shape
  * reaches the kernel it is meant to exercise. */
@@ -194,7 +196,8 @@ int meant_linear_fwd(const void* x, int64_t ldx, const void* w, const float* bia
 /* Fused q|k|v projection + rotary:  qkv[M, 3*H*Dh] = x[M,K] w[3*H*Dh, K]^T + bias, then the rotation of
  * meant_rotary_qk on the q and k blocks (tables may be NULL: plain projection).  In the bf16 tier the rotation
  * rides the GEMM epilogue (no extra pass over qkv) at every K % 8 == 0 (Dh % 8 == 0, R % 8 == 0), K % 64 != 0 included
- * (K-tail kernels, as meant_linear_fwd).   meant/attention.py:36-40, meant/xPosAttention.py:37-39 */
+ * (K-tail kernels, as meant_linear_fwd); any other (Dh, R), and the f32 tier, run the plain projection and then
+ * meant_rotary_qk in place.   meant/attention.py:36-40, meant/xPosAttention.py:37-39 */
 int meant_qkv_proj_fwd(const void* x, int64_t ldx, const void* w, const float* bias, void* qkv, int64_t M,
                        int64_t K, int64_t S, int H, int Dh, int R, const float* qa, const float* qb,
                        const float* ka, const float* kb, int dtype, void* stream);
@@ -238,7 +241,10 @@ int meant_gemm_f32_strided(const float* A, const float* B, float* C, int64_t M, 
  *   out[c] = t[c]*A[pos,c] + rot(t)[c]*B[pos,c]  for lanes c < R of every head,
  *   rot(t)[2j] = -t[2j+1], rot(t)[2j+1] = t[2j];   pos = row mod S.
  * qa,qb,ka,kb: float [S, R] (cos*scale, sin*scale for q and for k).  `transpose` != 0 applies
- * the adjoint (backward). */
+ * the adjoint (backward).  Any Dh > 0 and any even R in [0, Dh], both dtypes.  Dh % 8 == 0 with a 16-byte aligned qkv moves
+ * 16-byte chunks; any other Dh, or a base that is only element-aligned, is rotated pair by pair.  Lanes >= R of a head, the v
+ * block and the tables at or beyond column R of a row are never touched.  Tables padded from R to ceil8(R) columns with
+ * identity columns (a = 1, b = 0) rotate to the same values. */
 int meant_rotary_qk(void* qkv, int64_t T, int64_t S, int H, int Dh, int R, const float* qa, const float* qb,
                     const float* ka, const float* kb, int transpose, int dtype, void* stream);
 
@@ -251,9 +257,9 @@ int meant_rotary_qk(void* qkv, int64_t T, int64_t S, int H, int Dh, int R, const
  * key_mask: float [G, S] of {0,1} or NULL (adds (1-mask)*-1e9 to the scores);
  * causal: scores[i,j] = -inf for j > i;  scale is the caller's (the reference: 1/sqrt(dim), NOT 1/sqrt(Dh)).
  * bf16: fused flash kernels for Dh = 64, 96 (the reference's default: 8 heads at d = 768, meant/meant.py:149), 128, 160,
- * 192 and 256 (8 heads at d = 1280 / 1536 / 2048) (a caller with another head dim below 256 that is a multiple of 8 pads every
- * head to the next of these with zeros -- zero rows in the projection weight -- and keeps its own scale; other Dh take a
- * slow fp32 detour through `workspace`); f32: materialised scores in `workspace`. */
+ * 192 and 256 (8 heads at d = 1280 / 1536 / 2048) (a caller with another head dim below 256, a multiple of 8 or not, pads every
+ * head to one of these with zeros -- zero rows in the projection weight -- and keeps its own scale; other Dh given to this entry
+ * take a slow fp32 detour through `workspace`); f32: materialised scores in `workspace`, any Dh. */
 size_t meant_attn_ws(int64_t G, int64_t S, int H, int Dh, int dtype);
 /* what meant_attn_fwd alone needs (mask bias, tile flags); meant_attn_ws covers forward and backward (bf16: the backward's row
  * statistics and, for 256 < S <= 512 at Dh = 64, the single-pass backward's partial-dQ scratch of G*H*64 KiB) */
@@ -278,7 +284,9 @@ int meant_attn_drop_bwd(const void* qkv, const void* o, const void* do_, const f
 /* dqkv: act [G*S, 3*H*Dh] (every element written); do_: act [G*S, H*Dh].
  * If the rotary tables qa,qb,ka,kb (float [S, R], as in meant_rotary_qk) are given, dq and dk are returned
  * already pulled back through the rotation (the adjoint of meant_rotary_qk), i.e. dqkv is the gradient of
- * the un-rotated projection; pass NULLs (and R = 0) for the gradient of the rotated buffer. */
+ * the un-rotated projection; pass NULLs (and R = 0) for the gradient of the rotated buffer.  Any even R <= Dh: the bf16 kernels
+ * apply the adjoint themselves at R % 8 == 0 and R <= 64, otherwise the backward runs without tables and meant_rotary_qk
+ * (transpose = 1) follows in place. */
 int meant_attn_bwd(const void* qkv, const void* o, const void* do_, const float* lse, const float* key_mask,
                    void* dqkv, int64_t G, int64_t S, int H, int Dh, float scale, int causal, const float* qa,
                    const float* qb, const float* ka, const float* kb, int R, int dtype, void* workspace,

@@ -1046,16 +1046,15 @@ int attn_bf16_bwd(const bf16* qkv, const bf16* o, const bf16* dout, const float*
     if (rcg || !rot.qa) return rcg;
     return meant_rotary_qk(dqkv, G * S, S, H, Dh, rot.R, rot.qa, rot.qb, rot.ka, rot.kb, 1, MEANT_BF16, stream);
   }
-  if (rot.qa && rot.R > DH) {                          // the kernels' epilogues rotate at most 64 lanes of a head (a TimeSformer at
-    // Dh = 96 / 128 rotates all Dh): the backward without tables, then the adjoint in place, as the fp32 tier does
+  if (rot.qa && (rot.R > DH || rot.R % 8 != 0)) {      // the kernels' epilogues rotate whole 8-lane chunks, at most 64 lanes of a head (a
+    // TimeSformer at Dh = 96 / 128 rotates all Dh): the backward without tables, then the adjoint in place, as the fp32 tier does
     const int rcn = attn_bf16_bwd(qkv, o, dout, lse, key_mask, dqkv, G, S, H, Dh, scale, causal, RotTables{nullptr, nullptr, nullptr, nullptr, 0},
                                   ws, ws_bytes, stream);
     if (rcn) return rcn;
     return meant_rotary_qk(dqkv, G * S, S, H, Dh, rot.R, rot.qa, rot.qb, rot.ka, rot.kb, 1, MEANT_BF16, stream);
   }
-  if (attn_short_ok(S, Dh) && (!rot.qa || (rot.R % 8 == 0 && rot.R <= DH)))
-    return attn_short_bwd(qkv, dout, lse, key_mask, dqkv, G, S, H, Dh, scale, causal, rot, stream);
-  MEANT_REQUIRE(!rot.qa || (rot.R % 8 == 0 && rot.R <= DH), MEANT_ERR_UNSUPPORTED, "attn_bwd: rotary dim must be a multiple of 8 and <= 64");
+  // tables from here on: R % 8 == 0 and R <= 64 <= Dh, what the kernels' own adjoint takes
+  if (attn_short_ok(S, Dh)) return attn_short_bwd(qkv, dout, lse, key_mask, dqkv, G, S, H, Dh, scale, causal, rot, stream);
   int rc = attn_bf16_check("attn_bwd", G, S, H, Dh);
   if (rc) return rc;
   const AttnWs L(G, S, H, Dh);

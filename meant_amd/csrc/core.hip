@@ -137,6 +137,8 @@ const char* const k_routes[MEANT_ROUTE_COUNT] = {
     "attn_generic", "attn_cls", "attn_short", "nt_overlap", "attn_bwd1",
     "attn_fwd_d160", "attn_fwd_d192", "attn_fwd_d256", "attn_bwd_d160", "attn_bwd_d192", "attn_bwd_d256",
     "temporal_long", "emb_seg", "sort_ids", "nt128k", "nt256k", "select_rows",
+    "rotary_qk", "rotary_pairs",   // every meant_rotary_qk launch; those of the pair-by-pair kernel (Dh % 8 != 0 or an unaligned base)
+    "nt_rot",                       // every bf16 NT GEMM launched with the rotary epilogue, whichever nt* route it takes
 };
 std::atomic<long long> g_route[MEANT_ROUTE_COUNT];
 }  // namespace

@@ -171,6 +171,40 @@ __global__ __launch_bounds__(EW_THREADS) void rotary_kernel(T* __restrict__ qkv,
   }
 }
 
+// The same map by element access, for rows that are only element-aligned (Dh % 8 != 0: head dims such as 29 or 76, where neither a
+// head nor a token row starts on 16 bytes) or an unaligned base.  One thread = one pair (2j, 2j + 1) of the rotated prefix of one head
+// of q or k: two loads, two stores, the arithmetic of rotary_kernel on the stored values.  Columns >= R of a head and the v block are
+// not touched; the tables are read at columns 2j and 2j + 1 < R only.
+template <typename T, bool TRANSPOSE>
+__global__ __launch_bounds__(EW_THREADS) void rotary_pair_kernel(T* __restrict__ qkv, int64_t T_rows, int S, int H, int Dh, int R,
+                                                                  const float* __restrict__ qa, const float* __restrict__ qb,
+                                                                  const float* __restrict__ ka, const float* __restrict__ kb) {
+  const int ppr = R >> 1;                           // pairs per head
+  const int64_t per_row = (int64_t)2 * H * ppr;
+  const int64_t total = T_rows * per_row;
+  const int64_t ld = (int64_t)3 * H * Dh;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t t = i / per_row;
+    int rem = (int)(i - t * per_row);
+    const int which = rem / (H * ppr);              // 0 = q, 1 = k
+    rem -= which * H * ppr;
+    const int h = rem / ppr, c = (rem - h * ppr) * 2;
+    const int pos = (int)(t % S);
+    T* p = qkv + t * ld + (int64_t)which * H * Dh + h * Dh + c;
+    const float* A = (which ? ka : qa) + (int64_t)pos * R + c;
+    const float* B = (which ? kb : qb) + (int64_t)pos * R + c;
+    const float t0 = to_f(p[0]), t1 = to_f(p[1]);
+    float o0, o1;
+    if (!TRANSPOSE) rotary_pair(t0, t1, A[0], A[1], B[0], B[1], o0, o1);
+    else {
+      o0 = t0 * A[0] + t1 * B[1];
+      o1 = t1 * A[1] - t0 * B[0];
+    }
+    p[0] = from_f<T>(o0);
+    p[1] = from_f<T>(o1);
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // K7a patchify: out[(g,ph,pw), (p1,p2,c)] = img[g,c,ph*p+p1,pw*p+p2]
 template <typename TI, typename T>
@@ -494,14 +528,23 @@ extern "C" int meant_rotary_qk(void* qkv, int64_t T_rows, int64_t S, int H, int 
                                const float* ka, const float* kb, int transpose, int dtype, void* stream) {
   EW_REQ(qkv && qa && qb && ka && kb, "rotary_qk: null pointer");
   EW_REQ(T_rows > 0 && S > 0 && T_rows % S == 0, "rotary_qk: T=%lld must be a multiple of S=%lld", (long long)T_rows, (long long)S);
-  MEANT_REQUIRE(H > 0 && Dh % 8 == 0 && R % 2 == 0 && R <= Dh && R % 8 == 0, MEANT_ERR_UNSUPPORTED,
-                "rotary_qk: need Dh%%8==0 and rot_dim%%8==0 (Dh=%d R=%d)", Dh, R);
-  EW_REQ(meant_aligned16(qkv), "rotary_qk: 16-byte alignment");
+  EW_REQ(H > 0 && Dh > 0 && R >= 0 && R % 2 == 0 && R <= Dh, "rotary_qk: need Dh > 0 and an even rot_dim in [0, Dh] (Dh=%d R=%d)", Dh, R);
+  EW_REQ((uintptr_t)qkv % (dtype == MEANT_F32 ? 4 : 2) == 0, "rotary_qk: qkv is not aligned to its element type");
   if (R == 0) return MEANT_OK;
-  const int64_t items = T_rows * 2 * H * ((R + 7) / 8);
+  // 16-byte chunks where every head starts on one (Dh % 8 == 0 and an aligned base; at R % 8 != 0 the last chunk of a head rotates
+  // its leading pairs only and reads the tables below column R only); pair by pair otherwise
+  const bool chunks = Dh % 8 == 0 && meant_aligned16(qkv);
+  const int64_t items = T_rows * 2 * H * (chunks ? (R + 7) / 8 : R / 2);
+  meant_route_hit(ROUTE_ROTARY_QK);
+  if (!chunks) meant_route_hit(ROUTE_ROTARY_PAIRS);
   DISPATCH_DTYPE(dtype, T, {
-    if (transpose) hipLaunchKernelGGL((rotary_kernel<T, true>), dim3(ew_blocks(items)), dim3(EW_THREADS), 0, (hipStream_t)stream, (T*)qkv, T_rows, (int)S, H, Dh, R, qa, qb, ka, kb);
-    else hipLaunchKernelGGL((rotary_kernel<T, false>), dim3(ew_blocks(items)), dim3(EW_THREADS), 0, (hipStream_t)stream, (T*)qkv, T_rows, (int)S, H, Dh, R, qa, qb, ka, kb);
+    if (chunks) {
+      if (transpose) hipLaunchKernelGGL((rotary_kernel<T, true>), dim3(ew_blocks(items)), dim3(EW_THREADS), 0, (hipStream_t)stream, (T*)qkv, T_rows, (int)S, H, Dh, R, qa, qb, ka, kb);
+      else hipLaunchKernelGGL((rotary_kernel<T, false>), dim3(ew_blocks(items)), dim3(EW_THREADS), 0, (hipStream_t)stream, (T*)qkv, T_rows, (int)S, H, Dh, R, qa, qb, ka, kb);
+    } else {
+      if (transpose) hipLaunchKernelGGL((rotary_pair_kernel<T, true>), dim3(ew_blocks(items)), dim3(EW_THREADS), 0, (hipStream_t)stream, (T*)qkv, T_rows, (int)S, H, Dh, R, qa, qb, ka, kb);
+      else hipLaunchKernelGGL((rotary_pair_kernel<T, false>), dim3(ew_blocks(items)), dim3(EW_THREADS), 0, (hipStream_t)stream, (T*)qkv, T_rows, (int)S, H, Dh, R, qa, qb, ka, kb);
+    }
   });
   MEANT_LAUNCH_CHECK("rotary_qk");
   return MEANT_OK;

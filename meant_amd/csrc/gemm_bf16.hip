@@ -1327,6 +1327,7 @@ int gemm_bf16_nt_launch(const GemmBf16Args& a, hipStream_t stream) {
   MEANT_REQUIRE(!ext || (!a.rot_qa && !(a.epilogue & MEANT_EPI_SIGMOID)), MEANT_ERR_UNSUPPORTED, "gemm_bf16_nt: extended epilogue with rotary / sigmoid");
   MEANT_REQUIRE(!a.rot_qa || (!a.residual && !a.preact && !act), MEANT_ERR_UNSUPPORTED, "gemm_bf16_nt: rotary epilogue with residual / activation / preact");
   MEANT_REQUIRE(!a.sub || (a.sub_coef && (a.ldsub & 7) == 0 && meant_aligned16(a.sub)), MEANT_ERR_ARG, "gemm_bf16_nt: bad sub operand");
+  if (a.rot_qa) meant_route_hit(ROUTE_NT_ROT);
   // big tall problems: 256 x 256 tiles (half the operand bytes per FLOP) -- once there are enough of them to occupy at least
   // half the CUs (the temporal encoder's 1536^2 Linears make 36: four times as many 128 x 128 tiles finish in a third of the time)
   if (a.M >= 1024 && a.N % 256 == 0 && ceil_div(a.M, B2) * (a.N / B2) * 2 >= meant_num_cus()) {

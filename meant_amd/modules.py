@@ -187,12 +187,20 @@ class RotaryEmbedding(nn.Module):
         si = s ** -1
         return cos * s, sin * s, cos * si, sin * si
 
-    def tables(self, seq_len: int, device) -> tuple:
-        """(qa, qb, ka, kb) float32 [S, R] on `device`: out = t*a + rot(t)*b."""
+    def tables(self, seq_len: int, device, head_dim: Optional[int] = None) -> tuple:
+        """(qa, qb, ka, kb) float32 [S, R] on `device`: out = t*a + rot(t)*b.  head_dim: the head dim the attention kernels will see
+        (ops.run_head_dim); a rotary dim off the 8-grid is then padded to ceil8(R) identity columns where that head has room
+        (ops.pad_rotary_tables), and the padded tables are kept beside the plain ones."""
         key = (seq_len, str(device), self.freqs._version, self.freqs.data_ptr())
         hit = self._tables.get(key)
         if hit is not None:
-            return hit
+            if head_dim is None:
+                return hit
+            pkey = ("pad", head_dim) + key
+            padded = self._tables.get(pkey)
+            if padded is None:
+                padded = self._tables[pkey] = ops.pad_rotary_tables(hit, head_dim)
+            return padded
         with torch.no_grad():
             f = self.freqs.detach().float().cpu()
             pos = torch.arange(seq_len)
@@ -209,9 +217,9 @@ class RotaryEmbedding(nn.Module):
             t = tuple(x.contiguous().to(device) for x in t)
             if not self.use_xpos:
                 t = (t[0], t[1], t[0], t[1])
-        self._tables = {k: v for k, v in self._tables.items() if k[2:] == key[2:]}
+        self._tables = {k: v for k, v in self._tables.items() if k[-2:] == key[-2:]}
         self._tables[key] = t
-        return t
+        return t if head_dim is None else self.tables(seq_len, device, head_dim)
 
 
 def _rotate_pairs(t, a, b):
@@ -287,7 +295,7 @@ class attention(nn.Module):
         """pre: an nn.Linear that the caller would have applied to x right before this module (composed into q/k/v)"""
         if self.pos_emb is not None and getattr(self.pos_emb, 'learned_freq', False):
             return learned_rotary_attention(x, self, self.pos_emb, None, bool(self.mask), pre)
-        tables = self.pos_emb.tables(x.shape[1], x.device) if self.pos_emb is not None else None
+        tables = self.pos_emb.tables(x.shape[1], x.device, ops.run_head_dim(self.Dh, x.dtype)) if self.pos_emb is not None else None
         prew = (pre.weight, pre.bias) if pre is not None else None
         return ops.qkv_attention(x, self.q.weight, self.q.bias, self.v.weight, self.v.bias, self.k.weight, self.k.bias,
                                  tables, None, bool(self.mask), self.num_heads, pre=prew)
@@ -321,7 +329,7 @@ class xPosAttention(nn.Module):
             return score_dropout_attention(x, self, self.xPos, attention_mask, bool(self.mask), float(self.dropout.p), _seed(), pre)
         if getattr(self.xPos, 'learned_freq', False):
             return learned_rotary_attention(x, self, self.xPos, attention_mask, bool(self.mask), pre)
-        tables = self.xPos.tables(x.shape[1], x.device)
+        tables = self.xPos.tables(x.shape[1], x.device, ops.run_head_dim(self.Dh, x.dtype))
         prew = (pre.weight, pre.bias) if pre is not None else None
         return ops.qkv_attention(x, self.q.weight, self.q.bias, self.v.weight, self.v.bias, self.k.weight, self.k.bias,
                                  tables, attention_mask, bool(self.mask), self.num_heads, pre=prew)
@@ -885,8 +893,20 @@ class _TSAttention(nn.Module):
         self.to_out = nn.Sequential(Linear(inner, dim), nn.Identity())
 
     def forward(self, x, plan, tables, group_mask=None, cls_mask=None, residual=None, drop_p=0.0):
-        qkv = self.to_qkv(x)                                             # [b, 1 + f n, 3 inner]
-        out = ops.divided_attention(qkv, plan, tables, self.heads, self.scale, group_mask, cls_mask)
+        H, Dh = self.heads, self.dim_head
+        Dp = ops.divided_head_dim(Dh, x.dtype)
+        if Dp != Dh:
+            # dim_head % 8 != 0: every head zero-padded in the projection weight (differentiable, as ops.qkv_attention does), so the
+            # gathers, the attention core and the cls kernels see a head dim they take; the scale stays dim_head ** -0.5, the zero
+            # columns of v give zero output columns, which are dropped before to_out
+            w = self.to_qkv.weight
+            wp = torch.nn.functional.pad(w.view(3 * H, Dh, w.shape[1]), (0, 0, 0, Dp - Dh)).reshape(3 * H * Dp, w.shape[1])
+            qkv = ops.linear(x, wp)
+            out = ops.divided_attention(qkv, plan, tables, H, self.scale, group_mask, cls_mask)
+            out = out.view(*out.shape[:-1], H, Dp)[..., :Dh].reshape(*out.shape[:-1], H * Dh)
+        else:
+            qkv = self.to_qkv(x)                                         # [b, 1 + f n, 3 inner]
+            out = ops.divided_attention(qkv, plan, tables, H, self.scale, group_mask, cls_mask)
         if drop_p > 0.0:                                                 # Dropout after to_out (:101) sits before the block's `+ x`
             return ops.dropout(self.to_out[0](out), drop_p, _seed()) + residual
         return self.to_out[0](out, residual=residual)                    # the block's `+ x` rides the GEMM epilogue
@@ -979,7 +999,8 @@ class TimeSformer(nn.Module):
                     return None
                 cos = torch.cat((torch.ones(1, a.shape[1]), a.cos())).contiguous().to(device)   # row 0: cls, not rotated
                 sin = torch.cat((torch.zeros(1, a.shape[1]), a.sin())).contiguous().to(device)
-                return (cos, sin, cos, sin)
+                # a rotary dim off the 8-grid (dim_head 12, 20, 50): identity columns up to ceil8, which the padded head has room for
+                return ops.pad_rotary_tables((cos, sin, cos, sin), (self.dim_head + 7) & ~7)
 
             def tables_of(index):                                                             # index [G, S] long
                 G, S = index.shape

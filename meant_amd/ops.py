@@ -973,21 +973,62 @@ NATIVE_HEAD_DIMS = (64, 96, 128, 160, 192, 256)   # what the bf16 MFMA attention
 
 
 def _padded_head_dim(Dh):
-    """the native head dim a bf16 head of Dh columns is zero-padded to, or None (native already, Dh % 8 != 0, Dh > 256)"""
-    if Dh in NATIVE_HEAD_DIMS or Dh % 8 or Dh > 256:
+    """the native head dim a bf16 head of Dh columns is zero-padded to, or None (native already, Dh > 256).  Multiples of 8 go to
+    128 below 128 and to the next native dim above; any other Dh to the smallest native dim that holds it (29 -> 64, 76 -> 96)"""
+    if Dh in NATIVE_HEAD_DIMS or Dh > 256:
         return None
+    if Dh % 8:
+        return next(n for n in NATIVE_HEAD_DIMS if n > Dh)
     return 128 if Dh < 128 else next(n for n in NATIVE_HEAD_DIMS if n > Dh)
+
+
+def run_head_dim(Dh: int, dtype: torch.dtype) -> int:
+    """the head dim the attention kernels see for a module head of Dh columns in the tier of `dtype`: the padded dim where
+    qkv_attention pads (bf16 tier), Dh itself otherwise"""
+    return (_padded_head_dim(Dh) if dtype == torch.bfloat16 else None) or Dh
+
+
+def divided_head_dim(Dh: int, dtype: torch.dtype) -> int:
+    """the head dim a TimeSformer head of Dh columns runs at: Dh where Dh % 8 == 0 (as before); any other Dh is zero-padded, in the
+    bf16 tier to the smallest native dim that holds it, in the fp32 tier (and above 256) to ceil8(Dh), which is what
+    meant_gather_rows_rot and the cls kernels take"""
+    if Dh % 8 == 0:
+        return Dh
+    return (_padded_head_dim(Dh) if dtype == torch.bfloat16 else None) or (Dh + 7) & ~7
+
+
+def pad_rotary_tables(tables, head_dim: int):
+    """(qa, qb, ka, kb) float [S, R] with R % 8 != 0 -> the same tables at ceil8(R) columns, the new ones the identity (a = 1, b = 0):
+    the same rotation (x * 1 + rot(x) * 0 on lanes that were passed through before), on tables the projection GEMM's rotary epilogue,
+    the attention backward's in-kernel adjoint and meant_gather_rows_rot take.  Only where the head the kernels see (`head_dim`)
+    is a multiple of 8 with room for the padded columns; the tables come back as they are otherwise.  Tensors shared between the
+    q and the k side stay shared."""
+    if tables is None:
+        return None
+    R = tables[0].shape[1]
+    R8 = (R + 7) & ~7
+    if R8 == R or head_dim % 8 or R8 > head_dim:
+        return tables
+    done = {}
+    out = []
+    for i, tb in enumerate(tables):
+        if id(tb) not in done:
+            done[id(tb)] = torch.nn.functional.pad(tb, (0, R8 - R), value=1.0 if i % 2 == 0 else 0.0).contiguous()
+        out.append(done[id(tb)])
+    return tuple(out)
 
 
 def qkv_attention(x, wq, bq, wk, bk, wv, bv, tables, key_mask, causal, num_heads, pre=None):
     """pre = (W1, b1) of a Linear applied to x immediately before the projections (composed into them).
 
-    bf16 tier, head dims that are multiples of 8 up to 256 but not native (64 / 96 / 128 / 160 / 192 / 256; 96 = the
-    reference classes' default of 8 heads at d = 768, 160 / 192 / 256 = 8 heads at d = 1280 / 1536 / 2048): every head is
-    widened to the next native dim (128 below 128) by zero rows in the projection weights, so q, k, v come out of the GEMM already padded, the
+    bf16 tier, head dims up to 256 that are not native (64 / 96 / 128 / 160 / 192 / 256; 96 = the reference classes' default of
+    8 heads at d = 768, 160 / 192 / 256 = 8 heads at d = 1280 / 1536 / 2048): every head is widened to a native dim
+    (_padded_head_dim: multiples of 8 to 128 below 128 and to the next native dim above, any other Dh -- 29, 76, 100, 172 -- to the
+    smallest native dim that holds it) by zero rows in the projection weights, so q, k, v come out of the GEMM already padded, the
     scores are unchanged (zeros add nothing to q.k, the scale stays 1/sqrt(dim)), and the zero columns of v give zero
     columns of the output, which are dropped again.  The padding is built from the parameters with differentiable ops,
-    so their gradients need no special handling."""
+    so their gradients need no special handling.  `tables` with a rotary dim off the 8-grid: the caller pads them
+    (pad_rotary_tables, via RotaryEmbedding.tables(head_dim=run_head_dim(...))) so that the fused epilogue stays on."""
     wqkv = torch.cat([wq, wk, wv], dim=0)
     bqkv = torch.cat([bq, bk, bv], dim=0)
     if pre is not None:
