@@ -216,13 +216,18 @@ int meant_linear_bwd_dx_norm(const void* dy_scaled, int64_t lddy, const void* wT
                              void* stream);
 /* dx[M,K] = dy[M,N] w[N,K]   (wT is w transposed, [K,N], act dtype: see meant_transpose2d).  The reduction length is N: bf16
  * tier, any N % 8 == 0 on the MFMA kernels (N % 64 != 0: the K-tail forms, as meant_linear_fwd); K is free (K % 8 != 0 stores
- * element by element). */
+ * element by element).  N % 8 != 0 (or lddy % 8 != 0, or an unaligned operand) takes the exact-f32 engine on bf16 storage; a caller
+ * with such an N pads dy and wT to ceil8(N) zero columns with meant_pad_copy2d first and passes N = lddy = ceil8(N). */
 int meant_linear_bwd_dx(const void* dy, int64_t lddy, const void* wT, void* dx, int64_t lddx, int64_t M,
                         int64_t N, int64_t K, int dtype, void* stream);
 /* dw[N,K] += dy[M,N]^T x[M,K]  and  dbias[N] += colsum(dy)  -- float accumulators the caller zeroes
  * (or pre-loads: gradient buckets, accumulation across micro-batches).  dbias may be NULL.
  * workspace: meant_linear_bwd_dw_ws(M, N, K, dtype) bytes (0 unless the "deterministic" option is on: then the
- * per-workgroup partial sums go there and are added up in a fixed order); NULL / 0 otherwise. */
+ * per-workgroup partial sums go there and are added up in a fixed order); NULL / 0 otherwise.
+ * bf16 tier: the MFMA kernels need N >= 8, K >= 8, lddy % 8 == 0, ldx % 8 == 0 and 16-byte aligned dy, x; they fetch both operands in
+ * 8-column pieces, so N and K have to be the widths that are really there in multiples of 8: a caller with N % 8 != 0 (K % 8 != 0)
+ * pads dy (x) with zero columns to ceil8 first and passes the padded width with a dw of [ceil8(N), ceil8(K)] and a dbias of
+ * [ceil8(N)], which it cuts back.  Everything else takes the exact-f32 engine on bf16 storage. */
 size_t meant_linear_bwd_dw_ws(int64_t M, int64_t N, int64_t K, int dtype);
 int meant_linear_bwd_dw(const void* dy, int64_t lddy, const void* x, int64_t ldx, float* dw, float* dbias,
                         int64_t M, int64_t N, int64_t K, int dtype, void* workspace, size_t workspace_bytes,
@@ -362,17 +367,21 @@ int meant_patchify_raw(const void* images, int raw_dtype, float mean, float inv_
 /* ---- sequence mean-pool ------------------------------------------- meant/meant.py:231
  * x: act [G, S, d] -> out[g, col_off : col_off+d] of a [G, ld_out] buffer (the concat) whose storage type
  * is out_dtype: the pooled features and everything after them (temporal encoder, head: 0.06 % of the
- * FLOPs) run in fp32 also in the bf16 tier. */
+ * FLOPs) run in fp32 also in the bf16 tier.  Any d > 0, ld_out and col_off with 0 <= col_off, col_off + d <= ld_out: 16-byte
+ * accesses where d, ld_out and col_off are multiples of 8 and both bases are 16-byte aligned, element by element otherwise (the same
+ * sums in the same order).  x / dx are not touched at or beyond column d of a row, out / dout not outside [col_off, col_off + d)
+ * of a row.  Ordered sums, no atomics: the same bits on every run. */
 int meant_meanpool_fwd(const void* x, void* out, int64_t ld_out, int64_t col_off, int64_t G, int64_t S, int64_t d,
                        int dtype, int out_dtype, void* stream);
 int meant_meanpool_bwd(const void* dout, int64_t ld_out, int64_t col_off, void* dx, int64_t G, int64_t S, int64_t d,
                        int dtype, int out_dtype, void* stream);
 
 /* ---- small elementwise helpers ---- */
-/* y[r, :] = x[r, :] + v[(r mod period), :]  (temp_embedding add, meant/meant.py:141-142) */
+/* y[r, :] = x[r, :] + v[(r mod period), :]  (temp_embedding add, meant/meant.py:141-142).  Any d > 0: 16-byte accesses where
+ * d % 8 == 0 and x, y are 16-byte aligned, element by element otherwise; nothing is touched at or beyond column d of a row. */
 int meant_add_rowvec(const void* x, const float* v, void* y, int64_t rows, int64_t d, int64_t period, int dtype,
                      void* stream);
-/* dv[period, d] (float, overwritten) = sum over rows r = i mod period of dy[r, :] */
+/* dv[period, d] (float, overwritten) = sum over rows r = i mod period of dy[r, :]; any d > 0 (element access), ordered sums */
 int meant_add_rowvec_bwd(const void* dy, float* dv, int64_t rows, int64_t d, int64_t period, int dtype, void* stream);
 /* dx = dy * gelu'(pre) */
 int meant_gelu_bwd(const void* dy, const void* pre, void* dx, int64_t n, int dtype, void* stream);
@@ -396,7 +405,8 @@ int meant_transpose2d(const void* src, int dtype_src, void* dst, int dtype_dst, 
 int meant_pad_copy2d(const void* src, int64_t ld_src, int64_t cols_src, int dtype_src, void* dst, int64_t ld_dst,
                      int64_t cols_dst, int dtype_dst, int64_t rows, void* stream);
 /* embedding gather: out act [n, d] = table float [V, d] rows ids[n] (int64); and its scatter-add backward
- * into dtable float [V, d] (caller zeroes).            nn.Embedding at meant/meant.py:211 */
+ * into dtable float [V, d] (caller zeroes).            nn.Embedding at meant/meant.py:211
+ * Both take any d > 0 (the gather element by element where d % 8 != 0; the scatter-add is float atomics per element). */
 int meant_embedding_fwd(const float* table, const int64_t* ids, void* out, int64_t n, int64_t d, int64_t V, int dtype,
                         void* stream);
 int meant_embedding_bwd(const void* dout, const int64_t* ids, float* dtable, int64_t n, int64_t d, int64_t V, int dtype,

@@ -113,6 +113,25 @@ __global__ __launch_bounds__(EW_THREADS) void add_rowvec_kernel(const T* __restr
     store8<T>(y + r * d + ch * 8, o);
   }
 }
+// The same map by element access, for rows that are only element-aligned (d % 8 != 0: a model at text_dim + image_dim = 150) or an
+// unaligned base.  One thread = up to 8 consecutive columns of one row, each column guarded by c < d: neither x, v nor y is touched at
+// or beyond column d of a row.  The arithmetic of add_rowvec_kernel on the stored values.
+template <typename T>
+__global__ __launch_bounds__(EW_THREADS) void add_rowvec_elem_kernel(const T* __restrict__ x, const float* __restrict__ v,
+                                                                      T* __restrict__ y, int64_t rows, int d, int64_t period) {
+  const int nch = (d + 7) >> 3;
+  const int64_t total = rows * nch;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / nch;
+    const int c0 = (int)(i - r * nch) * 8;
+    const T* xp = x + r * d + c0;
+    const float* vp = v + (r % period) * d + c0;
+    T* yp = y + r * d + c0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+      if (c0 + k < d) yp[k] = from_f<T>(to_f(xp[k]) + vp[k]);
+  }
+}
 // dv[i][j] = sum over the rows r = i (mod period) of dy[r][j].  One workgroup = 64 consecutive (i, j) entries x 4 row groups (the
 // temporal embedding's gradient is 12 x 1536 entries over 1536 rows: one thread per entry left 72 workgroups walking 128 rows each)
 template <typename T>
@@ -368,6 +387,61 @@ __global__ __launch_bounds__(EW_THREADS) void meanpool_bwd_kernel(const TO* __re
   }
 }
 
+// The two pools by element access, for d, ld_out or col_off off the 8-grid (the concat of a model at text_dim = 100 writes the image
+// means at col_off = 100 of rows of 150) or unaligned bases.  The geometry and the order of every sum are those of the chunk kernels
+// above -- a thread owns up to 8 consecutive columns, a row group sums its rows in ascending order, the 8 row groups are combined in
+// ascending order: no atomics, the same bits on every run --, each column guarded by c < d: x / dx are not touched at or beyond
+// column d of a row, out / dout not outside [col_off, col_off + d) of a row.
+template <typename T, typename TO>
+__global__ __launch_bounds__(256) void meanpool_fwd_elem_kernel(const T* __restrict__ x, TO* __restrict__ out, int64_t ld_out,
+                                                                 int64_t col_off, int S, int d) {
+  __shared__ float red[8][32][9];
+  const int64_t g = blockIdx.x;
+  const int c0 = (blockIdx.y * 32 + (threadIdx.x & 31)) * 8;
+  const int rg = threadIdx.x >> 5;
+  float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (c0 < d) {
+    const T* base = x + g * (int64_t)S * d + c0;
+    for (int s = rg; s < S; s += 8) {
+      const T* xp = base + (int64_t)s * d;
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (c0 + k < d) acc[k] += to_f(xp[k]);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) red[rg][threadIdx.x & 31][k] = acc[k];
+  __syncthreads();
+  if (rg == 0 && c0 < d) {
+    const float inv = 1.0f / (float)S;
+    TO* op = out + g * ld_out + col_off + c0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      float s = 0.f;
+#pragma unroll
+      for (int r = 0; r < 8; ++r) s += red[r][threadIdx.x][k];
+      if (c0 + k < d) op[k] = from_f<TO>(s * inv);
+    }
+  }
+}
+template <typename T, typename TO>
+__global__ __launch_bounds__(EW_THREADS) void meanpool_bwd_elem_kernel(const TO* __restrict__ dout, int64_t ld_out, int64_t col_off,
+                                                                        T* __restrict__ dx, int64_t G, int S, int d) {
+  const int nch = (d + 7) >> 3;
+  const int64_t total = G * S * (int64_t)nch;
+  const float inv = 1.0f / (float)S;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int c0 = (int)(i % nch) * 8;
+    const int64_t gs = i / nch;
+    const int64_t g = gs / S;
+    const TO* sp = dout + g * ld_out + col_off + c0;
+    T* dp = dx + gs * d + c0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+      if (c0 + k < d) dp[k] = from_f<T>(to_f(sp[k]) * inv);
+  }
+}
+
 }  // namespace
 
 #define EW_REQ(c, ...) MEANT_REQUIRE(c, MEANT_ERR_ARG, __VA_ARGS__)
@@ -507,11 +581,18 @@ extern "C" int meant_pad_copy2d(const void* src, int64_t ld_src, int64_t cols_sr
   return MEANT_OK;
 }
 
+// 16-byte chunks where every row starts on one (d % 8 == 0, aligned bases); element by element otherwise
 extern "C" int meant_add_rowvec(const void* x, const float* v, void* y, int64_t rows, int64_t d, int64_t period, int dtype, void* stream) {
-  EW_REQ(x && v && y && rows > 0 && d > 0 && d % 8 == 0 && period > 0, "add_rowvec: bad argument");
-  DISPATCH_DTYPE(dtype, T,
-                 hipLaunchKernelGGL(add_rowvec_kernel<T>, dim3(ew_blocks(rows * (d / 8))), dim3(EW_THREADS), 0, (hipStream_t)stream,
-                                    (const T*)x, v, (T*)y, rows, (int)d, period));
+  EW_REQ(x && v && y && rows > 0 && d > 0 && d < (1LL << 30) && period > 0, "add_rowvec: bad argument");
+  if (d % 8 == 0 && meant_aligned16(x) && meant_aligned16(y)) {
+    DISPATCH_DTYPE(dtype, T,
+                   hipLaunchKernelGGL(add_rowvec_kernel<T>, dim3(ew_blocks(rows * (d / 8))), dim3(EW_THREADS), 0, (hipStream_t)stream,
+                                      (const T*)x, v, (T*)y, rows, (int)d, period));
+  } else {
+    DISPATCH_DTYPE(dtype, T,
+                   hipLaunchKernelGGL(add_rowvec_elem_kernel<T>, dim3(ew_blocks(rows * ceil_div(d, 8))), dim3(EW_THREADS), 0, (hipStream_t)stream,
+                                      (const T*)x, v, (T*)y, rows, (int)d, period));
+  }
   MEANT_LAUNCH_CHECK("add_rowvec");
   return MEANT_OK;
 }
@@ -597,26 +678,44 @@ extern "C" int meant_patchify(const void* images, int images_dtype, void* patche
   return MEANT_OK;
 }
 
+// the chunk kernels for the shapes they have always taken (d, ld_out and col_off multiples of 8, aligned bases); the element forms otherwise
+static bool meanpool_chunks(const void* x, const void* out, int64_t ld_out, int64_t col_off, int64_t d) {
+  return d % 8 == 0 && ld_out % 8 == 0 && col_off % 8 == 0 && meant_aligned16(x) && meant_aligned16(out);
+}
+
 extern "C" int meant_meanpool_fwd(const void* x, void* out, int64_t ld_out, int64_t col_off, int64_t G, int64_t S, int64_t d, int dtype, int out_dtype, void* stream) {
-  EW_REQ(x && out && G > 0 && S > 0 && d > 0 && d % 8 == 0 && ld_out % 8 == 0 && col_off % 8 == 0 && col_off + d <= ld_out, "meanpool_fwd: bad argument");
-  EW_REQ(G < 2147483647LL, "meanpool_fwd: too many groups");
+  EW_REQ(x && out && G > 0 && S > 0 && d > 0 && col_off >= 0 && col_off + d <= ld_out, "meanpool_fwd: bad argument");
+  EW_REQ(G < 2147483647LL && S < 2147483647LL && d < (1LL << 30), "meanpool_fwd: too many groups, rows or columns");
   const dim3 grid((unsigned)G, (unsigned)ceil_div(d, 256)), block(256);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MEANT_F32 && out_dtype == MEANT_F32) hipLaunchKernelGGL((meanpool_fwd_kernel<float, float>), grid, block, 0, st, (const float*)x, (float*)out, ld_out, col_off, (int)S, (int)d);
-  else if (dtype == MEANT_BF16 && out_dtype == MEANT_F32) hipLaunchKernelGGL((meanpool_fwd_kernel<bf16, float>), grid, block, 0, st, (const bf16*)x, (float*)out, ld_out, col_off, (int)S, (int)d);
-  else if (dtype == MEANT_BF16 && out_dtype == MEANT_BF16) hipLaunchKernelGGL((meanpool_fwd_kernel<bf16, bf16>), grid, block, 0, st, (const bf16*)x, (bf16*)out, ld_out, col_off, (int)S, (int)d);
-  else { meant_set_error("meanpool_fwd: unsupported dtype combination"); return MEANT_ERR_UNSUPPORTED; }
+#define POOL_FWD(KERNEL)                                                                                                                            \
+  do {                                                                                                                                              \
+    if (dtype == MEANT_F32 && out_dtype == MEANT_F32) hipLaunchKernelGGL((KERNEL<float, float>), grid, block, 0, st, (const float*)x, (float*)out, ld_out, col_off, (int)S, (int)d); \
+    else if (dtype == MEANT_BF16 && out_dtype == MEANT_F32) hipLaunchKernelGGL((KERNEL<bf16, float>), grid, block, 0, st, (const bf16*)x, (float*)out, ld_out, col_off, (int)S, (int)d); \
+    else if (dtype == MEANT_BF16 && out_dtype == MEANT_BF16) hipLaunchKernelGGL((KERNEL<bf16, bf16>), grid, block, 0, st, (const bf16*)x, (bf16*)out, ld_out, col_off, (int)S, (int)d); \
+    else { meant_set_error("meanpool_fwd: unsupported dtype combination"); return MEANT_ERR_UNSUPPORTED; }                                        \
+  } while (0)
+  if (meanpool_chunks(x, out, ld_out, col_off, d)) POOL_FWD(meanpool_fwd_kernel);
+  else POOL_FWD(meanpool_fwd_elem_kernel);
+#undef POOL_FWD
   MEANT_LAUNCH_CHECK("meanpool_fwd");
   return MEANT_OK;
 }
 extern "C" int meant_meanpool_bwd(const void* dout, int64_t ld_out, int64_t col_off, void* dx, int64_t G, int64_t S, int64_t d, int dtype, int out_dtype, void* stream) {
-  EW_REQ(dout && dx && G > 0 && S > 0 && d > 0 && d % 8 == 0 && ld_out % 8 == 0 && col_off % 8 == 0, "meanpool_bwd: bad argument");
-  const dim3 grid(ew_blocks(G * S * (d / 8))), block(EW_THREADS);
+  EW_REQ(dout && dx && G > 0 && S > 0 && d > 0 && col_off >= 0 && col_off + d <= ld_out, "meanpool_bwd: bad argument");
+  EW_REQ(S < 2147483647LL && d < (1LL << 30), "meanpool_bwd: too many rows or columns");
+  const dim3 grid(ew_blocks(G * S * ceil_div(d, 8))), block(EW_THREADS);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MEANT_F32 && out_dtype == MEANT_F32) hipLaunchKernelGGL((meanpool_bwd_kernel<float, float>), grid, block, 0, st, (const float*)dout, ld_out, col_off, (float*)dx, G, (int)S, (int)d);
-  else if (dtype == MEANT_BF16 && out_dtype == MEANT_F32) hipLaunchKernelGGL((meanpool_bwd_kernel<bf16, float>), grid, block, 0, st, (const float*)dout, ld_out, col_off, (bf16*)dx, G, (int)S, (int)d);
-  else if (dtype == MEANT_BF16 && out_dtype == MEANT_BF16) hipLaunchKernelGGL((meanpool_bwd_kernel<bf16, bf16>), grid, block, 0, st, (const bf16*)dout, ld_out, col_off, (bf16*)dx, G, (int)S, (int)d);
-  else { meant_set_error("meanpool_bwd: unsupported dtype combination"); return MEANT_ERR_UNSUPPORTED; }
+#define POOL_BWD(KERNEL)                                                                                                                            \
+  do {                                                                                                                                              \
+    if (dtype == MEANT_F32 && out_dtype == MEANT_F32) hipLaunchKernelGGL((KERNEL<float, float>), grid, block, 0, st, (const float*)dout, ld_out, col_off, (float*)dx, G, (int)S, (int)d); \
+    else if (dtype == MEANT_BF16 && out_dtype == MEANT_F32) hipLaunchKernelGGL((KERNEL<bf16, float>), grid, block, 0, st, (const float*)dout, ld_out, col_off, (bf16*)dx, G, (int)S, (int)d); \
+    else if (dtype == MEANT_BF16 && out_dtype == MEANT_BF16) hipLaunchKernelGGL((KERNEL<bf16, bf16>), grid, block, 0, st, (const bf16*)dout, ld_out, col_off, (bf16*)dx, G, (int)S, (int)d); \
+    else { meant_set_error("meanpool_bwd: unsupported dtype combination"); return MEANT_ERR_UNSUPPORTED; }                                        \
+  } while (0)
+  if (meanpool_chunks(dout, dx, ld_out, col_off, d)) POOL_BWD(meanpool_bwd_kernel);
+  else POOL_BWD(meanpool_bwd_elem_kernel);
+#undef POOL_BWD
   MEANT_LAUNCH_CHECK("meanpool_bwd");
   return MEANT_OK;
 }

@@ -391,6 +391,19 @@ __global__ __launch_bounds__(256) void embedding_fwd_kernel(const float* __restr
     }
   }
 }
+// the same gather element by element, for d % 8 != 0 (rows of the table and of `out` are then only element-aligned): a wave's lanes walk
+// consecutive columns e < d of its row
+template <typename T>
+__global__ __launch_bounds__(256) void embedding_fwd_elem_kernel(const float* __restrict__ table, const int64_t* __restrict__ ids,
+                                                                  T* __restrict__ out, int64_t n, int d, int64_t V) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < n; r += (int64_t)gridDim.x * 4) {
+    int64_t id = ids[r];
+    id = id < 0 ? 0 : (id >= V ? V - 1 : id);
+    const float* src = table + id * d;
+    for (int e = lane; e < d; e += 64) out[r * d + e] = from_f<T>(src[e]);
+  }
+}
 template <typename T>
 __global__ __launch_bounds__(256) void embedding_bwd_kernel(const T* __restrict__ dout, const int64_t* __restrict__ ids,
                                                              float* __restrict__ dtable, int64_t n, int d, int64_t V) {
@@ -601,10 +614,15 @@ extern "C" int meant_embedding_bwd_seg(const void* dout, const int64_t* sorted_i
 }
 
 extern "C" int meant_embedding_fwd(const float* table, const int64_t* ids, void* out, int64_t n, int64_t d, int64_t V, int dtype, void* stream) {
-  EMB_REQ(table && ids && out && n > 0 && d > 0 && d % 8 == 0 && V > 0, "embedding_fwd: bad argument");
+  EMB_REQ(table && ids && out && n > 0 && d > 0 && d < (1ll << 30) && V > 0, "embedding_fwd: bad argument");
   int64_t nb = ceil_div(n, 4); if (nb > 8192) nb = 8192;
-  DISPATCH_DTYPE(dtype, T,
-                 hipLaunchKernelGGL(embedding_fwd_kernel<T>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, table, ids, (T*)out, n, (int)d, V));
+  if (d % 8 == 0) {
+    DISPATCH_DTYPE(dtype, T,
+                   hipLaunchKernelGGL(embedding_fwd_kernel<T>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, table, ids, (T*)out, n, (int)d, V));
+  } else {
+    DISPATCH_DTYPE(dtype, T,
+                   hipLaunchKernelGGL(embedding_fwd_elem_kernel<T>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, table, ids, (T*)out, n, (int)d, V));
+  }
   MEANT_LAUNCH_CHECK("embedding_fwd");
   return MEANT_OK;
 }

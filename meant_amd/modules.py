@@ -381,7 +381,7 @@ class visionEncoder(nn.Module):
         fold: the stack's RMSNorm-into-Linear decision (an explicit argument so that a recomputation under
         torch.utils.checkpoint repeats the forward's path); None = by ops.fold_wanted()"""
         e, e2 = self.encode, self.encode2
-        n, res = ops.rmsnorm_fork(input, e[0].scale, e[0].eps)      # residual gradient is folded into this norm's backward
+        n, res = ops.rmsnorm_fork(input, e[0].scale, e[0].eps, any_width=True)      # residual gradient is folded into this norm's backward
         if COMPOSE_PRE_LINEAR and e[1].bias is not None:
             h = e[2].multi_mad(e[2].core(n, pre=e[1]))               # Linear(d,d) composed into the q/k/v projections
         else:
@@ -397,8 +397,8 @@ class visionEncoder(nn.Module):
         if fold:
             h, res = ops.norm_linear_gelu_norm(x1, e2[0].scale, e2[0].eps, e2[1].weight, e2[1].bias, e2[3].scale, e2[3].eps)
         else:
-            n, res = ops.rmsnorm_fork(x1, e2[0].scale, e2[0].eps)
-            h = ops.linear_gelu_rmsnorm(n, e2[1].weight, e2[1].bias, e2[3].scale, e2[3].eps)
+            n, res = ops.rmsnorm_fork(x1, e2[0].scale, e2[0].eps, any_width=True)
+            h = ops.linear_gelu_rmsnorm(n, e2[1].weight, e2[1].bias, e2[3].scale, e2[3].eps, any_width=True)
         if pool:
             return h, res
         return e2[4](h, residual=res)
@@ -421,7 +421,7 @@ class languageEncoder(nn.Module):
         e, e2 = self.encode, self.encode2
         p1 = e[4].p if self.training else 0.0
         p2 = e2[4].p if self.training else 0.0
-        n, res = ops.rmsnorm_fork(input, e[0].scale, e[0].eps)
+        n, res = ops.rmsnorm_fork(input, e[0].scale, e[0].eps, any_width=True)
         if COMPOSE_PRE_LINEAR and e[1].bias is not None:
             h = e[2].multi_mad(e[2].core(n, attention_mask, pre=e[1]))
         else:
@@ -438,8 +438,8 @@ class languageEncoder(nn.Module):
         if fold:
             h, res = ops.norm_linear_gelu_norm(x1, e2[0].scale, e2[0].eps, e2[1].weight, e2[1].bias, e2[3].scale, e2[3].eps, p2, seed2)
         else:
-            n, res = ops.rmsnorm_fork(x1, e2[0].scale, e2[0].eps)
-            h = ops.linear_gelu_rmsnorm(n, e2[1].weight, e2[1].bias, e2[3].scale, e2[3].eps, p2, seed2)
+            n, res = ops.rmsnorm_fork(x1, e2[0].scale, e2[0].eps, any_width=True)
+            h = ops.linear_gelu_rmsnorm(n, e2[1].weight, e2[1].bias, e2[3].scale, e2[3].eps, p2, seed2, any_width=True)
         if pool:
             return h, res
         return e2[5](h, residual=res)

@@ -68,8 +68,9 @@ class _WeightCache:
     dies.  Tensors without a stable identity (results of F.pad / cat / arithmetic) are converted without being cached, so
     nothing can accumulate from per-step temporaries.  `pad_rows` appends zero rows to the (concatenated) weight before
     the conversion: the padded bf16 / transposed copies of a vocabulary matrix are built once per optimizer step instead
-    of once per call.  `pad_cols` appends zero columns to the (untransposed) compute-dtype copy: the K-padded weight of a
-    Linear whose K is not a multiple of 8 (see _k_pad).  Thread-safe (autograd worker threads, nn.DataParallel replicas)."""
+    of once per call.  `pad_cols` appends zero columns to the compute-dtype copy: untransposed, the K-padded weight of a Linear
+    whose K is not a multiple of 8 (see _k_pad); transposed, the [K, ceil8(N)] operand of the input gradient of a Linear whose N
+    is not one (see _n_pad_ok).  Thread-safe (autograd worker threads, nn.DataParallel replicas)."""
 
     def __init__(self):
         self._store = {}
@@ -98,8 +99,12 @@ class _WeightCache:
             w = _c(w.float())
             N, K = w.shape
             dd = F32 if dtype == torch.float32 else BF16
-            if pad_cols:
-                assert not transposed
+            if pad_cols and transposed:
+                wT = torch.empty((K, N), device=w.device, dtype=torch.float32)
+                check(lib.meant_transpose2d(_p(w), F32, _p(wT), F32, N, K, _stream()), "transpose2d")
+                out = torch.empty((K, N + pad_cols), device=w.device, dtype=dtype)
+                check(lib.meant_pad_copy2d(_p(wT), N, N, F32, _p(out), N + pad_cols, N + pad_cols, dd, K, _stream()), "pad_copy2d")
+            elif pad_cols:
                 out = torch.empty((N, K + pad_cols), device=w.device, dtype=dtype)
                 check(lib.meant_pad_copy2d(_p(w), K, K, F32, _p(out), K + pad_cols, K + pad_cols, dd, N, _stream()), "pad_copy2d")
             elif transposed:
@@ -147,10 +152,10 @@ weights = _WeightCache()
 
 # ---------------------------------------------------------------------------------------------
 def _norm_width(d: int, any_width: bool, what: str) -> None:
-    """The norm ops below take d % 8 == 0 unless the caller opts in: the widths of the model path (the embedding and the GEMM
-    epilogues around these norms need them; a whole model at an odd width is not supported).  The norm modules (RMSNorm, LayerNorm,
-    utils/rms_norm.py:16-57) take any d > 0 and pass any_width=True: the library serves the other widths with its one-row-per-workgroup
-    kernels (csrc/norm.hip)."""
+    """The norm ops below take d % 8 == 0 unless the caller opts in: the widths of the packed / fused kernels, which is what a caller
+    that did not ask gets.  The norm modules (RMSNorm, LayerNorm, utils/rms_norm.py:16-57) and the encoder layers (a model at
+    text_dim = 100, image_dim = 50) take any d > 0 and pass any_width=True: the library serves the other widths with its
+    one-row-per-workgroup kernels (csrc/norm.hip)."""
     if d % 8 and not any_width:
         raise _lib.MeantHipError(f"meant_amd.ops.{what}: d = {d} is not a multiple of 8 (any_width=True, as the norm modules pass, "
                                  "takes any width)")
@@ -783,6 +788,35 @@ def _sink_of(param, site: str):
     return ent
 
 
+def _n_pad_ok(N: int, dtype: torch.dtype) -> bool:
+    """output widths whose backward products are moved onto the MFMA kernels by zero columns up to ceil8(N): bf16 tier, N >= 8 and
+    not a multiple of 8 (rows of dY are then not 16-byte aligned, and the C ABI would take both products on the exact-f32 engine).
+    N < 8 (class heads) stays where it was"""
+    return dtype == torch.bfloat16 and N >= 8 and N % 8 != 0
+
+
+def _linear_bwd_npad(dy2, x2, params, need_dx, has_bias, pad_rows, K):
+    """_linear_bwd_raw for _n_pad_ok widths.  ONE copy pass turns dY into [M, ceil8(N)] with zero columns; it feeds both products:
+    dX = dYp WTp^T on the K-tail NT kernels (reduction length ceil8(N); WTp [K, ceil8(N)] = the transposed weight with zero columns,
+    from the weight cache), written at its own width K; dW / db = dYp^T x through [ceil8(N), K8] / [ceil8(N)] accumulators -- the
+    TN kernels stage dY in 16-byte chunks clamped to its width, so they have to see the padded width, and then store that many
+    rows -- that are cut back to [N, K] / [N].  The gradient always goes back to autograd: a sink's view is [N, K]."""
+    M, N = dy2.shape
+    N8 = (N + 7) & ~7
+    K8 = x2.shape[1]
+    dyp = _pad_cols(dy2, N8)
+    dx = None
+    if need_dx:
+        wT = weights.get(params, dy2.dtype, True, pad_rows, pad_cols=N8 - N)           # [K, N8]
+        dx = torch.empty((M, K), device=dy2.device, dtype=dy2.dtype)
+        check(lib.meant_linear_bwd_dx(_p(dyp), N8, _p(wT), _p(dx), K, M, N8, K, _dt(dy2), _stream()), "linear_bwd_dx")
+    dw = torch.zeros((N8, K8), device=dy2.device, dtype=torch.float32)
+    db = torch.zeros(N8, device=dy2.device, dtype=torch.float32) if has_bias else None
+    _bwd_dw(dyp, x2, dw, db)
+    dw = dw[:N] if K8 == K else _pad_cols(dw[:N], K)
+    return dx, dw, (db[:N] if has_bias else None)
+
+
 def _linear_bwd_raw(dy2, x2, params, need_dx, has_bias, pad_rows=0, bias_param=None, site="linear", K=None):
     """returns dx2 (or None), dW [sum N_i (+ pad_rows), K] fp32, db [same] fp32 or None; dW / db are None when they went
     straight into the parameters' gradient sinks.  K: the Linear's own reduction length where x2 is the K-padded copy of
@@ -790,6 +824,8 @@ def _linear_bwd_raw(dy2, x2, params, need_dx, has_bias, pad_rows=0, bias_param=N
     M, N = dy2.shape
     K8 = x2.shape[1]
     K = K8 if K is None else K
+    if _n_pad_ok(N, dy2.dtype):
+        return _linear_bwd_npad(dy2, x2, params, need_dx, has_bias, pad_rows, K)
     dx = None
     if need_dx:
         wT = weights.get(params, dy2.dtype, True, pad_rows)             # [K, N]
@@ -921,13 +957,19 @@ class _QKVAttention(torch.autograd.Function):
         Dh = D // num_heads
         x2 = _c(x).view(G * S, d)
         w_f = _c(wqkv.detach().float())
-        w_c = cast(w_f, x.dtype)                                              # [3D, d] in the compute dtype
+        if x.dtype == torch.bfloat16 and d % 8:
+            # a model width off the 8-grid: both operands get zero columns up to ceil8(d), as _k_pad does for ops.linear, so that the
+            # projection keeps the MFMA kernel and its rotary epilogue; backward keeps the padded copy of x for the weight gradient
+            d8 = (d + 7) & ~7
+            x2, w_c = _pad_cols(x2, d8), _pad_cols(w_f, d8, x.dtype)
+        else:
+            w_c = cast(w_f, x.dtype)                                          # [3D, d] in the compute dtype
         bias_f = _c(bqkv.detach().float())
         dt = _dt(x)
         qa, qb, ka, kb = tables if tables is not None else (None, None, None, None)
         R = qa.shape[1] if qa is not None else 0
         qkv = torch.empty((G * S, 3 * D), device=x.device, dtype=x.dtype)
-        check(lib.meant_qkv_proj_fwd(_p(x2), x2.stride(0), _p(w_c), _p(bias_f), _p(qkv), G * S, d, S, num_heads, Dh, R,
+        check(lib.meant_qkv_proj_fwd(_p(x2), x2.stride(0), _p(w_c), _p(bias_f), _p(qkv), G * S, x2.shape[1], S, num_heads, Dh, R,
                                      _p(qa), _p(qb), _p(ka), _p(kb), dt, _stream()), "qkv_proj_fwd")
         o = torch.empty((G * S, D), device=x.device, dtype=x.dtype)
         lse = torch.empty((G, num_heads, S, 2), device=x.device, dtype=torch.float32)
@@ -963,9 +1005,12 @@ class _QKVAttention(torch.autograd.Function):
             check(lib.meant_transpose2d(_p(w_f), F32, _p(wT), dt, N, K, _stream()), "transpose2d")
             dx = torch.empty((M, K), device=do2.device, dtype=do2.dtype)
             check(lib.meant_linear_bwd_dx(_p(dqkv), N, _p(wT), _p(dx), K, M, N, K, dt, _stream()), "linear_bwd_dx")
-        dw = torch.zeros((N, K), device=do2.device, dtype=torch.float32)
+        K8 = x2.shape[1]                                                      # ceil8(d) where forward padded x
+        dw = torch.zeros((N, K8), device=do2.device, dtype=torch.float32)
         db = torch.zeros(N, device=do2.device, dtype=torch.float32)
         _bwd_dw(dqkv, x2, dw, db)
+        if K8 != K:
+            dw = _pad_cols(dw, K)
         return (dx.view(G, S, d) if dx is not None else None), dw, db, None, None, None, None, None
 
 
