@@ -1,3 +1,4 @@
 """Drop-in `utils` package exporting RMSNorm (reference: utils/__init__.py, `from utils import RMSNorm`
-at meant/meant.py:13)."""
+at meant/meant.py:13) and f1_metrics (`from utils import f1_metrics` at in_loop_train.py:30, test_run.py:27)."""
 from meant_amd.modules import RMSNorm  # noqa: F401
+from meant_amd.metrics import f1_metrics  # noqa: F401

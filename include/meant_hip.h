@@ -88,7 +88,8 @@ int meant_get_option(const char* name, int* value);
  * "attn_generic", "attn_cls", "attn_short", "attn_fwd_d160" ... "attn_bwd_d256", "temporal_long" (the temporal attention
  * core's long-lag kernels, forward and backward each count one), "emb_seg" (meant_embedding_bwd_seg), "sort_ids" (meant_sort_ids), "select_rows" (meant_select_rows),
  * "rotary_qk" (every meant_rotary_qk launch), "rotary_pairs" (those of its pair-by-pair kernel: Dh % 8 != 0 or an unaligned base)
- * and "nt_rot" (every bf16 NT GEMM launched with the rotary epilogue, on top of the nt* route it takes));
+ * "nt_rot" (every bf16 NT GEMM launched with the rotary epilogue, on top of the nt* route it takes) and "metrics_rows" /
+ * "metrics_wave" / "metrics_labels" (meant_metrics_update by form, every meant_metrics_update_labels launch));
  * -1 for an unknown name.  The names label routes, not kernels: "nt256s" / "nt256s_rot" count launches of the streaming
  * GEMM (whichever kernel implements it), "nt_split" the ragged head + tail split.  Tests use it to prove that a shape
  * reaches the kernel it is meant to exercise. */
@@ -466,6 +467,32 @@ int meant_softmax_ce_bwd(const void* logits, int64_t ld, const int64_t* target, 
 size_t meant_select_rows_ws(int64_t T);
 int meant_select_rows(const int64_t* target, int64_t T, int64_t V, int64_t ignore_index, int32_t* idx, int32_t* inv,
                       int64_t* target_sel, int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- classification counts (utils/f1_metrics.py, fed per batch at in_loop_train.py:208-241, 281-319, 339-359) ----
+ * Everything the reference's seven metrics (accuracy, F1 / precision / recall, macro and micro) are computed from, counted on the
+ * device.  scores [B, ld], columns 0..C-1 are the classes (MEANT_F32 | MEANT_BF16; the columns C..ld-1, the padding of a
+ * vocabulary GEMM, are never candidates and may hold anything); target int64 [B].
+ * state int64 [3C + 4], zeroed once by the caller: tp[C], npred[C], ntarget[C], then n_rows, n_ignored, n_invalid, n_nan.
+ * confusion: NULL or int64 [C, C], row = target, column = prediction.  The calls only ever ADD to both, and every counter is an
+ * integer: any number of updates, in any order and with any workgroup arrival order, leaves bit-identical contents, and the
+ * states of several devices may be summed.
+ * Per row (the semantics of torch's scores.argmax(dim=1)): the prediction is the index of the greatest of the C columns, the
+ * lowest index on a tie, a NaN counting as greater than everything (the first NaN's index).
+ *   target == ignore_index            : n_ignored += 1 and nothing else
+ *   target otherwise outside [0, C)   : n_invalid += 1 and nothing else (no address is formed from it)
+ *   every other row                   : n_rows, npred[pred], ntarget[target] += 1; tp[pred] += 1 if pred == target;
+ *                                       confusion[target * C + pred] += 1; n_nan += 1 if one of its C columns is a NaN
+ * The scores of an ignored or invalid row are not read.  meant_metrics_update_labels does the same from predictions int64 [B];
+ * one outside [0, C) makes the row invalid; it never adds to n_nan.
+ * Forms (route names of meant_route_count): "metrics_rows" for C <= 16, a lane per row, the counters summed per workgroup in LDS,
+ * one global integer atomic per non-zero counter and workgroup; "metrics_wave" above, a wave per row, 16-byte loads when scores
+ * is 16-byte aligned and a row is a multiple of 16 bytes, element loads otherwise; "metrics_labels" counts every
+ * meant_metrics_update_labels launch.  One launch each, no workspace.
+ * A null scores / pred / target / state, B < 0, C <= 0, ld < C, an unknown dtype or a misaligned operand: MEANT_ERR_ARG;
+ * B >= 2^40: MEANT_ERR_UNSUPPORTED; both before any launch.  B == 0: MEANT_OK without a launch. */
+int meant_metrics_update(const void* scores, int64_t ld, int dtype, const int64_t* target, int64_t B, int C, int64_t ignore_index,
+                         int64_t* state, int64_t* confusion, void* stream);
+int meant_metrics_update_labels(const int64_t* pred, const int64_t* target, int64_t B, int C, int64_t ignore_index,
+                                int64_t* state, int64_t* confusion, void* stream);
 /* out_accum[0] += sum(x^2) over a flat float buffer (global gradient norm; caller zeroes the scalar) */
 int meant_sumsq_f32(const float* x, int64_t n, float* out_accum, void* stream);
 /* One AdamW step (torch.optim.AdamW semantics, `step` >= 1 for the bias corrections) over flat float buffers.

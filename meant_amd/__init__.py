@@ -12,6 +12,7 @@ from .modules import (  # noqa: F401
     meant, meant_vision, meant_tweet, meant_vqa, meant_language_pretrainer, meant_vision_pretrainer, TimeSformer,
 )
 
-from . import parallel, train, data  # noqa: F401,E402
+from . import parallel, train, data, metrics  # noqa: F401,E402
+from .metrics import f1_metrics  # noqa: F401,E402
 
 __version__ = "0.1.0"

@@ -85,6 +85,8 @@ SIGNATURES = {
     "meant_softmax_ce_bwd": (_i, [_p, _i64, _p, _p, _i64, _i64, _i64, _p, _p, _i, _p]),
     "meant_select_rows_ws": (_sz, [_i64]),
     "meant_select_rows": (_i, [_p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _sz, _p]),
+    "meant_metrics_update": (_i, [_p, _i64, _i, _p, _i64, _i, _i64, _p, _p, _p]),
+    "meant_metrics_update_labels": (_i, [_p, _p, _i64, _i, _i64, _p, _p, _p]),
     "meant_sumsq_f32": (_i, [_p, _i64, _p, _p]),
     "meant_adamw_f32": (_i, [_p, _p, _p, _p, _i64, _f, _f, _f, _f, _f, _i64, _p, _f, _f, _p]),
     "meant_embedding_bwd_sorted": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i, _p]),

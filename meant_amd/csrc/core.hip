@@ -139,6 +139,7 @@ const char* const k_routes[MEANT_ROUTE_COUNT] = {
     "temporal_long", "emb_seg", "sort_ids", "nt128k", "nt256k", "select_rows",
     "rotary_qk", "rotary_pairs",   // every meant_rotary_qk launch; those of the pair-by-pair kernel (Dh % 8 != 0 or an unaligned base)
     "nt_rot",                       // every bf16 NT GEMM launched with the rotary epilogue, whichever nt* route it takes
+    "metrics_rows", "metrics_wave", "metrics_labels",   // meant_metrics_update by form (C <= 16 / above); every meant_metrics_update_labels launch
 };
 std::atomic<long long> g_route[MEANT_ROUTE_COUNT];
 }  // namespace

@@ -147,17 +147,20 @@ class TrainStep:
     """forward -> CE on probabilities -> backward (+ overlapped gradient all-reduce) -> clip + AdamW."""
 
     def __init__(self, model: torch.nn.Module, lr: float = 5e-5, weight_decay: float = 1e-2, max_grad_norm: float = 1.0,
-                 bucket_mb: float = 64.0, direct_grads: bool = True, micro_batches: int = 1):
+                 bucket_mb: float = 64.0, direct_grads: bool = True, micro_batches: int = 1, metrics=None):
         """micro_batches: run a step's batch as this many equal slices, one forward/backward each, gradients accumulated in the
         reducer's buckets (reducer.no_sync) -- the same gradients with 1/micro_batches of the activations in flight (the
         reference's CLI default of 12 encoder layers at 128 samples per GPU).
         direct_grads (GradReducer): parameter gradients are accumulated straight into the flat buckets by the backward
         kernels; pass False if the model's parameters are also differentiated outside this step (torch.autograd.grad,
-        several backward passes per optimizer step without reducer.no_sync())"""
+        several backward passes per optimizer step without reducer.no_sync())
+        metrics (meant_amd.metrics.f1_metrics or None): when given, every step adds its batch to it -- metrics.update(out, target)
+        on the detached output, one more launch and no host read; None leaves the step's launches as they are"""
         self.model = model
         self.reducer = GradReducer(model.parameters(), bucket_mb=bucket_mb, direct_grads=direct_grads)
         self.opt = FusedAdamW(self.reducer, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
         self.micro_batches = max(1, int(micro_batches))
+        self.metrics = metrics
 
     def __call__(self, *inputs, target):
         self.reducer.prepare()
@@ -187,4 +190,24 @@ class TrainStep:
             out = torch.cat(outs)
         self.reducer.wait()
         self.opt.step()
+        if self.metrics is not None:
+            self.metrics.update(out.detach(), target)
         return loss.detach(), out.detach()
+
+
+def evaluate(model: torch.nn.Module, batches: Iterable, metrics, target_index: int = -1):
+    """Score `batches` with `model` into `metrics` (the validation / test loops of in_loop_train.py:281-319, 339-359): the model
+    in eval() mode under torch.no_grad(), one forward and one metrics.update per batch, no host read; the model's previous
+    training flag is restored at the end.  A batch is a sequence of tensors: the one at `target_index` is the target, the
+    others are the model's positional inputs in order.  Returns `metrics`; read it with metrics.compute() / show()."""
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            for batch in batches:
+                batch = list(batch)
+                target = batch.pop(target_index)
+                metrics.update(model(*batch), target)
+    finally:
+        model.train(was_training)
+    return metrics
