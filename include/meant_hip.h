@@ -76,6 +76,10 @@ int meant_num_cus(void);
  *                            dS through LDS into the dQ product; persistent workgroups) / the dQ pass followed by the dK, dV pass
  *   "temporal_long"    0|1   the temporal attention core runs its long-lag kernels for L > 64 only / at every lag (a measuring
  *                            switch: tools/probe_temporal_lag.py times both kernel families at L <= 64 with it)
+ *   "kv_skip"          3|0   bits: which GEMMs around a key-masked bf16 attention (ops: the fused q|k|v projection) leave out the rows of
+ *                            padded key blocks (meant_kv_live_rows).  1: the k|v columns of the projection's weight gradient reduce
+ *                            over the live 64-row blocks only (meant_linear_bwd_dw_rows); 2: the forward projection computes k|v for
+ *                            the live 256-row panels only (meant_qkv_proj_fwd_live); 0: every GEMM takes all rows
  *   "nt_pp"            1     read-only: the streaming GEMM runs in its ping-pong form (setting any other value fails with
  *                            MEANT_ERR_UNSUPPORTED: the lock-step kernel was removed); not read from the environment
  */
@@ -83,7 +87,7 @@ int meant_set_option(const char* name, int value);
 int meant_get_option(const char* name, int* value);
 /* how many launches took a given kernel route since the last reset ("nt128", "nt256", "nt256s", "nt256s_rot",
  * "nt128k", "nt256k" (the K-tail forms of the 128 x 128 and 256 x 256 one-tile kernels: K % 64 != 0),
- * "nt_split", "nt_overlap", "tn128", "tn256", "tn256_det", "tn_tail", "gemm_f32", "attn_fwd", "attn_fwd_d128",
+ * "nt_split", "nt_overlap", "tn128", "tn256", "tn256_det", "tn256_rows" (meant_linear_bwd_dw_rows on its list), "tn_tail", "gemm_f32", "attn_fwd", "attn_fwd_d128",
  * "attn_fwd_d96", "attn_bwd" (the two-pass form), "attn_bwd1" (the single-pass form), "attn_bwd_d128", "attn_bwd_d96",
  * "attn_generic", "attn_cls", "attn_short", "attn_fwd_d160" ... "attn_bwd_d256", "temporal_long" (the temporal attention
  * core's long-lag kernels, forward and backward each count one), "emb_seg" (meant_embedding_bwd_seg), "sort_ids" (meant_sort_ids), "select_rows" (meant_select_rows),
@@ -198,10 +202,17 @@ int meant_linear_fwd(const void* x, int64_t ldx, const void* w, const float* bia
  * meant_rotary_qk on the q and k blocks (tables may be NULL: plain projection).  In the bf16 tier the rotation
  * rides the GEMM epilogue (no extra pass over qkv) at every K % 8 == 0 (Dh % 8 == 0, R % 8 == 0), K % 64 != 0 included
  * (K-tail kernels, as meant_linear_fwd); any other (Dh, R), and the f32 tier, run the plain projection and then
- * meant_rotary_qk in place.   meant/attention.py:36-40, meant/xPosAttention.py:37-39 */
+ * meant_rotary_qk in place.   meant/attention.py:36-40, meant/xPosAttention.py:37-39
+ * meant_qkv_proj_fwd_live, kv_lists: NULL (the same call), or the lists of meant_kv_live_rows(key mask, M / S, S, ...) of the attention that will read qkv (bf16 tier,
+ * S % 256 == 0; ignored otherwise).  The k | v columns of the DEAD 256-row panels -- rows the attention never reads -- are then zeros on
+ * return, and where the streaming GEMM takes the projection (H*Dh % 256 == 0, its usual shape rules) they are never computed: the q
+ * section runs over all row panels, the k | v section over the live ones.  Every other element is what it is without the lists. */
 int meant_qkv_proj_fwd(const void* x, int64_t ldx, const void* w, const float* bias, void* qkv, int64_t M,
                        int64_t K, int64_t S, int H, int Dh, int R, const float* qa, const float* qb,
                        const float* ka, const float* kb, int dtype, void* stream);
+int meant_qkv_proj_fwd_live(const void* x, int64_t ldx, const void* w, const float* bias, void* qkv, int64_t M,
+                            int64_t K, int64_t S, int H, int Dh, int R, const float* qa, const float* qb,
+                            const float* ka, const float* kb, const void* kv_lists, int dtype, void* stream);
 /* Linear with its input RMSNorm folded in (see "RMSNorm folded into the Linear" above).
  * forward : y = act(row_scale[m] (x w^T) + bias) (+ residual); w = W diag(g) in the act dtype; preact as in meant_linear_fwd.
  * backward: dx[M,K] = dy_scaled[M,N] w  -  coef[m] x[m,:]  (+ dres) (+ dres_pooled[m / group_rows, :] / group_rows),
@@ -233,6 +244,14 @@ size_t meant_linear_bwd_dw_ws(int64_t M, int64_t N, int64_t K, int dtype);
 int meant_linear_bwd_dw(const void* dy, int64_t lddy, const void* x, int64_t ldx, float* dw, float* dbias,
                         int64_t M, int64_t N, int64_t K, int dtype, void* workspace, size_t workspace_bytes,
                         void* stream);
+/* The same "+=" over a LIST of 64-row blocks of the token axis: rows_list[0 .. *rows_count) are ascending block indices (block b = rows
+ * 64 b .. 64 b + 63), both in device memory -- the count is read by the kernel, never by the host -- and every row of dy OUTSIDE the listed
+ * blocks must be zero (the dK / dV rows of padded key blocks, see meant_kv_live_rows).  bf16 tier with M % 64 == 0, N % 256 == 0,
+ * K % 256 == 0, M >= 4096 and the "deterministic" option off: the 256 x 256 MFMA kernel walks the listed blocks only, its token-axis
+ * splits sharing them evenly.  Every other case sums all M rows as meant_linear_bwd_dw does (same workspace rule): the same sums. */
+int meant_linear_bwd_dw_rows(const void* dy, int64_t lddy, const void* x, int64_t ldx, float* dw, float* dbias,
+                             const int* rows_list, const int* rows_count, int64_t M, int64_t N, int64_t K, int dtype,
+                             void* workspace, size_t workspace_bytes, void* stream);
 
 /* generic strided batched GEMM, float storage, f32 MFMA (exact fp32 products):
  * C[b1,b2][m,n] = alpha * sum_k A[b1,b2](m,k) * B[b1,b2](k,n)   (+ C if accumulate)
@@ -270,6 +289,21 @@ size_t meant_attn_ws(int64_t G, int64_t S, int H, int Dh, int dtype);
 /* what meant_attn_fwd alone needs (mask bias, tile flags); meant_attn_ws covers forward and backward (bf16: the backward's row
  * statistics and, for 256 < S <= 512 at Dh = 64, the single-pass backward's partial-dQ scratch of G*H*64 KiB) */
 size_t meant_attn_fwd_ws(int64_t G, int64_t S, int H, int Dh, int dtype);
+/* Live-row lists of a key-masked attention over G sequences of S tokens (S % 256 == 0), for the GEMMs around it.  A 64-row block of
+ * the [G * S] token rows is DEAD when the bf16 attention kernels skip its key tile outright: all of its 64 keys are padding and every
+ * query row of the sequence has a live visible key (key 0 under the causal mask, any key otherwise) -- the kernels then never read the
+ * block's K / V rows and write exact zeros into its dK / dV rows.  It is the kernels' own rule, one device function shared with their mask
+ * preparation.  A 256-row panel is dead when its four blocks are.
+ * lists (int32 words, meant_kv_live_rows_ws(G, S) bytes; nblk = G * S / 64, npan = nblk / 4):
+ *   [0] live blocks, [1] live panels, [2] dead panels, [3 .. 63] unused
+ *   [64 ..)               the live blocks, ascending                                  (nblk words, the first [0] valid)
+ *   [64 + nblk ..)        the live panels, ordered by position range: all panels p with p mod (S / 256) == 0 first, ascending, then
+ *                         == 1, ... -- the order in which the rotary projection walks its row panels   (npan words, [1] valid)
+ *   [64 + nblk + npan ..) the dead panels, in the same order                          (npan words, [2] valid)
+ *   then nblk words of scratch.
+ * No host synchronisation: the counts stay on the device. */
+size_t meant_kv_live_rows_ws(int64_t G, int64_t S);
+int meant_kv_live_rows(const float* key_mask, int64_t G, int64_t S, int causal, void* lists, size_t lists_bytes, void* stream);
 int meant_attn_fwd(const void* qkv, void* o, float* lse, const float* key_mask, int64_t G, int64_t S, int H,
                    int Dh, float scale, int causal, int dtype, void* workspace, size_t workspace_bytes,
                    void* stream);

@@ -40,6 +40,9 @@ SIGNATURES = {
     "meant_linear_bwd_dx": (_i, [_p, _i64, _p, _p, _i64, _i64, _i64, _i64, _i, _p]),
     "meant_linear_bwd_dw_ws": (_sz, [_i64, _i64, _i64, _i]),
     "meant_linear_bwd_dw": (_i, [_p, _i64, _p, _i64, _p, _p, _i64, _i64, _i64, _i, _p, _sz, _p]),
+    "meant_linear_bwd_dw_rows": (_i, [_p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _i, _p, _sz, _p]),
+    "meant_kv_live_rows_ws": (_sz, [_i64, _i64]),
+    "meant_kv_live_rows": (_i, [_p, _i64, _i64, _i, _p, _sz, _p]),
     "meant_set_option": (_i, [C.c_char_p, _i]),
     "meant_get_option": (_i, [C.c_char_p, C.POINTER(_i)]),
     "meant_route_count": (_i64, [C.c_char_p]),
@@ -55,6 +58,7 @@ SIGNATURES = {
     "meant_attn_fwd": (_i, [_p, _p, _p, _p, _i64, _i64, _i, _i, _f, _i, _i, _p, _sz, _p]),
     "meant_attn_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i, _i, _f, _i, _p, _p, _p, _p, _i, _i, _p, _sz, _p]),
     "meant_qkv_proj_fwd": (_i, [_p, _i64, _p, _p, _p, _i64, _i64, _i64, _i, _i, _i, _p, _p, _p, _p, _i, _p]),
+    "meant_qkv_proj_fwd_live": (_i, [_p, _i64, _p, _p, _p, _i64, _i64, _i64, _i, _i, _i, _p, _p, _p, _p, _p, _i, _p]),
     "meant_gather_rows": (_i, [_p, _p, _p, _p, _i64, _i64, _i, _p]),
     "meant_gather_rows_rot": (_i, [_p, _p, _p, _i64, _i64, _i, _i, _i, _p, _p, _p, _p, _i, _p]),
     "meant_group_scatter": (_i, [_p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i, _p]),

@@ -51,10 +51,19 @@ extern "C" int meant_linear_fwd(const void* x, int64_t ldx, const void* w, const
 
 // Fused q|k|v projection + rotary (meant/attention.py:36-40, meant/xPosAttention.py:37-39): qkv[M, 3D] = x W^T + b with
 // the rotary / xPos rotation of the q and k blocks applied in the GEMM epilogue (bf16 tier) or by the rotary kernel.
-extern "C" int meant_qkv_proj_fwd(const void* x, int64_t ldx, const void* w, const float* bias, void* qkv, int64_t M, int64_t K,
-                                  int64_t S, int H, int Dh, int R, const float* qa, const float* qb, const float* ka,
-                                  const float* kb, int dtype, void* stream) {
+extern "C" int meant_qkv_proj_fwd_live(const void* x, int64_t ldx, const void* w, const float* bias, void* qkv, int64_t M, int64_t K,
+                                       int64_t S, int H, int Dh, int R, const float* qa, const float* qb, const float* ka,
+                                       const float* kb, const void* kv_lists, int dtype, void* stream) {
   MEANT_REQUIRE(x && w && qkv && H > 0 && Dh > 0 && S > 0 && M % S == 0, MEANT_ERR_ARG, "qkv_proj_fwd: bad argument");
+  // kv_lists (meant_kv_live_rows of the attention's key mask, bf16 tier, S % 256 == 0): the k | v columns of its dead row panels are not
+  // computed where the streaming kernel takes the projection, and are zeros on return whichever kernel took it
+  const bool listed = kv_lists && dtype == MEANT_BF16 && S % 256 == 0;
+  const int* const lists = (const int*)kv_lists;
+  const int64_t nblk = M / 64, npan = M / 256;
+  const auto zero_dead = [&]() {
+    return zero_panels_launch((bf16*)qkv + (int64_t)H * Dh, 3 * (int64_t)H * Dh, 2 * (int64_t)H * Dh, lists + 64 + nblk + npan, lists + 2, npan,
+                              (hipStream_t)stream);
+  };
   const bool rot = qa != nullptr;
   MEANT_REQUIRE(!rot || (qb && ka && kb && R > 0 && R % 2 == 0 && R <= Dh), MEANT_ERR_ARG, "qkv_proj_fwd: bad rotary tables");
   const int64_t D = (int64_t)H * Dh, N = 3 * D;
@@ -65,11 +74,31 @@ extern "C" int meant_qkv_proj_fwd(const void* x, int64_t ldx, const void* w, con
     a.M = M; a.N = N; a.K = K; a.bias = bias;
     a.rot_qa = qa; a.rot_qb = qb; a.rot_ka = ka; a.rot_kb = kb;
     a.rot_S = (int)S; a.rot_D = (int)D; a.rot_Dh = Dh; a.rot_R = R;
-    return gemm_bf16_nt_launch(a, (hipStream_t)stream);
+    if (listed) {
+      // two launches: the q section over all row panels, the k | v section (B, bias and C moved to column D) over the live ones
+      GemmBf16Args q = a, kv = a;
+      q.N = D;
+      kv.N = 2 * D; kv.col0 = (int)D;
+      kv.B = a.B + D * K; kv.C = a.C + D; kv.bias = bias ? bias + D : nullptr;
+      kv.panel_list = lists + 64 + nblk; kv.panel_count = lists + 1;
+      if (D % 256 == 0 && gemm_bf16_nt_streams(q) && gemm_bf16_nt_streams(kv)) {
+        int rc = gemm_bf16_nt_launch(q, (hipStream_t)stream);
+        if (!rc) rc = gemm_bf16_nt_launch(kv, (hipStream_t)stream);
+        return rc ? rc : zero_dead();
+      }
+    }
+    const int rc = gemm_bf16_nt_launch(a, (hipStream_t)stream);
+    return rc || !listed ? rc : zero_dead();
   }
   int rc = meant_linear_fwd(x, ldx, w, bias, nullptr, 0, qkv, N, nullptr, M, N, K, MEANT_EPI_NONE, dtype, stream);
-  if (rc || !rot) return rc;
-  return meant_rotary_qk(qkv, M, S, H, Dh, R, qa, qb, ka, kb, 0, dtype, stream);
+  if (!rc && rot) rc = meant_rotary_qk(qkv, M, S, H, Dh, R, qa, qb, ka, kb, 0, dtype, stream);
+  return rc || !listed ? rc : zero_dead();
+}
+
+extern "C" int meant_qkv_proj_fwd(const void* x, int64_t ldx, const void* w, const float* bias, void* qkv, int64_t M, int64_t K,
+                                  int64_t S, int H, int Dh, int R, const float* qa, const float* qb, const float* ka,
+                                  const float* kb, int dtype, void* stream) {
+  return meant_qkv_proj_fwd_live(x, ldx, w, bias, qkv, M, K, S, H, Dh, R, qa, qb, ka, kb, nullptr, dtype, stream);
 }
 
 extern "C" int meant_linear_bwd_dx(const void* dy, int64_t lddy, const void* wT, void* dx, int64_t lddx, int64_t M, int64_t N,
@@ -147,6 +176,30 @@ extern "C" int meant_linear_bwd_dw(const void* dy, int64_t lddy, const void* x, 
     return gemm_bf16_tn_launch((const bf16*)dy, lddy, (const bf16*)x, ldx, dw, dbias, M, N, K, workspace, workspace_bytes, (hipStream_t)stream);
   meant_set_error("linear_bwd_dw: unknown dtype %d", dtype);
   return MEANT_ERR_ARG;
+}
+
+extern "C" int meant_linear_bwd_dw_rows(const void* dy, int64_t lddy, const void* x, int64_t ldx, float* dw, float* dbias, const int* rows_list,
+                                        const int* rows_count, int64_t M, int64_t N, int64_t K, int dtype, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+  MEANT_REQUIRE(rows_list && rows_count, MEANT_ERR_ARG, "linear_bwd_dw_rows: null list");
+  // only the bf16 MFMA kernel reads the list; everything else sums all rows (the rows outside the list are zero: same result)
+  if (dtype != MEANT_BF16) return meant_linear_bwd_dw(dy, lddy, x, ldx, dw, dbias, M, N, K, dtype, workspace, workspace_bytes, stream);
+  MEANT_REQUIRE(dy && x && dw, MEANT_ERR_ARG, "linear_bwd_dw_rows: null pointer");
+  MEANT_REQUIRE(M > 0 && N > 0 && K > 0 && lddy >= N && ldx >= K, MEANT_ERR_ARG, "linear_bwd_dw_rows: bad shape");
+  if (N < 8 || K < 8 || (lddy & 7) || (ldx & 7) || !meant_aligned16(dy) || !meant_aligned16(x))
+    return meant_linear_bwd_dw(dy, lddy, x, ldx, dw, dbias, M, N, K, dtype, workspace, workspace_bytes, stream);
+  return gemm_bf16_tn_rows_launch((const bf16*)dy, lddy, (const bf16*)x, ldx, dw, dbias, rows_list, rows_count, M, N, K, workspace, workspace_bytes,
+                                  (hipStream_t)stream);
+}
+
+extern "C" size_t meant_kv_live_rows_ws(int64_t G, int64_t S) { return G > 0 && S > 0 && S % 256 == 0 ? kv_live_rows_bytes(G, S) : 0; }
+
+extern "C" int meant_kv_live_rows(const float* key_mask, int64_t G, int64_t S, int causal, void* lists, size_t lists_bytes, void* stream) {
+  MEANT_REQUIRE(key_mask && lists && G > 0 && S > 0, MEANT_ERR_ARG, "kv_live_rows: null pointer or bad shape");
+  MEANT_REQUIRE(S % 256 == 0, MEANT_ERR_UNSUPPORTED, "kv_live_rows: S=%lld must be a multiple of 256", (long long)S);
+  MEANT_REQUIRE(lists_bytes >= kv_live_rows_bytes(G, S) && (reinterpret_cast<uintptr_t>(lists) & 3) == 0, MEANT_ERR_WORKSPACE,
+                "kv_live_rows: the list buffer needs %zu bytes (meant_kv_live_rows_ws), got %zu", kv_live_rows_bytes(G, S), lists_bytes);
+  return kv_live_rows_launch(key_mask, G, S, causal, (int*)lists, (hipStream_t)stream);
 }
 
 extern "C" size_t meant_attn_ws(int64_t G, int64_t S, int H, int Dh, int dtype) {

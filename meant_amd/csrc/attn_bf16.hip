@@ -40,16 +40,15 @@ namespace {
 //          (key 0 under the causal mask, any key otherwise) -- rows with no live key keep the reference's uniform
 //          softmax over the padding and therefore need every tile.
 constexpr float DEAD_BIAS = -1e8f, LIVE_BIAS = -1e6f;
-__global__ __launch_bounds__(64) void attn_prep_mask_kernel(const float* __restrict__ km, float* __restrict__ bias2,
-                                                             int* __restrict__ flags, int S, int nt, int causal, unsigned* __restrict__ ctr) {
-  const int g = blockIdx.y, t = blockIdx.x, lane = threadIdx.x;
-  if (ctr && g == 0 && t == 0 && lane < 8) ctr[lane * 16] = 0u;   // the single-pass backward's per-XCD item counters
+// this lane's key of tile t of group g: its bias
+__device__ __forceinline__ float key_tile_bias(const float* __restrict__ km, int g, int t, int S, int lane) {
   const int key = t * KV_TILE + lane;
-  float b = 0.f;
-  if (key >= S) b = -INFINITY;
-  else if (km) b = fmaf(km[(int64_t)g * S + key], PADL2, -PADL2);
-  bias2[((int64_t)g * nt + t) * KV_TILE + lane] = b;
-  const int any = __any(b != 0.f);
+  if (key >= S) return -INFINITY;
+  return km ? fmaf(km[(int64_t)g * S + key], PADL2, -PADL2) : 0.f;
+}
+// flag bit 1 (one wave per tile, b = key_tile_bias of every lane).  The ONE definition of "this tile's keys are never read and its dK / dV
+// rows are exact zeros": the mask kernel and the live-row lists of the q|k|v projection GEMMs (kv_live_flag_kernel) both call it.
+__device__ __forceinline__ int key_tile_skippable(const float* __restrict__ km, int g, int S, int causal, float b, int lane) {
   int skip = 0;
   if (km && __all(b <= DEAD_BIAS)) {
     const float* kg = km + (int64_t)g * S;
@@ -60,7 +59,86 @@ __global__ __launch_bounds__(64) void attn_prep_mask_kernel(const float* __restr
       skip = __any(live);
     }
   }
+  return skip;
+}
+__global__ __launch_bounds__(64) void attn_prep_mask_kernel(const float* __restrict__ km, float* __restrict__ bias2,
+                                                             int* __restrict__ flags, int S, int nt, int causal, unsigned* __restrict__ ctr) {
+  const int g = blockIdx.y, t = blockIdx.x, lane = threadIdx.x;
+  if (ctr && g == 0 && t == 0 && lane < 8) ctr[lane * 16] = 0u;   // the single-pass backward's per-XCD item counters
+  const float b = key_tile_bias(km, g, t, S, lane);
+  bias2[((int64_t)g * nt + t) * KV_TILE + lane] = b;
+  const int any = __any(b != 0.f);
+  const int skip = key_tile_skippable(km, g, S, causal, b, lane);
   if (lane == 0) flags[(int64_t)g * nt + t] = any | (skip << 1);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Live-row lists for the GEMMs around the attention core (the q|k|v projection and its two gradients): a 64-row block of the [G * S]
+// token rows is DEAD when key_tile_skippable holds for it -- no kernel reads its K / V rows and its dK / dV rows are exact zeros -- a
+// 256-row panel when its four blocks are.  S % 256 == 0, so blocks and panels never straddle two sequences.
+//   kv_live_flag_kernel : live[block] = 0 / 1, one wave per block (the mask kernel's grid);
+//   kv_live_lists_kernel: one workgroup compacts them into out = [n live blocks, n live panels, n dead panels, 61 words unused |
+//                         live blocks, ascending | live panels | dead panels].  The panel lists are ordered by position range (all panels p with
+//                         p mod (S / 256) == 0 first, ascending, then == 1, ...): the order in which the rotary projection walks its panels.
+// Counts stay on the device: the GEMMs read them there, their grids are sized for the full problem.
+constexpr int KV_LIST_HDR = 64;
+__global__ __launch_bounds__(64) void kv_live_flag_kernel(const float* __restrict__ km, int* __restrict__ live, int S, int nt, int causal) {
+  const int g = blockIdx.y, t = blockIdx.x, lane = threadIdx.x;
+  const float b = key_tile_bias(km, g, t, S, lane);
+  const int skip = key_tile_skippable(km, g, S, causal, b, lane);
+  if (lane == 0) live[(int64_t)g * nt + t] = !skip;
+}
+
+__global__ __launch_bounds__(1024) void kv_live_lists_kernel(const int* __restrict__ live, int* __restrict__ out, int nblk, int P) {
+  __shared__ int s_cnt[1024];
+  __shared__ int s_tot[3];
+  const int tid = threadIdx.x;
+  const int npan = nblk >> 2, Q = npan / P;
+  int* const blocks = out + KV_LIST_HDR;
+  int* const panels = blocks + nblk;
+  int* const dead = panels + npan;
+  // exclusive prefix of this thread's count over the workgroup (Hillis-Steele in LDS); the total lands in s_tot[slot]
+  auto scan = [&](int mine, int slot) {
+    __syncthreads();
+    s_cnt[tid] = mine;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {
+      const int v = tid >= d ? s_cnt[tid - d] : 0;
+      __syncthreads();
+      s_cnt[tid] += v;
+      __syncthreads();
+    }
+    if (tid == 1023) s_tot[slot] = s_cnt[1023];
+    return s_cnt[tid] - mine;
+  };
+  {  // blocks: thread `tid` owns the contiguous run [lo, hi)
+    const int per = (nblk + 1023) / 1024, lo = min(tid * per, nblk), hi = min(lo + per, nblk);
+    int mine = 0;
+    for (int i = lo; i < hi; ++i) mine += live[i] != 0;
+    int at = scan(mine, 0);
+    for (int i = lo; i < hi; ++i)
+      if (live[i]) blocks[at++] = i;
+  }
+  {  // panels, in walk order: slot j is panel (j % Q) * P + j / Q
+    const int per = (npan + 1023) / 1024, lo = min(tid * per, npan), hi = min(lo + per, npan);
+    auto panel_of = [&](int j) { return (j % Q) * P + j / Q; };
+    auto is_live = [&](int p) { return (live[4 * p] | live[4 * p + 1] | live[4 * p + 2] | live[4 * p + 3]) != 0; };
+    int mine = 0;
+    for (int j = lo; j < hi; ++j) mine += is_live(panel_of(j));
+    int at = scan(mine, 1);
+    int atd = lo - at;                                   // dead panels before this run: slots before it that are not live
+    for (int j = lo; j < hi; ++j) {
+      const int p = panel_of(j);
+      if (is_live(p)) panels[at++] = p;
+      else dead[atd++] = p;
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    out[0] = s_tot[0];
+    out[1] = s_tot[1];
+    out[2] = npan - s_tot[1];
+  }
 }
 
 // packed per-group tile masks: masks[g] = {bit t: tile t needs the bias / tail path,
@@ -1067,4 +1145,22 @@ int attn_bf16_bwd(const bf16* qkv, const bf16* o, const bf16* dout, const float*
   if (one_pass) return attn_bwd1_launch(qkv, o, dout, lse, m.bias2, m.flags, m.masks, dqkv, m.ws1, G, S, H, scale, causal, rot, stream);
   const BwdArgs a{qkv, o, dout, lse, m.bias2, m.flags, dqkv, (float*)ws, m.masks, G * (int64_t)H * S, (int)S, H, scale, causal, (int)G, (int)ceil_div(S, 128), rot};
   return switch_hd(Dh, [&](auto hd) { return launch_bwd<decltype(hd)::value>(a, H, G, causal, stream); });
+}
+
+// live 64-row blocks / 256-row panels of the [G * S] token rows under `key_mask` (see kv_live_flag_kernel); lists: kv_live_rows_bytes(G, S)
+size_t kv_live_rows_bytes(int64_t G, int64_t S) {
+  const int64_t nblk = G * (S / KV_TILE), npan = nblk / 4;
+  return (size_t)(KV_LIST_HDR + 2 * nblk + 2 * npan) * sizeof(int);
+}
+
+int kv_live_rows_launch(const float* key_mask, int64_t G, int64_t S, int causal, int* lists, hipStream_t stream) {
+  MEANT_REQUIRE(key_mask && lists && S % 256 == 0 && G > 0 && G <= 65535 && G * (S / KV_TILE) < (1LL << 30), MEANT_ERR_UNSUPPORTED,
+                "kv_live_rows: needs a key mask, S %% 256 == 0 and G <= 65535 (G=%lld S=%lld)", (long long)G, (long long)S);
+  const int nt = (int)(S / KV_TILE), nblk = (int)(G * nt);
+  int* live = lists + KV_LIST_HDR + nblk + 2 * (nblk / 4);
+  hipLaunchKernelGGL(kv_live_flag_kernel, dim3((unsigned)nt, (unsigned)G), dim3(64), 0, stream, key_mask, live, (int)S, nt, causal);
+  MEANT_LAUNCH_CHECK("kv_live_flag");
+  hipLaunchKernelGGL(kv_live_lists_kernel, dim3(1), dim3(1024), 0, stream, live, lists, nblk, (int)(S / 256));
+  MEANT_LAUNCH_CHECK("kv_live_lists");
+  return MEANT_OK;
 }

@@ -50,7 +50,7 @@ int meant_raise_dyn_lds(const void* kernel, int bytes);
   } while (0)
 
 enum meant_option_id {
-  MEANT_OPT_NT_STREAM = 0, MEANT_OPT_NT_DYNAMIC, MEANT_OPT_DETERMINISTIC, MEANT_OPT_NT_GRID_CAP, MEANT_OPT_ATTN_SHORT, MEANT_OPT_NT_RAGGED, MEANT_OPT_ATTN_BWD1, MEANT_OPT_TEMPORAL_LONG, MEANT_OPT_COUNT
+  MEANT_OPT_NT_STREAM = 0, MEANT_OPT_NT_DYNAMIC, MEANT_OPT_DETERMINISTIC, MEANT_OPT_NT_GRID_CAP, MEANT_OPT_ATTN_SHORT, MEANT_OPT_NT_RAGGED, MEANT_OPT_ATTN_BWD1, MEANT_OPT_TEMPORAL_LONG, MEANT_OPT_KV_SKIP, MEANT_OPT_COUNT
 };
 int meant_opt(int id);
 
@@ -60,7 +60,7 @@ enum meant_route_id {
   ROUTE_ATTN_BWD_D128, ROUTE_ATTN_BWD_D96, ROUTE_ATTN_GENERIC, ROUTE_ATTN_CLS, ROUTE_ATTN_SHORT, ROUTE_NT_OVERLAP, ROUTE_ATTN_BWD1,
   ROUTE_ATTN_FWD_D160, ROUTE_ATTN_FWD_D192, ROUTE_ATTN_FWD_D256, ROUTE_ATTN_BWD_D160, ROUTE_ATTN_BWD_D192, ROUTE_ATTN_BWD_D256, ROUTE_TEMPORAL_LONG,
   ROUTE_EMB_SEG, ROUTE_SORT_IDS, ROUTE_NT128K, ROUTE_NT256K, ROUTE_SELECT_ROWS, ROUTE_ROTARY_QK, ROUTE_ROTARY_PAIRS, ROUTE_NT_ROT,
-  ROUTE_METRICS_ROWS, ROUTE_METRICS_WAVE, ROUTE_METRICS_LABELS,
+  ROUTE_METRICS_ROWS, ROUTE_METRICS_WAVE, ROUTE_METRICS_LABELS, ROUTE_TN256_ROWS,
   MEANT_ROUTE_COUNT
 };
 void meant_route_hit(int route);

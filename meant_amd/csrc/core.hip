@@ -82,6 +82,7 @@ const OptionDef k_options[MEANT_OPT_COUNT] = {
     {"nt_ragged", "MEANT_NT_RAGGED", 1},           // 0: ragged M as streaming head + 128 x 128 tail launch instead of the overlapped last row tile
     {"attn_bwd1", "MEANT_ATTN_BWD1", 1},           // 0: attention backward always as two passes (dQ, then dK / dV) instead of the single-pass kernel where it applies
     {"temporal_long", "MEANT_TEMPORAL_LONG", 0},   // 1: the temporal core runs the long-lag kernels at every lag (tools/probe_temporal_lag.py's like-for-like row); 0: only for L > 64
+    {"kv_skip", "MEANT_KV_SKIP", 3},               // bits: which GEMMs around a key-masked attention leave out the rows of padded key blocks (1: the k|v weight gradient, 2: the forward projection); 0: none
 };
 // "nt_pp" (the streaming GEMM in its ping-pong form) is no longer a choice: it reads 1 and cannot be set to anything else
 bool is_nt_pp(const char* name) { return name && !strcmp(name, "nt_pp"); }
@@ -140,6 +141,7 @@ const char* const k_routes[MEANT_ROUTE_COUNT] = {
     "rotary_qk", "rotary_pairs",   // every meant_rotary_qk launch; those of the pair-by-pair kernel (Dh % 8 != 0 or an unaligned base)
     "nt_rot",                       // every bf16 NT GEMM launched with the rotary epilogue, whichever nt* route it takes
     "metrics_rows", "metrics_wave", "metrics_labels",   // meant_metrics_update by form (C <= 16 / above); every meant_metrics_update_labels launch
+    "tn256_rows",                   // the 256 x 256 dW kernel reducing over a list of live 64-row blocks (meant_linear_bwd_dw_rows)
 };
 std::atomic<long long> g_route[MEANT_ROUTE_COUNT];
 }  // namespace

@@ -108,8 +108,9 @@ __device__ __forceinline__ void nt_store_row8(const GemmBf16Args& a, int64_t m, 
       *reinterpret_cast<bf16x8*>(a.preact + m * a.ldc + n) = p;
     }
     if (a.rot_qa) {
-      const int sec = (int)(n / a.rot_D);
-      const int c = (int)((n - (int64_t)sec * a.rot_D) % a.rot_Dh);
+      const int64_t nq = n + a.col0;                 // column inside the q|k|v row (a launch may cover a part of it)
+      const int sec = (int)(nq / a.rot_D);
+      const int c = (int)((nq - (int64_t)sec * a.rot_D) % a.rot_Dh);
       if (sec < 2 && c < a.rot_R) {
         const int pos = (int)(m % a.rot_S);
         const float* A = (sec ? a.rot_ka : a.rot_qa) + (int64_t)pos * a.rot_R + c;
@@ -473,8 +474,8 @@ __device__ __forceinline__ void nt256_wave_epilogue(const GemmBf16Args& a, f32x4
   const unsigned rS = ROT ? (unsigned)a.rot_S : 1u;
   const bool bigS = rS >= 256u;                        // then a lane's 16 rows of a tile wrap around S at most once
   if (ROT) {
-    const int sec = __builtin_amdgcn_readfirstlane((int)((n0 + wn * 64) / a.rot_D));
-    const int c = (int)((n - (int64_t)sec * a.rot_D) % a.rot_Dh);
+    const int sec = __builtin_amdgcn_readfirstlane((int)((a.col0 + n0 + wn * 64) / a.rot_D));   // col0: the launch's first column of the q|k|v row
+    const int c = (int)((a.col0 + n - (int64_t)sec * a.rot_D) % a.rot_Dh);
     tile_rot = sec < 2;
     rot_on = tile_rot && c < a.rot_R;
     tabA = (sec ? a.rot_ka : a.rot_qa) + (rot_on ? c : 0);
@@ -689,10 +690,16 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt256p_kernel(GemmBf16Args a
   const int wm = wave >> 2, wn = wave & 3;
   const bool leader = wm == 0;
   const int nk = (int)(a.K / BK);
-  const int ntiles = ntm * ntn, G = gridDim.x;
+  // Rotary mode with a panel list (the k|v section of a key-masked q|k|v projection): only the row panels plist[0 .. *panel_count) exist for
+  // this launch -- the count is read here, the grid is the full problem's -- and tile row i of the walk is panel plist[i]; the list
+  // comes in walk order (see rotP below).  Everything else (`listed` false) is the code it was.
+  typedef const __attribute__((address_space(4))) int* panel_list_t;
+  const bool listed = MODE == NTE_ROT && a.panel_list != nullptr;
+  const panel_list_t plist = (panel_list_t)a.panel_list;
+  const int ntiles = (listed ? __builtin_amdgcn_readfirstlane(*a.panel_count) : ntm) * ntn, G = gridDim.x;
   const int CH = G >> 3, xcd = blockIdx.x & 7;
   int tile = xcd * CH + (blockIdx.x >> 3);
-  const bool dynamic = sched != nullptr && nk >= 8;
+  const bool dynamic = sched != nullptr && nk >= (listed ? 9 : 8);
   auto leave = [&]() {
     if (sched && threadIdx.x == 0) {
       if (atomicAdd(&sched->done, 1u) == (unsigned)G - 1u) {
@@ -725,9 +732,17 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt256p_kernel(GemmBf16Args a
   // at a time the working set halves and every tile touches it.
   const int rotP = MODE == NTE_ROT ? (mode >> 16) : 1;
   const int rotQ = MODE == NTE_ROT && rotP > 1 ? ntm / rotP : 1;
+  // (row panel, column tile) -> origins; origin(t): of tile t of the walk
+  auto origin_at = [&](int tm, int tn, const bf16*& pa, const bf16*& pb, int64_t& m0, int64_t& n0) {
+    m0 = (int64_t)tm * B2;
+    n0 = (int64_t)tn * B2;
+    pa = a.A + m0 * a.lda;
+    pb = a.B + n0 * a.ldb;
+  };
   auto origin = [&](int t, const bf16*& pa, const bf16*& pb, int64_t& m0, int64_t& n0) {
     int tm = t / ntn;
     const int tn = t - tm * ntn;
+    if (MODE == NTE_ROT && listed) { origin_at(plist[tm], tn, pa, pb, m0, n0); return; }
     if (MODE == NTE_ROT && rotP > 1) { const int r = tm / rotQ; tm = (tm - r * rotQ) * rotP + r; }
     m0 = (int64_t)tm * B2;
     m0 = m0 + B2 <= a.M ? m0 : a.M - B2;               // ragged M: the last row tile is moved up to END at row M (see the launcher)
@@ -776,6 +791,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt256p_kernel(GemmBf16Args a
   // group's MFMAs) and pinned in front of its barrier, so that nothing but the moves sits between a step's last barrier and the next
   // step's first DMA piece.  ring slot of A_n: sA; B_n sits in the next one, B_{n+1} goes to sA + 3, A_{n+2} to sA + 4 (mod 5).
   int kspecial = dynamic ? 2 : -1;                     // the draw: request in step 2, published behind it, read in step 4
+  int next_tm = 0, next_tn = 0;                        // listed panels: the drawn tile's panel and column tile between steps 4 and 5
   int sA = 0;
   unsigned aoff = 0, boff = T2_BYTES, dB = lds0 + 3 * T2_BYTES, dA = lds0 + 4 * T2_BYTES;
   for (;;) {
@@ -883,9 +899,16 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt256p_kernel(GemmBf16Args a
           const unsigned got = (unsigned)__builtin_amdgcn_readfirstlane((int)req);
           next = (int)got;
           has_next = next >= 0;
-          if (has_next) origin(next, pAn, pBn, m0n, n0n);
+          if (MODE == NTE_ROT && listed) {
+            // the panel index is one more (scalar) load: requested here, turned into the origins behind step 5 -- the first wait
+            // of that step's MFMA half has covered it by then -- which is in time for the cursors of step nk - 3 >= 6
+            const int tq = next / ntn;
+            next_tn = next - tq * ntn;
+            next_tm = plist[has_next ? tq : 0];
+          } else if (has_next) origin(next, pAn, pBn, m0n, n0n);
         }
-        kspecial = kt == 2 ? 4 : -1;
+        if (MODE == NTE_ROT && kt == 5 && has_next) origin_at(next_tm, next_tn, pAn, pBn, m0n, n0n);
+        kspecial = kt == 2 ? 4 : (MODE == NTE_ROT && listed && kt == 4) ? 5 : -1;
       }
     }
     kspecial = dynamic ? 2 : -1;
@@ -1061,12 +1084,23 @@ __device__ __forceinline__ void tn256_frag_issue(unsigned addr, u32x2& lo, u32x2
 // 32..63 were last read in the follower's second load half and are refilled by waves 4-7, whose L0 of step t comes behind the
 // barrier that follows those reads' completion.
 // Steps past the end of the split keep prefetching its last rows (never read): no branch in the loop distinguishes them.
-template <bool DET>
+//
+// ROWS: the reduction runs over a LIST of 64-row blocks of the token axis (`rows`, ascending block indices; `*rows_count` of them, read
+// here: the host never learns the count) instead of over all of M -- the k|v columns of the q|k|v projection's weight gradient, whose
+// dK / dV rows are exact zeros for every block of padded keys the attention skipped.  A step's token rows are block rows[base + t]; a
+// split's share is ceil(count / splits) blocks (`rows_per_split` carries the number of splits), so the splits stay balanced whatever
+// the padding.  The cursors become pointers that are READY when the load half wants them: in step t the index of block t + 4 is
+// requested by a scalar load at the top of the first MFMA half and, behind the last MFMA of the second one, turned into the dY rows the
+// next step's load half will ask for (with the X rows of block t + 3, whose index came a step earlier); the load halves only move them.  A wave touches its split's part of the
+// list once in the prologue (a vector load the prologue's counted wait covers), so that those scalar loads find it in the XCD's L2.
+template <bool DET, bool ROWS = false>
 __global__ __launch_bounds__(512, 2) void gemm_bf16_tn256p_kernel(const bf16* __restrict__ dY, int64_t lddy, const bf16* __restrict__ X,
                                                                    int64_t ldx, float* __restrict__ dW, float* __restrict__ dbias,
                                                                    int64_t M, int64_t N, int64_t K, int ntn, int ntk,
                                                                    int64_t rows_per_split, float* __restrict__ part,
-                                                                   float* __restrict__ pbias) {
+                                                                   float* __restrict__ pbias, const int* __restrict__ rows,
+                                                                   const int* __restrict__ rows_count) {
+  static_assert(!(DET && ROWS), "the row-list form has no deterministic variant");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wn = wave >> 2, wk = wave & 3;
@@ -1077,10 +1111,27 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn256p_kernel(const bf16* __
   const int split = __builtin_amdgcn_readfirstlane(bid / (ntn * ntk));
   const int tn = tile / ntk, tk = tile - tn * ntk;
   const int64_t n0 = (int64_t)tn * 256, k0 = (int64_t)tk * 256;
-  const int64_t mbeg = (int64_t)split * rows_per_split;
-  const int64_t mend = (mbeg + rows_per_split < M) ? mbeg + rows_per_split : M;
-  if (mbeg >= mend) return;
-  const int nt = __builtin_amdgcn_readfirstlane((int)((mend - mbeg + TN_BKM - 1) / TN_BKM));
+  int64_t mbeg = 0;
+  int nt;
+  typedef const __attribute__((address_space(4))) int* rows_list_t;   // scalar loads
+  rows_list_t rl = nullptr;                            // ROWS: this split's part of the list
+  int touch = 0;
+  if (ROWS) {
+    const int cnt = __builtin_amdgcn_readfirstlane(*rows_count);
+    const int nsplit = (int)rows_per_split;
+    const int share = __builtin_amdgcn_readfirstlane((cnt + nsplit - 1) / nsplit);
+    const int base = split * share;
+    nt = cnt - base < share ? cnt - base : share;
+    if (nt <= 0) return;
+    rl = (rows_list_t)(rows + base);
+    // one word per 64-byte line of the split's part (its first 1024 blocks: more than a split of the step's shapes has)
+    touch = rows[base + (lane * 16 < nt ? lane * 16 : 0)];
+  } else {
+    mbeg = (int64_t)split * rows_per_split;
+    const int64_t mend = (mbeg + rows_per_split < M) ? mbeg + rows_per_split : M;
+    if (mbeg >= mend) return;
+    nt = __builtin_amdgcn_readfirstlane((int)((mend - mbeg + TN_BKM - 1) / TN_BKM));
+  }
   const bool do_bias = dbias != nullptr;
 
   f32x16 acc[4][2];
@@ -1108,17 +1159,27 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn256p_kernel(const bf16* __
     vX[p] = (unsigned)((r * ldx + c * 8) * 2) + (3072 - 1024 * p);
   }
   const unsigned lds0 = lds_addr(smem) + wave * 4096;
-  const bf16* pY = dY + mbeg * lddy + n0;
-  const bf16* pX = X + mbeg * ldx + k0;
+  // ROWS: first rows of block i of the split's list (clamped to its last one), in dY and in X
+  auto rowsY = [&](int blk) { return dY + (int64_t)blk * (TN_BKM * lddy) + n0; };
+  auto rowsX = [&](int blk) { return X + (int64_t)blk * (TN_BKM * ldx) + k0; };
+  auto blk_at = [&](int i) { return rl[i < nt ? i : nt - 1]; };
+  const int b0 = ROWS ? blk_at(0) : 0, b1 = ROWS ? blk_at(1) : 0, b2 = ROWS ? blk_at(2) : 0;
+  int bn = ROWS ? blk_at(3) : 0;                       // ROWS: the block of step t + 3 at the top of step t
+  const bf16* pY = ROWS ? rowsY(b0) : dY + mbeg * lddy + n0;
+  const bf16* pX = ROWS ? rowsX(b0) : X + mbeg * ldx + k0;
   const int64_t stepY = (int64_t)TN_BKM * lddy, stepX = (int64_t)TN_BKM * ldx;
   // prologue: dY_0, X_0, dY_1 (the last step's rows again when the split has a single step)
-  const bf16* qY = nt > 1 ? pY + stepY : pY;           // cursor of the dY pieces: two steps ahead of the step that issues them
+  const bf16* qY = ROWS ? rowsY(b1) : nt > 1 ? pY + stepY : pY;   // cursor of the dY pieces: two steps ahead of the step that issues them
   glds16_x4(pY, vY, lds0);
   glds16_x4(pX, vX, lds0 + T2_BYTES);
   glds16_x4(qY, vY, lds0 + 2 * T2_BYTES);
-  const bf16* qX = nt > 1 ? pX + stepX : pX;           // cursor of the X pieces: one step ahead
-  qY = nt > 2 ? qY + stepY : qY;
+  const bf16* qX = ROWS ? rowsX(b1) : nt > 1 ? pX + stepX : pX;   // cursor of the X pieces: one step ahead
+  qY = ROWS ? rowsY(b2) : nt > 2 ? qY + stepY : qY;
+  // ROWS: what the cursors become in step 0's second load half (X of step 2, dY of step 3)
+  const bf16* nxtX = ROWS ? rowsX(b2) : nullptr;
+  const bf16* nxtY = ROWS ? rowsY(bn) : nullptr;
   asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+  if (ROWS) asm volatile("" ::"v"(touch));             // (the list touch has landed: hipcc waits for it here, behind the counted wait)
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
   if (!leader) {                                       // the follower's one-interval lag
@@ -1156,8 +1217,15 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn256p_kernel(const bf16* __
         bhi[1][j] = lds_read_tr16<(2 * ph + 1) * 8192 + 2048>(xa + boff[j]);
       }
     };
+    int bnew = 0;
     auto mfma_half = [&](int ph) {
       lds_wait_all();
+      // ROWS: the block of step t + 4 -- requested behind the wait (nothing of this wave's is in flight on the counter the fragment
+      // reads use), picked up behind the last MFMA of the step's second half
+      if (ROWS && ph == 0) {
+        bnew = blk_at(t + 4);
+        __builtin_amdgcn_sched_barrier(0);
+      }
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
@@ -1201,14 +1269,22 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn256p_kernel(const bf16* __
     const int n_s3 = n_sA + 3 >= RING ? n_sA + 3 - RING : n_sA + 3, n_s4 = n_sA + 4 >= RING ? n_sA + 4 - RING : n_sA + 4;
     unsigned n_ya = sbase + (unsigned)n_sA * T2_BYTES, n_xa = sbase + (unsigned)n_sB * T2_BYTES;
     unsigned n_dX = lds0 + (unsigned)n_s3 * T2_BYTES, n_dY = lds0 + (unsigned)n_s4 * T2_BYTES;
-    const bf16* n_qX = t + 2 < nt ? qX + stepX : qX;
-    const bf16* n_qY = t + 3 < nt ? qY + stepY : qY;
+    const bf16* n_qX = ROWS ? nxtX : t + 2 < nt ? qX + stepX : qX;
+    const bf16* n_qY = ROWS ? nxtY : t + 3 < nt ? qY + stepY : qY;
     asm volatile("" : "+s"(n_sA), "+s"(n_ya), "+s"(n_xa), "+s"(n_dX), "+s"(n_dY), "+s"(n_qX), "+s"(n_qY));
     __builtin_amdgcn_sched_barrier(0);
     if (!leader) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // follower: its pieces of the next step must be in before the leader's L0
     PP_BAR();
     mfma_half(1);
     __builtin_amdgcn_sched_barrier(0);
+    if (ROWS) {                                        // the next step's cursors: X of step t + 3 (block bn), dY of step t + 4 (block bnew)
+      asm volatile("" : "+s"(bnew));
+      nxtX = rowsX(bn);
+      nxtY = rowsY(bnew);
+      bn = bnew;
+      asm volatile("" : "+s"(nxtX), "+s"(nxtY), "+s"(bn));
+      __builtin_amdgcn_sched_barrier(0);
+    }
     if (leader) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     PP_BAR();
     sA = n_sA; ya = n_ya; xa = n_xa; dXs = n_dX; dYs = n_dY; qX = n_qX; qY = n_qY;
@@ -1269,6 +1345,19 @@ __global__ __launch_bounds__(256) void tn256_reduce_kernel(const float* __restri
   }
 }
 
+// write-only: zeros into `cpr` 16-byte chunks per row of the listed 256-row panels
+__global__ __launch_bounds__(256) void zero_panels_kernel(bf16* __restrict__ C, int64_t ldc, int cpr, const int* __restrict__ panels,
+                                                          const int* __restrict__ count) {
+  const int n = *count;
+  for (int i = blockIdx.x; i < n; i += gridDim.x) {
+    bf16* const base = C + (int64_t)panels[i] * B2 * ldc;
+    for (int idx = threadIdx.x; idx < B2 * cpr; idx += 256) {
+      const int r = idx / cpr, c = idx - r * cpr;
+      *reinterpret_cast<u32x4*>(base + (int64_t)r * ldc + c * 8) = u32x4{0u, 0u, 0u, 0u};
+    }
+  }
+}
+
 }  // namespace
 
 // Scheduler slot of (current device, stream); nullptr when the table is full or the symbol cannot be resolved.
@@ -1306,10 +1395,29 @@ extern "C" int64_t meant_debug_nt_steals(void) {
   return n;
 }
 
+// does this launch take the streaming kernel with whole row panels (the M % 256 == 0 form)?  The launcher's own route test, for callers that
+// hand it a panel list.
+bool gemm_bf16_nt_streams(const GemmBf16Args& a) {
+  return a.M >= 1024 && a.M % B2 == 0 && a.N % 256 == 0 && ceil_div(a.M, B2) * (a.N / B2) * 2 >= meant_num_cus() && meant_opt(MEANT_OPT_NT_STREAM) != 0 &&
+         a.K % BK == 0 && a.K >= 4 * BK && (a.ldc & 7) == 0 && (!a.residual || (a.ldr & 7) == 0);
+}
+
+// zero the `cols` columns at C of the 256-row panels panels[0 .. *count) (device memory): the k | v rows nobody computed
+int zero_panels_launch(bf16* C, int64_t ldc, int64_t cols, const int* panels, const int* count, int64_t npan, hipStream_t stream) {
+  MEANT_REQUIRE(C && panels && count && cols % 8 == 0 && (ldc & 7) == 0 && meant_aligned16(C) && cols < (1 << 20), MEANT_ERR_ARG, "zero_panels: bad argument");
+  if (npan <= 0) return MEANT_OK;
+  hipLaunchKernelGGL(zero_panels_kernel, dim3((unsigned)(npan < 2048 ? npan : 2048)), dim3(256), 0, stream, C, ldc, (int)(cols / 8), panels, count);
+  MEANT_LAUNCH_CHECK("zero_panels");
+  return MEANT_OK;
+}
+
 int gemm_bf16_nt_launch(const GemmBf16Args& a, hipStream_t stream) {
   MEANT_REQUIRE(a.A && a.B && a.C, MEANT_ERR_ARG, "gemm_bf16_nt: null pointer");
-  MEANT_REQUIRE(!a.rot_qa || (a.N == 3 * (int64_t)a.rot_D && a.rot_Dh % 8 == 0 && a.rot_R % 8 == 0 && (a.ldc & 7) == 0 && a.rot_D % a.rot_Dh == 0),
-                MEANT_ERR_ARG, "gemm_bf16_nt: rotary epilogue needs N = 3*H*Dh, Dh %% 8 == 0, rot_dim %% 8 == 0");
+  MEANT_REQUIRE(!a.rot_qa || (a.rot_D > 0 && a.col0 >= 0 && a.col0 % a.rot_D == 0 && a.N % a.rot_D == 0 && a.col0 + a.N <= 3 * (int64_t)a.rot_D &&
+                              a.rot_Dh % 8 == 0 && a.rot_R % 8 == 0 && (a.ldc & 7) == 0 && a.rot_D % a.rot_Dh == 0),
+                MEANT_ERR_ARG, "gemm_bf16_nt: rotary epilogue needs whole q / k / v sections of H*Dh columns, Dh %% 8 == 0, rot_dim %% 8 == 0");
+  MEANT_REQUIRE(!a.panel_list || (a.rot_qa && a.panel_count && gemm_bf16_nt_streams(a)), MEANT_ERR_UNSUPPORTED,
+                "gemm_bf16_nt: a panel list needs the rotary epilogue on the streaming kernel");
   MEANT_REQUIRE(a.K >= 8 && a.K % 8 == 0, MEANT_ERR_UNSUPPORTED, "gemm_bf16_nt: K=%lld must be a multiple of 8 (use the fp32 tier otherwise)", (long long)a.K);
   MEANT_REQUIRE((a.lda % 8) == 0 && (a.ldb % 8) == 0 && meant_aligned16(a.A) && meant_aligned16(a.B), MEANT_ERR_ARG,
                 "gemm_bf16_nt: operands must be 16-byte aligned with row strides that are multiples of 8");
@@ -1501,7 +1609,7 @@ int gemm_bf16_tn_launch(const bf16* dY, int64_t lddy, const bf16* X, int64_t ldx
       meant_route_hit(ROUTE_TN256_DET);
       MEANT_RAISE_LDS(gemm_bf16_tn256p_kernel<true>, RING * T2_BYTES);
       hipLaunchKernelGGL(gemm_bf16_tn256p_kernel<true>, grid, dim3(512), RING * T2_BYTES, stream, dY, lddy, X, ldx, dW, dbias, M, N, K, (int)ntn2,
-                         (int)ntk2, rows2, part, pbias);
+                         (int)ntk2, rows2, part, pbias, (const int*)nullptr, (const int*)nullptr);
       MEANT_LAUNCH_CHECK("gemm_bf16_tn256<det>");
       hipLaunchKernelGGL(tn256_reduce_kernel, dim3((unsigned)ceil_div(N * K / 4, 256)), dim3(256), 0, stream, part, dbias ? pbias : nullptr, dW, dbias,
                          N, K, (int)ntk2, (int)(ntn2 * ntk2), (int)splits2);
@@ -1511,7 +1619,7 @@ int gemm_bf16_tn_launch(const bf16* dY, int64_t lddy, const bf16* X, int64_t ldx
     meant_route_hit(ROUTE_TN256);
     MEANT_RAISE_LDS(gemm_bf16_tn256p_kernel<false>, RING * T2_BYTES);
     hipLaunchKernelGGL(gemm_bf16_tn256p_kernel<false>, grid, dim3(512), RING * T2_BYTES, stream, dY, lddy, X, ldx, dW, dbias, M, N, K, (int)ntn2,
-                       (int)ntk2, rows2, (float*)nullptr, (float*)nullptr);
+                       (int)ntk2, rows2, (float*)nullptr, (float*)nullptr, (const int*)nullptr, (const int*)nullptr);
     MEANT_LAUNCH_CHECK("gemm_bf16_tn256");
     return MEANT_OK;
   }
@@ -1529,5 +1637,24 @@ int gemm_bf16_tn_launch(const bf16* dY, int64_t lddy, const bf16* X, int64_t ldx
                      ldx, dW, M, N, K, (int)ntn, (int)ntk, rows_per);
   MEANT_LAUNCH_CHECK("gemm_bf16_tn");
   if (dbias) return colsum_launch(dY, lddy, dbias, M, N, MEANT_BF16, 1, stream);
+  return MEANT_OK;
+}
+
+// The same over a list of 64-row blocks of the token axis (gemm_bf16_tn256p_kernel<false, true>): dW += sum over the listed blocks; every row
+// of dY outside them is zero by the caller's word, so whatever the list form does not take -- the deterministic option, shapes the
+// 256 x 256 kernel does not serve -- runs the full reduction instead and adds the same sums.
+int gemm_bf16_tn_rows_launch(const bf16* dY, int64_t lddy, const bf16* X, int64_t ldx, float* dW, float* dbias, const int* rows,
+                             const int* rows_count, int64_t M, int64_t N, int64_t K, void* ws, size_t ws_bytes, hipStream_t stream) {
+  const bool listed = rows && rows_count && !meant_opt(MEANT_OPT_DETERMINISTIC) && M % TN_BKM == 0 && tn256_ok(M, N, K) && (lddy % 8) == 0 &&
+                      (ldx % 8) == 0 && meant_aligned16(dY) && meant_aligned16(X) && M / TN_BKM < (1LL << 30);
+  if (!listed) return gemm_bf16_tn_launch(dY, lddy, X, ldx, dW, dbias, M, N, K, ws, ws_bytes, stream);
+  const int64_t ntn2 = N / 256, ntk2 = K / 256;
+  int64_t splits2, rows2;
+  tn256_geometry(M, N, K, splits2, rows2);             // sized for the full M: the count is known on the device only
+  meant_route_hit(ROUTE_TN256_ROWS);
+  MEANT_RAISE_LDS((gemm_bf16_tn256p_kernel<false, true>), RING * T2_BYTES);
+  hipLaunchKernelGGL((gemm_bf16_tn256p_kernel<false, true>), dim3((unsigned)(ntn2 * ntk2 * splits2)), dim3(512), RING * T2_BYTES, stream, dY, lddy,
+                     X, ldx, dW, dbias, M, N, K, (int)ntn2, (int)ntk2, splits2, (float*)nullptr, (float*)nullptr, rows, rows_count);
+  MEANT_LAUNCH_CHECK("gemm_bf16_tn256<rows>");
   return MEANT_OK;
 }

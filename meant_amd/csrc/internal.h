@@ -42,13 +42,24 @@ struct GemmBf16Args {
   const float* sub_coef = nullptr;           // [M]
   const float* bres = nullptr;               // float [M / bres_rows, N]: one row per group of bres_rows consecutive output rows
   int bres_rows = 1; float bres_scale = 1.f; //   (the gradient of a sequence mean, broadcast over the sequence's tokens)
+  // rotary epilogue over a PART of the q|k|v row: column n of this launch is column col0 + n of the row (B, bias and C are the caller's,
+  // already offset), and, streaming kernel only, the 256-row panels panel_list[0 .. *panel_count) alone (device memory, in the walk order
+  // of meant_kv_live_rows; null = all panels).  gemm_bf16_nt_launch rejects a list on any other route.
+  int col0 = 0;
+  const int* panel_list = nullptr; const int* panel_count = nullptr;
 };
 int gemm_bf16_nt_launch(const GemmBf16Args& a, hipStream_t stream);
+bool gemm_bf16_nt_streams(const GemmBf16Args& a);   // the launch takes the streaming kernel over whole 256-row panels (what a panel list needs)
+int zero_panels_launch(bf16* C, int64_t ldc, int64_t cols, const int* panels, const int* count, int64_t npan, hipStream_t stream);
 // dW[N,K] (float, +=) = dY[M,N]^T X[M,K], reduction over the token axis M; dbias[N] += colsum(dY)
 // ws: partial-sum workspace of gemm_bf16_tn_ws(M, N, K) bytes, used (and required) only with the `deterministic` option
 int gemm_bf16_tn_launch(const bf16* dY, int64_t lddy, const bf16* X, int64_t ldx, float* dW, float* dbias,
                         int64_t M, int64_t N, int64_t K, void* ws, size_t ws_bytes, hipStream_t stream);
 size_t gemm_bf16_tn_ws(int64_t M, int64_t N, int64_t K);
+// the same reduction over the 64-row blocks rows[0 .. *rows_count) of the token axis only (ascending block indices, count read on the
+// device); every row of dY outside the listed blocks must be zero
+int gemm_bf16_tn_rows_launch(const bf16* dY, int64_t lddy, const bf16* X, int64_t ldx, float* dW, float* dbias, const int* rows,
+                             const int* rows_count, int64_t M, int64_t N, int64_t K, void* ws, size_t ws_bytes, hipStream_t stream);
 
 // column sums: out[N] (+)= sum_m x[m, n]
 int colsum_launch(const void* x, int64_t ldx, float* out, int64_t M, int64_t N, int dtype, int accumulate, hipStream_t stream);
@@ -74,6 +85,9 @@ int attn_bf16_bwd(const bf16* qkv, const bf16* o, const bf16* dout, const float*
                   hipStream_t stream);
 size_t attn_bf16_ws(int64_t G, int64_t S, int H, int Dh);
 size_t attn_bf16_fwd_ws(int64_t G, int64_t S, int H, int Dh);
+// live 64-row blocks and 256-row panels of the [G * S] token rows under a key mask, by the attention kernels' own "skip this key tile" rule
+size_t kv_live_rows_bytes(int64_t G, int64_t S);
+int kv_live_rows_launch(const float* key_mask, int64_t G, int64_t S, int causal, int* lists, hipStream_t stream);
 // S <= 16: one wave per (group, head) (attn_short.hip); same layouts, statistics and semantics, no workspace
 bool attn_short_ok(int64_t S, int Dh);
 int attn_short_fwd(const bf16* qkv, bf16* o, float* lse, const float* key_mask, int64_t G, int64_t S, int H, int Dh, float scale,

@@ -722,6 +722,40 @@ def _bwd_dw(dy2, x2, dw, db):
           "linear_bwd_dw")
 
 
+def _bwd_dw_rows(dy2, x2, dw, db, lists):
+    """the same over the live 64-row blocks of `lists` (kv_live_rows) only: every row of dy2 outside them is zero"""
+    M, N = dy2.shape
+    K = x2.shape[1]
+    dt = _dt(dy2)
+    wsb = lib.meant_linear_bwd_dw_ws(M, N, K, dt)          # the deterministic option sums all rows, through its workspace
+    ws = torch.empty(wsb, device=dy2.device, dtype=torch.uint8) if wsb else None
+    check(lib.meant_linear_bwd_dw_rows(_p(dy2), dy2.stride(0), _p(x2), x2.stride(0), _p(dw), _p(db), lists.data_ptr() + 4 * KV_LIST_HEADER,
+                                       lists.data_ptr(), M, N, K, dt, _p(ws), wsb, _stream()), "linear_bwd_dw_rows")
+
+
+KV_LIST_HEADER = 64        # int32 words in front of the lists of meant_kv_live_rows (include/meant_hip.h): [live blocks, live panels, dead panels, ...]
+KV_SKIP_DW, KV_SKIP_FWD = 1, 2          # bits of the library option "kv_skip": the k|v weight gradient, the forward projection
+
+
+def kv_live_rows(key_mask, causal):
+    """int32 device tensor of meant_kv_live_rows for a float key mask [G, S], S % 256 == 0: counts and lists of the 64-row blocks /
+    256-row panels of the [G * S] token rows whose keys the bf16 attention kernels do not skip outright.  No host synchronisation."""
+    S = key_mask.shape[-1]
+    G = key_mask.numel() // S
+    nbytes = lib.meant_kv_live_rows_ws(G, S)
+    lists = torch.empty(nbytes // 4, device=key_mask.device, dtype=torch.int32)
+    check(lib.meant_kv_live_rows(_p(key_mask), G, S, int(causal), _p(lists), nbytes, _stream()), "kv_live_rows")
+    return lists
+
+
+def _kv_skip_bits(x, key_mask, S, D, Dh):
+    """which of the GEMMs around this attention leave out the rows of padded key blocks (option "kv_skip"): only the bf16 MFMA path
+    with a key mask, whole 256-row panels per sequence and q | k | v sections that are whole 256-column tiles"""
+    if key_mask is None or x.dtype != torch.bfloat16 or S % 256 or D % 256 or Dh not in NATIVE_HEAD_DIMS:
+        return 0
+    return _lib.get_option("kv_skip")
+
+
 # Gradient sinks: a gradient reducer (meant_amd.parallel.GradReducer(direct_grads=True)) registers, per parameter, the
 # view of its flat bucket that IS the parameter's .grad.  A Linear whose weight (and bias) have a sink accumulates dW / db
 # straight into those views -- the C ABI's contract is "+=" -- and reports to the reducer, instead of handing autograd a
@@ -968,25 +1002,32 @@ class _QKVAttention(torch.autograd.Function):
         dt = _dt(x)
         qa, qb, ka, kb = tables if tables is not None else (None, None, None, None)
         R = qa.shape[1] if qa is not None else 0
+        km = _c(key_mask.float()) if key_mask is not None else None
+        skip = _kv_skip_bits(x, km, S, D, Dh)
+        lists = kv_live_rows(km, causal) if skip else None                    # built once, on the device; backward reads the same lists
         qkv = torch.empty((G * S, 3 * D), device=x.device, dtype=x.dtype)
-        check(lib.meant_qkv_proj_fwd(_p(x2), x2.stride(0), _p(w_c), _p(bias_f), _p(qkv), G * S, x2.shape[1], S, num_heads, Dh, R,
-                                     _p(qa), _p(qb), _p(ka), _p(kb), dt, _stream()), "qkv_proj_fwd")
+        if skip & KV_SKIP_FWD:                                                # the k | v rows of dead panels: not computed, zeros
+            check(lib.meant_qkv_proj_fwd_live(_p(x2), x2.stride(0), _p(w_c), _p(bias_f), _p(qkv), G * S, x2.shape[1], S, num_heads, Dh, R,
+                                              _p(qa), _p(qb), _p(ka), _p(kb), _p(lists), dt, _stream()), "qkv_proj_fwd_live")
+        else:
+            check(lib.meant_qkv_proj_fwd(_p(x2), x2.stride(0), _p(w_c), _p(bias_f), _p(qkv), G * S, x2.shape[1], S, num_heads, Dh, R,
+                                         _p(qa), _p(qb), _p(ka), _p(kb), dt, _stream()), "qkv_proj_fwd")
         o = torch.empty((G * S, D), device=x.device, dtype=x.dtype)
         lse = torch.empty((G, num_heads, S, 2), device=x.device, dtype=torch.float32)
-        km = _c(key_mask.float()) if key_mask is not None else None
         scale = 1.0 / math.sqrt(Dh * num_heads) if scale is None else float(scale)
         wsb = lib.meant_attn_fwd_ws(G, S, num_heads, Dh, dt)
         ws = torch.empty(max(wsb, 16), device=x.device, dtype=torch.uint8)
         check(lib.meant_attn_fwd(_p(qkv), _p(o), _p(lse), _p(km), G, S, num_heads, Dh, scale, int(causal), dt, _p(ws), wsb,
                                  _stream()), "attn_fwd")
-        ctx.save_for_backward(x2, qkv, o, lse, km, w_f)
+        ctx.save_for_backward(x2, qkv, o, lse, km, w_f, lists)
+        ctx.kv_skip = skip
         ctx.tables = tables
         ctx.meta = (G, S, d, D, Dh, num_heads, scale, int(causal))
         return o.view(G, S, D)
 
     @staticmethod
     def backward(ctx, do):
-        x2, qkv, o, lse, km, w_f = ctx.saved_tensors
+        x2, qkv, o, lse, km, w_f, lists = ctx.saved_tensors
         G, S, d, D, Dh, H, scale, causal = ctx.meta
         do2 = _c(do).view(G * S, D)
         dt = _dt(do2)
@@ -1008,7 +1049,13 @@ class _QKVAttention(torch.autograd.Function):
         K8 = x2.shape[1]                                                      # ceil8(d) where forward padded x
         dw = torch.zeros((N, K8), device=do2.device, dtype=torch.float32)
         db = torch.zeros(N, device=do2.device, dtype=torch.float32)
-        _bwd_dw(dqkv, x2, dw, db)
+        if ctx.kv_skip & KV_SKIP_DW:
+            # the dk / dv rows of the key blocks the attention skipped are exact zeros: the k|v columns reduce over the live blocks only
+            # (their bias gradient rides the same launch), the q columns over all rows, both into the one dw / db
+            _bwd_dw(dqkv[:, :D], x2, dw[:D], db[:D])
+            _bwd_dw_rows(dqkv[:, D:], x2, dw[D:], db[D:], lists)
+        else:
+            _bwd_dw(dqkv, x2, dw, db)
         if K8 != K:
             dw = _pad_cols(dw, K)
         return (dx.view(G, S, d) if dx is not None else None), dw, db, None, None, None, None, None
