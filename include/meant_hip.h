@@ -89,7 +89,7 @@ int meant_get_option(const char* name, int* value);
  * "nt128k", "nt256k" (the K-tail forms of the 128 x 128 and 256 x 256 one-tile kernels: K % 64 != 0),
  * "nt_split", "nt_overlap", "tn128", "tn256", "tn256_det", "tn256_rows" (meant_linear_bwd_dw_rows on its list), "tn_tail", "gemm_f32", "attn_fwd", "attn_fwd_d128",
  * "attn_fwd_d96", "attn_bwd" (the two-pass form), "attn_bwd1" (the single-pass form), "attn_bwd_d128", "attn_bwd_d96",
- * "attn_generic", "attn_cls", "attn_short", "attn_fwd_d160" ... "attn_bwd_d256", "temporal_long" (the temporal attention
+ * "attn_generic", "attn_cls", "attn_cls_split", "rows_elem", "attn_short", "attn_fwd_d160" ... "attn_bwd_d256", "temporal_long" (the temporal attention
  * core's long-lag kernels, forward and backward each count one), "emb_seg" (meant_embedding_bwd_seg), "sort_ids" (meant_sort_ids), "select_rows" (meant_select_rows),
  * "rotary_qk" (every meant_rotary_qk launch), "rotary_pairs" (those of its pair-by-pair kernel: Dh % 8 != 0 or an unaligned base)
  * "nt_rot" (every bf16 NT GEMM launched with the rotary epilogue, on top of the nt* route it takes) and "metrics_rows" /
@@ -337,7 +337,9 @@ int meant_attn_bwd(const void* qkv, const void* o, const void* do_, const float*
  * the time attention, '(b f) n' for the space attention, the cls key / value in front of every group) and lets the cls
  * query attend to every token.  The core itself is meant_attn_fwd / _bwd on the regrouped buffer; these move the rows.
  * dst[r, :] = src[idx[r], :] for idx[r] >= 0, zeros for idx[r] == -1, fill[:] (act [W]) for idx[r] == -2; rows of W
- * elements, W % 8 == 0.  (Regrouping, its inverse for the outputs, and the cls-token concatenation of :211-213.) */
+ * elements.  Any W > 0: 16-byte accesses at W % 8 == 0 (16-byte aligned src, dst, fill), element by element otherwise (element
+ * alignment; route "rows_elem"); the stored bits are copied, nothing is touched at or beyond column W of a row.  (Regrouping, its
+ * inverse for the outputs, and the cls-token concatenation of :211-213.) */
 int meant_gather_rows(const void* src, const int32_t* idx, const void* fill, void* dst, int64_t n, int64_t W, int dtype,
                       void* stream);
 /* The regrouping gather of a packed q|k|v buffer (rows of 3 * H * Dh) with the rotary map applied on the way: row r of dst is
@@ -363,15 +365,37 @@ int meant_attn_cls_fwd(const void* qkv, void* out, int64_t ld_out, float* stats,
 int meant_attn_cls_bwd(const void* qkv, const void* out, int64_t ld_out, const void* dout, int64_t ld_dout,
                        const float* stats, const float* key_mask, void* dqkv, int64_t B, int64_t L, int H, int Dh,
                        float scale, int dtype, void* stream);
+/* the largest L the pair above takes at head dim Dh (backward != 0: meant_attn_cls_bwd's bound, half the forward's); 0 for a
+ * head dim it refuses.  Host arithmetic. */
+int64_t meant_attn_cls_max_len(int Dh, int backward);
+/* The same attention over key segments, for L past those bounds (route "attn_cls_split"): a workgroup per (head, video, segment)
+ * handles ceil(L / nseg) keys, a second kernel merges the segments of a (video, head) in the order 0 ... nseg - 1 (forward:
+ * m = max m_s, l = sum l_s e^(m_s - m), o = sum o_s e^(m_s - m) / l; backward: dq = sum of the segments' partial dq, added to row
+ * 0).  Same contract as the pair above in every other respect -- stats format (a forward of one pair may be followed by the
+ * backward of the other), masked keys, strided out rows written in [0, H*Dh) only, dqkv ADDED to -- and no atomics or completion
+ * counters: two runs give the same bits.  nseg = 0: the smallest count whose segment fits the LDS bound of the respective
+ * direction; nseg >= 1: taken as given, MEANT_ERR_UNSUPPORTED if a segment does not fit (or nseg > 65535), nseg > L:
+ * MEANT_ERR_ARG.  Dh % 8 == 0, Dh <= 256, B, H <= 65535, L < 2^31; row offsets are 64-bit.  workspace:
+ * meant_attn_cls_split_ws(B, L, H, Dh, nseg) bytes = B*H*nseg*(Dh+2) floats (host arithmetic; nseg = 0 sizes for the backward's
+ * count, which also covers the forward's; 0 for arguments the entries refuse), 16-byte aligned; too small: MEANT_ERR_WORKSPACE. */
+size_t meant_attn_cls_split_ws(int64_t B, int64_t L, int H, int Dh, int nseg);
+int meant_attn_cls_split_fwd(const void* qkv, void* out, int64_t ld_out, float* stats, const float* key_mask, int64_t B,
+                             int64_t L, int H, int Dh, float scale, int nseg, int dtype, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int meant_attn_cls_split_bwd(const void* qkv, const void* out, int64_t ld_out, const void* dout, int64_t ld_dout,
+                             const float* stats, const float* key_mask, void* dqkv, int64_t B, int64_t L, int H, int Dh,
+                             float scale, int nseg, int dtype, void* workspace, size_t workspace_bytes, void* stream);
 
 /* time token shift of the patch tokens of x act [B, 1 + frames*n, d] (PreTokenShift, src/meant/timesformer_pytorch.py:28-53):
  * columns [0, d/3) from the next frame, [d/3, 2d/3) unchanged, [2d/3, 3(d/3)) from the previous frame, zeros beyond the
- * clip's ends; the cls row and any remainder columns pass through.  d % 8 == 0.  transpose != 0: the adjoint (backward).
- * x != y. */
+ * clip's ends; the cls row and any remainder columns pass through.  Any d >= 3: 16-byte accesses at d % 8 == 0, element by
+ * element otherwise (element alignment; route "rows_elem").  transpose != 0: the adjoint (backward).  x != y. */
 int meant_token_shift(const void* x, void* y, int64_t B, int64_t frames, int64_t n, int64_t d, int transpose, int dtype,
                       void* stream);
 /* inverted dropout y = x * keep / (1 - p) (nn.Dropout at :70,:101): counter-based mask from (seed, element index), so the
- * backward is the same call on dy.  n % 8 == 0. */
+ * backward is the same call on dy.  Any n > 0: element i takes part i & 7 of the draw for i >> 3, so the first 8 * (n / 8)
+ * outputs are those of the call on that prefix; at n % 8 != 0 (route "rows_elem") the full groups of 8 take 16-byte accesses where
+ * x and y are 16-byte aligned, everything else goes element by element (element alignment). */
 int meant_dropout(const void* x, void* y, int64_t n, float p, uint64_t seed, int dtype, void* stream);
 
 /* ---- temporal attention core ----------------------------- meant/temporal.py:44-56
@@ -423,7 +447,8 @@ int meant_gelu_bwd(const void* dy, const void* pre, void* dx, int64_t n, int dty
 /* dx = dy * y * (1-y) */
 int meant_sigmoid_bwd(const void* dy, const void* y, void* dx, int64_t n, int dtype, void* stream);
 /* GEGLU ---------------------------------------------------- src/meant/timesformer_pytorch.py:60-63
- * h: act [rows, 2w] = [a | g]  ->  y: act [rows, w] = a * gelu(g);   dh = [dy * gelu(g) | dy * a * gelu'(g)] */
+ * h: act [rows, 2w] = [a | g]  ->  y: act [rows, w] = a * gelu(g);   dh = [dy * gelu(g) | dy * a * gelu'(g)].  Any w > 0: 16-byte
+ * accesses at w % 8 == 0, element by element otherwise (element alignment; route "rows_elem"), the same gelu / gelu' evaluation. */
 int meant_geglu_fwd(const void* h, void* y, int64_t rows, int64_t w, int dtype, void* stream);
 int meant_geglu_bwd(const void* h, const void* dy, void* dh, int64_t rows, int64_t w, int dtype, void* stream);
 /* y = a + b */

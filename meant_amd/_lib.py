@@ -64,6 +64,10 @@ SIGNATURES = {
     "meant_group_scatter": (_i, [_p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i, _p]),
     "meant_attn_cls_fwd": (_i, [_p, _p, _i64, _p, _p, _i64, _i64, _i, _i, _f, _i, _p]),
     "meant_attn_cls_bwd": (_i, [_p, _p, _i64, _p, _i64, _p, _p, _p, _i64, _i64, _i, _i, _f, _i, _p]),
+    "meant_attn_cls_max_len": (_i64, [_i, _i]),
+    "meant_attn_cls_split_ws": (_sz, [_i64, _i64, _i, _i, _i]),
+    "meant_attn_cls_split_fwd": (_i, [_p, _p, _i64, _p, _p, _i64, _i64, _i, _i, _f, _i, _i, _p, _sz, _p]),
+    "meant_attn_cls_split_bwd": (_i, [_p, _p, _i64, _p, _i64, _p, _p, _p, _i64, _i64, _i, _i, _f, _i, _i, _p, _sz, _p]),
     "meant_token_shift": (_i, [_p, _p, _i64, _i64, _i64, _i64, _i, _i, _p]),
     "meant_dropout": (_i, [_p, _p, _i64, _f, _u64, _i, _p]),
     "meant_temporal_attn_fwd": (_i, [_p, _p, _p, _p, _i64, _i, _i, _i, _f, _i, _p]),

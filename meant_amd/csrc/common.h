@@ -60,12 +60,14 @@ enum meant_route_id {
   ROUTE_ATTN_BWD_D128, ROUTE_ATTN_BWD_D96, ROUTE_ATTN_GENERIC, ROUTE_ATTN_CLS, ROUTE_ATTN_SHORT, ROUTE_NT_OVERLAP, ROUTE_ATTN_BWD1,
   ROUTE_ATTN_FWD_D160, ROUTE_ATTN_FWD_D192, ROUTE_ATTN_FWD_D256, ROUTE_ATTN_BWD_D160, ROUTE_ATTN_BWD_D192, ROUTE_ATTN_BWD_D256, ROUTE_TEMPORAL_LONG,
   ROUTE_EMB_SEG, ROUTE_SORT_IDS, ROUTE_NT128K, ROUTE_NT256K, ROUTE_SELECT_ROWS, ROUTE_ROTARY_QK, ROUTE_ROTARY_PAIRS, ROUTE_NT_ROT,
-  ROUTE_METRICS_ROWS, ROUTE_METRICS_WAVE, ROUTE_METRICS_LABELS, ROUTE_TN256_ROWS,
+  ROUTE_METRICS_ROWS, ROUTE_METRICS_WAVE, ROUTE_METRICS_LABELS, ROUTE_TN256_ROWS, ROUTE_ATTN_CLS_SPLIT, ROUTE_ROWS_ELEM,
   MEANT_ROUTE_COUNT
 };
 void meant_route_hit(int route);
 
 static inline bool meant_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// aligned to one element of the activation type (4 bytes fp32, 2 bytes bf16): what the element-access kernels need
+static inline bool meant_aligned_elem(const void* p, int dtype) { return (reinterpret_cast<uintptr_t>(p) & (dtype == MEANT_F32 ? 3 : 1)) == 0; }
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // ---- storage-type helpers (math is always float) ------------------------------------------------

@@ -142,6 +142,8 @@ const char* const k_routes[MEANT_ROUTE_COUNT] = {
     "nt_rot",                       // every bf16 NT GEMM launched with the rotary epilogue, whichever nt* route it takes
     "metrics_rows", "metrics_wave", "metrics_labels",   // meant_metrics_update by form (C <= 16 / above); every meant_metrics_update_labels launch
     "tn256_rows",                   // the 256 x 256 dW kernel reducing over a list of live 64-row blocks (meant_linear_bwd_dw_rows)
+    "attn_cls_split",               // every meant_attn_cls_split_fwd / _bwd call (the cls query's attention over key segments)
+    "rows_elem",                    // the element-access forms of gather_rows, token_shift, geglu_fwd / _bwd and dropout (rows off the 16-byte grid)
 };
 std::atomic<long long> g_route[MEANT_ROUTE_COUNT];
 }  // namespace

@@ -9,6 +9,9 @@
 //                              tile fits; scores by a thread per key, probabilities in LDS, the weighted sum by a thread per
 //                              head column.  The backward ADDS its dK / dV (every row) and dQ (row 0) to the gradient buffer
 //                              the regrouped attention's backward has already filled -- no separate tensor, no add pass.
+//   * meant_attn_cls_split_fwd/bwd -- the same for videos whose scores do not fit one workgroup's LDS: a workgroup per (video,
+//                              head, key segment), a small merge kernel in segment order; no atomics.
+//   * the element forms of gather_rows, token_shift and dropout for rows off the 16-byte grid (a TimeSformer at dim = 99 or 100).
 // All HBM / latency bound and small next to the GEMMs (a few hundred MB per layer).
 #include "common.h"
 
@@ -33,6 +36,21 @@ __global__ __launch_bounds__(DIV_THREADS) void gather_rows_kernel(const T* __res
       }
       store8s<T>(dst + r * W + ch * 8, v);
     }
+  }
+}
+
+// The same gather by element access, for rows that are only element-aligned (W % 8 != 0: the cls concatenation of a TimeSformer at
+// dim = 99 or 100): a wave per row, a lane per column, the stored bits copied.  Nothing is touched at or beyond column W of a row.
+template <typename T>
+__global__ __launch_bounds__(DIV_THREADS) void gather_rows_elem_kernel(const T* __restrict__ src, const int* __restrict__ idx, const T* __restrict__ fill,
+                                                                        T* __restrict__ dst, int64_t n, int W) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < n; r += (int64_t)gridDim.x * 4) {
+    const int id = idx[r];
+    const T* s = id >= 0 ? src + (int64_t)id * W : fill;
+    const bool live = id >= 0 || (id == -2 && fill);
+    T* d = dst + r * W;
+    for (int c = lane; c < W; c += 64) d[c] = live ? s[c] : from_f<T>(0.f);
   }
 }
 
@@ -260,6 +278,175 @@ __global__ __launch_bounds__(DIV_THREADS) void attn_cls_bwd_kernel(const T* __re
   }
 }
 
+// ---- cls query attention over key segments ------------------------------------------------------
+// The same attention for videos whose scores do not fit one workgroup's LDS: block = (head h, video b, segment z) scores the
+// SL = ceil(L / nseg) keys [z SL, min(L, (z + 1) SL)) only -- LDS p[SL] (+ ds[SL] in the backward) -- and a second, small kernel
+// combines the segments of a (video, head) in the order 0 ... nseg - 1.  No atomics and no completion counters: the two kernels
+// are ordered by the stream, every sum has a fixed order, two runs give the same bits.
+// workspace: float [B, H, nseg, Dh + 2] -- forward (local max, local sum of exp, unnormalised o[Dh]) per segment, backward the
+// segment's partial dQ[Dh] in the same slots.  A segment past the last key (ceil rounding: L = 5 in 4 segments of 2) has no key:
+// max -inf, sum 0, zeros; exp(-inf - m) = 0 drops it from the merge.
+template <typename T>
+__global__ __launch_bounds__(DIV_THREADS) void attn_cls_split_fwd_kernel(const T* __restrict__ qkv, float* __restrict__ ws,
+                                                                          const float* __restrict__ key_mask, int L, int H, int Dh, float scale, int SL) {
+  extern __shared__ float sm[];
+  float* p = sm;                                     // [SL]
+  float* red = sm + SL;                              // [4], then [rpi][Dh] partial outputs
+  const int h = blockIdx.x, tid = threadIdx.x;
+  const int64_t b = blockIdx.y, j0 = (int64_t)blockIdx.z * SL;
+  const int n = j0 < L ? (int)(L - j0 < SL ? L - j0 : SL) : 0;   // keys of this segment
+  const int64_t D = (int64_t)H * Dh, ld = 3 * D;
+  const T* base = qkv + b * L * ld + h * Dh;        // the cls row: the query
+  const T* seg = base + j0 * ld;                     // key j0 (read only where n > 0)
+  float mx = -INFINITY;
+  for (int j = tid; j < n; j += DIV_THREADS) {
+    const T* kr = seg + (int64_t)j * ld + D;
+    float s = 0.f;
+    for (int c = 0; c < Dh; c += 8) {
+      const Vec8<T> kv = load8<T>(kr + c), qv = load8<T>(base + c);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) s += kv.get(k) * qv.get(k);
+    }
+    s = cls_mask_score(s * scale, key_mask, b * L + j0 + j);
+    p[j] = s;
+    mx = fmaxf(mx, s);
+  }
+  mx = block_reduce(mx, red, true);
+  float sum = 0.f;
+  for (int j = tid; j < n; j += DIV_THREADS) {
+    const float e = __expf(p[j] - mx);
+    p[j] = e;
+    sum += e;
+  }
+  sum = block_reduce(sum, red, false);                // (its barriers also publish p[])
+  const int nc = Dh >> 3, rpi = DIV_THREADS / nc;     // row groups as in attn_cls_fwd_kernel
+  const int c8 = (tid % nc) * 8, rg = tid / nc;
+  float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int j = rg; rg < rpi && j < n; j += rpi) {
+    const Vec8<T> vv = load8<T>(seg + (int64_t)j * ld + 2 * D + c8);
+    const float pj = p[j];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) acc[k] += pj * vv.get(k);
+  }
+  float* part = red + 4;                             // [rpi][Dh]
+  if (rg < rpi) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) part[rg * Dh + c8 + k] = acc[k];
+  }
+  __syncthreads();
+  float* w = ws + ((b * H + h) * gridDim.z + blockIdx.z) * (Dh + 2);
+  if (tid == 0) { w[0] = mx; w[1] = sum; }
+  if (tid < Dh) {
+    float o = 0.f;
+    for (int r = 0; r < rpi; ++r) o += part[r * Dh + tid];
+    w[2 + tid] = o;                                  // unnormalised: the merge divides by the combined sum
+  }
+}
+
+// m = max_s m_s, l = sum_s l_s e^(m_s - m), o = sum_s o_s e^(m_s - m) / l, segments in order; block = (head, video), a thread per column
+template <typename T>
+__global__ __launch_bounds__(DIV_THREADS) void attn_cls_merge_fwd_kernel(const float* __restrict__ ws, T* __restrict__ out, int64_t ld_out,
+                                                                          float* __restrict__ stats, int H, int Dh, int nseg) {
+  const int h = blockIdx.x, tid = threadIdx.x, st = Dh + 2;
+  const int64_t b = blockIdx.y;
+  const float* w = ws + (b * H + h) * nseg * st;
+  float m = -INFINITY;
+  for (int s = 0; s < nseg; ++s) m = fmaxf(m, w[(int64_t)s * st]);
+  float l = 0.f, o = 0.f;
+  for (int s = 0; s < nseg; ++s) {
+    const float* ww = w + (int64_t)s * st;
+    const float f = __expf(ww[0] - m);
+    l += ww[1] * f;
+    if (tid < Dh) o += ww[2 + tid] * f;
+  }
+  if (tid < Dh) out[b * ld_out + h * Dh + tid] = from_f<T>(o / l);
+  if (tid == 0) { stats[(b * H + h) * 2] = m; stats[(b * H + h) * 2 + 1] = __logf(l); }
+}
+
+// stats (max, log sum) of the whole row make the segments independent: p and ds of the segment's own keys, read-modify-write of
+// its own dK / dV rows (rows disjoint across segments, columns across heads), its partial dQ to the workspace
+template <typename T>
+__global__ __launch_bounds__(DIV_THREADS) void attn_cls_split_bwd_kernel(const T* __restrict__ qkv, const T* __restrict__ out, int64_t ld_out,
+                                                                          const T* __restrict__ dout, int64_t ld_dout, const float* __restrict__ stats,
+                                                                          const float* __restrict__ key_mask, T* __restrict__ dqkv, float* __restrict__ ws,
+                                                                          int L, int H, int Dh, float scale, int SL) {
+  extern __shared__ float sm[];
+  float* p = sm;                                     // [SL]
+  float* ds = sm + SL;                               // [SL]
+  float* red = ds + SL;                              // [4], then [rpi][Dh] partial dQ
+  const int h = blockIdx.x, tid = threadIdx.x;
+  const int64_t b = blockIdx.y, j0 = (int64_t)blockIdx.z * SL;
+  const int n = j0 < L ? (int)(L - j0 < SL ? L - j0 : SL) : 0;
+  const int64_t D = (int64_t)H * Dh, ld = 3 * D;
+  const T* base = qkv + b * L * ld + h * Dh;
+  const T* seg = base + j0 * ld;
+  T* dseg = dqkv + b * L * ld + h * Dh + j0 * ld;
+  const T* dor = dout + b * ld_dout + h * Dh;
+  const T* orow = out + b * ld_out + h * Dh;
+  const float mx = stats[(b * H + h) * 2], lsum = stats[(b * H + h) * 2 + 1];
+  float delta = 0.f;                                  // dout . out
+  for (int c = tid; c < Dh; c += DIV_THREADS) delta += to_f(dor[c]) * to_f(orow[c]);
+  delta = block_reduce(delta, red, false);
+  for (int j = tid; j < n; j += DIV_THREADS) {
+    const T* kr = seg + (int64_t)j * ld + D;
+    const T* vr = seg + (int64_t)j * ld + 2 * D;
+    float s = 0.f, dp = 0.f;
+    for (int c = 0; c < Dh; c += 8) {
+      const Vec8<T> kv = load8<T>(kr + c), qv = load8<T>(base + c), vv = load8<T>(vr + c), dv = load8<T>(dor + c);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) { s += kv.get(k) * qv.get(k); dp += vv.get(k) * dv.get(k); }
+    }
+    const bool dead = key_mask && key_mask[b * L + j0 + j] == 0.f;
+    s = cls_mask_score(s * scale, key_mask, b * L + j0 + j);
+    const float pj = __expf((s - mx) - lsum);
+    p[j] = pj;
+    ds[j] = dead ? 0.f : pj * (dp - delta) * scale;  // d score_j * scale; a masked score is a constant
+  }
+  __syncthreads();
+  const int nc = Dh >> 3, rpi = DIV_THREADS / nc;
+  const int c8 = (tid % nc) * 8, rg = tid / nc;
+  const Vec8<T> qv = load8<T>(base + c8), dov = load8<T>(dor + c8);
+  float dq[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int j = rg; rg < rpi && j < n; j += rpi) {
+    const int64_t o = (int64_t)j * ld;
+    const Vec8<T> kv = load8<T>(seg + o + D + c8);
+    Vec8<T> gk = load8<T>(dseg + o + D + c8), gv = load8<T>(dseg + o + 2 * D + c8);
+    const float dsj = ds[j], pj = p[j];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      dq[k] += dsj * kv.get(k);
+      gk.set(k, gk.get(k) + dsj * qv.get(k));
+      gv.set(k, gv.get(k) + pj * dov.get(k));
+    }
+    store8<T>(dseg + o + D + c8, gk);
+    store8<T>(dseg + o + 2 * D + c8, gv);
+  }
+  float* part = red + 4;                             // [rpi][Dh]
+  if (rg < rpi) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) part[rg * Dh + c8 + k] = dq[k];
+  }
+  __syncthreads();
+  if (tid < Dh) {
+    float o = 0.f;
+    for (int r = 0; r < rpi; ++r) o += part[r * Dh + tid];
+    ws[((b * H + h) * gridDim.z + blockIdx.z) * (Dh + 2) + tid] = o;
+  }
+}
+
+// dQ = sum_s dQ_s in segment order, added to the q block of the cls row
+template <typename T>
+__global__ __launch_bounds__(DIV_THREADS) void attn_cls_merge_bwd_kernel(const float* __restrict__ ws, T* __restrict__ dqkv, int L, int H, int Dh, int nseg) {
+  const int h = blockIdx.x, tid = threadIdx.x, st = Dh + 2;
+  const int64_t b = blockIdx.y;
+  if (tid >= Dh) return;
+  const float* w = ws + (b * H + h) * nseg * st + tid;
+  float o = 0.f;
+  for (int s = 0; s < nseg; ++s) o += w[(int64_t)s * st];
+  T* d = dqkv + b * L * (3 * (int64_t)H * Dh) + h * Dh + tid;
+  *d = from_f<T>(to_f(*d) + o);
+}
+
 // time token shift (src/meant/timesformer_pytorch.py:28-53): of the patch tokens [b, f, n, d] the first d/3 columns come from
 // the NEXT frame, the second third stays, the third third comes from the PREVIOUS frame (zeros beyond the clip's ends); the
 // cls row and the columns past 3 * (d / 3) pass through.  transpose = the adjoint (the two shifts swap).  A thread moves 8
@@ -321,6 +508,50 @@ __global__ __launch_bounds__(DIV_THREADS) void dropout_kernel(const T* __restric
   }
 }
 
+// The shift by element access, for d % 8 != 0 (rows only element-aligned): a thread moves up to 8 consecutive columns of one row,
+// each guarded by c < d and each finding its own source frame; the stored bits are copied.
+template <typename T>
+__global__ __launch_bounds__(DIV_THREADS) void token_shift_elem_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t B, int f, int n, int d,
+                                                                        int chunk, int transpose) {
+  const int nch = (d + 7) >> 3;
+  const int64_t L = 1 + (int64_t)f * n, total = B * L * nch;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int c0 = (int)(i % nch) * 8;
+    const int64_t row = i / nch, b = row / L, t = row - b * L;
+    const int fr = t > 0 ? (int)((t - 1) / n) : 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int col = c0 + k;
+      if (col >= d) break;
+      const int sh = t > 0 ? shift_of(col, chunk, transpose) : 0, fi = fr + sh;
+      y[row * d + col] = fi < 0 || fi >= f ? from_f<T>(0.f) : x[(row + (int64_t)sh * n) * d + col];
+    }
+  }
+}
+
+// dropout at any n: element i takes part i & 7 of the draw for i >> 3, as dropout_kernel and the norm kernels at odd widths.  vec:
+// both bases 16-byte aligned -- full groups of 8 go through the 16-byte path (the arithmetic and bits of dropout_kernel), the
+// last, partial group element by element; otherwise every group goes element by element.
+template <typename T>
+__global__ __launch_bounds__(DIV_THREADS) void dropout_elem_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t n, float p, uint64_t seed, int vec) {
+  const int64_t n8 = (n + 7) >> 3;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x) {
+    float km[8];
+    keep_scale8(p, seed, (uint64_t)i * 8, km);
+    if (vec && i * 8 + 8 <= n) {
+      const Vec8<T> v = load8<T>(x + i * 8);
+      Vec8<T> o;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) o.set(k, v.get(k) * km[k]);
+      store8<T>(y + i * 8, o);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (i * 8 + k < n) y[i * 8 + k] = from_f<T>(to_f(x[i * 8 + k]) * km[k]);
+    }
+  }
+}
+
 inline int rows_blocks(int64_t n) {
   int64_t b = ceil_div(n, 4);
   return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
@@ -331,7 +562,15 @@ inline int rows_blocks(int64_t n) {
 #define DIV_REQ(cond, ...) MEANT_REQUIRE(cond, MEANT_ERR_ARG, __VA_ARGS__)
 
 extern "C" int meant_gather_rows(const void* src, const int32_t* idx, const void* fill, void* dst, int64_t n, int64_t W, int dtype, void* stream) {
-  DIV_REQ(src && idx && dst && n > 0 && W > 0 && W % 8 == 0 && W < (1LL << 30), "gather_rows: bad argument (W must be a multiple of 8)");
+  DIV_REQ(src && idx && dst && n > 0 && W > 0 && W < (1LL << 30), "gather_rows: bad argument");
+  if (W % 8) {                                       // rows off the 16-byte grid: element access, element alignment
+    DIV_REQ(meant_aligned_elem(src, dtype) && meant_aligned_elem(dst, dtype) && (!fill || meant_aligned_elem(fill, dtype)), "gather_rows: element alignment");
+    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(gather_rows_elem_kernel<T>, dim3(rows_blocks(n)), dim3(DIV_THREADS), 0, (hipStream_t)stream, (const T*)src,
+                                                idx, (const T*)fill, (T*)dst, n, (int)W));
+    MEANT_LAUNCH_CHECK("gather_rows");
+    meant_route_hit(ROUTE_ROWS_ELEM);
+    return MEANT_OK;
+  }
   DIV_REQ(meant_aligned16(src) && meant_aligned16(dst) && (!fill || meant_aligned16(fill)), "gather_rows: 16-byte alignment");
   DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(gather_rows_kernel<T>, dim3(rows_blocks(n)), dim3(DIV_THREADS), 0, (hipStream_t)stream, (const T*)src, idx,
                                               (const T*)fill, (T*)dst, n, (int)W));
@@ -414,9 +653,104 @@ extern "C" int meant_attn_cls_bwd(const void* qkv, const void* out, int64_t ld_o
   return MEANT_OK;
 }
 
+// ---- the same over key segments -----------------------------------------------------------------
+// the longest key list one workgroup holds: (arrays * L + 4 + rpi * Dh) floats within cls_check's budget; 0: head dim not taken
+static int64_t cls_max_len(int Dh, int arrays) {
+  if (Dh <= 0 || Dh > 256 || Dh % 8) return 0;
+  const int64_t rpi = DIV_THREADS / (Dh / 8);
+  return ((160 * 1024 - 1024) / (int64_t)sizeof(float) - 4 - rpi * Dh) / arrays;
+}
+
+extern "C" int64_t meant_attn_cls_max_len(int Dh, int backward) { return cls_max_len(Dh, backward ? 2 : 1); }
+
+// nseg_in = 0: the smallest count whose segment fits; >= 1: as given (refused if a segment does not fit)
+static int cls_split_plan(const char* name, int64_t B, int64_t L, int H, int Dh, int nseg_in, int arrays, int& nseg, int& SL, size_t& lds) {
+  MEANT_REQUIRE(L > 0 && L < (1LL << 31) && nseg_in >= 0 && nseg_in <= L, MEANT_ERR_ARG, "%s: L=%lld, nseg=%d (0 <= nseg <= L < 2^31)", name,
+                (long long)L, nseg_in);
+  int rc = cls_check(name, B, 1, H, Dh, lds, arrays);                    // B, H, Dh
+  if (rc) return rc;
+  const int64_t ns = nseg_in ? nseg_in : ceil_div(L, cls_max_len(Dh, arrays));
+  MEANT_REQUIRE(ns <= 65535, MEANT_ERR_UNSUPPORTED, "%s: %lld key segments (grid bound 65535)", name, (long long)ns);
+  nseg = (int)ns;
+  SL = (int)ceil_div(L, ns);
+  return cls_check(name, B, SL, H, Dh, lds, arrays);                     // a segment must fit
+}
+
+static size_t cls_split_bytes(int64_t B, int H, int Dh, int nseg) { return (size_t)B * H * nseg * (Dh + 2) * sizeof(float); }
+
+extern "C" size_t meant_attn_cls_split_ws(int64_t B, int64_t L, int H, int Dh, int nseg) {
+  if (B <= 0 || L <= 0 || H <= 0 || nseg < 0 || nseg > L || cls_max_len(Dh, 2) == 0) return 0;
+  const int64_t ns = nseg ? nseg : ceil_div(L, cls_max_len(Dh, 2));      // 0: the backward's count, the larger of the two
+  return cls_split_bytes(B, H, Dh, (int)ns);
+}
+
+extern "C" int meant_attn_cls_split_fwd(const void* qkv, void* out, int64_t ld_out, float* stats, const float* key_mask, int64_t B, int64_t L, int H,
+                                        int Dh, float scale, int nseg, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  DIV_REQ(qkv && out && stats && workspace && ld_out >= (int64_t)H * Dh && meant_aligned16(qkv) && meant_aligned16(workspace),
+          "attn_cls_split_fwd: bad argument");
+  DIV_REQ(dtype == MEANT_F32 || dtype == MEANT_BF16, "attn_cls_split_fwd: unknown dtype");
+  size_t lds;
+  int ns, SL;
+  int rc = cls_split_plan("attn_cls_split_fwd", B, L, H, Dh, nseg, 1, ns, SL, lds);
+  if (rc) return rc;
+  MEANT_REQUIRE(workspace_bytes >= cls_split_bytes(B, H, Dh, ns), MEANT_ERR_WORKSPACE, "attn_cls_split_fwd: workspace of %zu bytes, %zu needed",
+                workspace_bytes, cls_split_bytes(B, H, Dh, ns));
+  meant_route_hit(ROUTE_ATTN_CLS_SPLIT);
+  const dim3 grid((unsigned)H, (unsigned)B, (unsigned)ns), mgrid((unsigned)H, (unsigned)B), mblock((unsigned)ceil_div(Dh, 64) * 64);
+#define LAUNCH_CLS_SF(T)                                                                                                             \
+  {                                                                                                                                  \
+    MEANT_RAISE_LDS(attn_cls_split_fwd_kernel<T>, lds);                                                                              \
+    hipLaunchKernelGGL(attn_cls_split_fwd_kernel<T>, grid, dim3(DIV_THREADS), lds, (hipStream_t)stream, (const T*)qkv, (float*)workspace, key_mask, \
+                       (int)L, H, Dh, scale, SL);                                                                                    \
+    hipLaunchKernelGGL(attn_cls_merge_fwd_kernel<T>, mgrid, mblock, 0, (hipStream_t)stream, (const float*)workspace, (T*)out, ld_out, stats, H, Dh, ns); \
+  }
+  if (dtype == MEANT_F32) LAUNCH_CLS_SF(float) else LAUNCH_CLS_SF(bf16)
+#undef LAUNCH_CLS_SF
+  MEANT_LAUNCH_CHECK("attn_cls_split_fwd");
+  return MEANT_OK;
+}
+
+extern "C" int meant_attn_cls_split_bwd(const void* qkv, const void* out, int64_t ld_out, const void* dout, int64_t ld_dout, const float* stats,
+                                        const float* key_mask, void* dqkv, int64_t B, int64_t L, int H, int Dh, float scale, int nseg, int dtype,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+  DIV_REQ(qkv && out && dout && stats && dqkv && workspace && ld_out >= (int64_t)H * Dh && ld_dout >= (int64_t)H * Dh && ld_dout % 8 == 0 &&
+              meant_aligned16(qkv) && meant_aligned16(dout) && meant_aligned16(dqkv) && meant_aligned16(workspace),
+          "attn_cls_split_bwd: bad argument (ld_dout must be a multiple of 8)");
+  DIV_REQ(dtype == MEANT_F32 || dtype == MEANT_BF16, "attn_cls_split_bwd: unknown dtype");
+  size_t lds;
+  int ns, SL;
+  int rc = cls_split_plan("attn_cls_split_bwd", B, L, H, Dh, nseg, 2, ns, SL, lds);
+  if (rc) return rc;
+  MEANT_REQUIRE(workspace_bytes >= cls_split_bytes(B, H, Dh, ns), MEANT_ERR_WORKSPACE, "attn_cls_split_bwd: workspace of %zu bytes, %zu needed",
+                workspace_bytes, cls_split_bytes(B, H, Dh, ns));
+  meant_route_hit(ROUTE_ATTN_CLS_SPLIT);
+  const dim3 grid((unsigned)H, (unsigned)B, (unsigned)ns), mgrid((unsigned)H, (unsigned)B), mblock((unsigned)ceil_div(Dh, 64) * 64);
+#define LAUNCH_CLS_SB(T)                                                                                                             \
+  {                                                                                                                                  \
+    MEANT_RAISE_LDS(attn_cls_split_bwd_kernel<T>, lds);                                                                              \
+    hipLaunchKernelGGL(attn_cls_split_bwd_kernel<T>, grid, dim3(DIV_THREADS), lds, (hipStream_t)stream, (const T*)qkv, (const T*)out, ld_out, \
+                       (const T*)dout, ld_dout, stats, key_mask, (T*)dqkv, (float*)workspace, (int)L, H, Dh, scale, SL);             \
+    hipLaunchKernelGGL(attn_cls_merge_bwd_kernel<T>, mgrid, mblock, 0, (hipStream_t)stream, (const float*)workspace, (T*)dqkv, (int)L, H, Dh, ns); \
+  }
+  if (dtype == MEANT_F32) LAUNCH_CLS_SB(float) else LAUNCH_CLS_SB(bf16)
+#undef LAUNCH_CLS_SB
+  MEANT_LAUNCH_CHECK("attn_cls_split_bwd");
+  return MEANT_OK;
+}
+
 extern "C" int meant_token_shift(const void* x, void* y, int64_t B, int64_t frames, int64_t n, int64_t d, int transpose, int dtype, void* stream) {
-  DIV_REQ(x && y && x != y && B > 0 && frames > 0 && n > 0 && d >= 8 && d % 8 == 0 && d < (1LL << 30) && frames * n < (1LL << 30),
-          "token_shift: bad argument (d must be a positive multiple of 8)");
+  DIV_REQ(x && y && x != y && B > 0 && frames > 0 && n > 0 && d >= 3 && d < (1LL << 30) && frames * n < (1LL << 30),
+          "token_shift: bad argument (d >= 3)");
+  if (d % 8) {                                       // rows off the 16-byte grid: element access, element alignment
+    DIV_REQ(meant_aligned_elem(x, dtype) && meant_aligned_elem(y, dtype), "token_shift: element alignment");
+    int64_t nbe = ceil_div(B * (1 + frames * n) * ceil_div(d, 8), DIV_THREADS);
+    if (nbe > 8192) nbe = 8192;
+    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(token_shift_elem_kernel<T>, dim3((unsigned)nbe), dim3(DIV_THREADS), 0, (hipStream_t)stream, (const T*)x,
+                                                (T*)y, B, (int)frames, (int)n, (int)d, (int)(d / 3), transpose));
+    MEANT_LAUNCH_CHECK("token_shift");
+    meant_route_hit(ROUTE_ROWS_ELEM);
+    return MEANT_OK;
+  }
   DIV_REQ(meant_aligned16(x) && meant_aligned16(y), "token_shift: 16-byte alignment");
   const int64_t total = B * (1 + frames * n) * (d / 8);
   int64_t nb = ceil_div(total, DIV_THREADS);
@@ -428,7 +762,18 @@ extern "C" int meant_token_shift(const void* x, void* y, int64_t B, int64_t fram
 }
 
 extern "C" int meant_dropout(const void* x, void* y, int64_t n, float p, uint64_t seed, int dtype, void* stream) {
-  DIV_REQ(x && y && n > 0 && n % 8 == 0 && p >= 0.f && p < 1.f, "dropout: bad argument (n must be a multiple of 8, 0 <= p < 1)");
+  DIV_REQ(x && y && n > 0 && p >= 0.f && p < 1.f, "dropout: bad argument (n > 0, 0 <= p < 1)");
+  if (n % 8) {                                       // a last, partial group of 8: 16-byte body + element tail, or all by element
+    DIV_REQ(meant_aligned_elem(x, dtype) && meant_aligned_elem(y, dtype), "dropout: element alignment");
+    const int vec = meant_aligned16(x) && meant_aligned16(y);
+    int64_t nbe = ceil_div(ceil_div(n, 8), DIV_THREADS);
+    if (nbe > 8192) nbe = 8192;
+    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(dropout_elem_kernel<T>, dim3((unsigned)nbe), dim3(DIV_THREADS), 0, (hipStream_t)stream, (const T*)x, (T*)y,
+                                                n, p, seed, vec));
+    MEANT_LAUNCH_CHECK("dropout");
+    meant_route_hit(ROUTE_ROWS_ELEM);
+    return MEANT_OK;
+  }
   DIV_REQ(meant_aligned16(x) && meant_aligned16(y), "dropout: 16-byte alignment");
   int64_t nb = ceil_div(n / 8, DIV_THREADS);
   if (nb > 8192) nb = 8192;

@@ -300,7 +300,7 @@ __global__ __launch_bounds__(EW_THREADS) void patchify_raw_kernel(const TI* __re
 
 // ------------------------------------------------------------------------------------------------
 // GEGLU (src/meant/timesformer_pytorch.py:60-63): h = [a | g] of width 2w per row -> y = a * gelu(g) of width w;
-// backward: dh = [dy * gelu(g) | dy * a * gelu'(g)].  One pass each, 16-byte accesses (w % 8 == 0).
+// backward: dh = [dy * gelu(g) | dy * a * gelu'(g)].  One pass each, 16-byte accesses (w % 8 == 0; other widths: the element forms below).
 template <typename T>
 __global__ __launch_bounds__(EW_THREADS) void geglu_fwd_kernel(const T* __restrict__ h, T* __restrict__ y, int64_t rows, int w) {
   const int cw = w >> 3;
@@ -332,6 +332,46 @@ __global__ __launch_bounds__(EW_THREADS) void geglu_bwd_kernel(const T* __restri
     }
     store8s<T>(dh + r * 2 * w + c, da);
     store8s<T>(dh + r * 2 * w + w + c, dg);
+  }
+}
+
+// The two by element access, for w % 8 != 0 (a TimeSformer at an odd dim: w = 4 dim, rows of h only element-aligned): a thread takes
+// up to 8 consecutive columns of one row, each guarded by c < w; the gelu / gelu' evaluation of the kernels above.
+template <typename T>
+__global__ __launch_bounds__(EW_THREADS) void geglu_fwd_elem_kernel(const T* __restrict__ h, T* __restrict__ y, int64_t rows, int w) {
+  const int cw = (w + 7) >> 3;
+  const int64_t total = rows * cw;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / cw;
+    const int c = (int)(i - r * cw) * 8;
+    const T* a = h + r * 2 * w + c;
+    const T* g = a + w;
+    T* o = y + r * w + c;
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+      if (c + k < w) o[k] = from_f<T>(to_f(a[k]) * gelu_erf(to_f(g[k])));
+  }
+}
+template <typename T>
+__global__ __launch_bounds__(EW_THREADS) void geglu_bwd_elem_kernel(const T* __restrict__ h, const T* __restrict__ dy, T* __restrict__ dh,
+                                                                     int64_t rows, int w) {
+  const int cw = (w + 7) >> 3;
+  const int64_t total = rows * cw;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / cw;
+    const int c = (int)(i - r * cw) * 8;
+    const T* a = h + r * 2 * w + c;
+    const T* g = a + w;
+    const T* d = dy + r * w + c;
+    T* da = dh + r * 2 * w + c;
+    T* dg = da + w;
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+      if (c + k < w) {
+        const float gk = to_f(g[k]), dk = to_f(d[k]);
+        da[k] = from_f<T>(dk * gelu_erf(gk));
+        dg[k] = from_f<T>(dk * to_f(a[k]) * gelu_erf_grad(gk));
+      }
   }
 }
 
@@ -512,7 +552,16 @@ extern "C" int meant_add(const void* a, const void* b, void* y, int64_t n, int d
 }
 
 extern "C" int meant_geglu_fwd(const void* h, void* y, int64_t rows, int64_t w, int dtype, void* stream) {
-  EW_REQ(h && y && rows >= 0 && w > 0 && w % 8 == 0 && w < (1LL << 30), "geglu_fwd: bad argument (w must be a multiple of 8)");
+  EW_REQ(h && y && rows >= 0 && w > 0 && w < (1LL << 30), "geglu_fwd: bad argument");
+  if (w % 8) {                                       // rows off the 16-byte grid: element access, element alignment
+    EW_REQ(meant_aligned_elem(h, dtype) && meant_aligned_elem(y, dtype), "geglu_fwd: element alignment");
+    if (rows == 0) return MEANT_OK;
+    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(geglu_fwd_elem_kernel<T>, dim3(ew_blocks(rows * ceil_div(w, 8))), dim3(EW_THREADS), 0, (hipStream_t)stream,
+                                                (const T*)h, (T*)y, rows, (int)w));
+    MEANT_LAUNCH_CHECK("geglu_fwd");
+    meant_route_hit(ROUTE_ROWS_ELEM);
+    return MEANT_OK;
+  }
   EW_REQ(meant_aligned16(h) && meant_aligned16(y), "geglu_fwd: 16-byte alignment");
   if (rows == 0) return MEANT_OK;
   const int64_t total = rows * (w >> 3);
@@ -522,7 +571,16 @@ extern "C" int meant_geglu_fwd(const void* h, void* y, int64_t rows, int64_t w, 
   return MEANT_OK;
 }
 extern "C" int meant_geglu_bwd(const void* h, const void* dy, void* dh, int64_t rows, int64_t w, int dtype, void* stream) {
-  EW_REQ(h && dy && dh && rows >= 0 && w > 0 && w % 8 == 0 && w < (1LL << 30), "geglu_bwd: bad argument (w must be a multiple of 8)");
+  EW_REQ(h && dy && dh && rows >= 0 && w > 0 && w < (1LL << 30), "geglu_bwd: bad argument");
+  if (w % 8) {
+    EW_REQ(meant_aligned_elem(h, dtype) && meant_aligned_elem(dy, dtype) && meant_aligned_elem(dh, dtype), "geglu_bwd: element alignment");
+    if (rows == 0) return MEANT_OK;
+    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(geglu_bwd_elem_kernel<T>, dim3(ew_blocks(rows * ceil_div(w, 8))), dim3(EW_THREADS), 0, (hipStream_t)stream,
+                                                (const T*)h, (const T*)dy, (T*)dh, rows, (int)w));
+    MEANT_LAUNCH_CHECK("geglu_bwd");
+    meant_route_hit(ROUTE_ROWS_ELEM);
+    return MEANT_OK;
+  }
   EW_REQ(meant_aligned16(h) && meant_aligned16(dy) && meant_aligned16(dh), "geglu_bwd: 16-byte alignment");
   if (rows == 0) return MEANT_OK;
   const int64_t total = rows * (w >> 3);

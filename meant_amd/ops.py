@@ -1929,7 +1929,8 @@ class _DividedAttention(torch.autograd.Function):
     (src/meant/timesformer_pytorch.py:108-145), entirely on the HIP path:
       forward : rows regrouped by an index table (meant_gather_rows; the cls row in front of every group) -> rotary in place
                 (identity row for the cls position) -> flash attention core -> rows back to token order by the inverse
-                table -> the cls query's attention over all tokens written into row 0 (meant_attn_cls_fwd);
+                table -> the cls query's attention over all tokens written into row 0 (meant_attn_cls_fwd; past its LDS bound,
+                ~38 k tokens forward and ~19 k backward, meant_attn_cls_split_fwd / _bwd over key segments);
       backward: the same tables in reverse, the attention backward with the rotary adjoint inside, meant_group_scatter
                 (copy of the group rows, sum of the cls rows), and the cls backward ADDING into that buffer.
     qkv [b, L, 3*H*Dh] -> out [b, L, H*Dh].  plan = (index [G, S] int32, idx_in [b*G*S], idx_out [b*L], idx_dog [b*G*S])."""
@@ -1961,7 +1962,13 @@ class _DividedAttention(torch.autograd.Function):
         out = gather_rows(og, idx_out).view(b, L, D)                             # row 0 of every sequence: zeros for now
         stats = torch.empty((b, H, 2), device=qkv.device, dtype=torch.float32)
         cm = _c(cls_mask.float()) if cls_mask is not None else None             # [b, L]
-        check(lib.meant_attn_cls_fwd(_p(q2), _p(out), L * D, _p(stats), _p(cm), b, L, H, Dh, float(scale), dt, _stream()), "attn_cls_fwd")
+        if not 0 < lib.meant_attn_cls_max_len(Dh, 0) < L:                       # (0: a head dim neither takes -- the old entry says so)
+            check(lib.meant_attn_cls_fwd(_p(q2), _p(out), L * D, _p(stats), _p(cm), b, L, H, Dh, float(scale), dt, _stream()), "attn_cls_fwd")
+        else:                                                                   # scores past one workgroup's LDS: over key segments
+            wsb = lib.meant_attn_cls_split_ws(b, L, H, Dh, 0)
+            ws = torch.empty(max(wsb, 16), device=qkv.device, dtype=torch.uint8)
+            check(lib.meant_attn_cls_split_fwd(_p(q2), _p(out), L * D, _p(stats), _p(cm), b, L, H, Dh, float(scale), 0, dt, _p(ws), wsb, _stream()),
+                  "attn_cls_split_fwd")
         ctx.save_for_backward(qkv, grouped, og, lse, km, out, stats, cm)
         ctx.plan, ctx.tables, ctx.meta = plan, tables, (b, L, D, H, Dh, G, S, float(scale))
         return out
@@ -1982,8 +1989,14 @@ class _DividedAttention(torch.autograd.Function):
                                  _p(qa), _p(qb), _p(ka), _p(kb), qa.shape[1] if qa is not None else 0, dt, _p(ws), wsb, _stream()), "attn_bwd")
         dqkv = torch.empty_like(qkv)
         check(lib.meant_group_scatter(_p(dgrouped), _p(index), _p(dqkv), b, L, G, S, 3 * D, dt, _stream()), "group_scatter")
-        check(lib.meant_attn_cls_bwd(_p(qkv), _p(out), L * D, _p(dout), L * D, _p(stats), _p(cm), _p(dqkv), b, L, H, Dh, scale, dt, _stream()),
-              "attn_cls_bwd")
+        if not 0 < lib.meant_attn_cls_max_len(Dh, 1) < L:
+            check(lib.meant_attn_cls_bwd(_p(qkv), _p(out), L * D, _p(dout), L * D, _p(stats), _p(cm), _p(dqkv), b, L, H, Dh, scale, dt, _stream()),
+                  "attn_cls_bwd")
+        else:                                                                   # the stats are shared: either forward may have run
+            wsb = lib.meant_attn_cls_split_ws(b, L, H, Dh, 0)
+            ws = torch.empty(max(wsb, 16), device=dout.device, dtype=torch.uint8)
+            check(lib.meant_attn_cls_split_bwd(_p(qkv), _p(out), L * D, _p(dout), L * D, _p(stats), _p(cm), _p(dqkv), b, L, H, Dh, scale, 0, dt,
+                                               _p(ws), wsb, _stream()), "attn_cls_split_bwd")
         return dqkv, None, None, None, None, None, None
 
 
