@@ -9,38 +9,16 @@ import numpy as np
 import pytest
 import torch
 
+from tests.attn_ref import BF16, LOG2E, _check, _mask, _reference, _rel, _run
 from tests.util import TOL, t, assert_close, assert_grad_close, pair, compare_param_grads
 
-BF16 = 1
 WIDE = (160, 192, 256)
-LOG2E = 1.0 / math.log(2.0)
 
 
 @pytest.fixture(scope="module")
 def dev():
     assert torch.cuda.is_available()
     return torch.device("cuda:0")
-
-
-def _mask(kind, G, S, rs):
-    m = np.ones((G, S), dtype=np.float32)
-    if kind == "suffix":                             # trailing padding of random length per group
-        for g in range(G):
-            p = rs.randint(0, max(1, (3 * S) // 4))
-            if p:
-                m[g, S - p:] = 0
-    elif kind == "holes":                            # padding in the middle: dead tiles between live ones at the longer S
-        for g in range(G):
-            a = rs.randint(1, max(2, S // 2)) if S > 1 else 0
-            b = rs.randint(a, S) if a < S else S
-            m[g, a:b] = 0
-    elif kind == "dead_group":                       # group 0 has no live key at all, the others a random suffix
-        m[0, :] = 0
-        for g in range(1, G):
-            p = rs.randint(0, max(1, S // 2))
-            if p:
-                m[g, S - p:] = 0
-    return None if kind == "none" else m
 
 
 def _rot_tables(S, R, xpos, seed):
@@ -53,104 +31,11 @@ def _rot_tables(S, R, xpos, seed):
     return [torch.from_numpy(a.astype(np.float32)) for a in (c * sc, s * sc, c / sc, s / sc)]
 
 
-def _rotate(x, a, b):
-    """x [G, S, H, Dh] float64, tables [S, R] float64: the rotation of _rot_tables on the first R lanes of every head"""
-    R = a.shape[1]
-    xr = x[..., :R]
-    sw = torch.stack([-xr[..., 1::2], xr[..., 0::2]], dim=-1).reshape(xr.shape)      # (-x[2j+1], x[2j])
-    y = xr * a[None, :, None, :] + sw * b[None, :, None, :]
-    return torch.cat([y, x[..., R:]], dim=-1)
-
-
-def _reference(qkv, do, mask, G, S, H, Dh, scale, causal, tables=None):
-    """float64 on the host: o, the log2-domain pair (m, log2 l) per (g, h, query), and dqkv.  Masked keys get the additive -1e9
-    with the score itself absorbed (as the fp32 sum s - 1e9 does in the reference); the score's gradient passes through unchanged.
-    With tables, qkv holds the rotated q / k and the gradient is taken through the rotation back to the unrotated inputs."""
-    D = H * Dh
-    x = qkv.double().cpu().view(G, S, 3, H, Dh)
-    if tables is not None:
-        qa, qb, ka, kb = (a.double() for a in tables)
-        # unrotated inputs whose rotation equals the bf16 inputs exactly in value: rotate -> attention -> adjoint
-        x0 = x.clone().requires_grad_()
-        q = _rotate(x0[:, :, 0], qa, qb)
-        k = _rotate(x0[:, :, 1], ka, kb)
-        q = q + (x[:, :, 0] - q).detach()
-        k = k + (x[:, :, 1] - k).detach()
-        v = x0[:, :, 2]
-        leaf = x0
-    else:
-        leaf = x.clone().requires_grad_()
-        q, k, v = leaf[:, :, 0], leaf[:, :, 1], leaf[:, :, 2]
-    q, k, v = (a.transpose(1, 2) for a in (q, k, v))                                   # [G, H, S, Dh]
-    s = (q @ k.transpose(-1, -2)) * scale
-    if mask is not None:
-        dead = torch.from_numpy(mask == 0)[:, None, None, :].expand_as(s)
-        s = torch.where(dead, s - s.detach() - 1e9, s)
-    if causal:
-        s = s.masked_fill(torch.ones(S, S, dtype=torch.bool).triu(1), float("-inf"))
-    t2 = s.detach() * LOG2E
-    m = t2.amax(dim=-1)
-    logl = torch.log2(torch.exp2(t2 - m[..., None]).sum(-1))
-    o = (torch.softmax(s, dim=-1) @ v).transpose(1, 2).reshape(G * S, D)
-    o.backward(do.double().cpu())
-    return o.detach(), torch.stack([m, logl], dim=-1), leaf.grad.reshape(G * S, 3 * D)
-
-
-def _run(qkv, do, mask, G, S, H, Dh, scale, causal, tables=None, route_names=None):
-    from meant_amd import _lib
-    from meant_amd._lib import lib, check
-    D, st = H * Dh, torch.cuda.current_stream().cuda_stream
-    o = torch.full((G * S, D), float("nan"), device=qkv.device, dtype=torch.bfloat16)
-    lse = torch.full((G, H, S, 2), float("nan"), device=qkv.device)
-    wsb = lib.meant_attn_ws(G, S, H, Dh, BF16)
-    ws = torch.empty(max(wsb, 16), device=qkv.device, dtype=torch.uint8)
-    km = torch.from_numpy(mask).to(qkv.device) if mask is not None else None
-    mp = km.data_ptr() if km is not None else None
-    tp = [a.to(qkv.device) for a in tables] if tables is not None else None
-    pp = [a.data_ptr() for a in tp] if tp is not None else [None] * 4
-    R = tables[0].shape[1] if tables is not None else 0
-    _lib.route_reset()
-    check(lib.meant_attn_fwd(qkv.data_ptr(), o.data_ptr(), lse.data_ptr(), mp, G, S, H, Dh, scale, causal, BF16, ws.data_ptr(), wsb, st), "attn_fwd")
-    dqkv = torch.full_like(qkv, float("nan"))
-    check(lib.meant_attn_bwd(qkv.data_ptr(), o.data_ptr(), do.data_ptr(), lse.data_ptr(), mp, dqkv.data_ptr(), G, S, H, Dh, scale, causal,
-                             pp[0], pp[1], pp[2], pp[3], R, BF16, ws.data_ptr(), wsb, st), "attn_bwd")
-    torch.cuda.synchronize()
-    routes = {r: _lib.route_count(r) for r in route_names or (f"attn_fwd_d{Dh}", f"attn_bwd_d{Dh}", "attn_generic", "attn_short", "attn_bwd1")}
-    return o, lse, dqkv, routes
-
-
 def _inputs(G, S, H, Dh, seed, dev):
     gen = torch.Generator().manual_seed(seed)
     qkv = torch.randn(G * S, 3 * H * Dh, generator=gen).bfloat16().to(dev)
     do = torch.randn(G * S, H * Dh, generator=gen).bfloat16().to(dev)
     return qkv, do
-
-
-def _rel(a, b):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return (a - b).abs().max().item() / max(b.abs().max().item(), 1e-12)
-
-
-def _check(o, lse, dqkv, ref, H, Dh, what):
-    o_r, st_r, g_r = ref
-    D = H * Dh
-    tol = TOL[torch.bfloat16]
-    assert not torch.isnan(o).any() and not torch.isnan(lse).any() and not torch.isnan(dqkv).any(), f"{what}: unwritten output"
-    assert _rel(o, o_r) <= tol["out"], f"{what}: o {_rel(o, o_r):.2e}"
-    st = lse.double().cpu()
-    em = (st[..., 0] - st_r[..., 0]).abs() - 1e-6 * st_r[..., 0].abs()              # m ~ -1.4e9 on fully padded rows: fp32 resolution
-    assert em.max().item() <= 1e-3, f"{what}: m off by {em.max().item():.2e}"
-    el = (st[..., 1] - st_r[..., 1]).abs().max().item()
-    assert el <= 1e-3, f"{what}: log2 l off by {el:.2e}"
-    # dQ and dK are structurally zero at S = 1 (one key: the softmax is constant): errors are taken against a floor of 1e-3 of the
-    # whole gradient's scale, where both sides hold rounding noise
-    gmax, gnorm = g_r.abs().max().item(), g_r.norm().item()
-    for name, sl in (("dq", slice(0, D)), ("dk", slice(D, 2 * D)), ("dv", slice(2 * D, 3 * D))):
-        a, b = dqkv[:, sl].double().cpu(), g_r[:, sl]
-        e = (a - b).abs().max().item() / max(b.abs().max().item(), 1e-3 * gmax)
-        assert e <= tol["gelem"], f"{what}: {name} {e:.2e}"
-        nb = b.norm().item()
-        assert abs(a.norm().item() - nb) <= tol["gnorm"] * max(nb, 1e-3 * gnorm), f"{what}: {name} norm {a.norm().item()} vs {nb}"
 
 
 def _assert_native(routes, Dh, what):

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests.attn_ref import _cls_grad_given_out, _cls_reference
 from tests.util import DTYPES, IDS, TOL, assert_close, assert_grad_close, compare_param_grads, pair
 
 pytestmark = pytest.mark.gpu
@@ -44,50 +45,6 @@ def cls_max_len(Dh, arrays):
 # ------------------------------------------------------------------------------------------------------------------------------
 # 1. kernels through the C ABI
 # ------------------------------------------------------------------------------------------------------------------------------
-def _cls_reference(qkv, mask, H, Dh, scale, dout):
-    """float64: o = softmax(scale q0 . K^T, masked keys filled with -max) V per (video, head), its stats and d(o . dout)/d qkv"""
-    B, L, _ = qkv.shape
-    D = H * Dh
-    x = qkv.double().clone().requires_grad_(True)
-    q0 = x[:, 0, :D].reshape(B, H, Dh)
-    k = x[:, :, D:2 * D].reshape(B, L, H, Dh)
-    v = x[:, :, 2 * D:].reshape(B, L, H, Dh)
-    s = torch.einsum("bhd,blhd->bhl", q0, k) * scale
-    if mask is not None:
-        s = s.masked_fill(mask[:, None, :] == 0, -torch.finfo(torch.float64).max)
-    mx = s.max(dim=-1).values
-    lse = torch.log(torch.exp(s - mx[..., None]).sum(dim=-1))
-    o = torch.einsum("bhl,blhd->bhd", torch.softmax(s, dim=-1), v).reshape(B, D)
-    (o * dout.double()).sum().backward()
-    return o.detach(), x.grad, mx.detach(), lse.detach()
-
-
-def _cls_grad_given_out(qkv, mask, H, Dh, scale, dout, out):
-    """float64 gradient of the same attention with delta = dout . out taken from the output the backward is handed (the kernel's
-    contract, as in every flash backward): ds = p (dout . v - delta), dq0 = scale ds K, dK = scale ds q0, dV = p dout; a masked
-    key has no score gradient.  With the exact output this is the autograd gradient (checked by the caller)."""
-    B, L, _ = qkv.shape
-    D = H * Dh
-    x = qkv.double()
-    q0 = x[:, 0, :D].reshape(B, H, Dh)
-    k = x[:, :, D:2 * D].reshape(B, L, H, Dh)
-    v = x[:, :, 2 * D:].reshape(B, L, H, Dh)
-    s = torch.einsum("bhd,blhd->bhl", q0, k) * scale
-    if mask is not None:
-        s = s.masked_fill(mask[:, None, :] == 0, -torch.finfo(torch.float64).max)
-    p = torch.softmax(s, dim=-1)
-    do = dout.double().reshape(B, H, Dh)
-    delta = (do * out.double().reshape(B, H, Dh)).sum(dim=-1)
-    ds = p * (torch.einsum("bhd,blhd->bhl", do, v) - delta[..., None])
-    if mask is not None:
-        ds = ds.masked_fill(mask[:, None, :] == 0, 0.0)
-    g = torch.zeros(B, L, 3, D, dtype=torch.float64)
-    g[:, 0, 0] = (scale * torch.einsum("bhl,blhd->bhd", ds, k)).reshape(B, D)
-    g[:, :, 1] = (scale * torch.einsum("bhl,bhd->blhd", ds, q0)).reshape(B, L, D)
-    g[:, :, 2] = torch.einsum("bhl,bhd->blhd", p, do).reshape(B, L, D)
-    return g
-
-
 def _cls_masks(B, L, rs):
     m_rand = torch.from_numpy((rs.rand(B, L) > 0.5).astype("float32"))
     m_key0 = torch.zeros(B, L)
