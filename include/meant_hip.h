@@ -92,8 +92,9 @@ int meant_get_option(const char* name, int* value);
  * "attn_generic", "attn_cls", "attn_cls_split", "rows_elem", "attn_short", "attn_fwd_d160" ... "attn_bwd_d256", "temporal_long" (the temporal attention
  * core's long-lag kernels, forward and backward each count one), "emb_seg" (meant_embedding_bwd_seg), "sort_ids" (meant_sort_ids), "select_rows" (meant_select_rows),
  * "rotary_qk" (every meant_rotary_qk launch), "rotary_pairs" (those of its pair-by-pair kernel: Dh % 8 != 0 or an unaligned base)
- * "nt_rot" (every bf16 NT GEMM launched with the rotary epilogue, on top of the nt* route it takes) and "metrics_rows" /
- * "metrics_wave" / "metrics_labels" (meant_metrics_update by form, every meant_metrics_update_labels launch));
+ * "nt_rot" (every bf16 NT GEMM launched with the rotary epilogue, on top of the nt* route it takes), "metrics_rows" /
+ * "metrics_wave" / "metrics_labels" (meant_metrics_update by form, every meant_metrics_update_labels launch), "score_capture"
+ * (every meant_score_capture launch) and "auroc_rank" (every meant_auroc_rank call with n > 0));
  * -1 for an unknown name.  The names label routes, not kernels: "nt256s" / "nt256s_rot" count launches of the streaming
  * GEMM (whichever kernel implements it), "nt_split" the ragged head + tail split.  Tests use it to prove that a shape
  * reaches the kernel it is meant to exercise. */
@@ -552,6 +553,45 @@ int meant_metrics_update(const void* scores, int64_t ld, int dtype, const int64_
                          int64_t* state, int64_t* confusion, void* stream);
 int meant_metrics_update_labels(const int64_t* pred, const int64_t* target, int64_t B, int C, int64_t ignore_index,
                                 int64_t* state, int64_t* confusion, void* stream);
+/* ---- AUROC (the paper's third number; utils/f1_metrics.py:3 imports torchmetrics' AUROC, train.py:63-65, 103-117) ----
+ * The area under the ROC curve is a rank statistic, so the scores have to be kept: meant_score_capture appends a batch's scores
+ * to device buffers (one launch per step, no host read), meant_auroc_rank sorts one class's scores and counts the statistic
+ * exactly, in integers.
+ * meant_score_capture: scores [B, ld] (MEANT_F32 | MEANT_BF16), columns col0 .. col0 + ncol - 1 are captured; target int64 [B].
+ * keys uint32 [ncol, capacity], class-major; labels int32 [capacity].  Row i of the batch goes to slot offset + i (the caller's
+ * running row count: host arithmetic).  The key is the order-preserving image of the score as float32 (bf16 widened exactly):
+ * -0.0 is made +0.0 first, so that the two tie, then the sign bit is flipped for a non-negative value and all bits for a negative
+ * one: key order = score order, -inf lowest, +inf highest.
+ *   target == ignore_index            : n_ignored += 1
+ *   target otherwise outside [0, C)   : n_invalid += 1 (no address is formed from it; the scores of these two kinds are not read)
+ *   one of the captured columns a NaN : n_nan += 1
+ *     ... and labels[slot] = -1, the row's keys = 0: the row is left out of every statistic
+ *   every other row                   : n_rows += 1, labels[slot] = target, keys[c, slot] = key of column col0 + c
+ * counters int64 [4] = n_rows, n_ignored, n_invalid, n_nan (the order of the tail of the meant_metrics_update state), zeroed once
+ * by the caller, only ever added to: through LDS, then one global integer atomic per non-zero counter and workgroup.
+ * One launch, no workspace; route name "score_capture".
+ * A null pointer, B < 0, C <= 0, ncol <= 0, col0 < 0, col0 + ncol > ld, offset < 0, offset + B > capacity, an unknown dtype or
+ * a misaligned operand: MEANT_ERR_ARG; capacity >= 2^31: MEANT_ERR_UNSUPPORTED; both before any launch.  B == 0: MEANT_OK
+ * without a launch. */
+int meant_score_capture(const void* scores, int64_t ld, int dtype, const int64_t* target, int64_t B, int C, int col0, int ncol,
+                        int64_t ignore_index, uint32_t* keys, int32_t* labels, int64_t capacity, int64_t offset, int64_t* counters,
+                        void* stream);
+/* meant_auroc_rank: keys uint32 [n] (one class's slice), labels int32 [n]; out int64 [3] = (2U, P, N), overwritten.
+ * P = entries with labels == positive, N = the other entries with labels >= 0; entries with labels < 0 take no part.
+ * 2U = sum over (positive i, negative j) of 2 [key_j < key_i] + [key_j == key_i]: the Mann-Whitney statistic with ties at one
+ * half, doubled so that it is an integer.  AUROC = 2U / (2 P N); 2U <= 2 P N < 2^63.
+ * How: the library's radix sort (the one behind meant_sort_ids) over (key, class) pairs by the full 32-bit key, then, with NP / PP
+ * the exclusive counts of negatives / positives before an entry and start(j) the first entry of j's run of equal keys,
+ *   2U = sum over positives of NP[start(j)] + sum over negatives of (P - PP[start(j)])
+ * by tile sums, one scan of the sums and a pass that applies them.  No position comes from an atomic and nothing waits on
+ * another workgroup; every quantity is an integer, so the result depends neither on timing nor on the order of equal keys.  The
+ * only atomics are integer adds into the total 2U, one per workgroup.  Route name "auroc_rank".
+ * A null out, n < 0, (n > 0:) a null keys / labels or a misaligned operand: MEANT_ERR_ARG; n >= 2^31: MEANT_ERR_UNSUPPORTED;
+ * a workspace that is null or smaller than meant_auroc_ws(n) (host arithmetic; 0 for n <= 0 and n >= 2^31), n > 0:
+ * MEANT_ERR_WORKSPACE; all before any launch.  workspace 16-byte aligned.  n == 0: out = (0, 0, 0). */
+size_t meant_auroc_ws(int64_t n);
+int meant_auroc_rank(const uint32_t* keys, const int32_t* labels, int64_t n, int positive, int64_t* out, void* workspace,
+                     size_t workspace_bytes, void* stream);
 /* out_accum[0] += sum(x^2) over a flat float buffer (global gradient norm; caller zeroes the scalar) */
 int meant_sumsq_f32(const float* x, int64_t n, float* out_accum, void* stream);
 /* One AdamW step (torch.optim.AdamW semantics, `step` >= 1 for the bias corrections) over flat float buffers.

@@ -95,7 +95,10 @@ SIGNATURES = {
     "meant_select_rows": (_i, [_p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _sz, _p]),
     "meant_metrics_update": (_i, [_p, _i64, _i, _p, _i64, _i, _i64, _p, _p, _p]),
     "meant_metrics_update_labels": (_i, [_p, _p, _i64, _i, _i64, _p, _p, _p]),
-    "meant_sumsq_f32": (_i, [_p, _i64, _p, _p]),
+    "meant_score_capture": (_i, [_p, _i64, _i, _p, _i64, _i, _i, _i, _i64, _p, _p, _i64, _i64, _p, _p]),
+    "meant_auroc_ws": (_sz, [_i64]),
+    "meant_auroc_rank": (_i, [_p, _p, _i64, _i, _p, _p, _sz, _p]),
+    "meant_sumsq_f32":(_i, [_p, _i64, _p, _p]),
     "meant_adamw_f32": (_i, [_p, _p, _p, _p, _i64, _f, _f, _f, _f, _f, _i64, _p, _f, _f, _p]),
     "meant_embedding_bwd_sorted": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i, _p]),
     "meant_embedding_bwd_sorted_range": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i, _p]),

@@ -144,6 +144,7 @@ const char* const k_routes[MEANT_ROUTE_COUNT] = {
     "tn256_rows",                   // the 256 x 256 dW kernel reducing over a list of live 64-row blocks (meant_linear_bwd_dw_rows)
     "attn_cls_split",               // every meant_attn_cls_split_fwd / _bwd call (the cls query's attention over key segments)
     "rows_elem",                    // the element-access forms of gather_rows, token_shift, geglu_fwd / _bwd and dropout (rows off the 16-byte grid)
+    "score_capture", "auroc_rank",  // every meant_score_capture launch; every meant_auroc_rank call with n > 0
 };
 std::atomic<long long> g_route[MEANT_ROUTE_COUNT];
 }  // namespace

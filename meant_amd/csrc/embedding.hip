@@ -4,9 +4,11 @@
 //   meant_embedding_bwd_sorted[_range]  over ids sorted by the caller, d <= 1024: runs of equal ids summed in registers, atomics only
 //                                       where a run crosses a wave's stretch
 //   meant_sort_ids                      LSD radix sort over 8-bit digits of the ids clamped into [0, V); equal ids keep their row order
+//   sort_u32_launch (internal.h)        the same passes over caller-made 32-bit keys with a 32-bit value each (auroc.hip)
 //   meant_embedding_bwd_seg             dtable[id, :] += sum of the rows of dout that carry id, any d % 8 == 0, no float atomics,
 //                                       bit-reproducible ("Embedding gradient at any width")
 #include "common.h"
+#include "internal.h"
 
 #define EMB_REQ(c, ...) MEANT_REQUIRE(c, MEANT_ERR_ARG, __VA_ARGS__)
 
@@ -26,9 +28,12 @@ __device__ __forceinline__ uint32_t sort_key(int64_t id, int64_t V) {     // cla
   return (uint32_t)(id < 0 ? 0 : (id >= V ? V - 1 : id));
 }
 
-// ghist[p][digit] += occurrences of digit p of every key (all passes); tile_hist[digit][tile] = pass 0's tile counts
-__global__ __launch_bounds__(256) void sort_hist_kernel(const int64_t* __restrict__ ids, int64_t n, int64_t V, int passes,
-                                                         uint32_t* __restrict__ ghist, uint32_t* __restrict__ tile_hist, int64_t ntiles) {
+// ghist[p][digit] += occurrences of digit p of every key (all passes); tile_hist[digit][tile] = pass 0's tile counts.
+// IDS: the keys are the clamped ids, otherwise the caller's `keys`
+template <bool IDS>
+__global__ __launch_bounds__(256) void sort_hist_kernel(const int64_t* __restrict__ ids, const uint32_t* __restrict__ keys, int64_t n, int64_t V,
+                                                         int passes, uint32_t* __restrict__ ghist, uint32_t* __restrict__ tile_hist,
+                                                         int64_t ntiles) {
   __shared__ uint32_t h[4][256];
   const int tid = threadIdx.x;
 #pragma unroll
@@ -38,7 +43,7 @@ __global__ __launch_bounds__(256) void sort_hist_kernel(const int64_t* __restric
   for (int i = 0; i < SORT_TILE / 256; ++i) {
     const int64_t j = base + i * 256 + tid;
     if (j < n) {
-      const uint32_t key = sort_key(ids[j], V);
+      const uint32_t key = IDS ? sort_key(ids[j], V) : keys[j];
       for (int p = 0; p < passes; ++p) atomicAdd(&h[p][(key >> (8 * p)) & 255u], 1u);
     }
   }
@@ -62,28 +67,6 @@ __global__ __launch_bounds__(256) void sort_count_kernel(const uint32_t* __restr
   }
   __syncthreads();
   tile_hist[(int64_t)tid * ntiles + blockIdx.x] = h[tid];
-}
-
-// inclusive sum over the 256 threads of a workgroup; *total = the workgroup's sum.  `wsum` is 4 words of LDS; two barriers.
-__device__ __forceinline__ uint32_t block_scan_incl(uint32_t x, uint32_t* wsum, uint32_t* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  __syncthreads();                                    // the previous call's readers are done with wsum
-  if (lane == 63) wsum[wave] = x;
-  __syncthreads();
-  uint32_t pre = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    const uint32_t s = wsum[w];
-    if (w < wave) pre += s;
-    tot += s;
-  }
-  *total = tot;
-  return x + pre;
 }
 
 // tile_hist[digit][tile] -> first output position of that tile's entries with that digit.  One workgroup per digit: its base is
@@ -175,10 +158,9 @@ int sort_passes(int64_t V) {
 }
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 struct SortWs { size_t ghist, tile_hist, buf[2], total; int nbuf; };
-SortWs sort_ws_layout(int64_t n, int64_t V) {
+SortWs sort_ws_layout(int64_t n, int passes) {
   SortWs w;
   const int64_t ntiles = ceil_div(n, SORT_TILE);
-  const int passes = sort_passes(V);
   w.nbuf = passes - 1 < 2 ? passes - 1 : 2;            // the last pass writes the caller's arrays
   size_t off = 0;
   w.ghist = off; off += align256(4 * 256 * sizeof(uint32_t));
@@ -518,9 +500,51 @@ __global__ __launch_bounds__(256) void embedding_bwd_sorted_kernel(const T* __re
 
 }  // namespace
 
+// The passes of one sort, over the clamped `ids` into the int64 arrays (sorted_ids, order) or over the caller's 32-bit (keys, vals)
+// into (keys_out, vals_out): the same kernels either way, only the first pass's reads and the last pass's writes differ.
+static int sort_run(const int64_t* ids, int64_t V, const uint32_t* keys, const uint32_t* vals, int64_t n, int passes, int64_t* sorted_ids,
+                    int64_t* order, uint32_t* keys_out, uint32_t* vals_out, const SortWs& w, char* base, hipStream_t st, const char* what) {
+  const bool from_ids = ids != nullptr;
+  uint32_t* ghist = (uint32_t*)(base + w.ghist);
+  uint32_t* tile_hist = (uint32_t*)(base + w.tile_hist);
+  uint32_t* bk[2] = {nullptr, nullptr};
+  uint32_t* bv[2] = {nullptr, nullptr};
+  for (int i = 0; i < w.nbuf; ++i) {
+    bk[i] = (uint32_t*)(base + w.buf[i]);
+    bv[i] = (uint32_t*)(base + w.buf[i] + align256((size_t)n * sizeof(uint32_t)));
+  }
+  const int64_t ntiles = ceil_div(n, SORT_TILE);
+  const dim3 grid((unsigned)ntiles), block(256);
+  const hipError_t e = hipMemsetAsync(ghist, 0, 4 * 256 * sizeof(uint32_t), st);
+  MEANT_REQUIRE(e == hipSuccess, MEANT_ERR_LAUNCH, "%s: clearing the digit counters failed: %s", what, hipGetErrorString(e));
+  if (from_ids) hipLaunchKernelGGL(sort_hist_kernel<true>, grid, block, 0, st, ids, keys, n, V, passes, ghist, tile_hist, ntiles);
+  else hipLaunchKernelGGL(sort_hist_kernel<false>, grid, block, 0, st, ids, keys, n, V, passes, ghist, tile_hist, ntiles);
+  for (int p = 0; p < passes; ++p) {
+    const bool first = p == 0, last = p == passes - 1;
+    const uint32_t* kin = first ? keys : bk[(p - 1) & 1];
+    const uint32_t* vin = first ? vals : bv[(p - 1) & 1];
+    uint32_t* kout = last ? keys_out : bk[p & 1];
+    uint32_t* vout = last ? vals_out : bv[p & 1];
+    const int shift = 8 * p;
+    if (!first) hipLaunchKernelGGL(sort_count_kernel, grid, block, 0, st, kin, n, shift, tile_hist, ntiles);
+    hipLaunchKernelGGL(sort_scan_kernel, dim3(256), block, 0, st, (const uint32_t*)(ghist + p * 256), tile_hist, ntiles);
+#define SORT_SCATTER(F, L)                                                                                                     \
+  hipLaunchKernelGGL((sort_scatter_kernel<F, L>), grid, block, 0, st, ids, kin, vin, n, V, shift, (const uint32_t*)tile_hist, \
+                     ntiles, kout, vout, sorted_ids, order)
+    const bool F = first && from_ids, L = last && from_ids;                // the int64 ends of meant_sort_ids
+    if (F && L) SORT_SCATTER(true, true);
+    else if (F) SORT_SCATTER(true, false);
+    else if (L) SORT_SCATTER(false, true);
+    else SORT_SCATTER(false, false);
+#undef SORT_SCATTER
+  }
+  MEANT_LAUNCH_CHECK(what);
+  return MEANT_OK;
+}
+
 extern "C" size_t meant_sort_ids_ws(int64_t n, int64_t V) {
   if (n <= 0 || V <= 0 || n >= (1ll << 31) || V >= (1ll << 31)) return 0;
-  return sort_ws_layout(n, V).total;
+  return sort_ws_layout(n, sort_passes(V)).total;
 }
 
 extern "C" int meant_sort_ids(const int64_t* ids, int64_t n, int64_t V, int64_t* sorted_ids, int64_t* order, void* workspace,
@@ -535,46 +559,25 @@ extern "C" int meant_sort_ids(const int64_t* ids, int64_t n, int64_t V, int64_t*
     const auto overlap = [len](const char* x, const char* y) { return x < y + len && y < x + len; };
     EMB_REQ(!overlap(a, o1) && !overlap(a, o2) && !overlap(o1, o2), "sort_ids: ids, sorted_ids and order must not overlap");
   }
-  const SortWs w = sort_ws_layout(n, V);
+  const int passes = sort_passes(V);
+  const SortWs w = sort_ws_layout(n, passes);
   MEANT_REQUIRE(workspace && workspace_bytes >= w.total, MEANT_ERR_WORKSPACE, "sort_ids: workspace of %zu bytes needed, %zu given", w.total, workspace_bytes);
   EMB_REQ((reinterpret_cast<uintptr_t>(workspace) & 3) == 0, "sort_ids: 4-byte workspace alignment");
-  hipStream_t st = (hipStream_t)stream;
-  char* base = (char*)workspace;
-  uint32_t* ghist = (uint32_t*)(base + w.ghist);
-  uint32_t* tile_hist = (uint32_t*)(base + w.tile_hist);
-  uint32_t* bk[2] = {nullptr, nullptr};
-  uint32_t* bv[2] = {nullptr, nullptr};
-  for (int i = 0; i < w.nbuf; ++i) {
-    bk[i] = (uint32_t*)(base + w.buf[i]);
-    bv[i] = (uint32_t*)(base + w.buf[i] + align256((size_t)n * sizeof(uint32_t)));
-  }
-  const int64_t ntiles = ceil_div(n, SORT_TILE);
-  const int passes = sort_passes(V);
-  const dim3 grid((unsigned)ntiles), block(256);
-  const hipError_t e = hipMemsetAsync(ghist, 0, 4 * 256 * sizeof(uint32_t), st);
-  MEANT_REQUIRE(e == hipSuccess, MEANT_ERR_LAUNCH, "sort_ids: clearing the digit counters failed: %s", hipGetErrorString(e));
-  hipLaunchKernelGGL(sort_hist_kernel, grid, block, 0, st, ids, n, V, passes, ghist, tile_hist, ntiles);
-  for (int p = 0; p < passes; ++p) {
-    const bool first = p == 0, last = p == passes - 1;
-    const uint32_t* kin = first ? nullptr : bk[(p - 1) & 1];
-    const uint32_t* vin = first ? nullptr : bv[(p - 1) & 1];
-    uint32_t* kout = last ? nullptr : bk[p & 1];
-    uint32_t* vout = last ? nullptr : bv[p & 1];
-    const int shift = 8 * p;
-    if (!first) hipLaunchKernelGGL(sort_count_kernel, grid, block, 0, st, kin, n, shift, tile_hist, ntiles);
-    hipLaunchKernelGGL(sort_scan_kernel, dim3(256), block, 0, st, (const uint32_t*)(ghist + p * 256), tile_hist, ntiles);
-#define SORT_SCATTER(F, L)                                                                                                     \
-  hipLaunchKernelGGL((sort_scatter_kernel<F, L>), grid, block, 0, st, ids, kin, vin, n, V, shift, (const uint32_t*)tile_hist, \
-                     ntiles, kout, vout, sorted_ids, order)
-    if (first && last) SORT_SCATTER(true, true);
-    else if (first) SORT_SCATTER(true, false);
-    else if (last) SORT_SCATTER(false, true);
-    else SORT_SCATTER(false, false);
-#undef SORT_SCATTER
-  }
-  MEANT_LAUNCH_CHECK("sort_ids");
+  const int rc = sort_run(ids, V, nullptr, nullptr, n, passes, sorted_ids, order, nullptr, nullptr, w, (char*)workspace, (hipStream_t)stream, "sort_ids");
+  if (rc != MEANT_OK) return rc;
   meant_route_hit(ROUTE_SORT_IDS);
   return MEANT_OK;
+}
+
+size_t sort_u32_ws(int64_t n) { return n <= 0 || n >= (1ll << 31) ? 0 : sort_ws_layout(n, 4).total; }
+
+int sort_u32_launch(const uint32_t* keys, const uint32_t* vals, int64_t n, uint32_t* keys_out, uint32_t* vals_out, void* ws, size_t ws_bytes,
+                    hipStream_t stream) {
+  EMB_REQ(keys && vals && keys_out && vals_out && n > 0 && n < (1ll << 31), "sort_u32: bad argument");
+  const SortWs w = sort_ws_layout(n, 4);
+  MEANT_REQUIRE(ws && ws_bytes >= w.total, MEANT_ERR_WORKSPACE, "sort_u32: workspace of %zu bytes needed, %zu given", w.total, ws_bytes);
+  EMB_REQ((reinterpret_cast<uintptr_t>(ws) & 3) == 0, "sort_u32: 4-byte workspace alignment");
+  return sort_run(nullptr, 0, keys, vals, n, 4, nullptr, nullptr, keys_out, vals_out, w, (char*)ws, stream, "sort_u32");
 }
 
 extern "C" size_t meant_embedding_bwd_seg_ws(int64_t n, int64_t d) {

@@ -100,3 +100,38 @@ size_t attn_bwd1_ws(int64_t G, int64_t S, int H, int Dh);
 int attn_bwd1_launch(const bf16* qkv, const bf16* o, const bf16* dout, const float* lse, const float* bias2, const int* flags,
                      const uint64_t* masks, bf16* dqkv, void* ws1, int64_t G, int64_t S, int H, float scale, int causal, RotTables rot,
                      hipStream_t stream);
+
+// the radix sort of embedding.hip over caller-made 32-bit keys with a 32-bit value each (all four digits): keys_out ascending,
+// equal keys in input order.  Not in place.  ws: sort_u32_ws(n) bytes, 4-byte aligned.  0 < n < 2^31.
+size_t sort_u32_ws(int64_t n);
+int sort_u32_launch(const uint32_t* keys, const uint32_t* vals, int64_t n, uint32_t* keys_out, uint32_t* vals_out, void* ws,
+                    size_t ws_bytes, hipStream_t stream);
+
+#ifdef __HIPCC__
+// inclusive scan over the 256 threads of a workgroup, of sums or (MAX) of maxima; *total = the workgroup's result.  `wsum` is 4 words
+// of LDS; two barriers.
+template <bool MAX>
+__device__ __forceinline__ uint32_t block_scan_incl_op(uint32_t x, uint32_t* wsum, uint32_t* total) {
+  const auto op = [](uint32_t a, uint32_t b) { return MAX ? (a > b ? a : b) : a + b; };
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t y = __shfl_up(x, o, 64);
+    if (lane >= o) x = op(x, y);
+  }
+  __syncthreads();                                    // the previous call's readers are done with wsum
+  if (lane == 63) wsum[wave] = x;
+  __syncthreads();
+  uint32_t pre = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const uint32_t s = wsum[w];
+    if (w < wave) pre = op(pre, s);
+    tot = op(tot, s);
+  }
+  *total = tot;
+  return op(x, pre);
+}
+__device__ __forceinline__ uint32_t block_scan_incl(uint32_t x, uint32_t* wsum, uint32_t* total) { return block_scan_incl_op<false>(x, wsum, total); }
+__device__ __forceinline__ uint32_t block_scan_incl_max(uint32_t x, uint32_t* wsum, uint32_t* total) { return block_scan_incl_op<true>(x, wsum, total); }
+#endif

@@ -13,6 +13,9 @@
 //          in registers and leave through LDS once per workgroup.
 //   labels (C > 16, predictions given): a lane per row, the class counters by global atomics, the row counters as above.
 // A row whose target is the ignore index or outside [0, C) is never read and forms no address.
+//   * meant_score_capture         -- the scores themselves, kept for the rank statistic of auroc.hip: a lane per row writes the
+//                                    order-preserving 32-bit image of each captured column and the row's label to the caller's
+//                                    buffers at a slot the host names; the same four row counters, through LDS as above.
 #include "common.h"
 #include <limits.h>
 
@@ -248,6 +251,51 @@ __global__ __launch_bounds__(MT_THREADS) void metrics_labels_kernel(const int64_
   mt_flush_tail(tail, t_rows, t_ign, t_inv, 0u, state, C);
 }
 
+// ---- score capture --------------------------------------------------------------------------------------------------------
+// the bits of an element widened to float32 (bf16: exactly, denormals included; no float instruction touches the value)
+__device__ __forceinline__ uint32_t sc_bits(const float* p) { return __builtin_bit_cast(uint32_t, *p); }
+__device__ __forceinline__ uint32_t sc_bits(const bf16* p) { return (uint32_t)__builtin_bit_cast(uint16_t, *p) << 16; }
+__device__ __forceinline__ bool sc_is_nan(uint32_t b) { return (b & 0x7fffffffu) > 0x7f800000u; }
+// unsigned order of the keys = order of the floats: -0.0 first becomes +0.0, then non-negative values get the sign bit set and
+// negative ones are complemented
+__device__ __forceinline__ uint32_t sc_key(uint32_t b) {
+  if (b == 0x80000000u) b = 0u;
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+template <typename T>
+__global__ __launch_bounds__(MT_THREADS) void score_capture_kernel(const T* __restrict__ scores, int64_t ld, const int64_t* __restrict__ target,
+                                                                    int64_t B, int C, int col0, int ncol, int64_t ignore_index,
+                                                                    uint32_t* __restrict__ keys, int32_t* __restrict__ labels, int64_t capacity,
+                                                                    int64_t offset, int64_t* __restrict__ counters) {
+  __shared__ unsigned tail[4];
+  const int lane = threadIdx.x & 63;
+  unsigned t_rows = 0, t_ign = 0, t_inv = 0, t_nan = 0;
+  const int64_t step = (int64_t)gridDim.x * MT_THREADS;
+  for (int64_t r0 = (int64_t)blockIdx.x * MT_THREADS + (threadIdx.x - lane); r0 < B; r0 += step) {     // wave-uniform: ballots below
+    const int64_t r = r0 + lane;
+    bool valid = false, ignored = false, invalid = false, nan = false;
+    if (r < B) {
+      const int64_t t = target[r];
+      const T* row = scores + r * ld + col0;
+      if (t == ignore_index) ignored = true;
+      else if (t < 0 || t >= C) invalid = true;
+      else {
+        for (int c = 0; c < ncol; ++c) nan = nan || sc_is_nan(sc_bits(row + c));
+        valid = !nan;
+      }
+      const int64_t slot = offset + r;                 // offset + B <= capacity: inside the buffers
+      labels[slot] = valid ? (int32_t)t : -1;
+      for (int c = 0; c < ncol; ++c) keys[(int64_t)c * capacity + slot] = valid ? sc_key(sc_bits(row + c)) : 0u;
+    }
+    t_rows += (unsigned)__popcll(__ballot(valid));
+    t_ign += (unsigned)__popcll(__ballot(ignored));
+    t_inv += (unsigned)__popcll(__ballot(invalid));
+    t_nan += (unsigned)__popcll(__ballot(nan));
+  }
+  mt_flush_tail(tail, t_rows, t_ign, t_inv, t_nan, counters, 0);
+}
+
 bool mt_aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 constexpr int64_t MT_MAX_ROWS = 1ll << 40;             // a workgroup's 32-bit LDS counters hold its share of this many rows
 
@@ -307,5 +355,29 @@ extern "C" int meant_metrics_update_labels(const int64_t* pred, const int64_t* t
     hipLaunchKernelGGL(metrics_labels_kernel, dim3(grid), dim3(MT_THREADS), 0, st, pred, target, B, C, ignore_index, state, confusion);
   MEANT_LAUNCH_CHECK("metrics_update_labels");
   meant_route_hit(ROUTE_METRICS_LABELS);
+  return MEANT_OK;
+}
+
+extern "C" int meant_score_capture(const void* scores, int64_t ld, int dtype, const int64_t* target, int64_t B, int C, int col0, int ncol,
+                                   int64_t ignore_index, uint32_t* keys, int32_t* labels, int64_t capacity, int64_t offset,
+                                   int64_t* counters, void* stream) {
+  MEANT_REQUIRE(scores && target && keys && labels && counters, MEANT_ERR_ARG, "score_capture: null scores / target / keys / labels / counters");
+  MEANT_REQUIRE(B >= 0 && C > 0 && ncol > 0 && col0 >= 0 && (int64_t)col0 + ncol <= ld, MEANT_ERR_ARG,
+                "score_capture: bad argument (B=%lld < 0, C=%d <= 0, ncol=%d <= 0, col0=%d < 0 or col0 + ncol > ld=%lld)", (long long)B, C, ncol,
+                col0, (long long)ld);
+  MEANT_REQUIRE(offset >= 0 && capacity >= 0 && B <= capacity && offset <= capacity - B, MEANT_ERR_ARG,
+                "score_capture: rows [%lld, %lld + %lld) do not fit the capacity %lld", (long long)offset, (long long)offset, (long long)B,
+                (long long)capacity);
+  MEANT_REQUIRE(dtype == MEANT_F32 || dtype == MEANT_BF16, MEANT_ERR_ARG, "score_capture: unknown dtype %d", dtype);
+  MEANT_REQUIRE(mt_aligned(scores, dtype == MEANT_F32 ? 4 : 2) && mt_aligned(target, 8) && mt_aligned(keys, 4) && mt_aligned(labels, 4) &&
+                    mt_aligned(counters, 8),
+                MEANT_ERR_ARG, "score_capture: operands must be aligned to their element size");
+  MEANT_REQUIRE(capacity < (1ll << 31), MEANT_ERR_UNSUPPORTED, "score_capture: capacity=%lld must be below 2^31", (long long)capacity);
+  if (B == 0) return MEANT_OK;
+  const unsigned grid = mt_grid(ceil_div(B, MT_THREADS), MT_ROWS_MAXGRID);
+  DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(score_capture_kernel<T>, dim3(grid), dim3(MT_THREADS), 0, (hipStream_t)stream, (const T*)scores, ld,
+                                              target, B, C, col0, ncol, ignore_index, keys, labels, capacity, offset, counters));
+  MEANT_LAUNCH_CHECK("score_capture");
+  meant_route_hit(ROUTE_SCORE_CAPTURE);
   return MEANT_OK;
 }

@@ -12,10 +12,17 @@ per batch, and a second one for `torch.isnan(out).any()` (in_loop_train.py:228).
 
 State layout (include/meant_hip.h): int64 [3C + 4] = tp[C], npred[C], ntarget[C], n_rows, n_ignored, n_invalid, n_nan.  All
 integers and only ever added to: two runs give the same bits, and a multi-GPU caller may `all_reduce` `m.state` as it is.
+
+The paper's other two numbers (train.py:63-65, 103-117): the Matthews coefficient follows from the same counts (`f1_metrics.mcc()`);
+the AUROC is a rank statistic and needs the scores, which `auroc.update` keeps on the device (meant_score_capture, one launch) until
+`auroc.statistic()` sorts them there and counts the Mann-Whitney statistic exactly (meant_auroc_rank).  `metric_group` feeds several
+such objects from one `TrainStep(metrics=...)` / `train.evaluate`.
 """
 from __future__ import annotations
 
 from typing import Optional
+
+import math
 
 import torch
 
@@ -139,6 +146,10 @@ class f1_metrics:
         """(accuracy, f1 macro, f1 micro, precision macro, precision micro, recall macro, recall micro), 0-d float32 tensors"""
         return tuple(v.float() for v in self.from_counts(self._host_state(), self.num_classes, self.absent_classes))
 
+    def mcc(self) -> torch.Tensor:
+        """Matthews correlation coefficient of the counted rows (multiclass form; at C = 2 the binary one), a 0-d float32 tensor"""
+        return self.mcc_from_counts(self._host_state(), self.num_classes).float()
+
     def per_class(self):
         """precision, recall, F1 (float64 [C]) and support = ntarget (int64 [C])"""
         return self.per_class_from_counts(self._host_state(), self.num_classes)
@@ -186,6 +197,17 @@ class f1_metrics:
         return _ratio(tp, npred), _ratio(tp, ntarget), _ratio(2 * tp, npred + ntarget), ntarget.long()
 
     @staticmethod
+    def mcc_from_counts(state: torch.Tensor, C: int) -> torch.Tensor:
+        """(c s - sum_k npred_k ntarget_k) / sqrt((s^2 - sum_k npred_k^2) (s^2 - sum_k ntarget_k^2)) with c = sum(tp) and s = n_rows, as
+        a 0-d float64 tensor; 0 where the denominator is 0 (nothing counted, one class predicted throughout, one class the only
+        target), as scikit-learn's matthews_corrcoef returns.  The sums are exact in float64 while s^2 stays below 2^53."""
+        tp, npred, ntarget, tail = _split(state, C)
+        c, s = tp.sum(), tail[0].double()
+        num = c * s - (npred * ntarget).sum()
+        den = (s * s - (npred * npred).sum()) * (s * s - (ntarget * ntarget).sum())
+        return num / den.sqrt() if den.item() > 0 else torch.zeros((), dtype=torch.float64)
+
+    @staticmethod
     def from_counts(state: torch.Tensor, C: int, absent_classes: str = "skip"):
         """The seven values, as 0-d float64 tensors, from a state tensor: per class p = tp / npred, r = tp / ntarget,
         f1 = 2 tp / (npred + ntarget), 0 where the denominator is 0; accuracy = micro F1 = micro precision = micro recall =
@@ -201,3 +223,189 @@ class f1_metrics:
         n = present.sum().double()
         macro = lambda x: _ratio((x * present).sum(), n)
         return micro, macro(f1), micro.clone(), macro(p), micro.clone(), macro(r), micro.clone()
+
+
+class auroc:
+    """Area under the ROC curve from scores kept on the device (the reference's torchmetrics AUROC, utils/f1_metrics.py:3).
+
+    update(pred, target): the tensors `f1_metrics.update` takes for scores -- pred [B, C] float32 / bfloat16 (float16 and float64
+    through `.float()`), target [B] integer -- or, at num_classes == 2, pred [B]: the score of the positive class.  One launch
+    (meant_score_capture) appends the batch to the device buffers: at num_classes == 2 the column `pos_label`, otherwise all C
+    columns, each class against the rest.  A row whose target is `ignore_index`, whose target is otherwise outside [0, C)
+    (`invalid_rows()`) or with a NaN among its captured scores (`nan_rows()`) is left out.  The buffers double when full, by device
+    copies sized from the host's own row count: `update` never reads the device.
+
+    statistic(): int64 [ncol, 3] on the CPU, per captured column (2U, P, N): P positives, N negatives and twice the Mann-Whitney
+    statistic, 2U = sum over (positive, negative) pairs of 2 [negative's score below] + [scores equal] -- exact integers
+    (meant_auroc_rank: a radix sort and integer scans on the device), the same bits for any batching.  The one place that reads back.
+    per_class(): float64 [ncol], 2U / (2 P N), NaN where P or N is 0.  compute(): a 0-d float32 tensor: that value at
+    num_classes == 2, otherwise the mean over the classes that have both a positive and a negative (macro average); NaN when no
+    class has both -- the area is undefined then (scikit-learn raises; torchmetrics could not be consulted for its convention).
+    -0.0 and +0.0 tie; scores are compared as float32 (bfloat16 widened exactly).
+    """
+
+    def __init__(self, num_classes: int = 2, set_name: str = "", pos_label: int = 1, ignore_index: int = -100, capacity: int = 65536,
+                 device=None):
+        if num_classes < 2:
+            raise ValueError("auroc: num_classes must be at least 2")
+        if num_classes == 2 and pos_label not in (0, 1):
+            raise ValueError("auroc: pos_label is 0 or 1")
+        if capacity <= 0:
+            raise ValueError("auroc: capacity must be positive")
+        self.num_classes, self.set_name = int(num_classes), set_name
+        self.pos_label, self.ignore_index = int(pos_label), int(ignore_index)
+        self.ncol = 1 if self.num_classes == 2 else self.num_classes
+        self.capacity = int(capacity)
+        self.count = 0                                   # slots handed out so far: the host's own sum of the batch sizes
+        self.keys: Optional[torch.Tensor] = None         # int32 [ncol, capacity] holding the uint32 keys, class-major
+        self.labels: Optional[torch.Tensor] = None       # int32 [capacity], -1 = left out
+        self.counters: Optional[torch.Tensor] = None     # int64 [4] = n_rows, n_ignored, n_invalid, n_nan
+        if device is not None:
+            self._alloc(torch.device(device))
+
+    # ---- device side ----------------------------------------------------------------------------
+    def _alloc(self, device):
+        self.keys = torch.empty(self.ncol, self.capacity, dtype=torch.int32, device=device)
+        self.labels = torch.empty(self.capacity, dtype=torch.int32, device=device)
+        self.counters = torch.zeros(4, dtype=torch.int64, device=device)
+
+    def _reserve(self, rows: int) -> None:
+        """room for `rows` more: double the buffers (device copies of the `count` slots in use, a size the host knows)"""
+        need = self.count + rows
+        if need <= self.capacity:
+            return
+        cap = self.capacity
+        while cap < need:
+            cap *= 2
+        if cap >= 1 << 31:
+            raise ValueError(f"auroc: {need} rows are beyond the 2^31 slots of one object")
+        keys = torch.empty(self.ncol, cap, dtype=torch.int32, device=self.keys.device)
+        labels = torch.empty(cap, dtype=torch.int32, device=self.keys.device)
+        keys[:, :self.count].copy_(self.keys[:, :self.count])
+        labels[:self.count].copy_(self.labels[:self.count])
+        self.keys, self.labels, self.capacity = keys, labels, cap
+
+    def update(self, pred: torch.Tensor, target: torch.Tensor) -> None:
+        C = self.num_classes
+        if not pred.is_cuda or not target.is_cuda:
+            dev = pred.device if pred.is_cuda else target.device if target.is_cuda else torch.device("cuda", torch.cuda.current_device())
+            pred, target = pred.to(dev), target.to(dev)
+        ops._need_gpu(pred, target)
+        if self.keys is None:
+            self._alloc(pred.device)
+        ops._need_gpu(self.keys)
+        pred = pred.detach()
+        if target.dtype.is_floating_point or target.dtype == torch.bool:
+            raise TypeError("auroc: target must be an integer tensor")
+        if not pred.dtype.is_floating_point:
+            raise TypeError("auroc: pred must be floating-point scores (a ranking needs them; labels have none)")
+        target = ops._c(target.reshape(-1).long())
+        B = target.shape[0]
+        if pred.dim() == 1 and C == 2:
+            pred = pred.unsqueeze(1)
+            col0 = 0
+        else:
+            if pred.dim() != 2 or pred.shape[1] != C:
+                raise ValueError(f"auroc: scores must be [{B}, {C}]" + (f" or [{B}]" if C == 2 else "") + f", got {tuple(pred.shape)}")
+            col0 = self.pos_label if C == 2 else 0
+        if pred.shape[0] != B:
+            raise ValueError(f"auroc: {pred.shape[0]} rows of scores for {B} targets")
+        if pred.dtype not in (torch.float32, torch.bfloat16):
+            pred = pred.float()                          # float16 (exact), float64
+        width = pred.shape[1]
+        if pred.stride(1) != 1 or (B > 1 and pred.stride(0) < width):
+            pred = pred.contiguous()
+        ld = pred.stride(0) if B > 1 else max(width, pred.stride(0))
+        self._reserve(B)
+        check(lib.meant_score_capture(ops._p(pred), ld, ops._dt(pred), ops._p(target), B, C, col0, self.ncol, self.ignore_index,
+                                      ops._p(self.keys), ops._p(self.labels), self.capacity, self.count, ops._p(self.counters),
+                                      ops._stream()), "score_capture")
+        self.count += B
+
+    def reset(self) -> None:
+        self.count = 0
+        if self.counters is not None:
+            self.counters.zero_()
+
+    def merge(self, other: "auroc") -> "auroc":
+        """append another object's captured rows (same classes and positive label) to this one's, on this one's device: after a
+        gather of the ranks' objects the statistic is that of all their rows"""
+        if (other.num_classes, other.pos_label, other.ncol) != (self.num_classes, self.pos_label, self.ncol):
+            raise ValueError("auroc.merge: different num_classes / pos_label")
+        if other.keys is None:
+            return self
+        if self.keys is None:
+            self._alloc(other.keys.device)
+        self._reserve(other.count)
+        a, b = self.count, self.count + other.count
+        self.keys[:, a:b].copy_(other.keys[:, :other.count])
+        self.labels[a:b].copy_(other.labels[:other.count])
+        self.counters += other.counters.to(self.counters.device)
+        self.count = b
+        return self
+
+    # ---- host side ------------------------------------------------------------------------------------
+    def statistic(self) -> torch.Tensor:
+        """int64 [ncol, 3] on the CPU: (2U, P, N) per captured column"""
+        if self.keys is None or self.count == 0:
+            return torch.zeros(self.ncol, 3, dtype=torch.int64)
+        n = self.count
+        with torch.cuda.device(self.keys.device):
+            out = torch.empty(self.ncol, 3, dtype=torch.int64, device=self.keys.device)
+            wsb = lib.meant_auroc_ws(n)
+            ws = torch.empty(wsb, dtype=torch.uint8, device=self.keys.device)
+            st = ops._stream()
+            for c in range(self.ncol):
+                positive = self.pos_label if self.num_classes == 2 else c
+                check(lib.meant_auroc_rank(ops._p(self.keys[c]), ops._p(self.labels), n, positive, ops._p(out[c]), ops._p(ws), wsb, st),
+                      "auroc_rank")
+            return out.cpu()
+
+    @staticmethod
+    def from_statistic(stat: torch.Tensor) -> torch.Tensor:
+        """float64 [ncol]: 2U / (2 P N), NaN where P or N is 0"""
+        u2, P, N = (stat[:, i].double() for i in range(3))
+        den = 2 * P * N
+        return torch.where(den > 0, u2 / den.clamp(min=1), torch.full_like(den, math.nan))
+
+    def per_class(self) -> torch.Tensor:
+        return self.from_statistic(self.statistic())
+
+    def compute(self) -> torch.Tensor:
+        a = self.per_class()
+        ok = ~torch.isnan(a)
+        return (a[ok].mean() if ok.any() else torch.tensor(math.nan, dtype=torch.float64)).float()
+
+    def _counter(self, k: int) -> int:
+        return 0 if self.counters is None else int(self.counters[k].item())
+
+    def invalid_rows(self) -> int:
+        return self._counter(2)
+
+    def nan_rows(self) -> int:
+        """rows left out because one of their captured scores is a NaN"""
+        return self._counter(3)
+
+    def show(self):
+        value = self.compute()
+        print(self.set_name + ' AUROC: ', value)
+        return value
+
+
+class metric_group:
+    """Several metric objects behind one `update` / `reset` / `show`, so that one `TrainStep(metrics=...)` or `train.evaluate` feeds
+    them all: metric_group(f1_metrics(2, "Train"), auroc(2, "Train"))"""
+
+    def __init__(self, *metrics):
+        self.metrics = tuple(metrics)
+
+    def update(self, pred: torch.Tensor, target: torch.Tensor) -> None:
+        for m in self.metrics:
+            m.update(pred, target)
+
+    def reset(self) -> None:
+        for m in self.metrics:
+            m.reset()
+
+    def show(self, *args, **kwargs):
+        return tuple(m.show(*args, **kwargs) if isinstance(m, f1_metrics) else m.show() for m in self.metrics)
