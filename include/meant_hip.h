@@ -94,7 +94,8 @@ int meant_get_option(const char* name, int* value);
  * "rotary_qk" (every meant_rotary_qk launch), "rotary_pairs" (those of its pair-by-pair kernel: Dh % 8 != 0 or an unaligned base)
  * "nt_rot" (every bf16 NT GEMM launched with the rotary epilogue, on top of the nt* route it takes), "metrics_rows" /
  * "metrics_wave" / "metrics_labels" (meant_metrics_update by form, every meant_metrics_update_labels launch), "score_capture"
- * (every meant_score_capture launch) and "auroc_rank" (every meant_auroc_rank call with n > 0));
+ * (every meant_score_capture launch), "auroc_rank" (every meant_auroc_rank call with n > 0), "ce_soft_wave" / "ce_soft_block"
+ * (meant_ce_probs_soft by form) and "vqa_score" (every meant_vqa_score_update launch));
  * -1 for an unknown name.  The names label routes, not kernels: "nt256s" / "nt256s_rot" count launches of the streaming
  * GEMM (whichever kernel implements it), "nt_split" the ragged head + tail split.  Tests use it to prove that a shape
  * reaches the kernel it is meant to exercise. */
@@ -592,6 +593,33 @@ int meant_score_capture(const void* scores, int64_t ld, int dtype, const int64_t
 size_t meant_auroc_ws(int64_t n);
 int meant_auroc_rank(const uint32_t* keys, const int32_t* labels, int64_t n, int positive, int64_t* out, void* workspace,
                      size_t workspace_bytes, void* stream);
+/* ---- soft-target cross-entropy and the VQA score (meant_vqa's own labels) ------ vqa.py:173,209,223; utils/custom_datasets.py:214-218
+ * nn.CrossEntropyLoss() (mean over the rows) of probs [B, ldp] (C valid columns, f32) against class-probability targets
+ * [B, ldt] (MEANT_F32 | MEANT_BF16).  row_loss[b] = sum_c t[b,c] * (logsumexp(probs[b,:]) - probs[b,c]);
+ * loss[0] = (sum_b row_loss[b]) / B, OVERWRITTEN (no zero fill by the caller); dprobs (optional, [B, ldd], must not alias probs):
+ * d loss / d probs = (T_b * softmax(probs[b,:])_c - t[b,c]) / B with T_b = sum_c t[b,c].  Targets are taken as they are: rows need
+ * not sum to 1 and an all-zero row contributes 0 to the loss and a zero gradient row (what torch computes).
+ * Evaluated per row as mx = max p, s = sum exp(p - mx), row = T log(s) + sum_c t_c (mx - p_c), softmax_c = exp(p_c - mx) / s: no
+ * term grows with a shift of the row.  Nothing at or beyond column C of a row is addressed; rows may start at any element.
+ * Forms (route names): "ce_soft_wave" for C <= 1024, a wave per row; "ce_soft_block" above, a 256-thread workgroup per row, the row
+ * in registers up to C = 4096 (probs and target read once, the gradient written once) and read twice beyond.  A second launch of
+ * one workgroup sums row_loss in an order fixed by B.  No atomics: the same call gives the same bits, whatever "deterministic" says.
+ * A null probs / target / row_loss / loss, B <= 0, C <= 0, ldp / ldt (/ ldd with dprobs) below C, an unknown target_dtype, a
+ * misaligned operand or dprobs == probs: MEANT_ERR_ARG; more than 2^31 - 1 workgroups (B in the block form, B / 4 in the wave form)
+ * or C within 1024 of 2^31: MEANT_ERR_UNSUPPORTED; both before any launch. */
+int meant_ce_probs_soft(const float* probs, int64_t ldp, const void* target, int64_t ldt, int target_dtype,
+                        float* row_loss, float* loss, float* dprobs, int64_t ldd, int64_t B, int64_t C, void* stream);
+/* VQA score counts.  For each row: j = argmax over the C score columns in torch's order (lowest index on a tie, a NaN above
+ * everything: the rule of meant_metrics_update); w = target[b, j].  scores [B, lds], target [B, ldt], each MEANT_F32 | MEANT_BF16.
+ * state = int64 [4], zeroed once by the caller, only ever added to: sum_fx += llrint((double)w * 2^32), rows += 1; a row whose w is
+ * not finite or outside [0, 16] is counted in state[3] (invalid) and left out of sum_fx and rows; a row with a NaN among its scores
+ * is scored by the rule above and also counted in state[2].  Only integers are added: any batching and any arrival order gives the
+ * same bits.  The VQA score is sum_fx / 2^32 / rows.  A wave per row over a capped grid, the four counters through LDS, one 64-bit
+ * integer atomic per non-zero counter and workgroup; route name "vqa_score".
+ * A null scores / target / state, B < 0, C <= 0, lds or ldt below C, an unknown dtype or a misaligned operand: MEANT_ERR_ARG;
+ * B >= 2^40 or C >= 2^31: MEANT_ERR_UNSUPPORTED; both before any launch.  B == 0: MEANT_OK without a launch. */
+int meant_vqa_score_update(const void* scores, int64_t lds, int scores_dtype, const void* target, int64_t ldt, int target_dtype,
+                           int64_t B, int64_t C, int64_t* state, void* stream);
 /* out_accum[0] += sum(x^2) over a flat float buffer (global gradient norm; caller zeroes the scalar) */
 int meant_sumsq_f32(const float* x, int64_t n, float* out_accum, void* stream);
 /* One AdamW step (torch.optim.AdamW semantics, `step` >= 1 for the bias corrections) over flat float buffers.

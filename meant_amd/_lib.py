@@ -98,6 +98,8 @@ SIGNATURES = {
     "meant_score_capture": (_i, [_p, _i64, _i, _p, _i64, _i, _i, _i, _i64, _p, _p, _i64, _i64, _p, _p]),
     "meant_auroc_ws": (_sz, [_i64]),
     "meant_auroc_rank": (_i, [_p, _p, _i64, _i, _p, _p, _sz, _p]),
+    "meant_ce_probs_soft": (_i, [_p, _i64, _p, _i64, _i, _p, _p, _p, _i64, _i64, _i64, _p]),
+    "meant_vqa_score_update": (_i, [_p, _i64, _i, _p, _i64, _i, _i64, _i64, _p, _p]),
     "meant_sumsq_f32":(_i, [_p, _i64, _p, _p]),
     "meant_adamw_f32": (_i, [_p, _p, _p, _p, _i64, _f, _f, _f, _f, _f, _i64, _p, _f, _f, _p]),
     "meant_embedding_bwd_sorted": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i, _p]),

@@ -61,7 +61,7 @@ enum meant_route_id {
   ROUTE_ATTN_FWD_D160, ROUTE_ATTN_FWD_D192, ROUTE_ATTN_FWD_D256, ROUTE_ATTN_BWD_D160, ROUTE_ATTN_BWD_D192, ROUTE_ATTN_BWD_D256, ROUTE_TEMPORAL_LONG,
   ROUTE_EMB_SEG, ROUTE_SORT_IDS, ROUTE_NT128K, ROUTE_NT256K, ROUTE_SELECT_ROWS, ROUTE_ROTARY_QK, ROUTE_ROTARY_PAIRS, ROUTE_NT_ROT,
   ROUTE_METRICS_ROWS, ROUTE_METRICS_WAVE, ROUTE_METRICS_LABELS, ROUTE_TN256_ROWS, ROUTE_ATTN_CLS_SPLIT, ROUTE_ROWS_ELEM,
-  ROUTE_SCORE_CAPTURE, ROUTE_AUROC_RANK,
+  ROUTE_SCORE_CAPTURE, ROUTE_AUROC_RANK, ROUTE_CE_SOFT_WAVE, ROUTE_CE_SOFT_BLOCK, ROUTE_VQA_SCORE,
   MEANT_ROUTE_COUNT
 };
 void meant_route_hit(int route);

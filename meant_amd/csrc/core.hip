@@ -145,6 +145,8 @@ const char* const k_routes[MEANT_ROUTE_COUNT] = {
     "attn_cls_split",               // every meant_attn_cls_split_fwd / _bwd call (the cls query's attention over key segments)
     "rows_elem",                    // the element-access forms of gather_rows, token_shift, geglu_fwd / _bwd and dropout (rows off the 16-byte grid)
     "score_capture", "auroc_rank",  // every meant_score_capture launch; every meant_auroc_rank call with n > 0
+    "ce_soft_wave", "ce_soft_block",   // meant_ce_probs_soft by form (C <= 1024: a wave per row / above: a workgroup per row)
+    "vqa_score",                    // every meant_vqa_score_update launch
 };
 std::atomic<long long> g_route[MEANT_ROUTE_COUNT];
 }  // namespace

@@ -16,6 +16,8 @@
 //   * meant_score_capture         -- the scores themselves, kept for the rank statistic of auroc.hip: a lane per row writes the
 //                                    order-preserving 32-bit image of each captured column and the row's label to the caller's
 //                                    buffers at a slot the host names; the same four row counters, through LDS as above.
+//   * meant_vqa_score_update      -- the VQA score of soft targets [B, C] (vqa.py:223; utils/custom_datasets.py:214-218): the wave form's
+//                                    argmax, then the target's weight at the predicted column, summed in 2^-32 units as an integer.
 #include "common.h"
 #include <limits.h>
 
@@ -148,12 +150,59 @@ template <typename T> __device__ __forceinline__ MtChunk<T> mt_load(const T* p) 
   return c;
 }
 
+// a wave's argmax over the C columns of the row at p, in torch's order; every lane gets (v, vi): the value and 0 <= vi < C
+template <typename T, bool VEC>
+__device__ __forceinline__ void mt_wave_argmax(const T* __restrict__ p, int C, int lane, float& v, int& vi) {
+  constexpr int E = MtChunk<T>::E;
+  v = -INFINITY;
+  vi = INT_MAX;                                        // INT_MAX: nothing taken yet (no candidate, or -inf only)
+  int first;                                           // this lane's lowest candidate column
+  if (VEC) {                                           // ld % E == 0: the chunk that holds column C - 1 lies inside the row
+    first = lane * E;
+    const int nfull = C / E, nchunks = (C + E - 1) / E;
+    int c = lane;
+    for (; c + 192 < nfull; c += 256) {                // four loads in flight per lane
+      MtChunk<T> k[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) k[u] = mt_load(p + (int64_t)(c + 64 * u) * E);
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+          const float x = k[u].get(e);
+          if (mt_takes(x, v)) { v = x; vi = (c + 64 * u) * E + e; }
+        }
+    }
+    for (; c < nchunks; c += 64) {
+      const MtChunk<T> k = mt_load(p + (int64_t)c * E);
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        const float x = k.get(e);
+        const int j = c * E + e;
+        if (j < C && mt_takes(x, v)) { v = x; vi = j; }
+      }
+    }
+  } else {
+    first = lane;
+    for (int j = lane; j < C; j += 64) {
+      const float x = to_f(p[j]);
+      if (mt_takes(x, v)) { v = x; vi = j; }
+    }
+  }
+  if (vi == INT_MAX && first < C) vi = first;          // all of this lane's candidates were -inf: the first of them
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(v, o, 64);
+    const int oi = __shfl_xor(vi, o, 64);
+    if (mt_better(ov, oi, v, vi)) { v = ov; vi = oi; }
+  }
+}
+
 template <typename T, bool VEC>
 __global__ __launch_bounds__(MT_WAVE_THREADS) void metrics_wave_kernel(const T* __restrict__ scores, int64_t ld, const int64_t* __restrict__ target,
                                                                    int64_t B, int C, int64_t ignore_index, int64_t* __restrict__ state,
                                                                    int64_t* __restrict__ confusion) {
   __shared__ unsigned tail[4];
-  constexpr int E = MtChunk<T>::E;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   unsigned t_rows = 0, t_ign = 0, t_inv = 0, t_nan = 0;                             // wave-uniform
   for (int64_t row = (int64_t)blockIdx.x * MT_WAVES + wave; row < B; row += (int64_t)gridDim.x * MT_WAVES) {
@@ -162,49 +211,9 @@ __global__ __launch_bounds__(MT_WAVE_THREADS) void metrics_wave_kernel(const T* 
                                 (unsigned)__builtin_amdgcn_readfirstlane((int)(u64)tl));
     if (t == ignore_index) { ++t_ign; continue; }
     if (t < 0 || t >= C) { ++t_inv; continue; }
-    const T* p = scores + row * ld;
-    float v = -INFINITY;
-    int vi = INT_MAX;                                  // INT_MAX: nothing taken yet (no candidate, or -inf only)
-    int first;                                         // this lane's lowest candidate column
-    if (VEC) {                                         // ld % E == 0: the chunk that holds column C - 1 lies inside the row
-      first = lane * E;
-      const int nfull = C / E, nchunks = (C + E - 1) / E;
-      int c = lane;
-      for (; c + 192 < nfull; c += 256) {              // four loads in flight per lane
-        MtChunk<T> k[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) k[u] = mt_load(p + (int64_t)(c + 64 * u) * E);
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-          for (int e = 0; e < E; ++e) {
-            const float x = k[u].get(e);
-            if (mt_takes(x, v)) { v = x; vi = (c + 64 * u) * E + e; }
-          }
-      }
-      for (; c < nchunks; c += 64) {
-        const MtChunk<T> k = mt_load(p + (int64_t)c * E);
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-          const float x = k.get(e);
-          const int j = c * E + e;
-          if (j < C && mt_takes(x, v)) { v = x; vi = j; }
-        }
-      }
-    } else {
-      first = lane;
-      for (int j = lane; j < C; j += 64) {
-        const float x = to_f(p[j]);
-        if (mt_takes(x, v)) { v = x; vi = j; }
-      }
-    }
-    if (vi == INT_MAX && first < C) vi = first;        // all of this lane's candidates were -inf: the first of them
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(v, o, 64);
-      const int oi = __shfl_xor(vi, o, 64);
-      if (mt_better(ov, oi, v, vi)) { v = ov; vi = oi; }
-    }
+    float v;
+    int vi;
+    mt_wave_argmax<T, VEC>(scores + row * ld, C, lane, v, vi);
     ++t_rows;
     if (v != v) ++t_nan;
     if (lane == 0 && vi >= 0 && vi < C) {              // vi < C always holds (lane 0 has column 0); never form an address beyond
@@ -216,6 +225,49 @@ __global__ __launch_bounds__(MT_WAVE_THREADS) void metrics_wave_kernel(const T* 
     }
   }
   mt_flush_tail(tail, t_rows, t_ign, t_inv, t_nan, state, C);
+}
+
+// ---- VQA score: the soft weight of the predicted answer ---------------------------------------------------------------------
+// state = int64 [4]: sum_fx (the weights in 2^-32 units), rows, nan rows, invalid rows.  The wave form's walk and argmax; the weight
+// is one element of the target row, read by every lane from the same address.
+enum { VQ_SUM = 0, VQ_ROWS, VQ_NAN, VQ_INVALID };
+constexpr float VQ_MAX_WEIGHT = 16.f;                  // a weight in [0, 16] is below 2^37 units: 2^26 rows of them fit an int64
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(MT_WAVE_THREADS) void vqa_score_kernel(const T* __restrict__ scores, int64_t lds, const void* __restrict__ target,
+                                                                    int64_t ldt, bool target_bf16, int64_t B, int C, int64_t* __restrict__ state) {
+  __shared__ u64 sum;
+  __shared__ unsigned tail[3];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  u64 t_fx = 0;                                                                     // wave-uniform, like the three counters
+  unsigned t_rows = 0, t_nan = 0, t_inv = 0;
+  for (int64_t row = (int64_t)blockIdx.x * MT_WAVES + wave; row < B; row += (int64_t)gridDim.x * MT_WAVES) {
+    float v;
+    int vi;
+    mt_wave_argmax<T, VEC>(scores + row * lds, C, lane, v, vi);
+    if (vi < 0 || vi >= C) vi = 0;                     // never holds (see metrics_wave_kernel); never form an address beyond
+    const int64_t at = row * ldt + vi;
+    const float w = target_bf16 ? (float)static_cast<const bf16*>(target)[at] : static_cast<const float*>(target)[at];
+    if (v != v) ++t_nan;
+    if (w >= 0.f && w <= VQ_MAX_WEIGHT) {              // false for a NaN
+      t_fx += (u64)llrint((double)w * 4294967296.0);
+      ++t_rows;
+    } else {
+      ++t_inv;
+    }
+  }
+  if (tid == 0) sum = 0;
+  if (tid < 3) tail[tid] = 0;
+  __syncthreads();
+  if (lane == 0) {
+    if (t_fx) atomicAdd(&sum, t_fx);
+    if (t_rows) atomicAdd(&tail[VQ_ROWS - 1], t_rows);
+    if (t_nan) atomicAdd(&tail[VQ_NAN - 1], t_nan);
+    if (t_inv) atomicAdd(&tail[VQ_INVALID - 1], t_inv);
+  }
+  __syncthreads();
+  if (tid == 0 && sum) atomicAdd(reinterpret_cast<u64*>(state + VQ_SUM), sum);
+  if (tid >= 1 && tid < 4 && tail[tid - 1]) mt_add(state + tid, tail[tid - 1]);
 }
 
 // ---- labels, C > MT_ROWS_MAXC --------------------------------------------------------------------------------------------
@@ -379,5 +431,36 @@ extern "C" int meant_score_capture(const void* scores, int64_t ld, int dtype, co
                                               target, B, C, col0, ncol, ignore_index, keys, labels, capacity, offset, counters));
   MEANT_LAUNCH_CHECK("score_capture");
   meant_route_hit(ROUTE_SCORE_CAPTURE);
+  return MEANT_OK;
+}
+
+extern "C" int meant_vqa_score_update(const void* scores, int64_t lds, int scores_dtype, const void* target, int64_t ldt, int target_dtype,
+                                      int64_t B, int64_t C, int64_t* state, void* stream) {
+  MEANT_REQUIRE(scores && target && state && B >= 0 && C > 0 && lds >= C && ldt >= C, MEANT_ERR_ARG,
+                "vqa_score_update: bad argument (null scores / target / state, B=%lld < 0, C=%lld <= 0, lds=%lld or ldt=%lld below C)",
+                (long long)B, (long long)C, (long long)lds, (long long)ldt);
+  MEANT_REQUIRE((scores_dtype == MEANT_F32 || scores_dtype == MEANT_BF16) && (target_dtype == MEANT_F32 || target_dtype == MEANT_BF16),
+                MEANT_ERR_ARG, "vqa_score_update: unknown dtype (scores %d, target %d)", scores_dtype, target_dtype);
+  MEANT_REQUIRE(mt_aligned(scores, scores_dtype == MEANT_F32 ? 4 : 2) && mt_aligned(target, target_dtype == MEANT_F32 ? 4 : 2) &&
+                    mt_aligned(state, 8),
+                MEANT_ERR_ARG, "vqa_score_update: operands must be aligned to their element size");
+  MEANT_REQUIRE(B < MT_MAX_ROWS && C <= INT_MAX, MEANT_ERR_UNSUPPORTED, "vqa_score_update: B=%lld must be below 2^40 rows per call and C=%lld below 2^31",
+                (long long)B, (long long)C);
+  if (B == 0) return MEANT_OK;
+  const int cus = meant_num_cus();
+  const unsigned grid = mt_grid(ceil_div(B, MT_WAVES), (int64_t)(cus > 0 ? cus : 256) * MT_WAVE_WGS_PER_CU);
+  const size_t esz = scores_dtype == MEANT_F32 ? 4 : 2;
+  const bool vec = meant_aligned16(scores) && ((size_t)lds * esz) % 16 == 0;                  // every row starts on 16 bytes
+  const bool tbf = target_dtype == MEANT_BF16;
+  DISPATCH_DTYPE(scores_dtype, T, {
+    if (vec)
+      hipLaunchKernelGGL((vqa_score_kernel<T, true>), dim3(grid), dim3(MT_WAVE_THREADS), 0, (hipStream_t)stream, (const T*)scores, lds, target, ldt,
+                         tbf, B, (int)C, state);
+    else
+      hipLaunchKernelGGL((vqa_score_kernel<T, false>), dim3(grid), dim3(MT_WAVE_THREADS), 0, (hipStream_t)stream, (const T*)scores, lds, target, ldt,
+                         tbf, B, (int)C, state);
+  });
+  MEANT_LAUNCH_CHECK("vqa_score_update");
+  meant_route_hit(ROUTE_VQA_SCORE);
   return MEANT_OK;
 }

@@ -17,6 +17,10 @@ The paper's other two numbers (train.py:63-65, 103-117): the Matthews coefficien
 the AUROC is a rank statistic and needs the scores, which `auroc.update` keeps on the device (meant_score_capture, one launch) until
 `auroc.statistic()` sorts them there and counts the Mann-Whitney statistic exactly (meant_auroc_rank).  `metric_group` feeds several
 such objects from one `TrainStep(metrics=...)` / `train.evaluate`.
+
+meant_vqa's labels are soft: a float [B, C] row of answer weights per question (utils/custom_datasets.py:214-218).  `f1_metrics`
+refuses them; `vqa_score` counts the number VQA results are reported in, the weight of the predicted answer averaged over the
+questions, the same way: one launch per batch (meant_vqa_score_update), integers only, read by `compute()` / `show()`.
 """
 from __future__ import annotations
 
@@ -389,6 +393,93 @@ class auroc:
     def show(self):
         value = self.compute()
         print(self.set_name + ' AUROC: ', value)
+        return value
+
+
+class vqa_score:
+    """The VQA score of soft labels, counted on the device: the answer weight of the predicted answer, averaged over the questions
+    (the reference's loop hands `out.cpu()` and the float [B, C] target of utils/custom_datasets.py:214-218 to its metrics at
+    vqa.py:223).
+
+    update(pred, target): pred [B, C] float32 / bfloat16 scores (float16 and float64 through `.float()`), target [B, C] floating
+    point of the same shape, float32 / bfloat16 read as they are and any other float type widened to float32; both may be column
+    slices of wider blocks.  The prediction is `pred.argmax(dim=1)` as torch computes it (lowest index on a tie, a NaN above
+    everything); the row scores `target[b, prediction]`.  A row whose weight there is not finite or outside [0, 16] is counted
+    in `invalid_rows()` and left out; a row with a NaN among its scores is scored all the same and counted in `nan_rows()`.  Tensors
+    on the CPU are copied to the current device.  One launch (meant_vqa_score_update), no host read.
+
+    `state` (int64 [4] = sum of the weights in 2^-32 units, rows, nan rows, invalid rows) only ever has integers added: any
+    batching gives the same bits, and the states of several devices may be summed.  `compute()` / `show()` make one copy of it.
+    """
+
+    def __init__(self, set_name: str = "", device=None):
+        self.set_name = set_name
+        self.state: Optional[torch.Tensor] = None        # allocated on the first update's device (or `device`)
+        if device is not None:
+            self._alloc(torch.device(device))
+
+    def _alloc(self, device):
+        self.state = torch.zeros(4, dtype=torch.int64, device=device)
+
+    def update(self, pred: torch.Tensor, target: torch.Tensor) -> None:
+        if not pred.dtype.is_floating_point or not target.dtype.is_floating_point:
+            raise TypeError("vqa_score: pred and target must be floating-point [B, C] tensors (scores and answer weights)")
+        if pred.dim() != 2 or target.shape != pred.shape:
+            raise ValueError(f"vqa_score: scores and weights must both be [B, C], got {tuple(pred.shape)} and {tuple(target.shape)}")
+        if not pred.is_cuda or not target.is_cuda:
+            dev = pred.device if pred.is_cuda else target.device if target.is_cuda else torch.device("cuda", torch.cuda.current_device())
+            pred, target = pred.to(dev), target.to(dev)
+        ops._need_gpu(pred, target)
+        if self.state is None:
+            self._alloc(pred.device)
+        ops._need_gpu(self.state)
+        B, C = pred.shape
+        if B == 0:
+            return
+        (pred, lds), (target, ldt) = (ops._rows(x if x.dtype in (torch.float32, torch.bfloat16) else x.float())     # float16 (exact), float64
+                                      for x in (pred.detach(), target.detach()))
+        check(lib.meant_vqa_score_update(ops._p(pred), lds, ops._dt(pred), ops._p(target), ldt, ops._dt(target), B, C, ops._p(self.state),
+                                         ops._stream()), "vqa_score_update")
+
+    def reset(self) -> None:
+        if self.state is not None:
+            self.state.zero_()
+
+    def merge(self, other: "vqa_score") -> "vqa_score":
+        """add another object's counts to this one's, on this one's device"""
+        if other.state is None:
+            return self
+        if self.state is None:
+            self._alloc(other.state.device)
+        self.state += other.state.to(self.state.device)
+        return self
+
+    def _host_state(self) -> torch.Tensor:
+        return torch.zeros(4, dtype=torch.int64) if self.state is None else self.state.cpu()
+
+    @staticmethod
+    def from_state(state: torch.Tensor) -> torch.Tensor:
+        """the mean score, a 0-d float64 tensor: sum_fx / 2^32 / rows, 0 for no rows (pure torch on the CPU)"""
+        if state.dtype != torch.int64 or state.numel() != 4:
+            raise ValueError(f"vqa_score: the state is int64 [4], got {state.dtype} [{state.numel()}]")
+        s = state.detach().reshape(-1).cpu()
+        rows = s[1].double()
+        return s[0].double() / 4294967296.0 / rows if rows.item() > 0 else torch.zeros((), dtype=torch.float64)
+
+    def compute(self) -> torch.Tensor:
+        return self.from_state(self._host_state())
+
+    def nan_rows(self) -> int:
+        """scored rows with a NaN among their scores"""
+        return 0 if self.state is None else int(self.state[2].item())
+
+    def invalid_rows(self) -> int:
+        """rows left out because the weight at their prediction is not finite or outside [0, 16]"""
+        return 0 if self.state is None else int(self.state[3].item())
+
+    def show(self):
+        value = self.compute()
+        print(self.set_name + ' VQA score: ', value)
         return value
 
 

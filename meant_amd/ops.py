@@ -59,6 +59,15 @@ def _c(t: torch.Tensor) -> torch.Tensor:
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _rows(x: torch.Tensor):
+    """(x, ld) of a 2-D x [B, C] as the row kernels read it: unit column stride and rows at least C apart, so a column slice of a
+    wider block stays in place with ld = its row stride; anything else is made contiguous"""
+    B, C = x.shape
+    if x.stride(1) != 1 or (B > 1 and x.stride(0) < C):
+        x = x.contiguous()
+    return x, (x.stride(0) if B > 1 else max(C, x.stride(0)))
+
+
 # ---------------------------------------------------------------------------------------------
 # weight cache: compute-dtype copy and transposed copy of an fp32 parameter, refreshed when the
 # parameter is updated in place (optimizer step bumps ._version) or replaced.

@@ -40,7 +40,39 @@ class _CEOnProbs(torch.autograd.Function):
         return dp * dloss, None
 
 
+class _CEOnProbsSoft(torch.autograd.Function):
+    """nn.CrossEntropyLoss()(probabilities, class-probability target [B, C]), as vqa.py:173,209 applies it to the Sigmoid output
+    with the answer weights of utils/custom_datasets.py:214-218: two launches (the rows, then their mean), no atomics."""
+
+    @staticmethod
+    def forward(ctx, probs, target):
+        ops._need_gpu(probs, target)
+        p = probs if probs.dtype == torch.float32 else probs.float()
+        t = target if target.dtype in (torch.float32, torch.bfloat16) else target.float()
+        B, C = p.shape
+        (p, ldp), (t, ldt) = ops._rows(p), ops._rows(t)                     # column slices of wider blocks are read in place
+        out = torch.empty(B + 1, device=p.device, dtype=torch.float32)      # row_loss [B], then the loss
+        dp = torch.empty(B, C, device=p.device, dtype=torch.float32)
+        check(lib.meant_ce_probs_soft(ops._p(p), ldp, ops._p(t), ldt, ops._dt(t), ops._p(out), out.data_ptr() + 4 * B, ops._p(dp), C, B, C,
+                                      ops._stream()), "ce_probs_soft")
+        ctx.save_for_backward(dp)
+        return out[B]
+
+    @staticmethod
+    def backward(ctx, dloss):
+        (dp,) = ctx.saved_tensors
+        return dp * dloss, None
+
+
 def cross_entropy_on_probs(probs: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """nn.CrossEntropyLoss()(probs, target) of probabilities [B, C]: target [B] of class indices (any integer type), or a
+    floating-point [B, C] of class probabilities / answer weights (rows need not sum to 1, may be all zero), read in place as
+    float32 or bfloat16 with its row stride, any other float type widened to float32."""
+    if target.dtype.is_floating_point and target.dim() == 2:
+        if target.shape != probs.shape:
+            raise ValueError(f"cross_entropy_on_probs: a class-probability target must have the shape of probs {tuple(probs.shape)}, "
+                             f"got {tuple(target.shape)}")
+        return _CEOnProbsSoft.apply(probs, target)
     return _CEOnProbs.apply(probs, target)
 
 
@@ -144,7 +176,11 @@ class CosineWarmRestarts:
 
 
 class TrainStep:
-    """forward -> CE on probabilities -> backward (+ overlapped gradient all-reduce) -> clip + AdamW."""
+    """forward -> CE on probabilities -> backward (+ overlapped gradient all-reduce) -> clip + AdamW.
+
+    step(*inputs, target=...): target is [B] class indices (in_loop_train.py:232) or a floating-point [B, C] of class
+    probabilities / answer weights, the soft labels of the VQA loop (vqa.py:173,209) -- cross_entropy_on_probs picks the loss
+    by the target's type; micro-batches slice either kind along the batch axis."""
 
     def __init__(self, model: torch.nn.Module, lr: float = 5e-5, weight_decay: float = 1e-2, max_grad_norm: float = 1.0,
                  bucket_mb: float = 64.0, direct_grads: bool = True, micro_batches: int = 1, metrics=None):
@@ -154,8 +190,9 @@ class TrainStep:
         direct_grads (GradReducer): parameter gradients are accumulated straight into the flat buckets by the backward
         kernels; pass False if the model's parameters are also differentiated outside this step (torch.autograd.grad,
         several backward passes per optimizer step without reducer.no_sync())
-        metrics (meant_amd.metrics.f1_metrics or None): when given, every step adds its batch to it -- metrics.update(out, target)
-        on the detached output, one more launch and no host read; None leaves the step's launches as they are"""
+        metrics (meant_amd.metrics.f1_metrics, vqa_score for soft [B, C] targets, a metric_group, or None): when given, every step
+        adds its batch to it -- metrics.update(out, target) on the detached output, one more launch and no host read; None leaves
+        the step's launches as they are"""
         self.model = model
         self.reducer = GradReducer(model.parameters(), bucket_mb=bucket_mb, direct_grads=direct_grads)
         self.opt = FusedAdamW(self.reducer, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
