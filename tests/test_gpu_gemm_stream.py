@@ -5,7 +5,12 @@ q|k|v projection and the vocabulary GEMM of the MLM head.  Reference: fp32 on th
 (the arithmetic of meant/meant.py:59-64,101-107 nn.Linear call sites, meant/attention.py:36-40, pretrain_mlm.py:74-89,160).
 
 Every case asserts its ROUTE through the library's launch counters, so that a change of the dispatch thresholds cannot
-silently orphan these tests again."""
+silently orphan these tests again.
+
+Element-exactness is not tested here: the bounds below are a few percent of the largest reference value, far above one term of a
+reduction (a dW that leaves out one of 36864 token rows passes them).  tests/test_gpu_gemm_exact.py runs every GEMM route on
+small-integer operands against an int64 reference at zero tolerance, at the smallest shape that reaches each route; this file keeps
+its role of testing the workload's own shapes."""
 import math
 
 import numpy as np
