@@ -233,21 +233,32 @@ def _rotate_pairs(t, a, b):
     return torch.cat((out.to(t.dtype), t[..., R:]), dim=-1)
 
 
-def learned_rotary_attention(x, mod, rot: RotaryEmbedding, key_mask, causal: bool, pre=None):
-    """softmax((rot q)(rot k)^T / sqrt(dim) [+ mask]) v for a rotary embedding with LEARNED frequencies: the q|k|v projection as one GEMM
-    (ops.linear), the rotation as tensor ops whose tables carry the gradient to `rot.freqs`, the attention core (HIP) on the rotated
-    buffer without tables.  `mod` holds the q / v / k Linears under the reference's names (the one called `v` produces the keys)."""
-    G, S, d = x.shape
-    H = mod.num_heads
+def _qkv_params(mod, pre=None):
+    """(wqkv [3D, d], bqkv [3D]) in the order (query, KEY, VALUE) from the q / v / k Linears `mod` holds under the reference's names
+    (the one called `v` produces the keys); pre: an nn.Linear applied to x right before them, composed in (ops.compose_linear)"""
     wqkv = torch.cat([mod.q.weight, mod.v.weight, mod.k.weight], dim=0)
     bqkv = torch.cat([mod.q.bias, mod.v.bias, mod.k.bias], dim=0)
     if pre is not None:
         wqkv, bqkv = ops.compose_linear(pre.weight, pre.bias, wqkv, bqkv)
-    D = wqkv.shape[0] // 3
-    qkv = ops.linear(x.reshape(G * S, d), wqkv, bqkv).view(G, S, 3, H, D // H)
+    return wqkv, bqkv
+
+
+def _rotate_learned(qkv, rot: RotaryEmbedding, G, S, H, D):
+    """packed q|k|v [G*S, 3D] with q and k rotated by tensor ops whose tables carry the gradient to `rot.freqs`"""
+    q5 = qkv.view(G, S, 3, H, D // H)
     qa, qb, ka, kb = rot.tables_autograd(S)
-    q, k = _rotate_pairs(qkv[:, :, 0], qa, qb), _rotate_pairs(qkv[:, :, 1], ka, kb)
-    packed = torch.stack((q, k, qkv[:, :, 2]), dim=2).reshape(G * S, 3 * D)
+    return torch.stack((_rotate_pairs(q5[:, :, 0], qa, qb), _rotate_pairs(q5[:, :, 1], ka, kb), q5[:, :, 2]), dim=2).reshape(G * S, 3 * D)
+
+
+def learned_rotary_attention(x, mod, rot: RotaryEmbedding, key_mask, causal: bool, pre=None):
+    """softmax((rot q)(rot k)^T / sqrt(dim) [+ mask]) v for a rotary embedding with LEARNED frequencies: the q|k|v projection as one GEMM
+    (ops.linear), the rotation as tensor ops whose tables carry the gradient to `rot.freqs`, the attention core (HIP) on the rotated
+    buffer without tables."""
+    G, S, d = x.shape
+    H = mod.num_heads
+    wqkv, bqkv = _qkv_params(mod, pre)
+    D = wqkv.shape[0] // 3
+    packed = _rotate_learned(ops.linear(x.reshape(G * S, d), wqkv, bqkv), rot, G, S, H, D)
     return ops.attention_core(packed, G, S, H, 1.0 / math.sqrt(D), None, causal, key_mask).view(G, S, D)
 
 
@@ -257,48 +268,57 @@ def score_dropout_attention(x, mod, rot: RotaryEmbedding, key_mask, causal: bool
     rotary by tables as everywhere else.  With learned rotary frequencies the rotation is done here, differentiably."""
     G, S, d = x.shape
     H = mod.num_heads
-    wqkv = torch.cat([mod.q.weight, mod.v.weight, mod.k.weight], dim=0)
-    bqkv = torch.cat([mod.q.bias, mod.v.bias, mod.k.bias], dim=0)
-    if pre is not None:
-        wqkv, bqkv = ops.compose_linear(pre.weight, pre.bias, wqkv, bqkv)
+    wqkv, bqkv = _qkv_params(mod, pre)
     D = wqkv.shape[0] // 3
     qkv = ops.linear(x.reshape(G * S, d), wqkv, bqkv)
     tables = None
     if rot is not None and getattr(rot, 'learned_freq', False):
-        q5 = qkv.view(G, S, 3, H, D // H)
-        qa, qb, ka, kb = rot.tables_autograd(S)
-        qkv = torch.stack((_rotate_pairs(q5[:, :, 0], qa, qb), _rotate_pairs(q5[:, :, 1], ka, kb), q5[:, :, 2]), dim=2).reshape(G * S, 3 * D)
+        qkv = _rotate_learned(qkv, rot, G, S, H, D)
     elif rot is not None:
         tables = rot.tables(S, x.device)
     return ops.attention_core_score_dropout(qkv, G, S, H, 1.0 / math.sqrt(D), p, seed, tables, causal, key_mask).view(G, S, D)
 
 
 # ------------------------------------------------------------------------------------------
-class attention(nn.Module):
-    """meant/attention.py:11-62: MHA over patches, pixel rotary on q,k, no mask, scale 1/sqrt(dim).
-    The Linear named `v` produces KEYS and the one named `k` produces VALUES (:36-37)."""
+class _MHA(nn.Module):
+    """what `attention`, `xPosAttention` and `temporal` share: the reference's constructor body (parameters register in its order:
+    multi_mad, q, v, k; `rot` = (attribute name, RotaryEmbedding) sits where the reference assigns it, behind `dropout`) and the
+    fused route of the two sequence modules.  The Linear named `v` produces KEYS and the one named `k` produces VALUES
+    (meant/attention.py:36-37)."""
 
-    def __init__(self, num_heads, dim, pos_emb: RotaryEmbedding, mask=False, droput=0.):
+    def __init__(self, num_heads, dim, mask, droput, rot=None):
         super().__init__()
         self.num_heads, self.dim = num_heads, dim
         self.Dh = int(dim / num_heads)
         self.dropout = nn.Dropout(droput)
-        self.pos_emb = pos_emb
+        if rot is not None:
+            setattr(self, *rot)
         self.mask = mask
         self.softmax = nn.Softmax(dim=-1)
         self.multi_mad = Linear(self.num_heads * self.Dh, self.dim)
-        self.q = Linear(self.dim, self.Dh * self.num_heads)
-        self.v = Linear(self.dim, self.Dh * self.num_heads)
-        self.k = Linear(self.dim, self.Dh * self.num_heads)
+        self.atten_size = self.Dh * self.num_heads
+        self.q = Linear(self.dim, self.atten_size)
+        self.v = Linear(self.dim, self.atten_size)
+        self.k = Linear(self.dim, self.atten_size)
 
-    def core(self, x, pre=None):
+    def _fused(self, x, rot, key_mask, pre):
         """pre: an nn.Linear that the caller would have applied to x right before this module (composed into q/k/v)"""
-        if self.pos_emb is not None and getattr(self.pos_emb, 'learned_freq', False):
-            return learned_rotary_attention(x, self, self.pos_emb, None, bool(self.mask), pre)
-        tables = self.pos_emb.tables(x.shape[1], x.device, ops.run_head_dim(self.Dh, x.dtype)) if self.pos_emb is not None else None
+        if rot is not None and getattr(rot, 'learned_freq', False):
+            return learned_rotary_attention(x, self, rot, key_mask, bool(self.mask), pre)
+        tables = rot.tables(x.shape[1], x.device, ops.run_head_dim(self.Dh, x.dtype)) if rot is not None else None
         prew = (pre.weight, pre.bias) if pre is not None else None
         return ops.qkv_attention(x, self.q.weight, self.q.bias, self.v.weight, self.v.bias, self.k.weight, self.k.bias,
-                                 tables, None, bool(self.mask), self.num_heads, pre=prew)
+                                 tables, key_mask, bool(self.mask), self.num_heads, pre=prew)
+
+
+class attention(_MHA):
+    """meant/attention.py:11-62: MHA over patches, pixel rotary on q,k, no mask, scale 1/sqrt(dim)."""
+
+    def __init__(self, num_heads, dim, pos_emb: RotaryEmbedding, mask=False, droput=0.):
+        super().__init__(num_heads, dim, mask, droput, ('pos_emb', pos_emb))
+
+    def core(self, x, pre=None):
+        return self._fused(x, self.pos_emb, None, pre)
 
     def forward(self, input):
         out = self.multi_mad(self.core(input))
@@ -307,52 +327,27 @@ class attention(nn.Module):
         return out
 
 
-class xPosAttention(nn.Module):
+class xPosAttention(_MHA):
     """meant/xPosAttention.py:11-66: as `attention` with xPos on q,k (:39), always-causal mask
     (:43-50) and the additive (1-mask)*-1e9 key-padding term (:54-56)."""
 
     def __init__(self, num_heads, dim, xPos: RotaryEmbedding, mask=True, droput=0.):
-        super().__init__()
-        self.num_heads, self.dim = num_heads, dim
-        self.Dh = int(dim / num_heads)
-        self.dropout = nn.Dropout(droput)
-        self.xPos = xPos
-        self.mask = mask
-        self.softmax = nn.Softmax(dim=-1)
-        self.multi_mad = Linear(self.num_heads * self.Dh, self.dim)
-        self.q = Linear(self.dim, self.Dh * self.num_heads)
-        self.v = Linear(self.dim, self.Dh * self.num_heads)
-        self.k = Linear(self.dim, self.Dh * self.num_heads)
+        super().__init__(num_heads, dim, mask, droput, ('xPos', xPos))
 
     def core(self, x, attention_mask=None, pre=None):
         if self.training and self.dropout.p > 0:              # xPosAttention.py:59: dropout on the SCORES (no reference model sets it)
             return score_dropout_attention(x, self, self.xPos, attention_mask, bool(self.mask), float(self.dropout.p), _seed(), pre)
-        if getattr(self.xPos, 'learned_freq', False):
-            return learned_rotary_attention(x, self, self.xPos, attention_mask, bool(self.mask), pre)
-        tables = self.xPos.tables(x.shape[1], x.device, ops.run_head_dim(self.Dh, x.dtype))
-        prew = (pre.weight, pre.bias) if pre is not None else None
-        return ops.qkv_attention(x, self.q.weight, self.q.bias, self.v.weight, self.v.bias, self.k.weight, self.k.bias,
-                                 tables, attention_mask, bool(self.mask), self.num_heads, pre=prew)
+        return self._fused(x, self.xPos, attention_mask, pre)
 
     def forward(self, input, attention_mask=None):
         return self.multi_mad(self.core(input, attention_mask))
 
 
-class temporal(nn.Module):
+class temporal(_MHA):
     """meant/temporal.py:12-60: the query is the last lag step only (:39), keys/values all L steps."""
 
     def __init__(self, num_heads, dim, mask=False, droput=0.):
-        super().__init__()
-        self.num_heads, self.dim = num_heads, dim
-        self.Dh = int(dim / num_heads)
-        self.dropout = nn.Dropout(droput)
-        self.mask = mask
-        self.softmax = nn.Softmax(dim=-1)
-        self.multi_mad = Linear(self.num_heads * self.Dh, self.dim)
-        self.atten_size = self.Dh * self.num_heads
-        self.q = Linear(self.dim, self.atten_size)
-        self.v = Linear(self.dim, self.atten_size)
-        self.k = Linear(self.dim, self.atten_size)
+        super().__init__(num_heads, dim, mask, droput)
 
     def forward(self, input):
         o = ops.temporal_attention(input, self.q.weight, self.q.bias, self.v.weight, self.v.bias, self.k.weight, self.k.bias,
@@ -363,6 +358,39 @@ class temporal(nn.Module):
 # ------------------------------------------------------------------------------------------
 def _seed() -> int:
     return int(torch.randint(0, 2 ** 62, (1,)).item())
+
+
+def _encoder_layer(e, e2, x, margs, p1, p2, pool, fold):
+    """the body of both encoder layers (meant/meant.py:55-75, :98-120): e / e2 = the layer's two ModuleLists, whose last entries are
+    the Linears that close each half; margs: what the attention module takes after x (the language layer's mask); p1 / p2: the
+    dropout probabilities fused into e[3] and e2[3].  The seeds are drawn here, in this order and only for p > 0: e[3]'s after
+    the attention (whose score dropout draws its own), e2[3]'s after x1 -- the order fixes every mask, and recomputation under
+    torch.utils.checkpoint replays it.
+    pool=True: return (h, res) instead of e2[-1](h) + res, for ops.pool_linear_cat.
+    fold: the stack's RMSNorm-into-Linear decision (an explicit argument so that a recomputation under
+    torch.utils.checkpoint repeats the forward's path); None = by ops.fold_wanted()"""
+    n, res = ops.rmsnorm_fork(x, e[0].scale, e[0].eps, any_width=True)      # residual gradient is folded into this norm's backward
+    if COMPOSE_PRE_LINEAR and e[1].bias is not None:
+        h = e[2].multi_mad(e[2].core(n, *margs, pre=e[1]))             # Linear(d,d) composed into the q/k/v projections
+    else:
+        h = e[2](e[1](n), *margs)
+    h = e[3](h, drop_p=p1, seed=_seed() if p1 > 0 else 0)
+    x1 = e[-1](h, residual=res)
+    fold = ops.norm_linear_ok(x1, e2[1].weight, fold)                 # encode2[0] rides encode2[1]'s GEMM as a per-row factor
+    seed2 = _seed() if p2 > 0 else 0
+    if pool and ops.pooled_norm_ok(x1, x1.shape[1]):             # the two norms beside the mean-pool emit the means themselves
+        if fold:
+            return ops.norm_linear_gelu_norm_pooled(x1, e2[0].scale, e2[0].eps, e2[1].weight, e2[1].bias, e2[3].scale, e2[3].eps, p2, seed2)
+        n, xm = ops.rmsnorm_fork_pooled(x1, e2[0].scale, e2[0].eps)
+        return ops.linear_gelu_rmsnorm_pooled(n, e2[1].weight, e2[1].bias, e2[3].scale, e2[3].eps, p2, seed2), xm
+    if fold:
+        h, res = ops.norm_linear_gelu_norm(x1, e2[0].scale, e2[0].eps, e2[1].weight, e2[1].bias, e2[3].scale, e2[3].eps, p2, seed2)
+    else:
+        n, res = ops.rmsnorm_fork(x1, e2[0].scale, e2[0].eps, any_width=True)
+        h = ops.linear_gelu_rmsnorm(n, e2[1].weight, e2[1].bias, e2[3].scale, e2[3].eps, p2, seed2, any_width=True)
+    if pool:
+        return h, res
+    return e2[-1](h, residual=res)
 
 
 class visionEncoder(nn.Module):
@@ -377,31 +405,8 @@ class visionEncoder(nn.Module):
         self.encode2 = nn.ModuleList([RMSNorm(dim), Linear(dim, dim), nn.GELU(), RMSNorm(dim), Linear(dim, dim)])
 
     def forward(self, input, pool: bool = False, fold=None):
-        """pool=True: return (h, res) instead of encode2[-1](h) + res, for ops.pool_linear_cat.
-        fold: the stack's RMSNorm-into-Linear decision (an explicit argument so that a recomputation under
-        torch.utils.checkpoint repeats the forward's path); None = by ops.fold_wanted()"""
-        e, e2 = self.encode, self.encode2
-        n, res = ops.rmsnorm_fork(input, e[0].scale, e[0].eps, any_width=True)      # residual gradient is folded into this norm's backward
-        if COMPOSE_PRE_LINEAR and e[1].bias is not None:
-            h = e[2].multi_mad(e[2].core(n, pre=e[1]))               # Linear(d,d) composed into the q/k/v projections
-        else:
-            h = e[2](e[1](n))
-        h = e[3](h)
-        x1 = e[4](h, residual=res)
-        fold = ops.norm_linear_ok(x1, e2[1].weight, fold)                 # encode2[0] rides encode2[1]'s GEMM as a per-row factor
-        if pool and ops.pooled_norm_ok(x1, x1.shape[1]):             # the two norms beside the mean-pool emit the means themselves
-            if fold:
-                return ops.norm_linear_gelu_norm_pooled(x1, e2[0].scale, e2[0].eps, e2[1].weight, e2[1].bias, e2[3].scale, e2[3].eps)
-            n, xm = ops.rmsnorm_fork_pooled(x1, e2[0].scale, e2[0].eps)
-            return ops.linear_gelu_rmsnorm_pooled(n, e2[1].weight, e2[1].bias, e2[3].scale, e2[3].eps), xm
-        if fold:
-            h, res = ops.norm_linear_gelu_norm(x1, e2[0].scale, e2[0].eps, e2[1].weight, e2[1].bias, e2[3].scale, e2[3].eps)
-        else:
-            n, res = ops.rmsnorm_fork(x1, e2[0].scale, e2[0].eps, any_width=True)
-            h = ops.linear_gelu_rmsnorm(n, e2[1].weight, e2[1].bias, e2[3].scale, e2[3].eps, any_width=True)
-        if pool:
-            return h, res
-        return e2[4](h, residual=res)
+        """pool, fold: see _encoder_layer"""
+        return _encoder_layer(self.encode, self.encode2, input, (), 0.0, 0.0, pool, fold)
 
 
 class languageEncoder(nn.Module):
@@ -417,32 +422,10 @@ class languageEncoder(nn.Module):
         self.encode2 = nn.ModuleList([RMSNorm(dim), Linear(dim, dim), nn.GELU(), RMSNorm(dim), nn.Dropout(), Linear(dim, dim)])
 
     def forward(self, input, attention_mask=None, pool: bool = False, fold=None):
-        """pool=True: return (h, res) instead of encode2[-1](h) + res, for ops.pool_linear_cat; fold: as visionEncoder.forward"""
+        """pool, fold: see _encoder_layer"""
         e, e2 = self.encode, self.encode2
-        p1 = e[4].p if self.training else 0.0
-        p2 = e2[4].p if self.training else 0.0
-        n, res = ops.rmsnorm_fork(input, e[0].scale, e[0].eps, any_width=True)
-        if COMPOSE_PRE_LINEAR and e[1].bias is not None:
-            h = e[2].multi_mad(e[2].core(n, attention_mask, pre=e[1]))
-        else:
-            h = e[2](e[1](n), attention_mask)
-        h = e[3](h, drop_p=p1, seed=_seed() if p1 > 0 else 0)
-        x1 = e[5](h, residual=res)
-        fold = ops.norm_linear_ok(x1, e2[1].weight, fold)                 # encode2[0] rides encode2[1]'s GEMM as a per-row factor
-        seed2 = _seed() if p2 > 0 else 0
-        if pool and ops.pooled_norm_ok(x1, x1.shape[1]):             # the two norms beside the mean-pool emit the means themselves
-            if fold:
-                return ops.norm_linear_gelu_norm_pooled(x1, e2[0].scale, e2[0].eps, e2[1].weight, e2[1].bias, e2[3].scale, e2[3].eps, p2, seed2)
-            n, xm = ops.rmsnorm_fork_pooled(x1, e2[0].scale, e2[0].eps)
-            return ops.linear_gelu_rmsnorm_pooled(n, e2[1].weight, e2[1].bias, e2[3].scale, e2[3].eps, p2, seed2), xm
-        if fold:
-            h, res = ops.norm_linear_gelu_norm(x1, e2[0].scale, e2[0].eps, e2[1].weight, e2[1].bias, e2[3].scale, e2[3].eps, p2, seed2)
-        else:
-            n, res = ops.rmsnorm_fork(x1, e2[0].scale, e2[0].eps, any_width=True)
-            h = ops.linear_gelu_rmsnorm(n, e2[1].weight, e2[1].bias, e2[3].scale, e2[3].eps, p2, seed2, any_width=True)
-        if pool:
-            return h, res
-        return e2[5](h, residual=res)
+        p1, p2 = (e[4].p, e2[4].p) if self.training else (0.0, 0.0)
+        return _encoder_layer(e, e2, input, (attention_mask,), p1, p2, pool, fold)
 
 
 class temporalEncoder(nn.Module):

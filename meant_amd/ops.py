@@ -7,6 +7,7 @@ fp32 (master weights), gradients of parameters are produced in fp32.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import os
 import threading
@@ -66,6 +67,19 @@ def _rows(x: torch.Tensor):
     if x.stride(1) != 1 or (B > 1 and x.stride(0) < C):
         x = x.contiguous()
     return x, (x.stride(0) if B > 1 else max(C, x.stride(0)))
+
+
+def _ws(nbytes: int, device, floor: int = 0):
+    """uint8 scratch of max(nbytes, floor) bytes for one library call, or None where that is zero: the call gets NULL either
+    way (the data pointer of an empty tensor is NULL too)"""
+    n = max(int(nbytes), floor)
+    return torch.empty(n, device=device, dtype=torch.uint8) if n else None
+
+
+def _rot(tables):
+    """(qa, qb, ka, kb, R) of rotary tables (qa, qb, ka, kb) float [S, R]; four None and R = 0 without tables"""
+    qa, qb, ka, kb = tables if tables is not None else (None, None, None, None)
+    return qa, qb, ka, kb, (qa.shape[1] if qa is not None else 0)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -180,13 +194,17 @@ def _rmsnorm_fwd_raw(x, scale, eps, drop_p, seed):
     return y, sc, rinv
 
 
-def _rmsnorm_bwd_raw(dy, x, sc, rinv, eps, drop_p, seed, dres=None, gelu_pre=None):
+def _norm_bwd_bufs(x):
+    """what every norm backward over the rows of x [..., d] allocates: (dx, float [d] for the gain's gradient, workspace, its
+    bytes, rows, d)"""
     d = x.shape[-1]
     rows = x.numel() // d
-    dx = torch.empty_like(x)
-    dscale = torch.empty(d, device=x.device, dtype=torch.float32)
     wsb = lib.meant_rmsnorm_bwd_ws(rows, d)
-    ws = torch.empty(wsb, device=x.device, dtype=torch.uint8)
+    return torch.empty_like(x), torch.empty(d, device=x.device, dtype=torch.float32), _ws(wsb, x.device), wsb, rows, d
+
+
+def _rmsnorm_bwd_raw(dy, x, sc, rinv, eps, drop_p, seed, dres=None, gelu_pre=None):
+    dx, dscale, ws, wsb, rows, d = _norm_bwd_bufs(x)
     check(lib.meant_rmsnorm_bwd(_p(dy), _p(x), _p(sc), _p(rinv), _p(dx), _p(dscale), rows, d, eps, drop_p, seed, _p(dres), _p(gelu_pre),
                                 _dt(x), _p(ws), wsb, _stream()), "rmsnorm_bwd")
     return dx, dscale
@@ -239,13 +257,8 @@ class _RMSNormPartial(torch.autograd.Function):
         x, sc, rinv = ctx.saved_tensors
         d_part, eps, has_off = ctx.args
         dy = _c(dy)
-        d = x.shape[-1]
-        rows = x.numel() // d
-        dx = torch.empty_like(x)
-        dscale = torch.empty(d, device=x.device, dtype=torch.float32)
+        dx, dscale, ws, wsb, rows, d = _norm_bwd_bufs(x)
         doff = torch.empty(d, device=x.device, dtype=torch.float32) if has_off else None
-        wsb = lib.meant_rmsnorm_bwd_ws(rows, d)
-        ws = torch.empty(wsb, device=x.device, dtype=torch.uint8)
         check(lib.meant_rmsnorm_partial_bwd(_p(dy), _p(x), _p(sc), _p(rinv), _p(dx), _p(dscale), _p(doff), rows, d, d_part, eps, _dt(x),
                                             _p(ws), wsb, _stream()), "rmsnorm_partial_bwd")
         return dx, dscale, doff, None, None
@@ -351,12 +364,7 @@ def pooled_norm_ok(x, group_rows: int) -> bool:
 
 
 def _rmsnorm_bwd_pooled_raw(dy, dy_pooled, x, sc, rinv, S, eps, drop_p, seed, dres, dres_pooled, gelu_pre):
-    d = x.shape[-1]
-    rows = x.numel() // d
-    dx = torch.empty_like(x)
-    dscale = torch.empty(d, device=x.device, dtype=torch.float32)
-    wsb = lib.meant_rmsnorm_bwd_ws(rows, d)
-    ws = torch.empty(wsb, device=x.device, dtype=torch.uint8)
+    dx, dscale, ws, wsb, rows, d = _norm_bwd_bufs(x)
     check(lib.meant_rmsnorm_bwd_pooled(_p(dy), int(dy_pooled), _p(x), _p(sc), _p(rinv), _p(dx), _p(dscale), rows, d, S, eps, drop_p, seed,
                                        _p(dres), int(dres_pooled), _p(gelu_pre), _dt(x), _p(ws), wsb, _stream()), "rmsnorm_bwd_pooled")
     return dx, dscale
@@ -415,12 +423,7 @@ class _GeluRMSNormPooled(torch.autograd.Function):
     def backward(ctx, dhm):
         pre, sc, rinv = ctx.saved_tensors
         eps, drop_p, seed = ctx.args
-        d = pre.shape[-1]
-        rows = pre.numel() // d
-        dpre = torch.empty_like(pre)
-        dscale = torch.empty(d, device=pre.device, dtype=torch.float32)
-        wsb = lib.meant_rmsnorm_bwd_ws(rows, d)
-        ws = torch.empty(wsb, device=pre.device, dtype=torch.uint8)
+        dpre, dscale, ws, wsb, rows, d = _norm_bwd_bufs(pre)
         dh = _c(dhm.float())
         check(lib.meant_rmsnorm_bwd_pooled(_p(dh), 1, None, _p(sc), _p(rinv), _p(dpre), _p(dscale), rows, d, ctx.S, eps, drop_p, seed,
                                            None, 0, _p(pre), _dt(pre), _p(ws), wsb, _stream()), "rmsnorm_bwd_pooled")
@@ -539,6 +542,35 @@ def _bias_grad_target(ctx, N, device):
     return torch.zeros(N, device=device, dtype=torch.float32), False
 
 
+def _fold_setup(ctx, weight, bias, gain0):
+    """forward set-up of both folded chains: W' = W diag(g0) and its bf16 copy, the bias (zeros without one: the chained norm
+    backward reads it), the parameters kept for, and claimed from, the gradient sinks"""
+    w_f, g_f, wp, wp_c = _scaled_weight(weight, gain0)
+    bias_f = _c(bias.detach().float()) if bias is not None else torch.zeros(weight.shape[0], device=weight.device, dtype=torch.float32)
+    ctx.weight, ctx.bias = weight, bias
+    _claim(weight, "linear"); _claim(bias, "linear")
+    return w_f, g_f, wp, wp_c, bias_f
+
+
+def _fold_backward(ctx, saved, dy, dy_pooled, a, S, dres2, dres_pooled):
+    """backward of both folded chains from the gradient dy of RMSNorm_3's output -- per token with the activation a, or
+    dy_pooled = 1: per sequence of S tokens, the activation formed from the pre-activation on load -- down to x:
+    meant_rmsnorm_bwd_chain (the bias gradient lands in its sink or a fresh vector), then the folded Linear's two GEMMs.
+    Returns (dx2, dg0, dW or None, db or None, dg3)"""
+    x2, r0, pre, sc3, rinv3, wp, w_f, g_f, bias_f = saved
+    eps0, eps3, drop_p, seed = ctx.args[:4]
+    K = x2.shape[1]
+    dpre_s, dscale3, ws, wsb, M, N = _norm_bwd_bufs(pre)
+    kcoef = torch.empty(M, device=x2.device, dtype=torch.float32)
+    db, db_sunk = _bias_grad_target(ctx, N, x2.device)
+    check(lib.meant_rmsnorm_bwd_chain(_p(dy), dy_pooled, _p(a), _p(sc3), _p(rinv3), _p(dpre_s), _p(dscale3), M, N, S, eps3, drop_p, seed, _p(pre),
+                                      _p(r0), _p(bias_f), eps0, K, _p(kcoef), _p(db), _dt(x2), _p(ws), wsb, _stream()), "rmsnorm_bwd_chain")
+    if db_sunk:
+        _sink_of(ctx.bias, "linear").report(ctx.bias)
+    dx, dw, dg0 = _norm_linear_backward(ctx, dpre_s, kcoef, x2, wp, w_f, g_f, dres2, dres_pooled, S)
+    return dx, dg0, dw, (None if (db_sunk or ctx.bias is None) else db), dscale3
+
+
 class _NormLinearGeluNorm(torch.autograd.Function):
     """(dropout(RMSNorm_3(gelu(Linear(RMSNorm_0(x))))), x): the encode2 chain of an encoder layer up to its last Linear
     (meant/meant.py:61-64, :103-107) with RMSNorm_0 folded into the Linear; the second output is x itself, the residual
@@ -551,8 +583,7 @@ class _NormLinearGeluNorm(torch.autograd.Function):
         K = shp[-1]
         x2 = _c(x).view(-1, K)
         M, N = x2.shape[0], weight.shape[0]
-        w_f, g_f, wp, wp_c = _scaled_weight(weight, gain0)
-        bias_f = _c(bias.detach().float()) if bias is not None else torch.zeros(N, device=x.device, dtype=torch.float32)
+        w_f, g_f, wp, wp_c, bias_f = _fold_setup(ctx, weight, bias, gain0)
         r0 = torch.empty(M, device=x.device, dtype=torch.float32)
         check(lib.meant_rmsnorm_stats(_p(x2), _p(r0), M, K, eps0, _dt(x2), _stream()), "rmsnorm_stats")
         a = torch.empty((M, N), device=x.device, dtype=x.dtype)
@@ -560,34 +591,20 @@ class _NormLinearGeluNorm(torch.autograd.Function):
         check(lib.meant_linear_fwd_rowscale(_p(x2), K, _p(wp_c), _p(bias_f), _p(r0), None, 0, _p(a), N, _p(pre), M, N, K, EPI_GELU,
                                             _dt(x2), _stream()), "linear_fwd_rowscale")
         y, sc3, rinv3 = _rmsnorm_fwd_raw(a, gain3, eps3, drop_p, seed)
-        ctx.weight, ctx.bias = weight, bias
-        _claim(weight, "linear"); _claim(bias, "linear")
-        ctx.save_for_backward(x2, r0, a, pre, sc3, rinv3, wp, w_f, g_f, bias_f)
+        ctx.save_for_backward(x2, r0, pre, sc3, rinv3, wp, w_f, g_f, bias_f, a)
         ctx.args = (eps0, eps3, drop_p, seed, shp)
         return y.view(*shp[:-1], N), x.view_as(x)
 
     @staticmethod
     def backward(ctx, dy, dres):
-        x2, r0, a, pre, sc3, rinv3, wp, w_f, g_f, bias_f = ctx.saved_tensors
-        eps0, eps3, drop_p, seed, shp = ctx.args
-        M, K = x2.shape
-        N = wp.shape[0]
+        *saved, a = ctx.saved_tensors
+        M, K = saved[0].shape
         dres2 = _c(dres).view(M, K) if dres is not None else None
         if dy is None:
             return dres, None, None, None, None, None, None, None, None
-        dy2 = _c(dy).view(M, N)
-        dpre_s = torch.empty_like(pre)
-        kcoef = torch.empty(M, device=x2.device, dtype=torch.float32)
-        dscale3 = torch.empty(N, device=x2.device, dtype=torch.float32)
-        db, db_sunk = _bias_grad_target(ctx, N, x2.device)
-        wsb = lib.meant_rmsnorm_bwd_ws(M, N)
-        ws = torch.empty(wsb, device=x2.device, dtype=torch.uint8)
-        check(lib.meant_rmsnorm_bwd_chain(_p(dy2), 0, _p(a), _p(sc3), _p(rinv3), _p(dpre_s), _p(dscale3), M, N, 1, eps3, drop_p, seed, _p(pre),
-                                          _p(r0), _p(bias_f), eps0, K, _p(kcoef), _p(db), _dt(x2), _p(ws), wsb, _stream()), "rmsnorm_bwd_chain")
-        if db_sunk:
-            _sink_of(ctx.bias, "linear").report(ctx.bias)
-        dx, dw, dg0 = _norm_linear_backward(ctx, dpre_s, kcoef, x2, wp, w_f, g_f, dres2, None, 1)
-        return dx.view(shp), dg0, None, dw, (None if (db_sunk or ctx.bias is None) else db), dscale3, None, None, None
+        dy2 = _c(dy).view(M, a.shape[1])
+        dx, dg0, dw, db, dscale3 = _fold_backward(ctx, saved, dy2, 0, a, 1, dres2, None)
+        return dx.view(ctx.args[4]), dg0, None, dw, db, dscale3, None, None, None
 
 
 def norm_linear_gelu_norm(x, gain0, eps0, weight, bias, gain3, eps3, drop_p=0.0, seed=0):
@@ -606,8 +623,7 @@ class _NormLinearGeluNormPooled(torch.autograd.Function):
         G, S, K = x.shape
         M, N = G * S, weight.shape[0]
         x2 = x.view(M, K)
-        w_f, g_f, wp, wp_c = _scaled_weight(weight, gain0)
-        bias_f = _c(bias.detach().float()) if bias is not None else torch.zeros(N, device=x.device, dtype=torch.float32)
+        w_f, g_f, wp, wp_c, bias_f = _fold_setup(ctx, weight, bias, gain0)
         r0 = torch.empty(M, device=x.device, dtype=torch.float32)
         xm = torch.empty((G, K), device=x.device, dtype=torch.float32)
         check(lib.meant_rmsnorm_fwd_pooled(_p(x2), _p(g_f), None, _p(r0), _p(xm), M, K, S, 1, 0, eps0, 0.0, 0, _dt(x2), _stream()),
@@ -620,33 +636,18 @@ class _NormLinearGeluNormPooled(torch.autograd.Function):
         sc3 = _c(gain3.detach().float())
         check(lib.meant_rmsnorm_fwd_pooled(_p(pre), _p(sc3), None, _p(rinv3), _p(hm), M, N, S, 0, 1, eps3, drop_p, seed, _dt(pre), _stream()),
               "rmsnorm_fwd_pooled")
-        ctx.weight, ctx.bias = weight, bias
-        _claim(weight, "linear"); _claim(bias, "linear")
         ctx.save_for_backward(x2, r0, pre, sc3, rinv3, wp, w_f, g_f, bias_f)
         ctx.args = (eps0, eps3, drop_p, seed, (G, S, K))
         return hm, xm
 
     @staticmethod
     def backward(ctx, dhm, dxm):
-        x2, r0, pre, sc3, rinv3, wp, w_f, g_f, bias_f = ctx.saved_tensors
-        eps0, eps3, drop_p, seed, (G, S, K) = ctx.args
-        M, N = G * S, wp.shape[0]
+        G, S, K = ctx.args[4]
         if dhm is None:
             raise RuntimeError("meant_amd: the pooled encoder tail received no gradient for its pooled activations")
-        dh = _c(dhm.float())
-        dpre_s = torch.empty_like(pre)
-        kcoef = torch.empty(M, device=x2.device, dtype=torch.float32)
-        dscale3 = torch.empty(N, device=x2.device, dtype=torch.float32)
-        db, db_sunk = _bias_grad_target(ctx, N, x2.device)
-        wsb = lib.meant_rmsnorm_bwd_ws(M, N)
-        ws = torch.empty(wsb, device=x2.device, dtype=torch.uint8)
-        check(lib.meant_rmsnorm_bwd_chain(_p(dh), 1, None, _p(sc3), _p(rinv3), _p(dpre_s), _p(dscale3), M, N, S, eps3, drop_p, seed, _p(pre),
-                                          _p(r0), _p(bias_f), eps0, K, _p(kcoef), _p(db), _dt(x2), _p(ws), wsb, _stream()), "rmsnorm_bwd_chain")
-        if db_sunk:
-            _sink_of(ctx.bias, "linear").report(ctx.bias)
         dxm_f = _c(dxm.float()) if dxm is not None else None
-        dx, dw, dg0 = _norm_linear_backward(ctx, dpre_s, kcoef, x2, wp, w_f, g_f, None, dxm_f, S)
-        return dx.view(G, S, K), dg0, None, dw, (None if (db_sunk or ctx.bias is None) else db), dscale3, None, None, None
+        dx, dg0, dw, db, dscale3 = _fold_backward(ctx, ctx.saved_tensors, _c(dhm.float()), 1, None, S, None, dxm_f)
+        return dx.view(G, S, K), dg0, None, dw, db, dscale3, None, None, None
 
 
 def norm_linear_gelu_norm_pooled(x, gain0, eps0, weight, bias, gain3, eps3, drop_p=0.0, seed=0):
@@ -671,13 +672,8 @@ class _LayerNorm(torch.autograd.Function):
     def backward(ctx, dy):
         x, g, stats = ctx.saved_tensors
         dy = _c(dy)
-        d = x.shape[-1]
-        rows = x.numel() // d
-        dx = torch.empty_like(x)
-        dg = torch.empty(d, device=x.device, dtype=torch.float32)
-        db = torch.empty(d, device=x.device, dtype=torch.float32)
-        wsb = lib.meant_rmsnorm_bwd_ws(rows, d)
-        ws = torch.empty(wsb, device=x.device, dtype=torch.uint8)
+        dx, dg, ws, wsb, rows, d = _norm_bwd_bufs(x)
+        db = torch.empty_like(dg)
         check(lib.meant_layernorm_bwd(_p(dy), _p(x), _p(g), _p(stats), _p(dx), _p(dg), _p(db), rows, d, _dt(x), _p(ws), wsb,
                                       _stream()), "layernorm_bwd")
         return dx, dg, db, None
@@ -726,7 +722,7 @@ def _bwd_dw(dy2, x2, dw, db):
     K = x2.shape[1]
     dt = _dt(dy2)
     wsb = lib.meant_linear_bwd_dw_ws(M, N, K, dt)          # non-zero only with the "deterministic" option
-    ws = torch.empty(wsb, device=dy2.device, dtype=torch.uint8) if wsb else None
+    ws = _ws(wsb, dy2.device)
     check(lib.meant_linear_bwd_dw(_p(dy2), dy2.stride(0), _p(x2), x2.stride(0), _p(dw), _p(db), M, N, K, dt, _p(ws), wsb, _stream()),
           "linear_bwd_dw")
 
@@ -737,7 +733,7 @@ def _bwd_dw_rows(dy2, x2, dw, db, lists):
     K = x2.shape[1]
     dt = _dt(dy2)
     wsb = lib.meant_linear_bwd_dw_ws(M, N, K, dt)          # the deterministic option sums all rows, through its workspace
-    ws = torch.empty(wsb, device=dy2.device, dtype=torch.uint8) if wsb else None
+    ws = _ws(wsb, dy2.device)
     check(lib.meant_linear_bwd_dw_rows(_p(dy2), dy2.stride(0), _p(x2), x2.stride(0), _p(dw), _p(db), lists.data_ptr() + 4 * KV_LIST_HEADER,
                                        lists.data_ptr(), M, N, K, dt, _p(ws), wsb, _stream()), "linear_bwd_dw_rows")
 
@@ -806,11 +802,6 @@ class GradSink:
             r._sink_report_rows(p, row_lo, row_hi, last)
 
 
-def _lib_option(name: str) -> int:
-    from . import _lib
-    return _lib.get_option(name)
-
-
 def _claim(param, site: str):
     """forward side of the sink protocol: remember that an op of kind `site` reads `param` in this step.  (Called from inside
     autograd.Function.forward, where grad mode is off: what matters is whether the parameter wants a gradient.)"""
@@ -838,6 +829,18 @@ def _n_pad_ok(N: int, dtype: torch.dtype) -> bool:
     return dtype == torch.bfloat16 and N >= 8 and N % 8 != 0
 
 
+def _dw_acc(rows, x2, K, has_bias, accumulate, keep=None):
+    """(dW [keep or rows, K], db or None) fp32 of a Linear whose saved input is x2 [M, K8]: zeroed [rows, K8] / [rows]
+    accumulators, filled by accumulate(dw, db) ("+=" launches), their first `keep` rows, and where x2 is the K-padded copy of
+    _k_pad (K8 = ceil8(K)) dW cut back to K columns by one copy pass"""
+    dw = torch.zeros((rows, x2.shape[1]), device=x2.device, dtype=torch.float32)
+    db = torch.zeros(rows, device=x2.device, dtype=torch.float32) if has_bias else None
+    accumulate(dw, db)
+    if keep is not None:
+        dw, db = dw[:keep], (db[:keep] if has_bias else None)
+    return (dw if x2.shape[1] == K else _pad_cols(dw, K)), db
+
+
 def _linear_bwd_npad(dy2, x2, params, need_dx, has_bias, pad_rows, K):
     """_linear_bwd_raw for _n_pad_ok widths.  ONE copy pass turns dY into [M, ceil8(N)] with zero columns; it feeds both products:
     dX = dYp WTp^T on the K-tail NT kernels (reduction length ceil8(N); WTp [K, ceil8(N)] = the transposed weight with zero columns,
@@ -846,18 +849,14 @@ def _linear_bwd_npad(dy2, x2, params, need_dx, has_bias, pad_rows, K):
     rows -- that are cut back to [N, K] / [N].  The gradient always goes back to autograd: a sink's view is [N, K]."""
     M, N = dy2.shape
     N8 = (N + 7) & ~7
-    K8 = x2.shape[1]
     dyp = _pad_cols(dy2, N8)
     dx = None
     if need_dx:
         wT = weights.get(params, dy2.dtype, True, pad_rows, pad_cols=N8 - N)           # [K, N8]
         dx = torch.empty((M, K), device=dy2.device, dtype=dy2.dtype)
         check(lib.meant_linear_bwd_dx(_p(dyp), N8, _p(wT), _p(dx), K, M, N8, K, _dt(dy2), _stream()), "linear_bwd_dx")
-    dw = torch.zeros((N8, K8), device=dy2.device, dtype=torch.float32)
-    db = torch.zeros(N8, device=dy2.device, dtype=torch.float32) if has_bias else None
-    _bwd_dw(dyp, x2, dw, db)
-    dw = dw[:N] if K8 == K else _pad_cols(dw[:N], K)
-    return dx, dw, (db[:N] if has_bias else None)
+    dw, db = _dw_acc(N8, x2, K, has_bias, lambda dw, db: _bwd_dw(dyp, x2, dw, db), keep=N)
+    return dx, dw, db
 
 
 def _linear_bwd_raw(dy2, x2, params, need_dx, has_bias, pad_rows=0, bias_param=None, site="linear", K=None):
@@ -882,11 +881,7 @@ def _linear_bwd_raw(dy2, x2, params, need_dx, has_bias, pad_rows=0, bias_param=N
             if has_bias:
                 bs_.report(bias_param)
             return dx, None, None
-    dw = torch.zeros((N, K8), device=dy2.device, dtype=torch.float32)
-    db = torch.zeros(N, device=dy2.device, dtype=torch.float32) if has_bias else None
-    _bwd_dw(dy2, x2, dw, db)
-    if K8 != K:
-        dw = _pad_cols(dw, K)
+    dw, db = _dw_acc(N, x2, K, has_bias, lambda dw, db: _bwd_dw(dy2, x2, dw, db))
     return dx, dw, db
 
 
@@ -936,7 +931,6 @@ def linear(x, weight, bias=None, residual=None, epilogue=EPI_NONE):
 # ---------------------------------------------------------------------------------------------
 def _gemm_f32(A, B, C, M, N, K, sA, sB, sC, alpha=1.0, accumulate=False):
     """C[m,n] (+)= alpha * sum_k A(m,k) B(k,n) on fp32 tensors with explicit (row, col) element strides"""
-    import ctypes
     arr = ctypes.c_int64 * 4
     check(lib.meant_gemm_f32_strided(_p(A), _p(B), _p(C), M, N, K, 1, 1, arr(0, 0, *sA), arr(0, 0, *sB), arr(0, 0, *sC),
                                      float(alpha), int(accumulate), _stream()), "gemm_f32_strided")
@@ -984,6 +978,43 @@ def compose_linear(w1, b1, wqkv, bqkv):
     return _ComposeLinear.apply(w1, b1, wqkv, bqkv)
 
 
+def _attn_fwd_raw(qkv2, km, G, S, H, Dh, scale, causal, drop=None):
+    """(o [G*S, H*Dh], lse) of the attention core on packed q | k | v rows qkv2 [G*S, 3*H*Dh], km = float key mask [G, S] or None.
+    drop = (p, seed): the materialised fp32 core with dropout on the scores (meant_attn_drop_fwd) instead of the fused kernels.
+    The workspace dies with the call"""
+    dt = _dt(qkv2)
+    o = torch.empty((G * S, H * Dh), device=qkv2.device, dtype=qkv2.dtype)
+    lse = torch.empty((G, H, S, 2), device=qkv2.device, dtype=torch.float32)
+    wsb = (lib.meant_attn_fwd_ws if drop is None else lib.meant_attn_drop_ws)(G, S, H, Dh, dt)
+    ws = _ws(wsb, qkv2.device, 16)
+    if drop is None:
+        check(lib.meant_attn_fwd(_p(qkv2), _p(o), _p(lse), _p(km), G, S, H, Dh, scale, causal, dt, _p(ws), wsb, _stream()), "attn_fwd")
+    else:
+        check(lib.meant_attn_drop_fwd(_p(qkv2), _p(o), _p(lse), _p(km), G, S, H, Dh, scale, causal, drop[0], drop[1], dt,
+                                      _p(ws), wsb, _stream()), "attn_drop_fwd")
+    return o, lse
+
+
+def _attn_bwd_raw(qkv2, o, do2, lse, km, G, S, H, Dh, scale, causal, tables, drop=None):
+    """dqkv of _attn_fwd_raw, w.r.t. the buffer as it was BEFORE the rotation by `tables`: the fused backward applies the rotary
+    adjoint inside the kernel, the dropout core's is followed by meant_rotary_qk's transposed pass.  The workspace dies with the
+    call, so a caller's later allocations do not sit on top of it"""
+    dt = _dt(do2)
+    dqkv = torch.empty_like(qkv2)
+    qa, qb, ka, kb, R = _rot(tables)
+    wsb = (lib.meant_attn_ws if drop is None else lib.meant_attn_drop_ws)(G, S, H, Dh, dt)
+    ws = _ws(wsb, do2.device, 16)
+    if drop is None:
+        check(lib.meant_attn_bwd(_p(qkv2), _p(o), _p(do2), _p(lse), _p(km), _p(dqkv), G, S, H, Dh, scale, causal,
+                                 _p(qa), _p(qb), _p(ka), _p(kb), R, dt, _p(ws), wsb, _stream()), "attn_bwd")
+    else:
+        check(lib.meant_attn_drop_bwd(_p(qkv2), _p(o), _p(do2), _p(lse), _p(km), _p(dqkv), G, S, H, Dh, scale, causal, drop[0], drop[1], dt,
+                                      _p(ws), wsb, _stream()), "attn_drop_bwd")
+        if tables is not None:
+            check(lib.meant_rotary_qk(_p(dqkv), G * S, S, H, Dh, R, _p(qa), _p(qb), _p(ka), _p(kb), 1, dt, _stream()), "rotary_qk^T")
+    return dqkv
+
+
 class _QKVAttention(torch.autograd.Function):
     """Fused q|k|v projection + rotary + attention core of meant/attention.py:35-57 and
     meant/xPosAttention.py:35-63 (up to, not including, multi_mad).
@@ -1009,8 +1040,7 @@ class _QKVAttention(torch.autograd.Function):
             w_c = cast(w_f, x.dtype)                                          # [3D, d] in the compute dtype
         bias_f = _c(bqkv.detach().float())
         dt = _dt(x)
-        qa, qb, ka, kb = tables if tables is not None else (None, None, None, None)
-        R = qa.shape[1] if qa is not None else 0
+        qa, qb, ka, kb, R = _rot(tables)
         km = _c(key_mask.float()) if key_mask is not None else None
         skip = _kv_skip_bits(x, km, S, D, Dh)
         lists = kv_live_rows(km, causal) if skip else None                    # built once, on the device; backward reads the same lists
@@ -1021,13 +1051,8 @@ class _QKVAttention(torch.autograd.Function):
         else:
             check(lib.meant_qkv_proj_fwd(_p(x2), x2.stride(0), _p(w_c), _p(bias_f), _p(qkv), G * S, x2.shape[1], S, num_heads, Dh, R,
                                          _p(qa), _p(qb), _p(ka), _p(kb), dt, _stream()), "qkv_proj_fwd")
-        o = torch.empty((G * S, D), device=x.device, dtype=x.dtype)
-        lse = torch.empty((G, num_heads, S, 2), device=x.device, dtype=torch.float32)
         scale = 1.0 / math.sqrt(Dh * num_heads) if scale is None else float(scale)
-        wsb = lib.meant_attn_fwd_ws(G, S, num_heads, Dh, dt)
-        ws = torch.empty(max(wsb, 16), device=x.device, dtype=torch.uint8)
-        check(lib.meant_attn_fwd(_p(qkv), _p(o), _p(lse), _p(km), G, S, num_heads, Dh, scale, int(causal), dt, _p(ws), wsb,
-                                 _stream()), "attn_fwd")
+        o, lse = _attn_fwd_raw(qkv, km, G, S, num_heads, Dh, scale, int(causal))
         ctx.save_for_backward(x2, qkv, o, lse, km, w_f, lists)
         ctx.kv_skip = skip
         ctx.tables = tables
@@ -1040,14 +1065,7 @@ class _QKVAttention(torch.autograd.Function):
         G, S, d, D, Dh, H, scale, causal = ctx.meta
         do2 = _c(do).view(G * S, D)
         dt = _dt(do2)
-        dqkv = torch.empty_like(qkv)
-        wsb = lib.meant_attn_ws(G, S, H, Dh, dt)
-        ws = torch.empty(max(wsb, 16), device=do2.device, dtype=torch.uint8)
-        qa, qb, ka, kb = ctx.tables if ctx.tables is not None else (None, None, None, None)
-        R = qa.shape[1] if qa is not None else 0
-        check(lib.meant_attn_bwd(_p(qkv), _p(o), _p(do2), _p(lse), _p(km), _p(dqkv), G, S, H, Dh, scale, causal,
-                                 _p(qa), _p(qb), _p(ka), _p(kb), R, dt, _p(ws), wsb, _stream()), "attn_bwd")
-        del ws
+        dqkv = _attn_bwd_raw(qkv, o, do2, lse, km, G, S, H, Dh, scale, causal, ctx.tables)    # its workspace is gone before wT, dx, dw
         M, N, K = G * S, 3 * D, d
         dx = None
         if ctx.needs_input_grad[0]:
@@ -1055,18 +1073,15 @@ class _QKVAttention(torch.autograd.Function):
             check(lib.meant_transpose2d(_p(w_f), F32, _p(wT), dt, N, K, _stream()), "transpose2d")
             dx = torch.empty((M, K), device=do2.device, dtype=do2.dtype)
             check(lib.meant_linear_bwd_dx(_p(dqkv), N, _p(wT), _p(dx), K, M, N, K, dt, _stream()), "linear_bwd_dx")
-        K8 = x2.shape[1]                                                      # ceil8(d) where forward padded x
-        dw = torch.zeros((N, K8), device=do2.device, dtype=torch.float32)
-        db = torch.zeros(N, device=do2.device, dtype=torch.float32)
-        if ctx.kv_skip & KV_SKIP_DW:
-            # the dk / dv rows of the key blocks the attention skipped are exact zeros: the k|v columns reduce over the live blocks only
-            # (their bias gradient rides the same launch), the q columns over all rows, both into the one dw / db
-            _bwd_dw(dqkv[:, :D], x2, dw[:D], db[:D])
-            _bwd_dw_rows(dqkv[:, D:], x2, dw[D:], db[D:], lists)
-        else:
-            _bwd_dw(dqkv, x2, dw, db)
-        if K8 != K:
-            dw = _pad_cols(dw, K)
+        def accumulate(dw, db):
+            if ctx.kv_skip & KV_SKIP_DW:
+                # the dk / dv rows of the key blocks the attention skipped are exact zeros: the k|v columns reduce over the live blocks
+                # only (their bias gradient rides the same launch), the q columns over all rows, both into the one dw / db
+                _bwd_dw(dqkv[:, :D], x2, dw[:D], db[:D])
+                _bwd_dw_rows(dqkv[:, D:], x2, dw[D:], db[D:], lists)
+            else:
+                _bwd_dw(dqkv, x2, dw, db)
+        dw, db = _dw_acc(N, x2, K, True, accumulate)                           # x2 is ceil8(d) wide where forward padded x
         return (dx.view(G, S, d) if dx is not None else None), dw, db, None, None, None, None, None
 
 
@@ -1255,6 +1270,39 @@ def meanpool_f32(a):
     return _MeanPoolCat.apply(a, None, torch.float32)
 
 
+def _pooled_parts(flat):
+    """(parts of four, their output widths N_p, out float [G, sum N_p]) of the flat argument list of a pooled tail"""
+    parts = [flat[i:i + 4] for i in range(0, len(flat), 4)]
+    _need_gpu(*[t for p in parts for t in p])
+    widths = [p[2].shape[0] for p in parts]
+    return parts, widths, torch.empty((parts[0][0].shape[0], sum(widths)), device=parts[0][0].device, dtype=torch.float32)
+
+
+def _pooled_part_fwd(hm, W, b, res, out, off):
+    """out[:, off:off + N] = hm W^T + b + res[:, off:off + N] for one part of the pooled tails: hm float [G, K], W [N, K] (the fp32
+    master weight, exact-f32 product), res and out float [G, Dt] with the same row stride"""
+    G, K = hm.shape
+    N, Dt = W.shape[0], out.shape[1]
+    w_f = _c(W.detach().float())
+    bias_f = _c(b.detach().float()) if b is not None else None
+    check(lib.meant_linear_fwd(_p(hm), K, _p(w_f), _p(bias_f), res.data_ptr() + off * 4, Dt, out.data_ptr() + off * 4, Dt, None,
+                               G, N, K, EPI_RESIDUAL, F32, _stream()), "linear_fwd")
+
+
+def _pooled_part_bwd(dout, off, hm, W, has_b):
+    """(d hm [G, K], dW [N, K], db [N] or None) of _pooled_part_fwd from the [G, N] slice of dout float [G, Dt] at column off"""
+    G, Dt = dout.shape
+    N, K = W.shape
+    dy_ptr = dout.data_ptr() + off * 4                                  # row stride Dt
+    wT = weights.get((W,), torch.float32, True)                        # [K, N]
+    dhm = torch.empty((G, K), device=dout.device, dtype=torch.float32)
+    check(lib.meant_linear_bwd_dx(dy_ptr, Dt, _p(wT), _p(dhm), K, G, N, K, F32, _stream()), "linear_bwd_dx")
+    dw = torch.zeros((N, K), device=dout.device, dtype=torch.float32)
+    db = torch.zeros(N, device=dout.device, dtype=torch.float32) if has_b else None
+    check(lib.meant_linear_bwd_dw(dy_ptr, Dt, _p(hm), K, _p(dw), _p(db), G, N, K, F32, None, 0, _stream()), "linear_bwd_dw")
+    return dhm, dw, db
+
+
 class _PoolLinearCat(torch.autograd.Function):
     """torch.cat([mean_s(h_a W_a^T + b_a + x_a), mean_n(h_b W_b^T + b_b + x_b)], -1): the LAST Linear (+ residual) of the last
     encoder layer of each stack followed by the sequence mean-pool (meant/meant.py:74 / :120 -> :231), evaluated as
@@ -1267,14 +1315,9 @@ class _PoolLinearCat(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, out_dtype, *flat):
-        parts = [flat[i:i + 4] for i in range(0, len(flat), 4)]
-        _need_gpu(*[t for p in parts for t in p])
-        G = parts[0][0].shape[0]
-        widths = [p[2].shape[0] for p in parts]
-        Dt = sum(widths)
-        dev = parts[0][0].device
-        out = torch.empty((G, Dt), device=dev, dtype=torch.float32)
-        xm = torch.empty((G, Dt), device=dev, dtype=torch.float32)    # mean_s(x_p), laid out like `out` (same row stride)
+        parts, widths, out = _pooled_parts(flat)
+        (G, Dt), dev = out.shape, out.device
+        xm = torch.empty_like(out)                                    # mean_s(x_p), laid out like `out` (same row stride)
         saved, off = [], 0
         for (h, x, W, b), N in zip(parts, widths):
             h, x = _c(h), _c(x)
@@ -1283,10 +1326,7 @@ class _PoolLinearCat(torch.autograd.Function):
             hm = torch.empty((G, K), device=dev, dtype=torch.float32)
             check(lib.meant_meanpool_fwd(_p(h), _p(hm), K, 0, G, S, K, _dt(h), F32, _stream()), "meanpool_fwd")
             check(lib.meant_meanpool_fwd(_p(x), _p(xm), Dt, off, G, S, N, _dt(x), F32, _stream()), "meanpool_fwd")
-            w_f = _c(W.detach().float())
-            bias_f = _c(b.detach().float()) if b is not None else None
-            check(lib.meant_linear_fwd(_p(hm), K, _p(w_f), _p(bias_f), xm.data_ptr() + off * 4, Dt, out.data_ptr() + off * 4, Dt, None,
-                                       G, N, K, EPI_RESIDUAL, F32, _stream()), "linear_fwd")
+            _pooled_part_fwd(hm, W, b, xm, out, off)
             saved.append((hm, W, b is not None, h.shape, h.dtype, off))
             off += N
         ctx.parts = saved
@@ -1300,14 +1340,8 @@ class _PoolLinearCat(torch.autograd.Function):
         for hm, W, has_b, hshape, hdt, off in ctx.parts:
             N, K = W.shape
             S = hshape[1]
-            dy_ptr = dout.data_ptr() + off * 4                              # [G, N] slice of dout, row stride Dt
             dti = F32 if hdt == torch.float32 else BF16
-            wT = weights.get((W,), torch.float32, True)                    # [K, N]
-            dhm = torch.empty((G, K), device=dout.device, dtype=torch.float32)
-            check(lib.meant_linear_bwd_dx(dy_ptr, Dt, _p(wT), _p(dhm), K, G, N, K, F32, _stream()), "linear_bwd_dx")
-            dw = torch.zeros((N, K), device=dout.device, dtype=torch.float32)
-            db = torch.zeros(N, device=dout.device, dtype=torch.float32) if has_b else None
-            check(lib.meant_linear_bwd_dw(dy_ptr, Dt, _p(hm), K, _p(dw), _p(db), G, N, K, F32, None, 0, _stream()), "linear_bwd_dw")
+            dhm, dw, db = _pooled_part_bwd(dout, off, hm, W, has_b)
             dh = torch.empty(hshape, device=dout.device, dtype=hdt)         # every token of a group gets d(mean h) / S
             check(lib.meant_meanpool_bwd(_p(dhm), K, 0, _p(dh), G, S, K, dti, F32, _stream()), "meanpool_bwd")
             dx = torch.empty(hshape[:2] + (N,), device=dout.device, dtype=hdt)
@@ -1321,23 +1355,13 @@ class _PooledLinearCat(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, out_dtype, *flat):
-        parts = [flat[i:i + 4] for i in range(0, len(flat), 4)]
-        _need_gpu(*[t for p in parts for t in p])
-        G = parts[0][0].shape[0]
-        widths = [p[2].shape[0] for p in parts]
-        Dt = sum(widths)
-        dev = parts[0][0].device
-        out = torch.empty((G, Dt), device=dev, dtype=torch.float32)
+        parts, widths, out = _pooled_parts(flat)
         # the generic fp32 GEMM wants residual stride == output stride: the means of x side by side, like `out`
         xs = _c(parts[0][1]) if len(parts) == 1 else torch.cat([p[1] for p in parts], dim=1)
         saved, off = [], 0
         for (hm, xm, W, b), N in zip(parts, widths):
             hm = _c(hm)
-            K = hm.shape[1]
-            w_f = _c(W.detach().float())
-            bias_f = _c(b.detach().float()) if b is not None else None
-            check(lib.meant_linear_fwd(_p(hm), K, _p(w_f), _p(bias_f), xs.data_ptr() + off * 4, Dt, out.data_ptr() + off * 4, Dt, None,
-                                       G, N, K, EPI_RESIDUAL, F32, _stream()), "linear_fwd")
+            _pooled_part_fwd(hm, W, b, xs, out, off)
             saved.append((hm, W, b is not None, off))
             off += N
         ctx.parts = saved
@@ -1346,17 +1370,11 @@ class _PooledLinearCat(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         dout = cast(_c(dout), torch.float32)
-        G, Dt = dout.shape
+        Dt = dout.shape[1]
         grads = [None]
         for hm, W, has_b, off in ctx.parts:
-            N, K = W.shape
-            dy_ptr = dout.data_ptr() + off * 4
-            wT = weights.get((W,), torch.float32, True)
-            dhm = torch.empty((G, K), device=dout.device, dtype=torch.float32)
-            check(lib.meant_linear_bwd_dx(dy_ptr, Dt, _p(wT), _p(dhm), K, G, N, K, F32, _stream()), "linear_bwd_dx")
-            dw = torch.zeros((N, K), device=dout.device, dtype=torch.float32)
-            db = torch.zeros(N, device=dout.device, dtype=torch.float32) if has_b else None
-            check(lib.meant_linear_bwd_dw(dy_ptr, Dt, _p(hm), K, _p(dw), _p(db), G, N, K, F32, None, 0, _stream()), "linear_bwd_dw")
+            N = W.shape[0]
+            dhm, dw, db = _pooled_part_bwd(dout, off, hm, W, has_b)
             dxm = dout[:, off:off + N] if Dt == N else dout[:, off:off + N].contiguous()
             grads += [dhm, dxm, dw, db]
         return tuple(grads)
@@ -1457,13 +1475,13 @@ def _aux_stream(device):
 
 def _emb_sorted_bwd_ok(n: int, d: int) -> bool:
     """shapes whose embedding gradient is summed in sorted-id order (meant_embedding_bwd_sorted)"""
-    return d <= 1024 and d % 8 == 0 and (n >= 4096 or bool(_lib_option("deterministic")))
+    return d <= 1024 and d % 8 == 0 and (n >= 4096 or bool(_lib.get_option("deterministic")))
 
 
 def _emb_seg_bwd_ok(n: int, d: int) -> bool:
     """shapes meant_embedding_bwd_seg takes: any width that is a multiple of 8 (enough tokens for a sort to pay, or the promise of
     option "deterministic" to keep)"""
-    return d % 8 == 0 and (n >= 4096 or bool(_lib_option("deterministic")))
+    return d % 8 == 0 and (n >= 4096 or bool(_lib.get_option("deterministic")))
 
 
 def _emb_bwd_route(n: int, d: int) -> str:
@@ -1482,7 +1500,7 @@ def _sort_ids(ids_flat: torch.Tensor, V: int):
     n = ids_flat.numel()
     sorted_ids, order = torch.empty_like(ids_flat), torch.empty_like(ids_flat)
     wsb = lib.meant_sort_ids_ws(n, V)
-    ws = torch.empty(wsb, device=ids_flat.device, dtype=torch.uint8)
+    ws = _ws(wsb, ids_flat.device)
     check(lib.meant_sort_ids(_p(ids_flat), n, V, _p(sorted_ids), _p(order), _p(ws), wsb, _stream()), "sort_ids")
     return sorted_ids, order
 
@@ -1556,7 +1574,7 @@ class _Embedding(torch.autograd.Function):
             nsl = sink.row_slices(ctx.table) if sink is not None else 1
             if route == "seg":
                 wsb = lib.meant_embedding_bwd_seg_ws(n, d)
-                ws = torch.empty(wsb, device=dout.device, dtype=torch.uint8)
+                ws = _ws(wsb, dout.device)
                 for c in range(nsl):                     # row slices as below; one slice is the whole table
                     lo, hi = V * c // nsl, V * (c + 1) // nsl
                     check(lib.meant_embedding_bwd_seg(_p(dout), _p(sorted_ids), _p(order), _p(dtab), n, d, V, lo, hi, _dt(dout), _p(ws), wsb,
@@ -1745,7 +1763,7 @@ def select_rows(target, V: int, ignore_index: int = -100) -> SelectedRows:
     tsel = torch.empty(T, device=dev, dtype=torch.int64)
     count = torch.empty(1, device=dev, dtype=torch.int32)
     wsb = lib.meant_select_rows_ws(T)
-    ws = torch.empty(max(wsb, 16), device=dev, dtype=torch.uint8)
+    ws = _ws(wsb, dev, 16)
     check(lib.meant_select_rows(_p(tgt), T, int(V), int(ignore_index), _p(idx), _p(inv), _p(tsel), _p(count), _p(ws), wsb, _stream()),
           "select_rows")
     if n_host is None:
@@ -1794,105 +1812,46 @@ def softmax_cross_entropy(logits, target, ignore_index: int = -100):
 class _AttentionCore(torch.autograd.Function):
     """softmax(q k^T * scale [+ key padding]) v per group of S rows, on packed [G*S, 3*H*Dh] (q | k | v).  `tables` =
     (qa, qb, ka, kb) float [S, R] rotate q and k first (meant_rotary_qk); the backward applies the adjoint inside the
-    attention backward kernel and returns the gradient w.r.t. the UNROTATED buffer."""
-
-    @staticmethod
-    def forward(ctx, qkv, tables, G, S, H, scale, causal, key_mask):
-        _need_gpu(qkv)
-        dt = _dt(qkv)
-        D3 = qkv.shape[-1]
-        D = D3 // 3
-        Dh = D // H
-        qa, qb, ka, kb = tables if tables is not None else (None, None, None, None)
-        R = qa.shape[1] if qa is not None else 0
-        q2 = qkv.reshape(G * S, D3)
-        if qa is not None:
-            q2 = q2.clone() if q2.data_ptr() == qkv.data_ptr() else q2
-            check(lib.meant_rotary_qk(_p(q2), G * S, S, H, Dh, R, _p(qa), _p(qb), _p(ka), _p(kb), 0, dt, _stream()), "rotary_qk")
-        else:
-            q2 = _c(q2)
-        o = torch.empty((G * S, D), device=qkv.device, dtype=qkv.dtype)
-        lse = torch.empty((G, H, S, 2), device=qkv.device, dtype=torch.float32)
-        km = _c(key_mask.float()) if key_mask is not None else None
-        wsb = lib.meant_attn_fwd_ws(G, S, H, Dh, dt)
-        ws = torch.empty(max(wsb, 16), device=qkv.device, dtype=torch.uint8)
-        check(lib.meant_attn_fwd(_p(q2), _p(o), _p(lse), _p(km), G, S, H, Dh, float(scale), int(causal), dt, _p(ws), wsb, _stream()), "attn_fwd")
-        ctx.save_for_backward(q2, o, lse, km)
-        ctx.tables, ctx.meta, ctx.in_shape = tables, (G, S, H, Dh, float(scale), int(causal)), qkv.shape
-        return o
-
-    @staticmethod
-    def backward(ctx, do):
-        q2, o, lse, km = ctx.saved_tensors
-        G, S, H, Dh, scale, causal = ctx.meta
-        do2 = _c(do)
-        dt = _dt(do2)
-        dqkv = torch.empty_like(q2)
-        wsb = lib.meant_attn_ws(G, S, H, Dh, dt)
-        ws = torch.empty(max(wsb, 16), device=do2.device, dtype=torch.uint8)
-        qa, qb, ka, kb = ctx.tables if ctx.tables is not None else (None, None, None, None)
-        R = qa.shape[1] if qa is not None else 0
-        check(lib.meant_attn_bwd(_p(q2), _p(o), _p(do2), _p(lse), _p(km), _p(dqkv), G, S, H, Dh, scale, causal,
-                                 _p(qa), _p(qb), _p(ka), _p(kb), R, dt, _p(ws), wsb, _stream()), "attn_bwd")
-        return dqkv.view(ctx.in_shape), None, None, None, None, None, None, None
-
-
-class _AttentionCoreScoreDropout(torch.autograd.Function):
-    """_AttentionCore with dropout on the score matrix (meant/xPosAttention.py:59: after the causal fill and the padding term, before
-    the softmax).  The fused kernels never see a score matrix; this runs the materialised fp32 core (meant_attn_drop_fwd / _bwd): rotary
-    by meant_rotary_qk in front, its adjoint behind the backward.  No reference model sets the probability above zero."""
+    attention backward kernel and returns the gradient w.r.t. the UNROTATED buffer.
+    drop_p not None (0 included): dropout on the score matrix (meant/xPosAttention.py:59: after the causal fill and the padding
+    term, before the softmax).  The fused kernels never see a score matrix; this runs the materialised fp32 core
+    (meant_attn_drop_fwd / _bwd), the rotary adjoint behind the backward.  No reference model sets the probability above zero."""
 
     @staticmethod
     def forward(ctx, qkv, tables, G, S, H, scale, causal, key_mask, drop_p, seed):
         _need_gpu(qkv)
         dt = _dt(qkv)
         D3 = qkv.shape[-1]
-        D = D3 // 3
-        Dh = D // H
-        qa, qb, ka, kb = tables if tables is not None else (None, None, None, None)
-        R = qa.shape[1] if qa is not None else 0
+        Dh = D3 // 3 // H
+        qa, qb, ka, kb, R = _rot(tables)
         q2 = qkv.reshape(G * S, D3)
         if qa is not None:
             q2 = q2.clone() if q2.data_ptr() == qkv.data_ptr() else q2
             check(lib.meant_rotary_qk(_p(q2), G * S, S, H, Dh, R, _p(qa), _p(qb), _p(ka), _p(kb), 0, dt, _stream()), "rotary_qk")
         else:
             q2 = _c(q2)
-        o = torch.empty((G * S, D), device=qkv.device, dtype=qkv.dtype)
-        lse = torch.empty((G, H, S, 2), device=qkv.device, dtype=torch.float32)
         km = _c(key_mask.float()) if key_mask is not None else None
-        wsb = lib.meant_attn_drop_ws(G, S, H, Dh, dt)
-        ws = torch.empty(max(wsb, 16), device=qkv.device, dtype=torch.uint8)
-        check(lib.meant_attn_drop_fwd(_p(q2), _p(o), _p(lse), _p(km), G, S, H, Dh, float(scale), int(causal), float(drop_p), int(seed), dt,
-                                      _p(ws), wsb, _stream()), "attn_drop_fwd")
+        drop = None if drop_p is None else (float(drop_p), int(seed))
+        o, lse = _attn_fwd_raw(q2, km, G, S, H, Dh, float(scale), int(causal), drop)
         ctx.save_for_backward(q2, o, lse, km)
-        ctx.tables, ctx.meta, ctx.in_shape = tables, (G, S, H, Dh, float(scale), int(causal), float(drop_p), int(seed)), qkv.shape
+        ctx.tables, ctx.meta, ctx.in_shape = tables, (G, S, H, Dh, float(scale), int(causal), drop), qkv.shape
         return o
 
     @staticmethod
     def backward(ctx, do):
         q2, o, lse, km = ctx.saved_tensors
-        G, S, H, Dh, scale, causal, drop_p, seed = ctx.meta
-        do2 = _c(do)
-        dt = _dt(do2)
-        dqkv = torch.empty_like(q2)
-        wsb = lib.meant_attn_drop_ws(G, S, H, Dh, dt)
-        ws = torch.empty(max(wsb, 16), device=do2.device, dtype=torch.uint8)
-        check(lib.meant_attn_drop_bwd(_p(q2), _p(o), _p(do2), _p(lse), _p(km), _p(dqkv), G, S, H, Dh, scale, causal, drop_p, seed, dt,
-                                      _p(ws), wsb, _stream()), "attn_drop_bwd")
-        if ctx.tables is not None:
-            qa, qb, ka, kb = ctx.tables
-            check(lib.meant_rotary_qk(_p(dqkv), G * S, S, H, Dh, qa.shape[1], _p(qa), _p(qb), _p(ka), _p(kb), 1, dt, _stream()), "rotary_qk^T")
+        dqkv = _attn_bwd_raw(q2, o, _c(do), lse, km, *ctx.meta[:6], ctx.tables, ctx.meta[6])
         return dqkv.view(ctx.in_shape), None, None, None, None, None, None, None, None, None
 
 
 def attention_core_score_dropout(qkv, G, S, H, scale, drop_p, seed, tables=None, causal=False, key_mask=None):
     """attention_core with dropout(drop_p) on the score matrix; `seed` selects the mask (forward and backward share it)"""
-    return _AttentionCoreScoreDropout.apply(qkv, tables, int(G), int(S), int(H), float(scale), bool(causal), key_mask, float(drop_p), int(seed))
+    return _AttentionCore.apply(qkv, tables, int(G), int(S), int(H), float(scale), bool(causal), key_mask, float(drop_p), int(seed))
 
 
 def attention_core(qkv, G, S, H, scale, tables=None, causal=False, key_mask=None):
     """qkv: [G*S, 3*H*Dh] (or any shape with that many elements per row) -> o [G*S, H*Dh]"""
-    return _AttentionCore.apply(qkv, tables, int(G), int(S), int(H), float(scale), bool(causal), key_mask)
+    return _AttentionCore.apply(qkv, tables, int(G), int(S), int(H), float(scale), bool(causal), key_mask, None, 0)
 
 
 class _GEGLU(torch.autograd.Function):
@@ -1956,18 +1915,14 @@ class _DividedAttention(torch.autograd.Function):
         dt = _dt(qkv)
         q2 = qkv.view(b * L, D3)
         if tables is not None:                                                  # regrouped and rotated in one pass: [b G S, 3 D]
-            qa, qb, ka, kb = tables
+            qa, qb, ka, kb, R = _rot(tables)
             grouped = torch.empty((b * G * S, D3), device=qkv.device, dtype=qkv.dtype)
-            check(lib.meant_gather_rows_rot(_p(q2), _p(idx_in), _p(grouped), b * G * S, S, H, Dh, qa.shape[1], _p(qa), _p(qb), _p(ka), _p(kb),
+            check(lib.meant_gather_rows_rot(_p(q2), _p(idx_in), _p(grouped), b * G * S, S, H, Dh, R, _p(qa), _p(qb), _p(ka), _p(kb),
                                             dt, _stream()), "gather_rows_rot")
         else:                                                                   # rotary_emb=False: learned positions were added to x instead
             grouped = gather_rows(q2, idx_in)
-        og = torch.empty((b * G * S, D), device=qkv.device, dtype=qkv.dtype)
-        lse = torch.empty((b * G, H, S, 2), device=qkv.device, dtype=torch.float32)
         km = _c(group_mask.float()) if group_mask is not None else None         # [b G, S]
-        wsb = lib.meant_attn_fwd_ws(b * G, S, H, Dh, dt)
-        ws = torch.empty(max(wsb, 16), device=qkv.device, dtype=torch.uint8)
-        check(lib.meant_attn_fwd(_p(grouped), _p(og), _p(lse), _p(km), b * G, S, H, Dh, float(scale), 0, dt, _p(ws), wsb, _stream()), "attn_fwd")
+        og, lse = _attn_fwd_raw(grouped, km, b * G, S, H, Dh, float(scale), 0)
         out = gather_rows(og, idx_out).view(b, L, D)                             # row 0 of every sequence: zeros for now
         stats = torch.empty((b, H, 2), device=qkv.device, dtype=torch.float32)
         cm = _c(cls_mask.float()) if cls_mask is not None else None             # [b, L]
@@ -1975,7 +1930,7 @@ class _DividedAttention(torch.autograd.Function):
             check(lib.meant_attn_cls_fwd(_p(q2), _p(out), L * D, _p(stats), _p(cm), b, L, H, Dh, float(scale), dt, _stream()), "attn_cls_fwd")
         else:                                                                   # scores past one workgroup's LDS: over key segments
             wsb = lib.meant_attn_cls_split_ws(b, L, H, Dh, 0)
-            ws = torch.empty(max(wsb, 16), device=qkv.device, dtype=torch.uint8)
+            ws = _ws(wsb, qkv.device, 16)
             check(lib.meant_attn_cls_split_fwd(_p(q2), _p(out), L * D, _p(stats), _p(cm), b, L, H, Dh, float(scale), 0, dt, _p(ws), wsb, _stream()),
                   "attn_cls_split_fwd")
         ctx.save_for_backward(qkv, grouped, og, lse, km, out, stats, cm)
@@ -1990,12 +1945,7 @@ class _DividedAttention(torch.autograd.Function):
         dout = _c(dout)
         dt = _dt(dout)
         dog = gather_rows(dout.view(b * L, D), idx_dog)                          # position 0 of every group: zeros (its output was dropped)
-        dgrouped = torch.empty_like(grouped)
-        wsb = lib.meant_attn_ws(b * G, S, H, Dh, dt)
-        ws = torch.empty(max(wsb, 16), device=dout.device, dtype=torch.uint8)
-        qa, qb, ka, kb = ctx.tables if ctx.tables is not None else (None, None, None, None)
-        check(lib.meant_attn_bwd(_p(grouped), _p(og), _p(dog), _p(lse), _p(km), _p(dgrouped), b * G, S, H, Dh, scale, 0,
-                                 _p(qa), _p(qb), _p(ka), _p(kb), qa.shape[1] if qa is not None else 0, dt, _p(ws), wsb, _stream()), "attn_bwd")
+        dgrouped = _attn_bwd_raw(grouped, og, dog, lse, km, b * G, S, H, Dh, scale, 0, ctx.tables)
         dqkv = torch.empty_like(qkv)
         check(lib.meant_group_scatter(_p(dgrouped), _p(index), _p(dqkv), b, L, G, S, 3 * D, dt, _stream()), "group_scatter")
         if not 0 < lib.meant_attn_cls_max_len(Dh, 1) < L:
@@ -2003,7 +1953,7 @@ class _DividedAttention(torch.autograd.Function):
                   "attn_cls_bwd")
         else:                                                                   # the stats are shared: either forward may have run
             wsb = lib.meant_attn_cls_split_ws(b, L, H, Dh, 0)
-            ws = torch.empty(max(wsb, 16), device=dout.device, dtype=torch.uint8)
+            ws = _ws(wsb, dout.device, 16)
             check(lib.meant_attn_cls_split_bwd(_p(qkv), _p(out), L * D, _p(dout), L * D, _p(stats), _p(cm), _p(dqkv), b, L, H, Dh, scale, 0, dt,
                                                _p(ws), wsb, _stream()), "attn_cls_split_bwd")
         return dqkv, None, None, None, None, None, None
