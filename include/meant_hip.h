@@ -32,6 +32,8 @@ enum meant_dtype { MEANT_F32 = 0, MEANT_BF16 = 1 };
 /* storage-only types of raw inputs (meant_patchify_raw): the reference keeps its price graphs as float64 .npy
  * (in_loop_train.py:48,589); uint8 is what a rendered chart is before anyone converts it */
 enum meant_raw_dtype { MEANT_RAW_F32 = 0, MEANT_RAW_BF16 = 1, MEANT_RAW_F64 = 2, MEANT_RAW_U8 = 3 };
+/* storage types of an attention mask as meant_mlm_mask reads it (the models take float or int64 masks; U8 is also torch.bool) */
+enum meant_mask_dtype { MEANT_MASK_F32 = 0, MEANT_MASK_BF16 = 1, MEANT_MASK_I64 = 2, MEANT_MASK_U8 = 3, MEANT_MASK_I32 = 4 };
 
 enum meant_status {
   MEANT_OK = 0,
@@ -620,6 +622,53 @@ int meant_ce_probs_soft(const float* probs, int64_t ldp, const void* target, int
  * B >= 2^40 or C >= 2^31: MEANT_ERR_UNSUPPORTED; both before any launch.  B == 0: MEANT_OK without a launch. */
 int meant_vqa_score_update(const void* scores, int64_t lds, int scores_dtype, const void* target, int64_t ldt, int target_dtype,
                            int64_t B, int64_t C, int64_t* state, void* stream);
+/* ---- pretraining collators on the device ------ utils/custom_datasets.py:41-57 (mask_tokens), :116-126 (mask_image); pretrain_mim.py:198-204
+ * One masking rule, in integers, shared by the four entries below.  With fin = the two xor-shift-multiply rounds and the last
+ * xor-shift of the splitmix64 finaliser:
+ *   bits(seed, stream, idx)   = fin(seed + (idx | (uint64)stream << 60) * 0x9E3779B97F4A7C15)
+ *   draw24(seed, stream, idx) = bits >> 40
+ *   idx = sample_id * E + e   (E = elements per sample: S tokens, or C*Hh*Ww; e = position in the sample's own storage order)
+ * Element e of sample sample_id is CHOSEN iff draw24(seed, 0, idx) < threshold, threshold = floor(p * 2^24) computed by the caller
+ * in double (at most 2^24): the device compares integers only.  sample_id = sample_ids[row] (int64 on the device), or
+ * sample_base + row with sample_ids NULL: keyed by the dataset index, a sample's mask is the same in any batch, at any batch size and
+ * on any number of ranks.  sample_id * E must stay below 2^60: checked before any launch against sample_base + rows, or against
+ * id_bound (the caller's exclusive bound on the values of sample_ids); beyond: MEANT_ERR_UNSUPPORTED.  No atomics in any of them.
+ *
+ * meant_mlm_mask: ids int64 [B, S] -> ids_out, labels int64 [B, S], one launch.  A position is open when its id is none of the
+ * n_special (0..16) values of special_ids (int64 on the device) and attention_mask (optional, [B, S] of meant_mask_dtype) is not 0
+ * there; an open position that the rule chooses gets labels = its id, every other position ignore_index.  A chosen position's id is
+ * replaced by a second draw r = draw24(seed, 1, idx): r < t_replace: mask_id; r < t_replace + t_random: bits(seed, 2, idx) % V;
+ * otherwise kept (t_replace = 2^24, t_random = 0 is utils/custom_datasets.py:56; floor(0.8 * 2^24), floor(0.1 * 2^24) the BERT
+ * recipe).  ids_out may be ids itself; labels must overlap neither.  More than 2^38 tokens: MEANT_ERR_UNSUPPORTED. */
+int meant_mlm_mask(const int64_t* ids, const void* attention_mask, int mask_dtype, const int64_t* sample_ids, int64_t sample_base,
+                   int64_t id_bound, const int64_t* special_ids, int n_special, int64_t B, int64_t S, uint64_t seed,
+                   uint32_t threshold, uint32_t t_replace, uint32_t t_random, int64_t mask_id, int64_t V, int64_t ignore_index,
+                   int64_t* ids_out, int64_t* labels, void* stream);
+/* meant_patchify_raw with the rule applied on load: patch element = chosen ? mask_value : ((float)x - mean) * inv_std, the draw keyed
+ * by the element's (c, y, x) place in the raw image (e = (c*Hh + y)*Ww + x), not by its place in the patch row; the mask comes after
+ * the normalisation, as mask_image masks the transformed tensor.  Same raw and output dtypes, any C, any p dividing Hh and Ww.  No
+ * masked image is written anywhere.  threshold = 0 gives meant_patchify_raw's output. */
+int meant_patchify_raw_masked(const void* images, int raw_dtype, float mean, float inv_std, void* patches, int64_t G, int C, int Hh,
+                              int Ww, int p, int dtype, uint64_t seed, uint32_t threshold, const int64_t* sample_ids,
+                              int64_t sample_base, int64_t id_bound, float mask_value, void* stream);
+/* nn.L1Loss() of out act [B, Co, Hh, Ww] (contiguous, Co <= C: pretrain_mim.py:204 compares against labels[:, 0:3]) against the
+ * labels of mask_image, regenerated per element from the same raw images [B, C, Hh, Ww] and never stored:
+ *   label = chosen ? ((float)x - mean) * inv_std : unmasked_label          (unmasked_label = -100 is the reference's fill)
+ * fwd: loss[0] = sum |out - label| / N with N = B*Co*Hh*Ww, and count[0] = the chosen elements among the N; both OVERWRITTEN.  A
+ * workgroup owns 4096 consecutive elements and leaves one partial sum and one count in the workspace (meant_mim_l1_ws(N) bytes), a
+ * second launch of one workgroup adds them in an order fixed by N (in double): two runs give the same bits.
+ * bwd: dout (act, must not be out) = sign(out - label) * g[0] / N, 0 where they are equal; g is read from the device.
+ * on_masked = 1 (the SimMIM form): sum and divisor cover the chosen elements only -- the divisor is count[0] clamped to at least 1,
+ * which bwd reads from the count fwd wrote -- and dout is 0 elsewhere.  More than 2^40 elements: MEANT_ERR_UNSUPPORTED. */
+size_t meant_mim_l1_ws(int64_t N);
+int meant_mim_l1_fwd(const void* out, int dtype, const void* images, int raw_dtype, float mean, float inv_std, int64_t B, int C, int Co,
+                     int Hh, int Ww, uint64_t seed, uint32_t threshold, const int64_t* sample_ids, int64_t sample_base,
+                     int64_t id_bound, float unmasked_label, int on_masked, float* loss, int64_t* count, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int meant_mim_l1_bwd(const void* out, int dtype, const void* images, int raw_dtype, float mean, float inv_std, int64_t B, int C, int Co,
+                     int Hh, int Ww, uint64_t seed, uint32_t threshold, const int64_t* sample_ids, int64_t sample_base,
+                     int64_t id_bound, float unmasked_label, int on_masked, const float* g, const int64_t* count, void* dout,
+                     void* stream);
 /* out_accum[0] += sum(x^2) over a flat float buffer (global gradient norm; caller zeroes the scalar) */
 int meant_sumsq_f32(const float* x, int64_t n, float* out_accum, void* stream);
 /* One AdamW step (torch.optim.AdamW semantics, `step` >= 1 for the bias corrections) over flat float buffers.

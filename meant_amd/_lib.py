@@ -21,7 +21,7 @@ F32, BF16 = 0, 1
 RAW_F32, RAW_BF16, RAW_F64, RAW_U8 = 0, 1, 2, 3      # meant_raw_dtype (input pipeline)
 EPI_NONE, EPI_GELU, EPI_RESIDUAL, EPI_SIGMOID = 0, 1, 2, 4
 
-_p, _i, _i64, _f, _u64, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64, C.c_size_t
+_p, _i, _i64, _f, _u64, _sz, _u32 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64, C.c_size_t, C.c_uint32
 
 # name -> (restype, argtypes); mirrors include/meant_hip.h one to one
 SIGNATURES = {
@@ -100,6 +100,11 @@ SIGNATURES = {
     "meant_auroc_rank": (_i, [_p, _p, _i64, _i, _p, _p, _sz, _p]),
     "meant_ce_probs_soft": (_i, [_p, _i64, _p, _i64, _i, _p, _p, _p, _i64, _i64, _i64, _p]),
     "meant_vqa_score_update": (_i, [_p, _i64, _i, _p, _i64, _i, _i64, _i64, _p, _p]),
+    "meant_mlm_mask": (_i, [_p, _p, _i, _p, _i64, _i64, _p, _i, _i64, _i64, _u64, _u32, _u32, _u32, _i64, _i64, _i64, _p, _p, _p]),
+    "meant_patchify_raw_masked": (_i, [_p, _i, _f, _f, _p, _i64, _i, _i, _i, _i, _i, _u64, _u32, _p, _i64, _i64, _f, _p]),
+    "meant_mim_l1_ws": (_sz, [_i64]),
+    "meant_mim_l1_fwd": (_i, [_p, _i, _p, _i, _f, _f, _i64, _i, _i, _i, _i, _u64, _u32, _p, _i64, _i64, _f, _i, _p, _p, _p, _sz, _p]),
+    "meant_mim_l1_bwd": (_i, [_p, _i, _p, _i, _f, _f, _i64, _i, _i, _i, _i, _u64, _u32, _p, _i64, _i64, _f, _i, _p, _p, _p, _p]),
     "meant_sumsq_f32":(_i, [_p, _i64, _p, _p]),
     "meant_adamw_f32": (_i, [_p, _p, _p, _p, _i64, _f, _f, _f, _f, _f, _i64, _p, _f, _f, _p]),
     "meant_embedding_bwd_sorted": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i, _p]),

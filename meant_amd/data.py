@@ -17,6 +17,8 @@ What this does instead (one process per GPU, the GPU is the consumer):
     batch AHEAD of the consumer on a producer thread, so it overlaps both the GPU step and the Python that launches it;
   * the global mean / std are one streaming pass over the array (`global_mean_std`), not two in-place passes that
     rewrite 19.3 MB per sample.
+  * the pretraining collators (utils/custom_datasets.py:41-57, :116-126) run on the device from the raw batch: `MLMCollator`,
+    `MIMCollator`, keyed by the dataset indices that `with_index=True` appends to every batch (csrc/collate.hip).
 The loader is an iterator of `(graphs, tweets, macds, attention_masks, labels)` like the reference's
 `customDataset` (in_loop_train.py:62-76), so the reference's loop body runs on it unchanged.  On a CPU device it
 degrades to plain slicing (used by the CPU tests).
@@ -57,6 +59,86 @@ def shard_indices(n: int, rank: int, world: int, batch_size: int, shuffle: bool,
     return order[:, rank, :].reshape(-1)
 
 
+# ---- pretraining collators on the device (csrc/collate.hip) ----------------------------------------------------------
+_M64 = (1 << 64) - 1
+_GOLDEN = 0x9E3779B97F4A7C15
+
+
+def _fin(z: int) -> int:
+    """the finaliser of the library's counter hash: two xor-shift-multiply rounds and a last xor-shift, on 64 bits"""
+    z &= _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def collate_seed(seed: int, epoch: int) -> int:
+    """the masking rule's seed for one epoch: bits(seed, stream 3, epoch) of the rule itself, i.e.
+    fin(seed + (epoch | 3 << 60) * golden).  Never seed + epoch: the rule adds idx * golden to its seed, so seeds that differ by a
+    multiple of golden give each other's masks at a shifted index; a hashed seed has no such neighbour."""
+    epoch = int(epoch)
+    if not 0 <= epoch < (1 << 60):
+        raise ValueError(f"collate_seed: epoch {epoch} outside [0, 2^60)")
+    return _fin((int(seed) & _M64) + (epoch | (3 << 60)) * _GOLDEN)
+
+
+class MLMCollator:
+    """mlm_dataset.mask_tokens (utils/custom_datasets.py:41-57) as a call on device tensors:
+
+        collate = MLMCollator(mask_id=tok.mask_token_id, special_ids=tok.all_special_ids, vocab_size=len(tok))
+        for ids, mask, index in DeviceBatchLoader(input_ids, attention_mask, batch_size=64, with_index=True):
+            ids_masked, labels = collate(ids, mask, index)
+            loss = model.loss(ids_masked, mask, labels)
+
+    One kernel launch, no host draw, no label upload.  The mask of a sample depends on (seed, epoch, its dataset index) alone --
+    not on the batch it arrives in, the batch size or the number of ranks; `set_epoch` changes all of them."""
+
+    def __init__(self, p: float = 0.15, *, mask_id: int, special_ids=(), vocab_size: int, replace: float = 1.0, random: float = 0.0,
+                 ignore_index: int = -100, seed: int = 0):
+        from . import ops
+        ops.draw_threshold(p)
+        special_ids = tuple(int(v) for v in special_ids)
+        if len(special_ids) > 16:
+            raise ValueError(f"MLMCollator: at most 16 special ids, got {len(special_ids)}")
+        self.p, self.mask_id, self.special_ids, self.vocab_size = float(p), int(mask_id), special_ids, int(vocab_size)
+        self.replace, self.random, self.ignore_index, self.seed = float(replace), float(random), int(ignore_index), int(seed)
+        self.epoch = 0
+
+    def set_epoch(self, epoch: int):
+        self.epoch = int(epoch)
+
+    @property
+    def epoch_seed(self) -> int:
+        return collate_seed(self.seed, self.epoch)
+
+    def __call__(self, ids, attention_mask=None, sample_ids=None, sample_base: int = 0):
+        """(ids_masked, labels), both int64 on ids' device; sample_ids: the int64 device tensor of dataset indices a loader built
+        with `with_index=True` appends (None: sample_base + row)"""
+        from . import ops
+        return ops.mlm_mask(ids, attention_mask, sample_ids, mask_id=self.mask_id, special_ids=self.special_ids, vocab_size=self.vocab_size,
+                            p=self.p, replace=self.replace, random=self.random, ignore_index=self.ignore_index, seed=self.epoch_seed,
+                            sample_base=sample_base)
+
+
+class MIMCollator:
+    """mim_dataset.mask_image (utils/custom_datasets.py:116-126) as a rule, not as tensors: it holds (p, mask_value, unmasked_label,
+    on_masked, seed, epoch) and produces nothing.  `meant_vision_pretrainer.loss(images, collator, sample_ids)` applies the rule twice
+    -- on load in the patch embedding, and per element in the L1 loss -- so neither the masked image nor the label tensor exists."""
+
+    def __init__(self, p: float = 0.15, mask_value: float = 0.0, unmasked_label: float = -100.0, on_masked: bool = False, seed: int = 0):
+        from . import ops
+        ops.draw_threshold(p)
+        self.p, self.mask_value, self.unmasked_label = float(p), float(mask_value), float(unmasked_label)
+        self.on_masked, self.seed, self.epoch = bool(on_masked), int(seed), 0
+
+    def set_epoch(self, epoch: int):
+        self.epoch = int(epoch)
+
+    @property
+    def epoch_seed(self) -> int:
+        return collate_seed(self.seed, self.epoch)
+
+
 class DeviceBatchLoader:
     """Double-buffered host -> device batch stream.
 
@@ -67,7 +149,7 @@ class DeviceBatchLoader:
     `arrays` are host numpy arrays (or memmaps) with a common leading dimension; `None` entries stay `None`."""
 
     def __init__(self, *arrays: Optional[np.ndarray], batch_size: int, device="cuda", shuffle: bool = False, seed: int = 0,
-                 rank: int = 0, world: int = 1, drop_last: bool = True, pin_source_bytes: int = 0):
+                 rank: int = 0, world: int = 1, drop_last: bool = True, pin_source_bytes: int = 0, with_index: bool = False):
         assert any(a is not None for a in arrays), "no data"
         self.arrays = arrays
         self.n = next(a.shape[0] for a in arrays if a is not None)
@@ -76,6 +158,7 @@ class DeviceBatchLoader:
         self.batch_size, self.shuffle, self.seed, self.rank, self.world = batch_size, shuffle, seed, rank, world
         self.device = torch.device(device)
         self.epoch = 0
+        self.with_index = bool(with_index)               # every batch ends with the int64 device tensor of its dataset indices
         self.on_gpu = self.device.type == "cuda"
         assert drop_last, "partial batches are dropped (the kernels are tuned for the fixed batch shape)"
         self._stage = None
@@ -135,6 +218,9 @@ class DeviceBatchLoader:
         self._stage = [[pinned(a) for a in self.arrays] for _ in range(2)]
         self._dev = [[None if t is None else torch.empty_like(t, device=self.device) for t in s] for s in self._stage]
         self._ready = [None, None]
+        if self.with_index:
+            self._idx_stage = [pinned(np.empty((0,), dtype=np.int64)) for _ in range(2)]
+            self._idx_dev = [torch.empty_like(t, device=self.device) for t in self._idx_stage]
 
     def _fill_and_send(self, k: int, idx: np.ndarray):
         # multi-threaded gather straight into the pinned buffers (no intermediate copy, no conversion): each worker
@@ -152,10 +238,16 @@ class DeviceBatchLoader:
                         torch.index_select(torch.from_numpy(a) if not isinstance(a, torch.Tensor) else a, 0, sel, out=host[lo:hi])
         if any(staged):
             list(self._pool.map(part, range(nw)))
+        if self.with_index:
+            self._idx_stage[k].copy_(torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64)))
         if not self.on_gpu:
             self._dev[k] = [None if h is None else h.clone() for h in self._stage[k]]
+            if self.with_index:
+                self._idx_dev[k] = self._idx_stage[k].clone()
             return
         with torch.cuda.stream(self._stream):
+            if self.with_index:                              # the slice of shard_indices the batch was cut from rides the same stream
+                self._idx_dev[k].copy_(self._idx_stage[k], non_blocking=True)
             for i, (a, host, dev) in enumerate(zip(self.arrays, self._stage[k], self._dev[k])):
                 if host is None:
                     continue
@@ -199,7 +291,7 @@ class DeviceBatchLoader:
                 if b + 1 < nb:                            # batch b+1 is gathered and sent while the caller runs step b
                     pending = threading.Thread(target=produce, args=(k ^ 1, b + 1), daemon=True)
                     pending.start()
-                yield tuple(self._dev[k])
+                yield tuple(self._dev[k]) + ((self._idx_dev[k],) if self.with_index else ())
                 if self.on_gpu:
                     ev = torch.cuda.Event()
                     ev.record(torch.cuda.current_stream(self.device))

@@ -840,7 +840,25 @@ class meant_vision_pretrainer(nn.Module):
 
     def forward(self, images):
         dt = resolve_compute_dtype(self, images)
-        x = self.patchEmbed(images, dt)                                  # [B, n, d]
+        return self._decode(self.patchEmbed(images, dt))                 # [B, n, d] -> the decoder's image
+
+    def loss(self, images, collator, sample_ids=None, sample_base: int = 0):
+        """forward + nn.L1Loss (pretrain_mim.py:162,198-204) on RAW images [B, C, H, W] in their storage type, with the masking of
+        mim_dataset.mask_image applied on the device by `collator` (meant_amd.data.MIMCollator: the rule's parameters): the patch
+        embedding reads the pixels through the mask (ops.patchify_masked, with this model's own normalisation), the loss regenerates
+        the labels per element from the same pixels (ops.mim_l1_loss).  Neither the masked image nor the labels are ever stored, and
+        the host sends the raw batch alone.  sample_ids: the int64 device tensor of dataset indices (DeviceBatchLoader(...,
+        with_index=True)); None: sample_base + row."""
+        dt = resolve_compute_dtype(self, images)
+        pat, seed = self.patchEmbed[0], collator.epoch_seed
+        rule = dict(prob=collator.p, seed=seed, sample_ids=sample_ids, sample_base=sample_base)
+        patches = ops.patchify_masked(images, pat.p, dt, pat.norm_mean, pat.norm_std, mask_value=collator.mask_value, **rule)
+        out = self._decode(self.patchEmbed[1](patches)).contiguous()
+        return ops.mim_l1_loss(out, images, mean=pat.norm_mean, std=pat.norm_std, unmasked_label=collator.unmasked_label,
+                               on_masked=collator.on_masked, **rule)
+
+    def _decode(self, x):
+        """the path behind the patch embedding, shared by forward and loss: the encoder and the decoder on embedded patches [B, n, d]"""
         fold = ops.stack_fold(len(self.visionEncoders), x.numel() // x.shape[-1], x.shape[-1])
         for enc in self.visionEncoders:
             x = enc(x, fold=fold)

@@ -1446,6 +1446,168 @@ def patchify(images, p: int, dtype: torch.dtype, mean: float = 0.0, std: float =
     return out
 
 
+# ---------------------------------------------------------------------------------------------
+# Pretraining collators on the device (csrc/collate.hip; utils/custom_datasets.py:41-57, :116-126).  One integer rule decides what is
+# masked from (seed, dataset index, position); the routes below allocate their outputs and call the library, nothing else.
+DRAW_BITS = 24
+ID_BOUND = 1 << 31            # what sample_ids are taken to stay below unless the caller says otherwise (the 2^60 check of the rule)
+_MASK_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.int64: 2, torch.uint8: 3, torch.bool: 3, torch.int32: 4}
+_special_cache = {}
+
+
+def draw_threshold(p: float) -> int:
+    """floor(p * 2^24) in double: the integer the device compares its 24-bit draws against"""
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"meant_amd: a masking probability must lie in [0, 1], got {p}")
+    return int(math.floor(p * (1 << DRAW_BITS)))
+
+
+def _sample_ids(sample_ids, rows: int, what: str):
+    if sample_ids is None:
+        return None
+    if sample_ids.dtype != torch.int64 or sample_ids.numel() != rows:
+        raise ValueError(f"{what}: sample_ids must be int64 [{rows}], got {sample_ids.dtype} {tuple(sample_ids.shape)}")
+    return _c(sample_ids)
+
+
+def _special_ids(special_ids, device):
+    """the special-token list as a device tensor: a sequence is uploaded once per (values, device); a tensor must be int64 and live on
+    the current HIP device like every other operand (the kernel reads it: a host tensor raises the no-CPU-fallback error)"""
+    if special_ids is None:
+        return None, 0
+    if isinstance(special_ids, torch.Tensor):
+        if special_ids.dtype != torch.int64:
+            raise ValueError(f"mlm_mask: special_ids must be int64, got {special_ids.dtype}")
+        if special_ids.numel() > 16:
+            raise ValueError(f"mlm_mask: at most 16 special ids, got {special_ids.numel()}")
+        _need_gpu(special_ids)
+        t = _c(special_ids.reshape(-1))
+        return (t if t.numel() else None), t.numel()
+    key = (tuple(int(v) for v in special_ids), device)
+    if len(key[0]) > 16:
+        raise ValueError(f"mlm_mask: at most 16 special ids, got {len(key[0])}")
+    if not key[0]:
+        return None, 0
+    t = _special_cache.get(key)
+    if t is None:
+        t = _special_cache[key] = torch.tensor(key[0], dtype=torch.int64, device=device)
+    return t, len(key[0])
+
+
+def mlm_mask(ids, attention_mask=None, sample_ids=None, *, mask_id: int, special_ids=(), vocab_size: int, p: float = 0.15,
+             replace: float = 1.0, random: float = 0.0, ignore_index: int = -100, seed: int = 0, sample_base: int = 0,
+             id_bound: int = ID_BOUND, out=None):
+    """mlm_dataset.mask_tokens (utils/custom_datasets.py:41-57) on the device: ids int64 [B, S] -> (masked ids, labels).  A position
+    is chosen with probability p unless its id is a special id or attention_mask is 0 there; labels carry the original id at the
+    chosen positions and ignore_index elsewhere.  A chosen id becomes mask_id with probability `replace`, a uniform id below
+    vocab_size with probability `random`, and stays otherwise (1.0 / 0.0: the reference; 0.8 / 0.1: BERT's recipe).  The draws are
+    keyed by (seed, sample id, position): sample_ids int64 [B] on the device, or sample_base + row.  `out=ids` masks in place.
+    No gradient."""
+    _need_gpu(ids, attention_mask, sample_ids, out)
+    if ids.dim() != 2 or ids.dtype != torch.int64:
+        raise ValueError(f"mlm_mask: ids must be int64 [B, S], got {ids.dtype} {tuple(ids.shape)}")
+    if replace < 0.0 or random < 0.0 or replace + random > 1.0:
+        raise ValueError(f"mlm_mask: replace = {replace} and random = {random} must be probabilities that sum to at most 1")
+    ids = _c(ids)
+    B, S = ids.shape
+    mdt = 0
+    if attention_mask is not None:
+        if attention_mask.dtype not in _MASK_DTYPES or tuple(attention_mask.shape) != (B, S):
+            raise ValueError(f"mlm_mask: attention_mask must be [B, S] float32 / bfloat16 / int64 / int32 / uint8 / bool, got "
+                             f"{attention_mask.dtype} {tuple(attention_mask.shape)}")
+        attention_mask = _c(attention_mask)
+        mdt = _MASK_DTYPES[attention_mask.dtype]
+    sample_ids = _sample_ids(sample_ids, B, "mlm_mask")
+    spec, ns = _special_ids(special_ids, ids.device)
+    if out is None:
+        out = torch.empty_like(ids)
+    elif out.dtype != torch.int64 or out.shape != ids.shape or not out.is_contiguous():
+        raise ValueError("mlm_mask: out must be a contiguous int64 tensor of ids' shape")
+    labels = torch.empty_like(ids)
+    check(lib.meant_mlm_mask(_p(ids), _p(attention_mask), mdt, _p(sample_ids), int(sample_base), int(id_bound), _p(spec), ns, B, S,
+                             int(seed) & (2 ** 64 - 1), draw_threshold(p), draw_threshold(replace), draw_threshold(random), int(mask_id),
+                             int(vocab_size), int(ignore_index), _p(out), _p(labels), _stream()), "mlm_mask")
+    return out, labels
+
+
+def _raw_images(images, what: str):
+    if images.dim() != 4 or images.dtype not in _RAW_DTYPES:
+        raise TypeError(f"{what}: images must be [B, C, H, W] in float32 / bfloat16 / float64 / uint8 (their storage type), got "
+                        f"{images.dtype} {tuple(images.shape)}")
+    return _c(images)
+
+
+def patchify_masked(images, p: int, dtype: torch.dtype, mean: float = 0.0, std: float = 1.0, *, prob: float = 0.15, seed: int = 0,
+                    sample_ids=None, sample_base: int = 0, id_bound: int = ID_BOUND, mask_value: float = 0.0):
+    """`patchify` of the masked image of mim_dataset.mask_image (utils/custom_datasets.py:116-126) without the masked image: a patch
+    element is mask_value where the rule chooses the pixel element it comes from (probability `prob`, keyed by (seed, sample id,
+    (c, y, x))) and ((float)x - mean) / std elsewhere.  Raw pixels in their storage type; no gradient."""
+    _need_gpu(images, sample_ids)
+    images = _raw_images(images, "patchify_masked")
+    G, Cc, Hh, Ww = images.shape
+    sample_ids = _sample_ids(sample_ids, G, "patchify_masked")
+    out = torch.empty((G, (Hh // p) * (Ww // p), p * p * Cc), device=images.device, dtype=dtype)
+    check(lib.meant_patchify_raw_masked(_p(images), _RAW_DTYPES[images.dtype], float(mean), 1.0 / float(std), _p(out), G, Cc, Hh, Ww, p,
+                                        _dt(out), int(seed) & (2 ** 64 - 1), draw_threshold(prob), _p(sample_ids), int(sample_base),
+                                        int(id_bound), float(mask_value), _stream()), "patchify_raw_masked")
+    return out
+
+
+class _MimL1(torch.autograd.Function):
+    """L1Loss(out, labels[:, :Co]) with the labels of mask_image regenerated per element from the raw images; gradient to `out` only"""
+
+    @staticmethod
+    def forward(ctx, out, images, sample_ids, rule):
+        B, Co, Hh, Ww = out.shape
+        Cc = images.shape[1]
+        dev = out.device
+        loss = torch.empty(1, device=dev, dtype=torch.float32)
+        count = torch.empty(1, device=dev, dtype=torch.int64)
+        wsb = lib.meant_mim_l1_ws(out.numel())
+        ws = _ws(wsb, dev, 16)
+        head = (_RAW_DTYPES[images.dtype], rule["mean"], rule["inv_std"], B, Cc, Co, Hh, Ww, rule["seed"], rule["threshold"])
+        tail = (rule["sample_base"], rule["id_bound"], rule["unmasked_label"], rule["on_masked"])
+        check(lib.meant_mim_l1_fwd(_p(out), _dt(out), _p(images), *head, _p(sample_ids), *tail, _p(loss), _p(count), _p(ws), wsb, _stream()),
+              "mim_l1_fwd")
+        ctx.save_for_backward(out, images, sample_ids, count)
+        ctx.head, ctx.tail = head, tail
+        ctx.mark_non_differentiable(count)
+        return loss.view(()), count
+
+    @staticmethod
+    def backward(ctx, dloss, _dcount):
+        out, images, sample_ids, count = ctx.saved_tensors
+        g = dloss.reshape(1)
+        if g.dtype != torch.float32:
+            g = g.float()
+        g = _c(g)
+        _need_gpu(g)
+        dout = torch.empty_like(out)
+        check(lib.meant_mim_l1_bwd(_p(out), _dt(out), _p(images), *ctx.head, _p(sample_ids), *ctx.tail, _p(g), _p(count), _p(dout), _stream()),
+              "mim_l1_bwd")
+        return dout, None, None, None
+
+
+def mim_l1_loss(out, images, *, prob: float = 0.15, seed: int = 0, sample_ids=None, sample_base: int = 0, id_bound: int = ID_BOUND,
+                mean: float = 0.0, std: float = 1.0, unmasked_label: float = -100.0, on_masked: bool = False, return_count: bool = False):
+    """nn.L1Loss()(out, labels[:, 0:Co]) (pretrain_mim.py:162,204) for out [B, Co, H, W] (fp32 or bf16, Co <= C) against the labels of
+    mim_dataset.mask_image -- the normalised pixel where the rule chooses it, unmasked_label (-100) elsewhere -- regenerated from the raw
+    `images` [B, C, H, W] by the same (prob, seed, sample ids, mean, std) that patchify_masked was called with; no label tensor
+    exists.  on_masked: mean over the chosen elements only (SimMIM's form; an empty mask gives 0).  Ordered sums: the same call gives
+    the same bits.  return_count: also the int64 [1] device count of chosen elements among out's."""
+    _need_gpu(out, images, sample_ids)
+    images = _raw_images(images, "mim_l1_loss")
+    if out.dim() != 4 or out.shape[0] != images.shape[0] or out.shape[2:] != images.shape[2:] or not 0 < out.shape[1] <= images.shape[1]:
+        raise ValueError(f"mim_l1_loss: out {tuple(out.shape)} does not fit images {tuple(images.shape)} ([B, Co <= C, H, W])")
+    _dt(out)
+    sample_ids = _sample_ids(sample_ids, out.shape[0], "mim_l1_loss")
+    rule = dict(mean=float(mean), inv_std=1.0 / float(std), seed=int(seed) & (2 ** 64 - 1), threshold=draw_threshold(prob),
+                sample_base=int(sample_base), id_bound=int(id_bound), unmasked_label=float(unmasked_label), on_masked=int(bool(on_masked)))
+    loss, count = _MimL1.apply(_c(out), images, sample_ids, rule)
+    return (loss, count) if return_count else loss
+
+
 EMB_BF16_TABLE = os.environ.get("MEANT_EMB_BF16_TABLE", "1") == "1"     # 0: the bf16 tier's lookup reads the fp32 table (A/B measurements)
 
 
