@@ -305,7 +305,9 @@ size_t meant_attn_fwd_ws(int64_t G, int64_t S, int H, int Dh, int dtype);
  *                         == 1, ... -- the order in which the rotary projection walks its row panels   (npan words, [1] valid)
  *   [64 + nblk + npan ..) the dead panels, in the same order                          (npan words, [2] valid)
  *   then nblk words of scratch.
+ * The 64 is MEANT_KV_LIST_HDR: the one declaration of the header's length, for the library, its callers and the tests.
  * No host synchronisation: the counts stay on the device. */
+enum meant_kv_list_layout { MEANT_KV_LIST_HDR = 64 };
 size_t meant_kv_live_rows_ws(int64_t G, int64_t S);
 int meant_kv_live_rows(const float* key_mask, int64_t G, int64_t S, int causal, void* lists, size_t lists_bytes, void* stream);
 int meant_attn_fwd(const void* qkv, void* o, float* lse, const float* key_mask, int64_t G, int64_t S, int H,

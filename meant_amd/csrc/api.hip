@@ -61,7 +61,7 @@ extern "C" int meant_qkv_proj_fwd_live(const void* x, int64_t ldx, const void* w
   const int* const lists = (const int*)kv_lists;
   const int64_t nblk = M / 64, npan = M / 256;
   const auto zero_dead = [&]() {
-    return zero_panels_launch((bf16*)qkv + (int64_t)H * Dh, 3 * (int64_t)H * Dh, 2 * (int64_t)H * Dh, lists + 64 + nblk + npan, lists + 2, npan,
+    return zero_panels_launch((bf16*)qkv + (int64_t)H * Dh, 3 * (int64_t)H * Dh, 2 * (int64_t)H * Dh, lists + MEANT_KV_LIST_HDR + nblk + npan, lists + 2, npan,
                               (hipStream_t)stream);
   };
   const bool rot = qa != nullptr;
@@ -80,7 +80,7 @@ extern "C" int meant_qkv_proj_fwd_live(const void* x, int64_t ldx, const void* w
       q.N = D;
       kv.N = 2 * D; kv.col0 = (int)D;
       kv.B = a.B + D * K; kv.C = a.C + D; kv.bias = bias ? bias + D : nullptr;
-      kv.panel_list = lists + 64 + nblk; kv.panel_count = lists + 1;
+      kv.panel_list = lists + MEANT_KV_LIST_HDR + nblk; kv.panel_count = lists + 1;
       if (D % 256 == 0 && gemm_bf16_nt_streams(q) && gemm_bf16_nt_streams(kv)) {
         int rc = gemm_bf16_nt_launch(q, (hipStream_t)stream);
         if (!rc) rc = gemm_bf16_nt_launch(kv, (hipStream_t)stream);

@@ -80,8 +80,8 @@ __global__ __launch_bounds__(64) void attn_prep_mask_kernel(const float* __restr
 //   kv_live_lists_kernel: one workgroup compacts them into out = [n live blocks, n live panels, n dead panels, 61 words unused |
 //                         live blocks, ascending | live panels | dead panels].  The panel lists are ordered by position range (all panels p with
 //                         p mod (S / 256) == 0 first, ascending, then == 1, ...): the order in which the rotary projection walks its panels.
-// Counts stay on the device: the GEMMs read them there, their grids are sized for the full problem.
-constexpr int KV_LIST_HDR = 64;
+// Counts stay on the device: the GEMMs read them there, their grids are sized for the full problem.  The lists start MEANT_KV_LIST_HDR
+// words in (meant_hip.h).
 __global__ __launch_bounds__(64) void kv_live_flag_kernel(const float* __restrict__ km, int* __restrict__ live, int S, int nt, int causal) {
   const int g = blockIdx.y, t = blockIdx.x, lane = threadIdx.x;
   const float b = key_tile_bias(km, g, t, S, lane);
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(1024) void kv_live_lists_kernel(const int* __restri
   __shared__ int s_tot[3];
   const int tid = threadIdx.x;
   const int npan = nblk >> 2, Q = npan / P;
-  int* const blocks = out + KV_LIST_HDR;
+  int* const blocks = out + MEANT_KV_LIST_HDR;
   int* const panels = blocks + nblk;
   int* const dead = panels + npan;
   // exclusive prefix of this thread's count over the workgroup (Hillis-Steele in LDS); the total lands in s_tot[slot]
@@ -1150,14 +1150,14 @@ int attn_bf16_bwd(const bf16* qkv, const bf16* o, const bf16* dout, const float*
 // live 64-row blocks / 256-row panels of the [G * S] token rows under `key_mask` (see kv_live_flag_kernel); lists: kv_live_rows_bytes(G, S)
 size_t kv_live_rows_bytes(int64_t G, int64_t S) {
   const int64_t nblk = G * (S / KV_TILE), npan = nblk / 4;
-  return (size_t)(KV_LIST_HDR + 2 * nblk + 2 * npan) * sizeof(int);
+  return (size_t)(MEANT_KV_LIST_HDR + 2 * nblk + 2 * npan) * sizeof(int);
 }
 
 int kv_live_rows_launch(const float* key_mask, int64_t G, int64_t S, int causal, int* lists, hipStream_t stream) {
   MEANT_REQUIRE(key_mask && lists && S % 256 == 0 && G > 0 && G <= 65535 && G * (S / KV_TILE) < (1LL << 30), MEANT_ERR_UNSUPPORTED,
                 "kv_live_rows: needs a key mask, S %% 256 == 0 and G <= 65535 (G=%lld S=%lld)", (long long)G, (long long)S);
   const int nt = (int)(S / KV_TILE), nblk = (int)(G * nt);
-  int* live = lists + KV_LIST_HDR + nblk + 2 * (nblk / 4);
+  int* live = lists + MEANT_KV_LIST_HDR + nblk + 2 * (nblk / 4);
   hipLaunchKernelGGL(kv_live_flag_kernel, dim3((unsigned)nt, (unsigned)G), dim3(64), 0, stream, key_mask, live, (int)S, nt, causal);
   MEANT_LAUNCH_CHECK("kv_live_flag");
   hipLaunchKernelGGL(kv_live_lists_kernel, dim3(1), dim3(1024), 0, stream, live, lists, nblk, (int)(S / 256));

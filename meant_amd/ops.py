@@ -738,7 +738,7 @@ def _bwd_dw_rows(dy2, x2, dw, db, lists):
                                        lists.data_ptr(), M, N, K, dt, _p(ws), wsb, _stream()), "linear_bwd_dw_rows")
 
 
-KV_LIST_HEADER = 64        # int32 words in front of the lists of meant_kv_live_rows (include/meant_hip.h): [live blocks, live panels, dead panels, ...]
+KV_LIST_HEADER = _lib.KV_LIST_HDR       # int32 words in front of the lists of meant_kv_live_rows (include/meant_hip.h): [live blocks, live panels, dead panels, ...]
 KV_SKIP_DW, KV_SKIP_FWD = 1, 2          # bits of the library option "kv_skip": the k|v weight gradient, the forward projection
 
 
@@ -1451,7 +1451,8 @@ def patchify(images, p: int, dtype: torch.dtype, mean: float = 0.0, std: float =
 # masked from (seed, dataset index, position); the routes below allocate their outputs and call the library, nothing else.
 DRAW_BITS = 24
 ID_BOUND = 1 << 31            # what sample_ids are taken to stay below unless the caller says otherwise (the 2^60 check of the rule)
-_MASK_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.int64: 2, torch.uint8: 3, torch.bool: 3, torch.int32: 4}
+_MASK_DTYPES = {torch.float32: _lib.MASK_F32, torch.bfloat16: _lib.MASK_BF16, torch.int64: _lib.MASK_I64, torch.uint8: _lib.MASK_U8,
+                torch.bool: _lib.MASK_U8, torch.int32: _lib.MASK_I32}
 _special_cache = {}
 
 

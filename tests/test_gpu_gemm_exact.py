@@ -483,9 +483,10 @@ def test_dw_rows_lists_of_kv_live_rows(L, dev, mask, det):
     kmd = km.to(dev)
     L.check(L.lib.meant_kv_live_rows(kmd.data_ptr(), G, S, 0, lists.data_ptr(), nbytes, _stream()), "kv_live_rows")
     torch.cuda.synchronize()
-    assert lists[0].item() == len(blocks) and lists[64:64 + len(blocks)].tolist() == blocks
+    hdr = L.KV_LIST_HDR
+    assert lists[0].item() == len(blocks) and lists[hdr:hdr + len(blocks)].tolist() == blocks
     with case(L, f"dw tn256_rows (4096,256,512) kv_live_rows {mask}", deterministic=det) as c:
-        _blocks_case(L, dev, c, G * S, blocks, (lists.data_ptr() + 256, lists.data_ptr()), det, mask, live_rows=km.view(-1).to(torch.int64))
+        _blocks_case(L, dev, c, G * S, blocks, (lists.data_ptr() + 4 * hdr, lists.data_ptr()), det, mask, live_rows=km.view(-1).to(torch.int64))
 
 
 # ---- f: fused projection with the rotary epilogue --------------------------------------------------------------------------------------
