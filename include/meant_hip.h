@@ -118,6 +118,8 @@ int64_t meant_debug_nt_steals(void);
 int meant_rmsnorm_fwd(const void* x, const float* scale, void* y, float* rinv, int64_t rows, int64_t d,
                       float eps, float drop_p, uint64_t seed, int dtype, void* stream);
 /* dx: act [rows, d]; dscale: float [d] (overwritten); workspace: meant_rmsnorm_bwd_ws(rows, d) bytes.
+ * Every parameter gradient of this section (dscale, doffset, dbias_up, dgamma, dbeta) is an ordered sum: no atomics, the same bits
+ * on every run.
  * Optional fusions (NULL to disable): dres act [rows, d] is added to dx (the gradient of the residual
  * branch that shares x, meant/meant.py:71,74); gelu_pre act [rows, d]: x was gelu(gelu_pre), and dx is
  * multiplied by gelu'(gelu_pre) so that it is the gradient w.r.t. gelu_pre (meant/meant.py:64). */

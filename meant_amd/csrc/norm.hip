@@ -599,13 +599,26 @@ __global__ __launch_bounds__(NORM_THREADS, 2) void rmsnorm_bwd_packed_kernel(con
   }
 }
 
-// out[j] = sum_p partial[p, j]   (and optionally a second array at partial + np*d)
-__global__ void colreduce_kernel(const float* __restrict__ partial, float* __restrict__ out, int np, int d) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= d) return;
+// out[j] (+)= sum_p partial[p, j] in a FIXED order: the last step of every parameter gradient above.  The kernels keep their sums
+// ordered (registers, LDS, one partial row per workgroup); colsum_launch, which the Linear bias gradient uses, would add its row
+// strips with float atomics from 65 partial rows on, and the bits of dscale / dbias_up / dgamma / dbeta would change from run to run.
+// A workgroup takes COLRED_COLS columns; its row lanes stride the partial rows and are combined through LDS in lane order.
+constexpr int COLRED_COLS = 16, COLRED_LANES = NORM_THREADS / COLRED_COLS;
+__global__ __launch_bounds__(NORM_THREADS) void colreduce_kernel(const float* __restrict__ partial, float* __restrict__ out, int np, int64_t d,
+                                                                  int accumulate) {
+  __shared__ float red[COLRED_LANES][COLRED_COLS];
+  const int cl = threadIdx.x % COLRED_COLS, rl = threadIdx.x / COLRED_COLS;
+  const int64_t j = (int64_t)blockIdx.x * COLRED_COLS + cl;
   float s = 0.f;
-  for (int p = 0; p < np; ++p) s += partial[(int64_t)p * d + j];
-  out[j] = s;
+  if (j < d)
+    for (int p = rl; p < np; p += COLRED_LANES) s += partial[(int64_t)p * d + j];
+  red[rl][cl] = s;
+  __syncthreads();
+  if (rl == 0 && j < d) {
+    float t = accumulate ? out[j] : 0.f;
+    for (int l = 0; l < COLRED_LANES; ++l) t += red[l][cl];
+    out[j] = t;
+  }
 }
 
 template <typename T>
@@ -1135,11 +1148,13 @@ template <int N> using Int = std::integral_constant<int, N>;
 template <typename F> inline int switch_c(int C, F&& f) { return C == 1 ? f(Int<1>{}) : C == 2 ? f(Int<2>{}) : f(Int<3>{}); }
 template <typename F> inline int switch_v(int V, F&& f) { return V == 8 ? f(Int<8>{}) : f(Int<1>{}); }
 
-// the reductions of per-block partial rows every backward ends with: out1 from `partial`, out2 (if not null) from the plane after it
+// the ordered reductions of per-block partial rows every backward ends with: out1 from `partial`, out2 (if not null) from the plane after it
 inline int norm_colsums(const float* partial, int nb, int64_t d, float* out1, float* out2, int accumulate2, void* stream) {
-  int rc = colsum_launch(partial, d, out1, nb, d, MEANT_F32, 0, (hipStream_t)stream);
-  if (rc || !out2) return rc;
-  return colsum_launch(partial + (size_t)nb * d, d, out2, nb, d, MEANT_F32, accumulate2, (hipStream_t)stream);
+  const dim3 grid((unsigned)ceil_div(d, (int64_t)COLRED_COLS));
+  hipLaunchKernelGGL(colreduce_kernel, grid, dim3(NORM_THREADS), 0, (hipStream_t)stream, partial, out1, nb, d, 0);
+  if (out2) hipLaunchKernelGGL(colreduce_kernel, grid, dim3(NORM_THREADS), 0, (hipStream_t)stream, partial + (size_t)nb * d, out2, nb, d, accumulate2);
+  MEANT_LAUNCH_CHECK("norm_colsums");
+  return MEANT_OK;
 }
 
 // ---- launchers: each kernel template is named here and nowhere else ----

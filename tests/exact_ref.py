@@ -4,7 +4,9 @@ to equal an int64 reference with zero tolerance.  A dropped, doubled, misplaced 
 
 Helpers (not collected): integer generators, placement of operands as column slices of wider poisoned buffers, outputs inside
 sentinel-filled buffers, the exact comparison and the guard check.  Used by tests/test_gemm_exact_host.py (CPU: shows that the
-method rejects the mutants the relative bounds accept) and tests/test_gpu_gemm_exact.py (every GEMM route at the C ABI)."""
+method rejects the mutants the relative bounds accept) and tests/test_gpu_gemm_exact.py (every GEMM route at the C ABI); the
+generators at the end carry the method to the norm kernels' cross-row reductions (tests/test_norm_exact_host.py,
+tests/test_gpu_norm_exact.py)."""
 import numpy as np
 import torch
 
@@ -103,3 +105,55 @@ def assert_guard(buf, rows, cols, what=""):
     r, c = int(bad[0, 0]), int(bad[0, 1])
     raise AssertionError(f"{what}: {bad.shape[0]} guard elements overwritten; first at (row {r}, column {c}) of a [{rows}, {cols}] "
                          f"output in a [{buf.shape[0]}, {buf.shape[1]}] buffer")
+
+
+# ---- norm kernels: cross-row reductions on integers times powers of two (tests/test_norm_exact_host.py, tests/test_gpu_norm_exact.py) ----
+# Every backward entry of csrc/norm.hip takes its statistics as INPUTS, so with integer dy / x, rinv[row] = 2^e(row) and an integer
+# mean every term dy * x * rinv of a gain gradient is an integer in units of 2^POW2_LO: (dy * x) * r, dy * (x * r) and the fused
+# multiply-add of either are all exact, and so is their fp32 sum in any order while it stays below 2^24 of those units.
+POW2_LO, POW2_HI, POW2_PERIOD = -2, 2, 5      # e cycles through {-2, ..., 2}: period 5, coprime to the 4 wave slots and to R = 1, 2, 4
+POW2_DENOM = 1 << -POW2_LO                    # references of rinv-weighted sums are in units of 1 / POW2_DENOM
+
+
+def pow2_exponents(rows, shift=0):
+    """e(row) in {POW2_LO, ..., POW2_HI}: rows of one packed group, of one workgroup and of one grid-stride pass differ"""
+    return (torch.arange(int(rows), dtype=torch.int64) + shift) % POW2_PERIOD + POW2_LO
+
+
+def pow2(e):
+    return torch.pow(torch.tensor(2.0, dtype=torch.float64), e.double())
+
+
+def ln_stats(rows):
+    """LayerNorm statistics as inputs: (integer mean in [-2, 2] at period 3, exponent of rstd at period 5), both int64 [rows]"""
+    return torch.arange(int(rows), dtype=torch.int64) % 3 * 2 - 2, pow2_exponents(rows, 1)
+
+
+def expand_groups(dy_g, group_rows):
+    """[groups, d] -> [groups * group_rows, d]: row r sees dy_g[r // group_rows] (the division by group_rows goes into `denom`)"""
+    return dy_g.repeat_interleave(int(group_rows), dim=0)
+
+
+def rms_dscale_ref(dy, x, e):
+    """sum_r dy[r] * x[r] * 2^e[r] in units of 1 / POW2_DENOM, int64 [d]"""
+    return (dy * x * (1 << (e - POW2_LO))[:, None]).sum(0)
+
+
+def ln_dgamma_ref(dy, x, mean, e):
+    """sum_r dy[r] * (x[r] - mean[r]) * 2^e[r] in units of 1 / POW2_DENOM, int64 [d]"""
+    return (dy * (x - mean[:, None]) * (1 << (e - POW2_LO))[:, None]).sum(0)
+
+
+def colsum_ref(dy):
+    """doffset / dbeta: sum_r dy[r], int64 [d]"""
+    return dy.sum(0)
+
+
+def bits(buf):
+    """a copy of the buffer's bit patterns (the signed integer view of its width): two runs of one entry have to agree in these"""
+    return buf.view(_INT_VIEW[buf.dtype]).clone()
+
+
+def assert_exact_regime(want, terms_bound, what=""):
+    """a reference and the bound on the sum of the magnitudes of its terms (hence on every partial sum, in any order) stay below 2^24"""
+    assert int(want.abs().max().item()) <= int(terms_bound) < F32_INT_LIMIT, f"{what}: partial sums may reach {terms_bound} >= 2^24"
