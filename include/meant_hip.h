@@ -97,7 +97,8 @@ int meant_get_option(const char* name, int* value);
  * "nt_rot" (every bf16 NT GEMM launched with the rotary epilogue, on top of the nt* route it takes), "metrics_rows" /
  * "metrics_wave" / "metrics_labels" (meant_metrics_update by form, every meant_metrics_update_labels launch), "score_capture"
  * (every meant_score_capture launch), "auroc_rank" (every meant_auroc_rank call with n > 0), "ce_soft_wave" / "ce_soft_block"
- * (meant_ce_probs_soft by form) and "vqa_score" (every meant_vqa_score_update launch));
+ * (meant_ce_probs_soft by form), "vqa_score" (every meant_vqa_score_update launch), "grad_stats" (every meant_grad_stats_f32 call
+ * with n > 0) and "optim_step" (every meant_optim_step_f32 launch));
  * -1 for an unknown name.  The names label routes, not kernels: "nt256s" / "nt256s_rot" count launches of the streaming
  * GEMM (whichever kernel implements it), "nt_split" the ragged head + tail split.  Tests use it to prove that a shape
  * reaches the kernel it is meant to exercise. */
@@ -682,6 +683,56 @@ int meant_sumsq_f32(const float* x, int64_t n, float* out_accum, void* stream);
 int meant_adamw_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                     float eps, float weight_decay, int64_t step, const float* sumsq, float max_norm,
                     float grad_scale, void* stream);
+/* ---- guarded optimizer tail ------ in_loop_train.py:202-239 (GradScaler, clip_grad_norm_, scaler.step / update), :548-550 (-o)
+ * A second tail beside the two entries above, which stay as they are: the gradient statistics, the decision to skip a step with a
+ * non-finite gradient, the step count and the loss scale live in a state block on the device, and the host reads none of them.
+ * The caller owns MEANT_OPTIM_STATE_BYTES of device memory, 8-byte aligned, zero-filled once (and then, for loss scaling, its scale):
+ *   offset  type    content
+ *        0  double  sumsq: sum of the squares of the finite gradient elements of the step in flight
+ *        8  int64   nonfinite: inf / NaN gradient elements of the step in flight
+ *       16  int64   steps taken
+ *       24  int64   steps skipped
+ *       32  float   loss scale; a stored 0 reads as 1
+ *       36  int32   growth_tracker: finite steps since the scale last changed
+ *       40  float   global norm of the unscaled gradients of the last step taken, sqrt(sumsq) / scale: its clip coefficient is
+ *                   min(1, max_norm / (norm + 1e-6)).  (The coefficient itself cannot be kept here: meant_optim_step_f32 must not
+ *                   write the block, and meant_optim_finish is not told max_norm.)
+ *       44  int32   1 when the last step was skipped, else 0
+ *    48-63          reserved
+ * One step: meant_grad_stats_f32 over every bucket (first != 0 on the first), meant_optim_step_f32 over every bucket,
+ * meant_optim_finish once.  With data parallelism the statistics are taken from the REDUCED buckets, so every rank decides alike.
+ *
+ * meant_grad_stats_f32: a finite element of g [n] adds its square to sumsq, a non-finite one adds 1 to nonfinite and nothing to sumsq;
+ * first != 0 overwrites the two fields (a new step), first == 0 adds to them (the next bucket).  Two launches, no atomics: every
+ * span of consecutive elements (4096, more only beyond 2^28 elements: a function of n alone, never of the grid or the device) leaves
+ * one double partial and one count in the workspace, then one workgroup adds the partials in an order fixed by n, in double.  The
+ * same call gives the same bits on every run, whatever "deterministic" says.  16-byte loads, element loads on the n % 4 tail.
+ * Unlike torch, sumsq is a DOUBLE sum of the finite squares: a norm that would overflow float32 while every element is finite
+ * still clips correctly, where clip_grad_norm_ would scale such gradients to zero.  Route name "grad_stats".
+ * workspace: meant_grad_stats_ws(n) bytes (host arithmetic, monotone in n, 0 for n <= 0), 16-byte aligned.
+ *
+ * meant_optim_step_f32: one Adam / AdamW step over flat buffers.  Reads the state and never writes it, so every bucket of a step
+ * sees the same values.  nonfinite != 0: returns without storing to p, m or v.  Otherwise t = steps + 1, the bias corrections
+ * 1 - beta^t computed on the device in double, inv = 1 / scale, and with max_norm > 0 the clip coefficient
+ *   clip_scaled == 0:  c = min(1, max_norm / (sqrt(sumsq) * inv + 1e-6))      unscale, then clip
+ *   clip_scaled != 0:  c = min(1, max_norm / (sqrt(sumsq) + 1e-6))            clip what backward left, then unscale (the reference)
+ * (c = 1 with max_norm <= 0); the gradient is read as g * c * inv.  MEANT_OPTIM_ADAMW: the arithmetic of meant_adamw_f32 (decoupled
+ * decay).  MEANT_OPTIM_ADAM: torch.optim.Adam, weight_decay * p added to the gradient and no decoupled decay.  Route name "optim_step".
+ *
+ * meant_optim_finish: one tiny launch after the last bucket.  nonfinite != 0: skipped += 1 and, with dynamic != 0, scale *=
+ * backoff_factor, growth_tracker = 0.  Otherwise steps += 1 and, with dynamic != 0, torch's _amp_update_scale_: growth_tracker += 1;
+ * when it reaches growth_interval (>= 1), scale *= growth_factor only if the product is finite, and growth_tracker = 0.  Writes the
+ * words at offsets 40 (finite steps only) and 44.
+ *
+ * A null pointer, n < 0, a misaligned operand or an unknown kind: MEANT_ERR_ARG; a workspace that is too small: MEANT_ERR_WORKSPACE;
+ * both before any launch.  n == 0: MEANT_OK without a launch. */
+enum meant_optim_kind { MEANT_OPTIM_ADAMW = 0, MEANT_OPTIM_ADAM = 1 };
+enum meant_optim_state_layout { MEANT_OPTIM_STATE_BYTES = 64 };
+size_t meant_grad_stats_ws(int64_t n);
+int meant_grad_stats_f32(const float* g, int64_t n, void* state, int first, void* workspace, size_t workspace_bytes, void* stream);
+int meant_optim_step_f32(float* p, const float* g, float* m, float* v, int64_t n, int kind, float lr, float beta1, float beta2,
+                         float eps, float weight_decay, float max_norm, int clip_scaled, const void* state, void* stream);
+int meant_optim_finish(void* state, float growth_factor, float backoff_factor, int growth_interval, int dynamic, void* stream);
 
 #ifdef __cplusplus
 }

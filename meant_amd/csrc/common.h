@@ -62,6 +62,7 @@ enum meant_route_id {
   ROUTE_EMB_SEG, ROUTE_SORT_IDS, ROUTE_NT128K, ROUTE_NT256K, ROUTE_SELECT_ROWS, ROUTE_ROTARY_QK, ROUTE_ROTARY_PAIRS, ROUTE_NT_ROT,
   ROUTE_METRICS_ROWS, ROUTE_METRICS_WAVE, ROUTE_METRICS_LABELS, ROUTE_TN256_ROWS, ROUTE_ATTN_CLS_SPLIT, ROUTE_ROWS_ELEM,
   ROUTE_SCORE_CAPTURE, ROUTE_AUROC_RANK, ROUTE_CE_SOFT_WAVE, ROUTE_CE_SOFT_BLOCK, ROUTE_VQA_SCORE,
+  ROUTE_GRAD_STATS, ROUTE_OPTIM_STEP,
   MEANT_ROUTE_COUNT
 };
 void meant_route_hit(int route);

@@ -147,6 +147,7 @@ const char* const k_routes[MEANT_ROUTE_COUNT] = {
     "score_capture", "auroc_rank",  // every meant_score_capture launch; every meant_auroc_rank call with n > 0
     "ce_soft_wave", "ce_soft_block",   // meant_ce_probs_soft by form (C <= 1024: a wave per row / above: a workgroup per row)
     "vqa_score",                    // every meant_vqa_score_update launch
+    "grad_stats", "optim_step",     // every meant_grad_stats_f32 call with n > 0; every meant_optim_step_f32 launch
 };
 std::atomic<long long> g_route[MEANT_ROUTE_COUNT];
 }  // namespace

@@ -5,6 +5,11 @@ AdamW(lr 5e-5), CosineAnnealingWarmRestarts(T_0=7) stepped per epoch.  Here: bf1
 and the tail of the step is three kinds of HIP launches over the flat fp32 buckets of the gradient reducer
 (meant_amd/parallel.py) -- one sum-of-squares pass, one fused clip+AdamW pass per bucket -- instead of PyTorch's
 per-tensor foreach chains.  Nothing in the step synchronises with the host.
+
+The reference's own guard and its other driver choices are opt-in (GuardedAdam, through TrainStep(optimizer=, nonfinite=,
+loss_scale=, clip_scaled=)): a step with an inf / NaN gradient is skipped, `-o Adam`, and the GradScaler recipe itself, with
+the gradient statistics, the skip decision, the step count and the loss scale kept on the device; CosineAnnealing and LinearLR
+are the driver's other two `-lrst` schedulers.
 """
 from __future__ import annotations
 
@@ -13,7 +18,7 @@ from typing import Iterable, Optional
 
 import torch
 
-from . import ops
+from . import _lib, ops
 from ._lib import lib, check
 from .parallel import GradReducer
 
@@ -150,6 +155,157 @@ class FusedAdamW:
             d.copy_(s)
 
 
+class GuardedAdam:
+    """The reference's guarded step on the reducer's flat buckets, with every decision taken on the device:
+    `scaler.scale(loss).backward(); clip_grad_norm_; scaler.step(optimizer); scaler.update()` (in_loop_train.py:235-239) for
+    `-o AdamW` and `-o Adam` (:548-550; Adam's weight_decay is L2 added to the gradient).
+
+        red = GradReducer(model.parameters()); opt = GuardedAdam(red, kind="adam", loss_scale="dynamic", max_grad_norm=1.0)
+        red.prepare(); loss = f(model(x)); opt.scale(loss).backward(); red.wait(); opt.step()
+
+    A step whose reduced gradients hold an inf or a NaN changes no parameter and no moment and is counted as skipped; the step
+    count (the bias corrections' t), the loss scale and its growth tracker live in a 64-byte state block on the device
+    (include/meant_hip.h) that step() never reads back.  The statistics are taken after reducer.wait(), so every data-parallel
+    rank takes the same decision.  loss_scale: None (no scaling, the guard alone), a float (a fixed scale) or "dynamic"
+    (torch.amp.GradScaler's rule from init_scale).  clip_scaled=True clips the still-scaled gradients as the reference does
+    (clip_grad_norm_ before scaler.step); False unscales first, the documented torch recipe."""
+
+    KINDS = {"adamw": "OPTIM_ADAMW", "adam": "OPTIM_ADAM"}
+
+    def __init__(self, reducer: GradReducer, kind: str = "adamw", lr: float = 5e-5, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 1e-2, max_grad_norm: Optional[float] = None, clip_scaled: bool = False, loss_scale=None,
+                 init_scale: float = 65536.0, growth_factor: float = 2.0, backoff_factor: float = 0.5, growth_interval: int = 2000):
+        if kind not in self.KINDS:
+            raise ValueError(f"GuardedAdam: kind must be one of {sorted(self.KINDS)}, got {kind!r}")
+        if not (loss_scale is None or loss_scale == "dynamic" or (isinstance(loss_scale, (int, float)) and loss_scale > 0)):
+            raise ValueError(f"GuardedAdam: loss_scale must be None, a positive number or 'dynamic', got {loss_scale!r}")
+        self.reducer, self.kind, self._kind = reducer, kind, getattr(_lib, self.KINDS[kind])
+        self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
+        self.max_grad_norm, self.clip_scaled = max_grad_norm, bool(clip_scaled)
+        self.dynamic = loss_scale == "dynamic"
+        self.growth_factor, self.backoff_factor, self.growth_interval = growth_factor, backoff_factor, int(growth_interval)
+        self.flat_params = flatten_parameters(reducer)
+        self.exp_avg = [torch.zeros_like(f) for f in self.flat_params]
+        self.exp_avg_sq = [torch.zeros_like(f) for f in self.flat_params]
+        dev = self.flat_params[0].device if self.flat_params else torch.device("cuda")
+        self.state = torch.zeros(_lib.OPTIM_STATE_BYTES, device=dev, dtype=torch.uint8)
+        self._i64, self._f32, self._i32 = self.state.view(torch.int64), self.state.view(torch.float32), self.state.view(torch.int32)
+        self._scale = self._f32[8]                       # offset 32: a 0-dim view, read by scale() on the device
+        self._scaling = loss_scale is not None
+        self._scale.fill_(float(init_scale) if self.dynamic else float(loss_scale or 1.0))
+        nmax = max((b.flat.numel() for b in reducer.buckets), default=0)
+        self._ws = torch.empty(max(16, lib.meant_grad_stats_ws(nmax)), device=dev, dtype=torch.uint8)
+
+    def scale(self, loss: torch.Tensor) -> torch.Tensor:
+        """loss * scale with the scale read on the device; the loss itself when no loss scaling was asked for"""
+        return loss * self._scale if self._scaling else loss
+
+    @torch.no_grad()
+    def step(self):
+        st, state, first = ops._stream(), ops._p(self.state), 1
+        for b in self.reducer.buckets:
+            if b.flat.numel() == 0:
+                continue
+            check(lib.meant_grad_stats_f32(ops._p(b.flat), b.flat.numel(), state, first, ops._p(self._ws), self._ws.numel(), st),
+                  "grad_stats_f32")
+            first = 0
+        for b, p, m, v in zip(self.reducer.buckets, self.flat_params, self.exp_avg, self.exp_avg_sq):
+            check(lib.meant_optim_step_f32(ops._p(p), ops._p(b.flat), ops._p(m), ops._p(v), p.numel(), self._kind, self.lr,
+                                           self.betas[0], self.betas[1], self.eps, self.weight_decay, float(self.max_grad_norm or 0.0),
+                                           int(self.clip_scaled), state, st), "optim_step_f32")
+        check(lib.meant_optim_finish(state, self.growth_factor, self.backoff_factor, self.growth_interval, int(self.dynamic), st),
+              "optim_finish")
+        ops.weights.invalidate()        # always: the host does not know whether the step was taken
+
+    # the readers below copy from the device, and only when called
+    def get_scale(self) -> float:
+        s = self._scale.item()
+        return s if s != 0.0 else 1.0
+
+    def growth_tracker(self) -> int:
+        return int(self._i32[9].item())
+
+    def steps_taken(self) -> int:
+        return int(self._i64[2].item())
+
+    def steps_skipped(self) -> int:
+        return int(self._i64[3].item())
+
+    def last_skipped(self) -> bool:
+        return bool(self._i32[11].item())
+
+    def last_grad_norm(self) -> float:
+        """global norm of the unscaled gradients of the last step taken"""
+        return self._f32[10].item()
+
+    def state_dict(self):
+        return {"kind": self.kind, "state": self.state.clone(), "lr": self.lr, "exp_avg": [t.clone() for t in self.exp_avg],
+                "exp_avg_sq": [t.clone() for t in self.exp_avg_sq]}
+
+    def load_state_dict(self, sd):
+        """a GuardedAdam state dict, or a FusedAdamW one: its `step` becomes the steps taken, the scale stays as constructed"""
+        if "state" in sd:
+            self.state.copy_(sd["state"])
+        else:
+            scale = self._scale.clone()
+            self.state.zero_()
+            self._scale.copy_(scale)
+            self._i64[2].fill_(int(sd["step"]))
+        self.lr = sd["lr"]
+        for d, s in zip(self.exp_avg, sd["exp_avg"]):
+            d.copy_(s)
+        for d, s in zip(self.exp_avg_sq, sd["exp_avg_sq"]):
+            d.copy_(s)
+
+
+class _EpochSchedule:
+    """a learning rate that is a function of the epoch, stepped once per epoch (in_loop_train.py:280): lr_at(epoch) and the keys
+    of state_dict() come from the subclass"""
+    KEYS = ()
+
+    def step(self):
+        self.epoch += 1
+        self.opt.lr = self.lr_at(self.epoch)
+
+    def state_dict(self):
+        return {k: getattr(self, k) for k in ("epoch", "base_lr") + self.KEYS}
+
+    def load_state_dict(self, sd):
+        for k in ("epoch", "base_lr") + self.KEYS:
+            setattr(self, k, sd[k])
+        self.opt.lr = self.lr_at(self.epoch)
+
+
+class CosineAnnealing(_EpochSchedule):
+    """torch.optim.lr_scheduler.CosineAnnealingLR(T_max, eta_min) (in_loop_train.py:563), in its closed form:
+    lr(e) = eta_min + (base - eta_min) * (1 + cos(pi * e / T_max)) / 2, periodic past T_max as torch's is."""
+    KEYS = ("T_max", "eta_min")
+
+    def __init__(self, optimizer, T_max: int, eta_min: float = 0.0):
+        self.opt, self.T_max, self.eta_min = optimizer, T_max, eta_min
+        self.base_lr = optimizer.lr
+        self.epoch = 0
+
+    def lr_at(self, epoch: int) -> float:
+        return self.eta_min + (self.base_lr - self.eta_min) * (1 + math.cos(math.pi * epoch / self.T_max)) / 2
+
+
+class LinearLR(_EpochSchedule):
+    """torch.optim.lr_scheduler.LinearLR (in_loop_train.py:565 builds it with torch's defaults, which are the defaults here):
+    lr(e) = base * (start_factor + (end_factor - start_factor) * min(e, total_iters) / total_iters).  The learning rate is set to
+    base * start_factor at construction, as torch's scheduler does."""
+    KEYS = ("start_factor", "end_factor", "total_iters")
+
+    def __init__(self, optimizer, start_factor: float = 1.0 / 3, end_factor: float = 1.0, total_iters: int = 5):
+        self.opt, self.start_factor, self.end_factor, self.total_iters = optimizer, start_factor, end_factor, total_iters
+        self.base_lr = optimizer.lr
+        self.epoch = 0
+        optimizer.lr = self.lr_at(0)
+
+    def lr_at(self, epoch: int) -> float:
+        return self.base_lr * (self.start_factor + (self.end_factor - self.start_factor) * min(epoch, self.total_iters) / self.total_iters)
+
+
 class CosineWarmRestarts:
     """torch.optim.lr_scheduler.CosineAnnealingWarmRestarts(T_0, T_mult=1, eta_min) stepped once per epoch
     (in_loop_train.py:567, :280): lr(e) = eta_min + (base - eta_min) * (1 + cos(pi * (e mod T_0) / T_0)) / 2."""
@@ -183,7 +339,8 @@ class TrainStep:
     by the target's type; micro-batches slice either kind along the batch axis."""
 
     def __init__(self, model: torch.nn.Module, lr: float = 5e-5, weight_decay: float = 1e-2, max_grad_norm: float = 1.0,
-                 bucket_mb: float = 64.0, direct_grads: bool = True, micro_batches: int = 1, metrics=None):
+                 bucket_mb: float = 64.0, direct_grads: bool = True, micro_batches: int = 1, metrics=None,
+                 optimizer: str = "adamw", nonfinite: Optional[str] = None, loss_scale=None, clip_scaled: bool = False):
         """micro_batches: run a step's batch as this many equal slices, one forward/backward each, gradients accumulated in the
         reducer's buckets (reducer.no_sync) -- the same gradients with 1/micro_batches of the activations in flight (the
         reference's CLI default of 12 encoder layers at 128 samples per GPU).
@@ -192,10 +349,25 @@ class TrainStep:
         several backward passes per optimizer step without reducer.no_sync())
         metrics (meant_amd.metrics.f1_metrics, vqa_score for soft [B, C] targets, a metric_group, or None): when given, every step
         adds its batch to it -- metrics.update(out, target) on the detached output, one more launch and no host read; None leaves
-        the step's launches as they are"""
+        the step's launches as they are
+        optimizer ("adamw" | "adam", the driver's -o), nonfinite (None | "skip"), loss_scale (None | float | "dynamic"), clip_scaled:
+        with the defaults the tail is FusedAdamW, unguarded; optimizer="adam", nonfinite="skip" or any loss_scale builds GuardedAdam
+        instead -- a step with an inf or NaN gradient (a class index outside [0, C) poisons one, as does an overflow) is skipped on
+        the device and counted (opt.steps_skipped()), every micro-batch's loss goes through opt.scale() before backward, and the
+        loss returned stays the unscaled one"""
+        if optimizer not in ("adamw", "adam"):
+            raise ValueError(f"TrainStep: optimizer must be 'adamw' or 'adam', got {optimizer!r}")
+        if nonfinite not in (None, "skip"):
+            raise ValueError(f"TrainStep: nonfinite must be None or 'skip', got {nonfinite!r}")
         self.model = model
         self.reducer = GradReducer(model.parameters(), bucket_mb=bucket_mb, direct_grads=direct_grads)
-        self.opt = FusedAdamW(self.reducer, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+        if optimizer == "adamw" and nonfinite is None and loss_scale is None:
+            self.opt = FusedAdamW(self.reducer, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+            self._scale = None
+        else:
+            self.opt = GuardedAdam(self.reducer, kind=optimizer, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
+                                   clip_scaled=clip_scaled, loss_scale=loss_scale)
+            self._scale = self.opt.scale
         self.micro_batches = max(1, int(micro_batches))
         self.metrics = metrics
 
@@ -205,7 +377,7 @@ class TrainStep:
         if k == 1:
             out = self.model(*inputs)
             loss = cross_entropy_on_probs(out, target)
-            loss.backward()
+            (loss if self._scale is None else self._scale(loss)).backward()
         else:
             B = target.shape[0]
             assert B % k == 0, "micro_batches must divide the batch"
@@ -217,11 +389,11 @@ class TrainStep:
                     with self.reducer.no_sync():
                         o = self.model(*part)
                         li = cross_entropy_on_probs(o, target[sl]) * (1.0 / k)
-                        li.backward()
+                        (li if self._scale is None else self._scale(li)).backward()
                 else:
                     o = self.model(*part)
                     li = cross_entropy_on_probs(o, target[sl]) * (1.0 / k)
-                    li.backward()
+                    (li if self._scale is None else self._scale(li)).backward()
                 outs.append(o.detach())
                 loss = loss + li.detach()
             out = torch.cat(outs)
