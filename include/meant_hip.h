@@ -514,9 +514,14 @@ int meant_ce_probs(const float* probs, const int64_t* target, float* loss_accum,
                    void* stream);
 /* ---- large-vocabulary softmax cross-entropy (MLM pretrainer) ----------- pretrain_mlm.py:160,178
  * nn.CrossEntropyLoss() on logits act [T, ld] (V <= ld valid columns, the rest padding of the vocabulary GEMM),
- * target int64 [T] with `ignore_index` rows skipped.  fwd: row_loss[t] = logsumexp - logit[target] (0 if ignored),
- * lse[t] saved.  bwd: dlogits[t, j] = (softmax_j - [j == target]) * gscale[0] for j < V, 0 for ignored rows and for
- * the padding columns; gscale is a device scalar (d loss / n_valid), dlogits may alias logits. */
+ * target int64 [T] with `ignore_index` rows skipped: a row counts iff target != ignore_index && 0 <= target < V.  fwd:
+ * row_loss[t] = logsumexp - logit[target] (0 if the row does not count, whatever it holds), lse float [T, 2] saved: the pair
+ * (M, log S) with M the row maximum and S = sum_{j < V} exp(logit_j - M), so logsumexp = M + log S; the entries keep the two
+ * apart (row_loss = log S + (M - logit[target]), softmax_j = exp((logit_j - M) - log S)) and no term grows with a shift of
+ * the row.  A -inf logit is a masked column (probability 0); a row of nothing but -inf is NaN, as in torch.  bwd:
+ * dlogits[t, j] = (softmax_j - [j == target]) * gscale[0] for j < V, exact zeros for rows that do not count (their logits are
+ * not read) and for the padding columns, which the forward never reads; gscale is a device scalar (d loss / n_valid),
+ * dlogits may alias logits. */
 int meant_softmax_ce_fwd(const void* logits, int64_t ld, const int64_t* target, int64_t T, int64_t V, int64_t ignore_index,
                          float* row_loss, float* lse, int dtype, void* stream);
 int meant_softmax_ce_bwd(const void* logits, int64_t ld, const int64_t* target, const float* lse, int64_t T, int64_t V,

@@ -91,9 +91,12 @@ __global__ void ce_probs_kernel(const float* __restrict__ x, const int64_t* __re
 // ------------------------------------------------------------------------------------------------
 // Softmax cross-entropy over a large vocabulary (the MLM pretrainer's loss, pretrain_mlm.py:160,178:
 // nn.CrossEntropyLoss() on logits [T, V = 64001] with ignore_index = -100).  One workgroup per row, the row is read
-// ONCE in the forward (online max / sum-exp in the log2 domain) and once more in the backward, which writes
+// ONCE in the forward (online max / sum-exp) and once more in the backward, which writes
 // d logits = (softmax - onehot) * g in the activation dtype (zeros for ignored rows and for the padding columns
 // V..ld-1 that the padded vocabulary GEMM carries).  HBM-bound: 2 B per logit forward, 4 B per logit backward.
+// The row's statistics stay the pair (M, log S), M the row maximum and S = sum_j exp(x_j - M): row_loss = log S + (M - x_t)
+// and softmax_j = exp((x_j - M) - log S), so no term grows with a shift of the row (M + log S in one float loses
+// |M| 2^-24 of log S).  A -inf logit (a masked column) adds nothing: a (max, sum) pair is only ever rescaled from a finite max.
 template <typename T>
 __global__ __launch_bounds__(256) void softmax_ce_fwd_kernel(const T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ target,
                                                              int V, int64_t ignore_index, float* __restrict__ row_loss,
@@ -110,16 +113,19 @@ __global__ __launch_bounds__(256) void softmax_ce_fwd_kernel(const T* __restrict
 #pragma unroll
     for (int i = 1; i < 8; ++i) cm = fmaxf(cm, v.get(i));
     const float mn = fmaxf(m, cm);
+    // nothing but masked columns so far: exp(-inf - 0) = 0 keeps (m, s) = (-inf, 0), where exp(-inf - -inf) = NaN would stay in s
+    const float mr = mn == -INFINITY ? 0.f : mn;
     float acc = 0.f;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) acc += __expf(v.get(i) - mn);
-    s = s * __expf(m - mn) + acc;
+    for (int i = 0; i < 8; ++i) acc += __expf(v.get(i) - mr);
+    s = s * __expf(m - mr) + acc;                      // m == -inf: s == 0 and exp(-inf) == 0
     m = mn;
   }
   for (int j = (nchunk << 3) + tid; j < V; j += 256) {   // ragged tail (V = 64001)
     const float xv = to_f(x[j]);
     const float mn = fmaxf(m, xv);
-    s = s * __expf(m - mn) + __expf(xv - mn);
+    const float mr = mn == -INFINITY ? 0.f : mn;
+    s = s * __expf(m - mr) + __expf(xv - mr);
     m = mn;
   }
   // combine (m, s) pairs across the wave, then across the 4 waves
@@ -135,10 +141,11 @@ __global__ __launch_bounds__(256) void softmax_ce_fwd_kernel(const T* __restrict
   if (tid == 0) {
     float M = fmaxf(fmaxf(red_m[0], red_m[1]), fmaxf(red_m[2], red_m[3])), Ssum = 0.f;
     for (int w = 0; w < 4; ++w) Ssum += red_m[w] == -INFINITY ? 0.f : red_s[w] * __expf(red_m[w] - M);
-    const float lse = M + __logf(Ssum);
-    lse_out[row] = lse;
+    const float logS = logf(Ssum);                     // once per row: the accurate form costs nothing
+    lse_out[2 * row] = M;
+    lse_out[2 * row + 1] = logS;
     const int64_t t = target[row];
-    row_loss[row] = (t == ignore_index || t < 0 || t >= V) ? 0.f : lse - to_f(x[t]);
+    row_loss[row] = (t == ignore_index || t < 0 || t >= V) ? 0.f : logS + (M - to_f(x[t]));
   }
 }
 
@@ -152,18 +159,38 @@ __global__ __launch_bounds__(256) void softmax_ce_bwd_kernel(const T* __restrict
   const int tid = threadIdx.x;
   const int64_t t = target[row];
   const bool ignored = (t == ignore_index || t < 0 || t >= V);
-  const float g = ignored ? 0.f : gscale[0];
-  const float l = lse[row];
   const int nchunk_ld = (int)(ld >> 3);                // ld % 8 == 0 (checked by the launcher): covers the padding too
+  if (ignored) {                                       // the whole workgroup: zeros, whatever the row holds (it is not read)
+    Vec8<T> z;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) z.set(i, 0.f);
+    for (int c = tid; c < nchunk_ld; c += 256) store8<T>(dx + c * 8, z);
+    return;
+  }
+  const float g = gscale[0];
+  // softmax_j = exp((x_j - M) - log S) as exp2(fma(x_j - M, log2 e, -log2 S)): the parent form's subtract, multiply and v_exp_f32
+  const float LOG2E = 1.4426950408889634f;
+  const float M = lse[2 * row], nl2S = -lse[2 * row + 1] * LOG2E;
+  const int tc = (int)(t >> 3), ti = (int)(t & 7);     // 0 <= t < V < 2^31 here
   for (int c = tid; c < nchunk_ld; c += 256) {
     const Vec8<T> v = load8<T>(x + c * 8);
     Vec8<T> o;
+    if (c * 8 + 8 <= V) {                              // a whole chunk of the vocabulary: all but the last one or two of a row
+      const int tsel = c == tc ? ti : -1;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int j = c * 8 + i;
-      float d = (j < V && !ignored) ? __expf(v.get(i) - l) : 0.f;
-      if (j == t) d -= 1.f;
-      o.set(i, d * g);
+      for (int i = 0; i < 8; ++i) {
+        float d = __builtin_amdgcn_exp2f(fmaf(v.get(i) - M, LOG2E, nl2S));
+        if (i == tsel) d -= 1.f;
+        o.set(i, d * g);
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int j = c * 8 + i;
+        float d = j < V ? __builtin_amdgcn_exp2f(fmaf(v.get(i) - M, LOG2E, nl2S)) : 0.f;
+        if (j == t) d -= 1.f;
+        o.set(i, j < V ? d * g : 0.f);                 // the padding: zeros at any gscale and any content
+      }
     }
     store8<T>(dx + c * 8, o);
   }

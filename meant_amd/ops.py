@@ -1799,7 +1799,7 @@ class _SoftmaxCE(torch.autograd.Function):
         assert ld % 8 == 0 and V <= ld
         tgt = _c(target.long())
         row_loss = torch.empty(T, device=logits_pad.device, dtype=torch.float32)
-        lse = torch.empty(T, device=logits_pad.device, dtype=torch.float32)
+        lse = torch.empty(T, 2, device=logits_pad.device, dtype=torch.float32)      # (row max, log sum exp(x - max))
         check(lib.meant_softmax_ce_fwd(_p(logits_pad), ld, _p(tgt), T, V, int(ignore_index), _p(row_loss), _p(lse), _dt(logits_pad),
                                        _stream()), "softmax_ce_fwd")
         nvalid = ((tgt != ignore_index) & (tgt >= 0) & (tgt < V)).sum().clamp_(min=1).float()
