@@ -82,6 +82,9 @@ int meant_num_cus(void);
  *                            padded key blocks (meant_kv_live_rows).  1: the k|v columns of the projection's weight gradient reduce
  *                            over the live 64-row blocks only (meant_linear_bwd_dw_rows); 2: the forward projection computes k|v for
  *                            the live 256-row panels only (meant_qkv_proj_fwd_live); 0: every GEMM takes all rows
+ *   "qkv_by_id"        1|0|2 the first text layer's backward (q|k|v projection, RMSNorm, embedding) once per vocabulary id
+ *                            (meant_qkv_embed_bwd_by_id) instead of once per token: where the caller's rule says the tokens outnumber
+ *                            the ids enough / never / wherever the route applies.  Read by the callers; the entry point itself always runs
  *   "nt_pp"            1     read-only: the streaming GEMM runs in its ping-pong form (setting any other value fails with
  *                            MEANT_ERR_UNSUPPORTED: the lock-step kernel was removed); not read from the environment
  */
@@ -98,7 +101,8 @@ int meant_get_option(const char* name, int* value);
  * "metrics_wave" / "metrics_labels" (meant_metrics_update by form, every meant_metrics_update_labels launch), "score_capture"
  * (every meant_score_capture launch), "auroc_rank" (every meant_auroc_rank call with n > 0), "ce_soft_wave" / "ce_soft_block"
  * (meant_ce_probs_soft by form), "vqa_score" (every meant_vqa_score_update launch), "grad_stats" (every meant_grad_stats_f32 call
- * with n > 0) and "optim_step" (every meant_optim_step_f32 launch));
+ * with n > 0), "optim_step" (every meant_optim_step_f32 launch) and "qkv_by_id" (every meant_qkv_embed_bwd_by_id call that runs its
+ * shared stage));
  * -1 for an unknown name.  The names label routes, not kernels: "nt256s" / "nt256s_rot" count launches of the streaming
  * GEMM (whichever kernel implements it), "nt_split" the ragged head + tail split.  Tests use it to prove that a shape
  * reaches the kernel it is meant to exercise. */
@@ -505,6 +509,32 @@ size_t meant_embedding_bwd_seg_ws(int64_t n, int64_t d);
 int meant_embedding_bwd_seg(const void* dout, const int64_t* sorted_ids, const int64_t* order, float* dtable, int64_t n,
                             int64_t d, int64_t V, int64_t id_lo, int64_t id_hi, int dtype, void* workspace,
                             size_t workspace_bytes, void* stream);
+
+/* Backward of  x[t] = table[id[t]] -> n[t] = RMSNorm_gain(x[t]) -> qkv_pre[t] = W' n[t] + b'  once per vocabulary id instead of once per
+ * token (bf16 tier): everything up to qkv_pre depends on id[t] alone and its backward is linear in the incoming gradients, so the token
+ * gradients are summed by id first, D[v] = sum of dqkv[t] over the tokens with id v (fp32 sums over the sorted ids, no float atomics,
+ * a function of (sorted_ids, order, dqkv) alone), and the GEMMs and the norm backward run on V rows:
+ *   dw [N3, d] += D^T Ntab    db [N3] += colsum(dqkv)    dgain [d] = the norm gain's gradient (overwritten)
+ *   dtable [V, d] += RMSNorm backward of (D W', table row)  +  the sum of dres[t] over the tokens with that id
+ * dqkv: bf16 [n, N3], N3 = 3 H Dh, the gradient of the projection's output before the rotary map (what meant_attn_bwd returns with
+ * its tables).  dres: bf16 [n, d] or NULL, the gradient of the residual branch that shares x.  sorted_ids / order: of meant_sort_ids
+ * (ids clamped into [0, V) as meant_embedding_fwd clamps them).  table_bf16: the bf16 image [V, d] the lookup read.  wT: bf16 [d, N3],
+ * W' transposed.  kv_lists: NULL, or the lists of meant_kv_live_rows of the attention that produced dqkv: the k | v columns of the rows
+ * of dead 64-row blocks are exact zeros and are not read (needs n % 64 == 0).  D reaches the GEMMs as bf16 hi + lo images, D W' comes
+ * back as two bf16 images, and the norm backward on the V rows is fp32: no tensor of V rows is rounded to bf16 once for all the tokens
+ * of an id.
+ * stage: MEANT_BY_ID_SHARED runs everything that does not depend on the id range (dw, db, dgain and the per-id rows kept in the
+ * workspace); MEANT_BY_ID_TABLE adds rows [id_lo, id_hi) of the table's gradient from a workspace a SHARED stage filled.  Both bits:
+ * one call does all.  Calls with TABLE over a partition of [0, V) give bit for bit what one call over [0, V) gives.
+ * With option "deterministic" dw is an ordered sum and the whole result is bit-reproducible.
+ * d % 8 == 0, H Dh % 64 == 0, n and V below 2^31.  workspace: meant_qkv_embed_bwd_by_id_ws(n, d, N3, V) bytes (host arithmetic; read
+ * after option "deterministic" is set), 16-byte aligned.  Route name "qkv_by_id". */
+enum meant_by_id_stage { MEANT_BY_ID_SHARED = 1, MEANT_BY_ID_TABLE = 2 };
+size_t meant_qkv_embed_bwd_by_id_ws(int64_t n, int64_t d, int64_t N3, int64_t V);
+int meant_qkv_embed_bwd_by_id(const void* dqkv, const void* dres, const int64_t* sorted_ids, const int64_t* order,
+                              const void* table_bf16, const float* gain, float eps, const void* wT, const void* kv_lists,
+                              float* dw, float* db, float* dgain, float* dtable, int64_t n, int64_t d, int64_t N3, int64_t V,
+                              int64_t id_lo, int64_t id_hi, int stage, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- train-step tail ------------------------------------------- in_loop_train.py:232-238,547-548
  * CrossEntropyLoss (mean) applied to the model's probabilities [B, C] as the reference does: loss_accum[0] +=

@@ -83,6 +83,7 @@ const OptionDef k_options[MEANT_OPT_COUNT] = {
     {"attn_bwd1", "MEANT_ATTN_BWD1", 1},           // 0: attention backward always as two passes (dQ, then dK / dV) instead of the single-pass kernel where it applies
     {"temporal_long", "MEANT_TEMPORAL_LONG", 0},   // 1: the temporal core runs the long-lag kernels at every lag (tools/probe_temporal_lag.py's like-for-like row); 0: only for L > 64
     {"kv_skip", "MEANT_KV_SKIP", 3},               // bits: which GEMMs around a key-masked attention leave out the rows of padded key blocks (1: the k|v weight gradient, 2: the forward projection); 0: none
+    {"qkv_by_id", "MEANT_QKV_BY_ID", 1},           // first text layer's projection / norm / embedding gradients once per vocabulary id (meant_qkv_embed_bwd_by_id): 0 never, 1 where tokens outnumber ids enough (the callers' rule), 2 wherever it applies
 };
 // "nt_pp" (the streaming GEMM in its ping-pong form) is no longer a choice: it reads 1 and cannot be set to anything else
 bool is_nt_pp(const char* name) { return name && !strcmp(name, "nt_pp"); }
@@ -148,6 +149,7 @@ const char* const k_routes[MEANT_ROUTE_COUNT] = {
     "ce_soft_wave", "ce_soft_block",   // meant_ce_probs_soft by form (C <= 1024: a wave per row / above: a workgroup per row)
     "vqa_score",                    // every meant_vqa_score_update launch
     "grad_stats", "optim_step",     // every meant_grad_stats_f32 call with n > 0; every meant_optim_step_f32 launch
+    "qkv_by_id",                    // every meant_qkv_embed_bwd_by_id call that runs its shared (per-id) stage
 };
 std::atomic<long long> g_route[MEANT_ROUTE_COUNT];
 }  // namespace

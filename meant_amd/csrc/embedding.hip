@@ -179,8 +179,8 @@ SortWs sort_ws_layout(int64_t n, int passes) {
 // read-modify-write of its table row.  Two differences.  The width: grid.y cuts the row into column blocks of at most 128 8-column
 // chunks, so a lane still owns two chunks.  The runs that cross the stretch's ends: their partial sums go to the workspace slot
 // [stretch][0] (the run came in from the left) or [stretch][1] (it starts here and leaves to the right), and
-// emb_seg_cross_kernel / emb_seg_long_kernel add each such run's slots in an order that depends on the sorted ids alone.
-constexpr int SEG = 256;
+// seg_cross_kernel / seg_long_kernel (seg_sum.h) add each such run's slots in an order that depends on the sorted ids alone.
+#include "seg_sum.h"      // SEG, and the crossing-run passes seg_cross_kernel / seg_long_kernel
 template <typename T>
 __global__ __launch_bounds__(256) void emb_seg_kernel(const T* __restrict__ dout, const int64_t* __restrict__ sorted_ids,
                                                        const int64_t* __restrict__ order, float* __restrict__ dtable,
@@ -276,79 +276,6 @@ __global__ __launch_bounds__(256) void emb_seg_kernel(const T* __restrict__ dout
   }
   const bool open_right = j1 < n && sorted_ids[j1] == cur;
   flush(cur, open_left ? 0 : (open_right ? 1 : -1));
-}
-
-// The runs that cross stretch ends.  A run belongs to the stretch it STARTS in: its partial sums are slot 1 of that stretch and
-// slot 0 of every following stretch that begins with the same id (sorted ids: a contiguous range).
-// Short lists (at most SEG_SHORT partials; two for a typical id): one wave per (stretch, 256 columns) adds them in stretch order and
-// adds the sum to the table row.  It also leaves the list's length in longk[stretch] where the list is longer (0 otherwise), for
-// the kernel below.
-constexpr int SEG_SHORT = 16;
-__global__ __launch_bounds__(256) void emb_seg_cross_kernel(const int64_t* __restrict__ sorted_ids, const float* __restrict__ part,
-                                                             int* __restrict__ longk, float* __restrict__ dtable, int64_t n, int64_t d,
-                                                             int64_t V, int64_t id_lo, int64_t id_hi) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t s = (int64_t)blockIdx.x * 4 + wave, j0 = s * SEG, j1 = j0 + SEG;
-  if (j1 >= n) return;                                                    // the last stretch has nothing to its right (and no longk slot)
-  const int64_t id = sorted_ids[j1 - 1];
-  const bool owner = sorted_ids[j1] == id && !(j0 > 0 && sorted_ids[j0 - 1] == id)      // leaves to the right, did not come in from the left
-                     && id >= 0 && id < V && id >= id_lo && id < id_hi;
-  int64_t K = 0;
-  if (owner) {                                                            // wave-uniform
-    const int64_t nst = (n + SEG - 1) / SEG;
-    int64_t follow = 0;
-    for (int64_t t0 = s + 1;; t0 += 64) {
-      const int64_t t = t0 + lane;
-      const int k = __popcll(__ballot(t < nst && sorted_ids[t * SEG] == id));
-      follow += k;
-      if (k < 64) break;
-    }
-    K = follow + 1;
-  }
-  if (blockIdx.y == 0 && lane == 0) longk[s] = K > SEG_SHORT ? (int)K : 0;
-  if (K == 0 || K > SEG_SHORT) return;
-  const int64_t col = (int64_t)blockIdx.y * 256 + lane * 4;
-  if (col >= d) return;
-  f32x4 acc = *reinterpret_cast<const f32x4*>(part + (s * 2 + 1) * d + col);
-  for (int64_t k = 1; k < K; ++k) acc += *reinterpret_cast<const f32x4*>(part + (s + k) * 2 * d + col);
-  f32x4* dst = reinterpret_cast<f32x4*>(dtable + id * d + col);
-  *dst = *dst + acc;
-}
-
-// Long lists (a padding id: one partial per stretch it covers).  One workgroup per (stretch, 64 columns), at work only where
-// longk says so.  The list is cut into 16 equal pieces (a cut that depends on its length alone), 16 threads with 4 columns each sum
-// a piece in order, and the 16 pieces are added as a fixed binary tree: the sum depends on the sorted ids and the rows, on nothing else.
-__global__ __launch_bounds__(256) void emb_seg_long_kernel(const int64_t* __restrict__ sorted_ids, const float* __restrict__ part,
-                                                            const int* __restrict__ longk, float* __restrict__ dtable, int64_t d) {
-  __shared__ f32x4 red[16][16];
-  const int tid = threadIdx.x;
-  const int64_t s = blockIdx.x;
-  const int64_t K = longk[s];
-  if (K == 0) return;                                                     // uniform over the workgroup
-  const int64_t id = sorted_ids[s * SEG + SEG - 1];                       // in range: emb_seg_cross_kernel checked it
-  const int p = tid >> 4;
-  const int64_t col = (int64_t)blockIdx.y * 64 + (tid & 15) * 4;
-  const bool active = col < d;
-  const int64_t piece = (K + 15) / 16, k0 = p * piece, k1 = k0 + piece < K ? k0 + piece : K;
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  if (active) {
-#pragma unroll 4
-    for (int64_t k = k0; k < k1; ++k) {
-      const float* row = k == 0 ? part + (s * 2 + 1) * d : part + (s + k) * 2 * d;
-      acc += *reinterpret_cast<const f32x4*>(row + col);
-    }
-  }
-  red[p][tid & 15] = acc;
-  __syncthreads();
-#pragma unroll
-  for (int h = 8; h > 0; h >>= 1) {
-    if (p < h) red[p][tid & 15] += red[p + h][tid & 15];
-    __syncthreads();
-  }
-  if (p == 0 && active) {
-    f32x4* dst = reinterpret_cast<f32x4*>(dtable + id * d + col);
-    *dst = *dst + red[0][tid & 15];
-  }
 }
 
 size_t seg_part_bytes(int64_t n, int64_t d) { return (size_t)ceil_div(n, SEG) * 2 * (size_t)d * sizeof(float); }
@@ -606,10 +533,11 @@ extern "C" int meant_embedding_bwd_seg(const void* dout, const int64_t* sorted_i
                                     sorted_ids, order, dtable, (float*)workspace, n, d, V, id_lo, id_hi, cb_chunks));
   if (nst > 1) {
     int* longk = (int*)((char*)workspace + seg_part_bytes(n, d));
-    hipLaunchKernelGGL(emb_seg_cross_kernel, dim3((unsigned)ceil_div(nst - 1, 4), (unsigned)ceil_div(d, 256)), dim3(256), 0, st, sorted_ids,
-                       (const float*)workspace, longk, dtable, n, d, V, id_lo, id_hi);
-    hipLaunchKernelGGL(emb_seg_long_kernel, dim3((unsigned)(nst - 1), (unsigned)ceil_div(d, 64)), dim3(256), 0, st, sorted_ids,
-                       (const float*)workspace, (const int*)longk, dtable, d);
+    const SegAddRow add{dtable, id_lo, id_hi};
+    hipLaunchKernelGGL(seg_cross_kernel<SegAddRow>, dim3((unsigned)ceil_div(nst - 1, 4), (unsigned)ceil_div(d, 256)), dim3(256), 0, st, sorted_ids,
+                       (const float*)workspace, longk, add, n, d, V);
+    hipLaunchKernelGGL(seg_long_kernel<SegAddRow>, dim3((unsigned)(nst - 1), (unsigned)ceil_div(d, 64)), dim3(256), 0, st, sorted_ids,
+                       (const float*)workspace, (const int*)longk, add, d);
   }
   MEANT_LAUNCH_CHECK("embedding_bwd_seg");
   meant_route_hit(ROUTE_EMB_SEG);

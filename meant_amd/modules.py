@@ -360,7 +360,7 @@ def _seed() -> int:
     return int(torch.randint(0, 2 ** 62, (1,)).item())
 
 
-def _encoder_layer(e, e2, x, margs, p1, p2, pool, fold):
+def _encoder_layer(e, e2, x, margs, p1, p2, pool, fold, tokens=None):
     """the body of both encoder layers (meant/meant.py:55-75, :98-120): e / e2 = the layer's two ModuleLists, whose last entries are
     the Linears that close each half; margs: what the attention module takes after x (the language layer's mask); p1 / p2: the
     dropout probabilities fused into e[3] and e2[3].  The seeds are drawn here, in this order and only for p > 0: e[3]'s after
@@ -368,12 +368,17 @@ def _encoder_layer(e, e2, x, margs, p1, p2, pool, fold):
     torch.utils.checkpoint replays it.
     pool=True: return (h, res) instead of e2[-1](h) + res, for ops.pool_linear_cat.
     fold: the stack's RMSNorm-into-Linear decision (an explicit argument so that a recomputation under
-    torch.utils.checkpoint repeats the forward's path); None = by ops.fold_wanted()"""
-    n, res = ops.rmsnorm_fork(x, e[0].scale, e[0].eps, any_width=True)      # residual gradient is folded into this norm's backward
-    if COMPOSE_PRE_LINEAR and e[1].bias is not None:
-        h = e[2].multi_mad(e[2].core(n, *margs, pre=e[1]))             # Linear(d,d) composed into the q/k/v projections
+    torch.utils.checkpoint repeats the forward's path); None = by ops.fold_wanted()
+    tokens: a _TokenIds in place of x (then None): the layer looks its input up itself (see _by_id_source)"""
+    if tokens is not None:                                       # first language layer, backward once per vocabulary id: x is None
+        o, res = tokens.attend(e, *margs)
+        h = e[2].multi_mad(o)
     else:
-        h = e[2](e[1](n), *margs)
+        n, res = ops.rmsnorm_fork(x, e[0].scale, e[0].eps, any_width=True)      # residual gradient is folded into this norm's backward
+        if COMPOSE_PRE_LINEAR and e[1].bias is not None:
+            h = e[2].multi_mad(e[2].core(n, *margs, pre=e[1]))             # Linear(d,d) composed into the q/k/v projections
+        else:
+            h = e[2](e[1](n), *margs)
     h = e[3](h, drop_p=p1, seed=_seed() if p1 > 0 else 0)
     x1 = e[-1](h, residual=res)
     fold = ops.norm_linear_ok(x1, e2[1].weight, fold)                 # encode2[0] rides encode2[1]'s GEMM as a per-row factor
@@ -421,11 +426,11 @@ class languageEncoder(nn.Module):
         self.encode = nn.ModuleList([RMSNorm(dim), Linear(dim, dim), att, RMSNorm(dim), nn.Dropout(dropout), Linear(dim, dim)])
         self.encode2 = nn.ModuleList([RMSNorm(dim), Linear(dim, dim), nn.GELU(), RMSNorm(dim), nn.Dropout(), Linear(dim, dim)])
 
-    def forward(self, input, attention_mask=None, pool: bool = False, fold=None):
-        """pool, fold: see _encoder_layer"""
+    def forward(self, input, attention_mask=None, pool: bool = False, fold=None, tokens=None):
+        """pool, fold, tokens: see _encoder_layer"""
         e, e2 = self.encode, self.encode2
         p1, p2 = (e[4].p, e2[4].p) if self.training else (0.0, 0.0)
-        return _encoder_layer(e, e2, input, (attention_mask,), p1, p2, pool, fold)
+        return _encoder_layer(e, e2, input, (attention_mask,), p1, p2, pool, fold, tokens)
 
 
 class temporalEncoder(nn.Module):
@@ -497,20 +502,27 @@ def _ckpt_setting(model):
     return v if isinstance(v, bool) else int(v)
 
 
-def _run_stack(encoders, x, *args, checkpoint=False):
+def _run_stack(encoders, x, *args, checkpoint=False, tokens=None):
     """all encoder layers of one stack; returns either the token tensor, or -- with POOL_LAST_LINEAR -- the
-    (h, res, weight, bias) part that ops.pool_linear_cat pools.  checkpoint: bool, or the number of leading layers to recompute"""
+    (h, res, weight, bias) part that ops.pool_linear_cat pools.  checkpoint: bool, or the number of leading layers to recompute.
+    tokens: a _TokenIds for the first layer in place of x (None then); that layer is never recomputed (_by_id_source saw to it)"""
     n = len(encoders)
+    rows, d = (tokens.ids.numel(), tokens.table.shape[1]) if tokens is not None else (x.numel() // x.shape[-1], x.shape[-1])
     # big stacks fold their norms into the consumer Linears.  Decided ONCE per stack and passed down as an argument: the layers run
     # under torch.utils.checkpoint are re-run in backward, after the OTHER stack may have left a different process-wide hint
-    fold = ops.stack_fold(n, x.numel() // x.shape[-1], x.shape[-1])
+    fold = ops.stack_fold(n, rows, d)
     for i, enc in enumerate(encoders):
         ck = checkpoint if isinstance(checkpoint, bool) else i < checkpoint
+        kw = {}
+        if i == 0 and tokens is not None:
+            if ck:
+                raise RuntimeError("meant_amd: the by-id first layer cannot run under activation recomputation")
+            kw["tokens"] = tokens
         last = enc.encode2[-1]
         if POOL_LAST_LINEAR and i == n - 1 and isinstance(last, Linear):
-            h, res = _run_encoder(enc, x, *args, checkpoint=ck, pool=True, fold=fold)
+            h, res = _run_encoder(enc, x, *args, checkpoint=ck, pool=True, fold=fold, **kw)
             return (h, res, last.weight, last.bias)
-        x = _run_encoder(enc, x, *args, checkpoint=ck, fold=fold)
+        x = _run_encoder(enc, x, *args, checkpoint=ck, fold=fold, **kw)
     return x
 
 
@@ -544,6 +556,51 @@ def _pool_own_stream(compute_dtype, st):
     if not POOL_OWN_STREAM or not (isinstance(st, tuple) and st[0].dim() == 2):
         return st
     return ops.pooled_linear_cat([st], compute_dtype)
+
+
+class _TokenIds:
+    """The first language layer's input as token ids and their table instead of the looked-up rows, where that layer's backward runs
+    once per vocabulary id (option "qkv_by_id", ops.embed_qkv_attention).  The lookup then happens inside the layer, in one autograd
+    node with its RMSNorm, composed q|k|v projection and attention core -- on the stream the language stack runs on (in `meant` the
+    language stream, where _embed's lookup is on the main stream; the id presort rides the index stream either way)."""
+
+    def __init__(self, ids, table, dtype):
+        self.ids, self.table, self.dtype = ids, table, dtype
+
+    def attend(self, e, attention_mask=None):
+        """(attention core output, embedded tokens) for the layer's ModuleList e = [RMSNorm, Linear, xPosAttention, ...]"""
+        att = e[2]
+        wqkv, bqkv = _qkv_params(att, e[1])
+        tables = att.xPos.tables(self.ids.shape[1], self.ids.device, ops.run_head_dim(att.Dh, self.dtype)) if att.xPos is not None else None
+        return ops.embed_qkv_attention(self.ids, self.table, e[0].scale, e[0].eps, wqkv, bqkv, tables, attention_mask, bool(att.mask),
+                                       att.num_heads)
+
+
+def _by_id_source(mods, ids, dtype, encoders, ckpt=False):
+    """_TokenIds where everything ops.embed_qkv_attention asks for holds, else None: one plain nn.Embedding served by ops.embedding,
+    the bf16 tier, a first language layer that composes its Linear into the q|k|v projection and takes the fused attention route
+    (no learned rotary frequencies, no score dropout, a plain RMSNorm), not recomputed in backward, a table that wants a gradient,
+    and option "qkv_by_id" (ops.qkv_by_id_wanted: a host-side comparison of the token count with the table's rows)"""
+    if len(mods) != 1 or not len(encoders) or ckpt or not torch.is_grad_enabled() or not COMPOSE_PRE_LINEAR:
+        return None
+    emb, enc = mods[0], encoders[0]
+    if not (isinstance(emb, nn.Embedding) and emb.max_norm is None and not emb.sparse and ids.dtype in (torch.int64, torch.int32)):
+        return None
+    if not (isinstance(enc, languageEncoder) and ids.is_cuda and ids.dim() == 2 and emb.weight.requires_grad and emb.weight.dtype == torch.float32):
+        return None
+    e = enc.encode
+    att, norm = e[2], e[0]
+    if not (isinstance(att, xPosAttention) and isinstance(norm, RMSNorm) and isinstance(e[1], nn.Linear) and e[1].bias is not None):
+        return None
+    rot = att.xPos
+    if (rot is not None and getattr(rot, 'learned_freq', False)) or (att.training and att.dropout.p > 0):
+        return None
+    if getattr(norm, 'p', -1.) >= 0 or getattr(norm, 'bias', False) or norm.scale.shape[0] != emb.weight.shape[1]:
+        return None
+    V, d = emb.weight.shape
+    if not ops.qkv_by_id_shape_ok(d, att.atten_size, att.Dh, V, dtype) or not ops.qkv_by_id_wanted(ids.numel(), V):
+        return None
+    return _TokenIds(ids, emb.weight, dtype)
 
 
 def _embed(mods, ids, dtype):
@@ -602,14 +659,16 @@ class meant(nn.Module):
         B = images.shape[0]
         if images.is_cuda and TWO_STREAMS:
             ops.set_index_stream(images.device, _side_stream(images.device))     # the id sort rides the vision stream
-        words = _embed(self.embedding, tweets.reshape(B * self.lag, tweets.shape[2]), dt)
+        ck = _ckpt_setting(self)
+        ids2 = tweets.reshape(B * self.lag, tweets.shape[2])
+        tok = _by_id_source(self.embedding, ids2, dt, self.languageEncoders, ck if isinstance(ck, bool) else ck > 0)
+        words = _embed(self.embedding, ids2, dt) if tok is None else None
         if attention_mask is not None:
             attention_mask = attention_mask.reshape(B * self.lag, attention_mask.shape[2])
         # The language and the vision stacks are independent until the pooled concat: with TWO_STREAMS the vision
         # stack runs on a second HIP stream so that kernels with different bottlenecks (HBM-bound norms, load-path-bound
         # GEMMs, issue-bound attention) of the two stacks can share the chip.  Autograd replays each backward op on the
         # stream of its forward op, so the backward passes overlap the same way.
-        ck = _ckpt_setting(self)
         side = _side_stream(images.device) if (TWO_STREAMS and images.is_cuda and not ck) else None
         if side is not None:
             main = torch.cuda.current_stream()
@@ -622,14 +681,14 @@ class meant(nn.Module):
             hi = _hi_stream(images.device)
             hi.wait_stream(main)
             with torch.cuda.stream(hi):
-                words = _run_stack(self.languageEncoders, words, attention_mask, checkpoint=ck)
+                words = _run_stack(self.languageEncoders, words, attention_mask, checkpoint=ck, tokens=tok)
                 words = _pool_own_stream(dt, words)
             main.wait_stream(hi)
             for tt in (words if isinstance(words, tuple) else (words,)):
                 if tt is not None and tt.is_cuda:
                     tt.record_stream(main)
         else:
-            words = _run_stack(self.languageEncoders, words, attention_mask, checkpoint=ck)
+            words = _run_stack(self.languageEncoders, words, attention_mask, checkpoint=ck, tokens=tok)
         if side is not None:
             main.wait_stream(side)
             for tt in (img if isinstance(img, tuple) else (img,)):
@@ -693,9 +752,11 @@ class meant_tweet(nn.Module):
     def forward(self, tweets, attention_mask=None):
         dt = resolve_compute_dtype(self, None)
         B = tweets.shape[0]
-        words = _embed(self.embedding, tweets.reshape(B * self.lag, tweets.shape[2]), dt)
+        ids2 = tweets.reshape(B * self.lag, tweets.shape[2])
+        tok = _by_id_source(self.embedding, ids2, dt, self.languageEncoders)
+        words = _embed(self.embedding, ids2, dt) if tok is None else None
         attention_mask = attention_mask.reshape(B * self.lag, attention_mask.shape[2])     # required, as in :150
-        words = _run_stack(self.languageEncoders, words, attention_mask)
+        words = _run_stack(self.languageEncoders, words, attention_mask, tokens=tok)
         fused = _pool_parts(dt, words).view(B, self.lag, self.dim)
         for enc in self.temporal_encoding:
             fused = enc(fused)
@@ -726,8 +787,9 @@ class meant_vqa(nn.Module):
 
     def forward(self, tweets, images, attention_mask=None):
         dt = resolve_compute_dtype(self, images)
-        words = _embed(self.embedding, tweets, dt)
-        words = _run_stack(self.languageEncoders, words, attention_mask)
+        tok = _by_id_source(self.embedding, tweets, dt, self.languageEncoders)
+        words = _embed(self.embedding, tweets, dt) if tok is None else None
+        words = _run_stack(self.languageEncoders, words, attention_mask, tokens=tok)
         img = self.patchEmbed(images, dt)
         img = _run_stack(self.visionEncoders, img)
         fused = _pool_parts(dt, words, img)
@@ -769,10 +831,12 @@ class meant_language_pretrainer(nn.Module):
 
     def _encode(self, words, attention_mask):
         dt = resolve_compute_dtype(self, None)
-        x = _embed(self.embedding, words, dt)
-        fold = ops.stack_fold(len(self.languageEncoders), x.numel() // x.shape[-1], x.shape[-1])
-        for enc in self.languageEncoders:
-            x = enc(x, attention_mask=attention_mask, fold=fold)
+        tok = _by_id_source(self.embedding, words, dt, self.languageEncoders)
+        x = _embed(self.embedding, words, dt) if tok is None else None
+        rows, d = (words.numel(), tok.table.shape[1]) if tok is not None else (x.numel() // x.shape[-1], x.shape[-1])
+        fold = ops.stack_fold(len(self.languageEncoders), rows, d)
+        for i, enc in enumerate(self.languageEncoders):
+            x = enc(x, attention_mask=attention_mask, fold=fold, **({"tokens": tok} if tok is not None and i == 0 else {}))
         return x
 
     def _head_features(self, x):

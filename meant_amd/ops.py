@@ -1015,6 +1015,40 @@ def _attn_bwd_raw(qkv2, o, do2, lse, km, G, S, H, Dh, scale, causal, tables, dro
     return dqkv
 
 
+def _qkv_attn_fwd_raw(x, wqkv, bqkv, tables, key_mask, causal, num_heads, scale=None):
+    """forward of _QKVAttention on x [G, S, d]: (x2 as the projection read it, qkv, o, lse, float key mask, fp32 weight, kv lists,
+    kv-skip bits, (G, S, d, D, Dh, H, scale, causal))"""
+    _need_gpu(x, wqkv)
+    G, S, d = x.shape
+    D = wqkv.shape[0] // 3
+    Dh = D // num_heads
+    x2 = _c(x).view(G * S, d)
+    w_f = _c(wqkv.detach().float())
+    if x.dtype == torch.bfloat16 and d % 8:
+        # a model width off the 8-grid: both operands get zero columns up to ceil8(d), as _k_pad does for ops.linear, so that the
+        # projection keeps the MFMA kernel and its rotary epilogue; backward keeps the padded copy of x for the weight gradient
+        d8 = (d + 7) & ~7
+        x2, w_c = _pad_cols(x2, d8), _pad_cols(w_f, d8, x.dtype)
+    else:
+        w_c = cast(w_f, x.dtype)                                          # [3D, d] in the compute dtype
+    bias_f = _c(bqkv.detach().float())
+    dt = _dt(x)
+    qa, qb, ka, kb, R = _rot(tables)
+    km = _c(key_mask.float()) if key_mask is not None else None
+    skip = _kv_skip_bits(x, km, S, D, Dh)
+    lists = kv_live_rows(km, causal) if skip else None                    # built once, on the device; backward reads the same lists
+    qkv = torch.empty((G * S, 3 * D), device=x.device, dtype=x.dtype)
+    if skip & KV_SKIP_FWD:                                                # the k | v rows of dead panels: not computed, zeros
+        check(lib.meant_qkv_proj_fwd_live(_p(x2), x2.stride(0), _p(w_c), _p(bias_f), _p(qkv), G * S, x2.shape[1], S, num_heads, Dh, R,
+                                          _p(qa), _p(qb), _p(ka), _p(kb), _p(lists), dt, _stream()), "qkv_proj_fwd_live")
+    else:
+        check(lib.meant_qkv_proj_fwd(_p(x2), x2.stride(0), _p(w_c), _p(bias_f), _p(qkv), G * S, x2.shape[1], S, num_heads, Dh, R,
+                                     _p(qa), _p(qb), _p(ka), _p(kb), dt, _stream()), "qkv_proj_fwd")
+    scale = 1.0 / math.sqrt(Dh * num_heads) if scale is None else float(scale)
+    o, lse = _attn_fwd_raw(qkv, km, G, S, num_heads, Dh, scale, int(causal))
+    return x2, qkv, o, lse, km, w_f, lists, skip, (G, S, d, D, Dh, num_heads, scale, int(causal))
+
+
 class _QKVAttention(torch.autograd.Function):
     """Fused q|k|v projection + rotary + attention core of meant/attention.py:35-57 and
     meant/xPosAttention.py:35-63 (up to, not including, multi_mad).
@@ -1025,38 +1059,12 @@ class _QKVAttention(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, wqkv, bqkv, tables, key_mask, causal, num_heads, scale=None):
-        _need_gpu(x, wqkv)
-        G, S, d = x.shape
-        D = wqkv.shape[0] // 3
-        Dh = D // num_heads
-        x2 = _c(x).view(G * S, d)
-        w_f = _c(wqkv.detach().float())
-        if x.dtype == torch.bfloat16 and d % 8:
-            # a model width off the 8-grid: both operands get zero columns up to ceil8(d), as _k_pad does for ops.linear, so that the
-            # projection keeps the MFMA kernel and its rotary epilogue; backward keeps the padded copy of x for the weight gradient
-            d8 = (d + 7) & ~7
-            x2, w_c = _pad_cols(x2, d8), _pad_cols(w_f, d8, x.dtype)
-        else:
-            w_c = cast(w_f, x.dtype)                                          # [3D, d] in the compute dtype
-        bias_f = _c(bqkv.detach().float())
-        dt = _dt(x)
-        qa, qb, ka, kb, R = _rot(tables)
-        km = _c(key_mask.float()) if key_mask is not None else None
-        skip = _kv_skip_bits(x, km, S, D, Dh)
-        lists = kv_live_rows(km, causal) if skip else None                    # built once, on the device; backward reads the same lists
-        qkv = torch.empty((G * S, 3 * D), device=x.device, dtype=x.dtype)
-        if skip & KV_SKIP_FWD:                                                # the k | v rows of dead panels: not computed, zeros
-            check(lib.meant_qkv_proj_fwd_live(_p(x2), x2.stride(0), _p(w_c), _p(bias_f), _p(qkv), G * S, x2.shape[1], S, num_heads, Dh, R,
-                                              _p(qa), _p(qb), _p(ka), _p(kb), _p(lists), dt, _stream()), "qkv_proj_fwd_live")
-        else:
-            check(lib.meant_qkv_proj_fwd(_p(x2), x2.stride(0), _p(w_c), _p(bias_f), _p(qkv), G * S, x2.shape[1], S, num_heads, Dh, R,
-                                         _p(qa), _p(qb), _p(ka), _p(kb), dt, _stream()), "qkv_proj_fwd")
-        scale = 1.0 / math.sqrt(Dh * num_heads) if scale is None else float(scale)
-        o, lse = _attn_fwd_raw(qkv, km, G, S, num_heads, Dh, scale, int(causal))
+        x2, qkv, o, lse, km, w_f, lists, skip, meta = _qkv_attn_fwd_raw(x, wqkv, bqkv, tables, key_mask, causal, num_heads, scale)
         ctx.save_for_backward(x2, qkv, o, lse, km, w_f, lists)
         ctx.kv_skip = skip
         ctx.tables = tables
-        ctx.meta = (G, S, d, D, Dh, num_heads, scale, int(causal))
+        ctx.meta = meta
+        G, S, D = meta[0], meta[1], meta[3]
         return o.view(G, S, D)
 
     @staticmethod
@@ -1668,43 +1676,76 @@ def _sort_ids(ids_flat: torch.Tensor, V: int):
     return sorted_ids, order
 
 
+def _embedding_fwd_raw(ids, table, dtype):
+    """(contiguous int64 ids, table[ids] in `dtype`)"""
+    _need_gpu(ids, table)
+    ids_c = _c(ids.long())
+    V, d = table.shape
+    n = ids_c.numel()
+    out = torch.empty((*ids.shape, d), device=table.device, dtype=dtype)
+    if dtype == torch.bfloat16 and EMB_BF16_TABLE and d % 8 == 0 and V < (1 << 31):
+        # bf16 tier: rows copied from a bf16 image of the table (the weight cache's: rebuilt when the parameter changes, shared
+        # with a tied vocabulary decoder) instead of read as fp32 and rounded on the way -- same values, half the gather's reads
+        # (0.51 -> 0.37 ms at 786 k tokens of 768).  Ids are clamped into the table as meant_embedding_fwd clamps them.
+        tb = weights.get((table,), torch.bfloat16, False)
+        idx = ids_c.view(-1).clamp(0, V - 1).to(torch.int32)
+        check(lib.meant_gather_rows(_p(tb), _p(idx), None, _p(out), n, d, BF16, _stream()), "gather_rows")
+    else:
+        tf = _c(table.detach().float())
+        check(lib.meant_embedding_fwd(_p(tf), _p(ids_c), _p(out), n, d, V, F32 if dtype == torch.float32 else BF16, _stream()),
+              "embedding_fwd")
+    return ids_c, out
+
+
+def _presort_ids(ids_c, V, d, force=False):
+    """(sorted ids, order, event) made now, on a side stream, or None.
+    The backward sums rows in the order of the sorted ids.  The sort (meant_sort_ids: 7 small launches, kernels that do not
+    fill the chip) used to run in backward, where the embedding's gradient is the very last thing
+    of the step; the ids are known now, so it runs here on a side stream, beside the forward's big kernels.
+    force: whatever route the embedding's own backward would take (the by-id backward always reads the sorted ids)"""
+    if not EMB_PRESORT or (not force and _emb_bwd_route(ids_c.numel(), d) == "atomic"):
+        return None
+    main = torch.cuda.current_stream(ids_c.device)
+    side = _aux_stream(ids_c.device)
+    side.wait_stream(main)
+    with torch.cuda.stream(side):
+        sorted_ids, order = _sort_ids(ids_c.view(-1), V)
+        ev = torch.cuda.Event()
+        ev.record(side)
+    return sorted_ids, order, ev
+
+
+def _sorted_ids_now(presort, ids_c, V):
+    """the sorted ids and their order on the current stream: the forward's presort once its event has passed, or a sort made now"""
+    if presort is None:
+        return _sort_ids(ids_c.view(-1), V)
+    sorted_ids, order, ev = presort
+    cur = torch.cuda.current_stream(ids_c.device)
+    cur.wait_event(ev)
+    sorted_ids.record_stream(cur)            # allocated on the side stream, read on this one
+    order.record_stream(cur)
+    return sorted_ids, order
+
+
+def _table_grad_target(table, V, d, device):
+    """(sink or None, fp32 [V, d] the table's gradient is summed into): with a gradient sink (GradReducer(direct_grads=True)) the rows
+    are summed straight into the reducer's bucket view: no [V, d] zeros + autograd add per step (0.8 GB of traffic at V = 64001)
+    (not when another op reads the table as well -- the tied vocabulary decoder: see grad_sinks)"""
+    sink = _sink_of(table, "embedding") if grad_sinks else None
+    if sink is not None and (sink.view.shape != (V, d) or not sink.view.is_contiguous()):
+        sink = None
+    return sink, (sink.view if sink is not None else torch.zeros((V, d), device=device, dtype=torch.float32))
+
+
 class _Embedding(torch.autograd.Function):
     """nn.Embedding lookup (meant/meant.py:211) emitting the compute dtype directly."""
 
     @staticmethod
     def forward(ctx, ids, table, dtype):
-        _need_gpu(ids, table)
-        ids_c = _c(ids.long())
+        ids_c, out = _embedding_fwd_raw(ids, table, dtype)
         V, d = table.shape
-        n = ids_c.numel()
-        out = torch.empty((*ids.shape, d), device=table.device, dtype=dtype)
-        if dtype == torch.bfloat16 and EMB_BF16_TABLE and d % 8 == 0 and V < (1 << 31):
-            # bf16 tier: rows copied from a bf16 image of the table (the weight cache's: rebuilt when the parameter changes, shared
-            # with a tied vocabulary decoder) instead of read as fp32 and rounded on the way -- same values, half the gather's reads
-            # (0.51 -> 0.37 ms at 786 k tokens of 768).  Ids are clamped into the table as meant_embedding_fwd clamps them.
-            tb = weights.get((table,), torch.bfloat16, False)
-            idx = ids_c.view(-1).clamp(0, V - 1).to(torch.int32)
-            check(lib.meant_gather_rows(_p(tb), _p(idx), None, _p(out), n, d, BF16, _stream()), "gather_rows")
-        else:
-            tf = _c(table.detach().float())
-            check(lib.meant_embedding_fwd(_p(tf), _p(ids_c), _p(out), n, d, V, F32 if dtype == torch.float32 else BF16, _stream()),
-                  "embedding_fwd")
-        # The backward sums rows in the order of the sorted ids.  The sort (meant_sort_ids: 7 small launches, kernels that do not
-        # fill the chip) used to run in backward, where the embedding's gradient is the very last thing
-        # of the step; the ids are known now, so it runs here on a side stream, beside the forward's big kernels.
-        presort = None
-        route = _emb_bwd_route(n, d)
-        if EMB_PRESORT and ctx.needs_input_grad[1] and route != "atomic":
-            main = torch.cuda.current_stream(ids_c.device)
-            side = _aux_stream(ids_c.device)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                sorted_ids, order = _sort_ids(ids_c.view(-1), V)
-                ev = torch.cuda.Event()
-                ev.record(side)
-            presort = (sorted_ids, order, ev)
         ctx.save_for_backward(ids_c)
-        ctx.presort = presort
+        ctx.presort = _presort_ids(ids_c, V, d) if ctx.needs_input_grad[1] else None
         ctx.meta = (V, d)
         ctx.table = table                                # the Parameter itself: its gradient sink, if any, is looked up in backward
         _claim(table, "embedding")
@@ -1715,25 +1756,12 @@ class _Embedding(torch.autograd.Function):
         (ids_c,) = ctx.saved_tensors
         V, d = ctx.meta
         dout = _c(dout)
-        # with a gradient sink (GradReducer(direct_grads=True)) the rows are summed straight into the reducer's bucket view:
-        # no [V, d] zeros + autograd add per step (0.8 GB of traffic at V = 64001)
-        # (not when another op reads the table as well -- the tied vocabulary decoder: see grad_sinks)
-        sink = _sink_of(ctx.table, "embedding") if grad_sinks else None
-        if sink is not None and (sink.view.shape != (V, d) or not sink.view.is_contiguous()):
-            sink = None
-        dtab = sink.view if sink is not None else torch.zeros((V, d), device=dout.device, dtype=torch.float32)
+        sink, dtab = _table_grad_target(ctx.table, V, d, dout.device)
         n = ids_c.numel()
         route = _emb_bwd_route(n, d)
         if route != "atomic":                            # the other kernel is float atomics per token
             # index preparation (a sort of the token ids) is host-side plumbing; the reduction itself is the HIP kernel
-            if ctx.presort is not None:
-                sorted_ids, order, ev = ctx.presort
-                cur = torch.cuda.current_stream(dout.device)
-                cur.wait_event(ev)
-                sorted_ids.record_stream(cur)            # allocated on the side stream, read on this one
-                order.record_stream(cur)
-            else:
-                sorted_ids, order = _sort_ids(ids_c.view(-1), V)
+            sorted_ids, order = _sorted_ids_now(ctx.presort, ids_c, V)
             nsl = sink.row_slices(ctx.table) if sink is not None else 1
             if route == "seg":
                 wsb = lib.meant_embedding_bwd_seg_ws(n, d)
@@ -1768,6 +1796,88 @@ class _Embedding(torch.autograd.Function):
 
 def embedding(ids, table, dtype):
     return _Embedding.apply(ids, table, dtype)
+
+
+# The first text layer with its backward once per vocabulary id ("q|k|v projection and norm gradients per id").
+QKV_BY_ID_MIN_RATIO = 6       # option qkv_by_id = 1: tokens per table row from which the by-id backward is taken (ahead by more than the runs' spread from 6 on, level at 5: profiles/qkv_by_id_probe.txt)
+QKV_BY_ID_MIN_ROWS = 4096     # ... and the table rows from which: the table-sized dW product reaches the 256 x 256 MFMA route at 4096 rows, and nothing smaller than V = 64001 was measured
+
+
+def qkv_by_id_shape_ok(d: int, D: int, Dh: int, V: int, dtype: torch.dtype) -> bool:
+    """what _EmbedQKVAttention serves: the bf16 tier's lookup from the bf16 table image, the projection's 256-column tiles, a native head dim"""
+    return (dtype == torch.bfloat16 and EMB_BF16_TABLE and d % 8 == 0 and D % 256 == 0 and Dh in NATIVE_HEAD_DIMS and V < (1 << 31))
+
+
+def qkv_by_id_wanted(n_tokens: int, V: int) -> bool:
+    """option qkv_by_id: 0 never, 2 always, 1 where the tokens outnumber the rows of a table that is large enough by enough (host
+    arithmetic on shapes only)"""
+    opt = _lib.get_option("qkv_by_id")
+    return opt == 2 or (opt == 1 and V >= QKV_BY_ID_MIN_ROWS and n_tokens >= QKV_BY_ID_MIN_RATIO * V)
+
+
+class _EmbedQKVAttention(torch.autograd.Function):
+    """embedding lookup -> RMSNorm -> composed q|k|v projection -> attention core of the first language layer as ONE node:
+    (o [G, S, D], x [G, S, d]) with x the looked-up rows (the layer's residual operand).  The forward is the kernels of _Embedding,
+    _RMSNormFork and _QKVAttention in their order.  Everything up to the projection's output depends on a token's id alone, so the
+    backward sums the attention's dqkv by id and runs the projection's two gradient GEMMs and the norm backward on V rows
+    (meant_qkv_embed_bwd_by_id); the per-token n and x are not kept for it."""
+
+    @staticmethod
+    def forward(ctx, ids, table, gain, eps, wqkv, bqkv, tables, key_mask, causal, num_heads):
+        ids_c, x = _embedding_fwd_raw(ids, table, torch.bfloat16)
+        V, d = table.shape
+        presort = _presort_ids(ids_c, V, d, force=True)
+        n_, sc, _rinv = _rmsnorm_fwd_raw(x, gain, eps, 0.0, 0)
+        _x2, qkv, o, lse, km, w_f, lists, skip, meta = _qkv_attn_fwd_raw(n_, wqkv, bqkv, tables, key_mask, causal, num_heads)
+        ctx.save_for_backward(ids_c, qkv, o, lse, km, w_f, lists if skip & KV_SKIP_DW else None, sc)
+        ctx.presort, ctx.tables, ctx.meta, ctx.eps, ctx.table = presort, tables, meta, eps, table
+        _claim(table, "embedding")
+        G, S, D = meta[0], meta[1], meta[3]
+        return o.view(G, S, D), x
+
+    @staticmethod
+    def backward(ctx, do, dres):
+        ids_c, qkv, o, lse, km, w_f, lists, sc = ctx.saved_tensors
+        G, S, d, D, Dh, H, scale, causal = ctx.meta
+        table = ctx.table
+        V = table.shape[0]
+        n, N3 = G * S, 3 * D
+        do2 = _c(do).view(n, D)
+        dqkv = _attn_bwd_raw(qkv, o, do2, lse, km, G, S, H, Dh, scale, causal, ctx.tables)
+        dev = do2.device
+        wT = torch.empty((d, N3), device=dev, dtype=torch.bfloat16)
+        check(lib.meant_transpose2d(_p(w_f), F32, _p(wT), BF16, N3, d, _stream()), "transpose2d")
+        dw = torch.zeros((N3, d), device=dev, dtype=torch.float32)
+        db = torch.zeros(N3, device=dev, dtype=torch.float32)
+        dgain = torch.empty(d, device=dev, dtype=torch.float32)
+        dres2 = _c(dres).view(n, d) if dres is not None else None
+        sink, dtab = _table_grad_target(table, V, d, dev)
+        sorted_ids, order = _sorted_ids_now(ctx.presort, ids_c, V)
+        tb = weights.get((table,), torch.bfloat16, False)
+        wsb = lib.meant_qkv_embed_bwd_by_id_ws(n, d, N3, V)
+        ws = _ws(wsb, dev)
+        nsl = sink.row_slices(table) if sink is not None else 1
+
+        def call(lo, hi, stage):
+            check(lib.meant_qkv_embed_bwd_by_id(_p(dqkv), _p(dres2), _p(sorted_ids), _p(order), _p(tb), _p(sc), ctx.eps, _p(wT), _p(lists),
+                                                _p(dw), _p(db), _p(dgain), _p(dtab), n, d, N3, V, lo, hi, stage, _p(ws), wsb, _stream()),
+                  "qkv_embed_bwd_by_id")
+        if nsl > 1:                                      # the id-independent part once, then the table's rows slice by slice (see _Embedding)
+            call(0, 0, _lib.BY_ID_SHARED)
+            for c in range(nsl):
+                lo, hi = V * c // nsl, V * (c + 1) // nsl
+                call(lo, hi, _lib.BY_ID_TABLE)
+                sink.report_rows(table, lo, hi, c == nsl - 1)
+        else:
+            call(0, V, _lib.BY_ID_SHARED | _lib.BY_ID_TABLE)
+            if sink is not None:
+                sink.report(table)
+        return None, (None if sink is not None else dtab), dgain, None, dw, db, None, None, None, None
+
+
+def embed_qkv_attention(ids, table, gain, eps, wqkv, bqkv, tables, key_mask, causal, num_heads):
+    """(attention core output [G, S, D], embedded tokens [G, S, d]) of ids [G, S]; see _EmbedQKVAttention.  bf16 tier only."""
+    return _EmbedQKVAttention.apply(ids, table, gain, float(eps), wqkv, bqkv, tables, key_mask, bool(causal), num_heads)
 
 
 def cast(x: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
