@@ -25,7 +25,6 @@
 #include "attn_tiles.h"
 #include <type_traits>
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 namespace {
 

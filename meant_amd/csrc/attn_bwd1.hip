@@ -35,7 +35,6 @@
 #include "attn_tiles.h"
 #include <type_traits>
 
-static size_t align256_(size_t x) { return (x + 255) & ~(size_t)255; }
 
 namespace {
 
@@ -775,7 +774,7 @@ extern "C" int meant_lab_stamps1(void* dst, size_t bytes) {
 // workspace: [item counters: 8 x 16 words | partial dQ blocks of the upper key half (256 < S <= 512 only)]
 size_t attn_bwd1_ws(int64_t G, int64_t S, int H, int Dh) {
   if (Dh != DH || S > 512) return 0;
-  return 512 + (S > 256 ? align256_((size_t)G * H * 2 * 8 * 1024 * sizeof(float)) : 0);
+  return 512 + (S > 256 ? align256((size_t)G * H * 2 * 8 * 1024 * sizeof(float)) : 0);
 }
 
 bool attn_bwd1_ok(int64_t S, int Dh, int causal) {

@@ -223,7 +223,6 @@ __global__ __launch_bounds__(CL_THREADS) void mim_l1_bwd_kernel(L1Args a, const 
 }
 
 bool cl_aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-size_t cl_align256(size_t x) { return (x + 255) & ~(size_t)255; }
 size_t cl_raw_size(int raw_dtype) { return raw_dtype == MEANT_RAW_F64 ? 8 : raw_dtype == MEANT_RAW_F32 ? 4 : raw_dtype == MEANT_RAW_BF16 ? 2 : 1; }
 bool cl_raw_known(int raw_dtype) { return raw_dtype >= MEANT_RAW_F32 && raw_dtype <= MEANT_RAW_U8; }
 
@@ -328,7 +327,7 @@ extern "C" int meant_patchify_raw_masked(const void* images, int raw_dtype, floa
 
 extern "C" size_t meant_mim_l1_ws(int64_t N) {
   if (N <= 0 || N > (1ll << 40)) return 0;
-  return 2 * cl_align256((size_t)ceil_div(N, L1_SPAN) * 4);
+  return 2 * align256((size_t)ceil_div(N, L1_SPAN) * 4);
 }
 
 #define L1_DISPATCH(KERNEL, ...)                                                                                         \

@@ -71,6 +71,7 @@ static inline bool meant_aligned16(const void* p) { return (reinterpret_cast<uin
 // aligned to one element of the activation type (4 bytes fp32, 2 bytes bf16): what the element-access kernels need
 static inline bool meant_aligned_elem(const void* p, int dtype) { return (reinterpret_cast<uintptr_t>(p) & (dtype == MEANT_F32 ? 3 : 1)) == 0; }
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }   // the regions of a workspace start on 256 bytes
 
 // ---- storage-type helpers (math is always float) ------------------------------------------------
 template <typename T> struct Vec8;  // 8 contiguous elements

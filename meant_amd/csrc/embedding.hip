@@ -1,8 +1,8 @@
 // Embedding: the gather, and the gradient three ways.
 //   meant_embedding_fwd                 one wave per token row
 //   meant_embedding_bwd                 scatter-add with f32 atomics
-//   meant_embedding_bwd_sorted[_range]  over ids sorted by the caller, d <= 1024: runs of equal ids summed in registers, atomics only
-//                                       where a run crosses a wave's stretch
+//   meant_embedding_bwd_sorted[_range]  over ids sorted by the caller, d <= 1024: runs of equal ids summed in registers (seg_walk of
+//                                       seg_sum.h, as meant_embedding_bwd_seg), atomics only where a run crosses a wave's stretch
 //   meant_sort_ids                      LSD radix sort over 8-bit digits of the ids clamped into [0, V); equal ids keep their row order
 //   sort_u32_launch (internal.h)        the same passes over caller-made 32-bit keys with a 32-bit value each (auroc.hip)
 //   meant_embedding_bwd_seg             dtable[id, :] += sum of the rows of dout that carry id, any d % 8 == 0, no float atomics,
@@ -156,7 +156,6 @@ int sort_passes(int64_t V) {
   const int p = (bits + 7) / 8;
   return p < 1 ? 1 : p;
 }
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 struct SortWs { size_t ghist, tile_hist, buf[2], total; int nbuf; };
 SortWs sort_ws_layout(int64_t n, int passes) {
   SortWs w;
@@ -174,108 +173,24 @@ SortWs sort_ws_layout(int64_t n, int passes) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// The reduction.  As embedding_bwd_sorted_kernel above: a wave walks a stretch of 256 sorted entries, four rows
-// requested before the first is consumed, and sums a run of equal ids in registers; a run inside the stretch is a plain
-// read-modify-write of its table row.  Two differences.  The width: grid.y cuts the row into column blocks of at most 128 8-column
-// chunks, so a lane still owns two chunks.  The runs that cross the stretch's ends: their partial sums go to the workspace slot
-// [stretch][0] (the run came in from the left) or [stretch][1] (it starts here and leaves to the right), and
-// seg_cross_kernel / seg_long_kernel (seg_sum.h) add each such run's slots in an order that depends on the sorted ids alone.
-#include "seg_sum.h"      // SEG, and the crossing-run passes seg_cross_kernel / seg_long_kernel
+// The reduction at any width: seg_walk (seg_sum.h) over a stretch of 256 sorted entries.  grid.y cuts the row into column blocks of
+// at most 128 8-column chunks, so a lane still owns two chunks.  A run inside the stretch is a plain read-modify-write of its table
+// row.  The runs that cross the stretch's ends: their partial sums go to the workspace slot [stretch][0] (the run came in from the
+// left) or [stretch][1] (it starts here and leaves to the right), and seg_cross_kernel / seg_long_kernel (seg_sum.h) add each such
+// run's slots in an order that depends on the sorted ids alone.
+#include "seg_sum.h"      // SEG, the walk, and the crossing-run passes seg_cross_kernel / seg_long_kernel
 template <typename T>
 __global__ __launch_bounds__(256) void emb_seg_kernel(const T* __restrict__ dout, const int64_t* __restrict__ sorted_ids,
                                                        const int64_t* __restrict__ order, float* __restrict__ dtable,
                                                        float* __restrict__ part, int64_t n, int64_t d, int64_t V, int64_t id_lo,
                                                        int64_t id_hi, int cb_chunks) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t s = (int64_t)blockIdx.x * 4 + wave;
+  const int64_t s = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int64_t j0 = s * SEG;
   if (j0 >= n) return;
   const int64_t j1 = j0 + SEG < n ? j0 + SEG : n;
   if (sorted_ids[j1 - 1] < id_lo || sorted_ids[j0] >= id_hi) return;     // the ids are sorted: a stretch outside the range leaves at once
-  const int c0 = blockIdx.y * cb_chunks;                                   // this column block: chunks [c0, c0 + nch)
-  const int left = (int)(d >> 3) - c0;
-  const int nch = left < cb_chunks ? left : cb_chunks;
-  const bool has0 = lane < nch, has1 = lane + 64 < nch;
-  const int64_t col0 = (int64_t)(c0 + lane) * 8, col1 = (int64_t)(c0 + lane + 64) * 8;
-  float acc0[8], acc1[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) acc0[e] = acc1[e] = 0.f;
-  int64_t cur = sorted_ids[j0];
-  bool open_left = j0 > 0 && sorted_ids[j0 - 1] == cur;                  // the first run started in an earlier stretch
-
-  // slot < 0: the run is this wave's alone
-  auto flush = [&](int64_t id, int slot) {
-    if (id < 0 || id >= V || id < id_lo || id >= id_hi) return;
-    if (slot >= 0) {
-      float* row = part + (s * 2 + slot) * d;
-      Vec8<float> v;
-      if (has0) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v.set(e, acc0[e]);
-        store8<float>(row + col0, v);
-      }
-      if (has1) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v.set(e, acc1[e]);
-        store8<float>(row + col1, v);
-      }
-      return;
-    }
-    float* row = dtable + id * d;
-    if (has0) {
-      Vec8<float> v = load8<float>(row + col0);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v.set(e, v.get(e) + acc0[e]);
-      store8<float>(row + col0, v);
-    }
-    if (has1) {
-      Vec8<float> v = load8<float>(row + col1);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v.set(e, v.get(e) + acc1[e]);
-      store8<float>(row + col1, v);
-    }
-  };
-
-  for (int64_t jb = j0; jb < j1; jb += 64) {
-    const int64_t jl = jb + lane < j1 ? jb + lane : j1 - 1;
-    const long long my_id = sorted_ids[jl], my_ord = order[jl];
-    const int cnt = (int)(j1 - jb < 64 ? j1 - jb : 64);
-    for (int t0 = 0; t0 < cnt; t0 += 4) {
-      Vec8<T> r0[4], r1[4];
-      long long ids4[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int t = t0 + u < cnt ? t0 + u : cnt - 1;
-        ids4[u] = __shfl(my_id, t, 64);
-        const long long ord = __shfl(my_ord, t, 64);
-        const bool row_ok = ord >= 0 && ord < n;        // an order that is no permutation must not become an address
-        const T* src = dout + (row_ok ? ord : 0) * d;
-        r0[u] = Vec8<T>{};
-        r1[u] = Vec8<T>{};
-        if (has0 && row_ok) r0[u] = load8s<T>(src + col0);
-        if (has1 && row_ok) r1[u] = load8s<T>(src + col1);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        if (t0 + u >= cnt) break;
-        const int64_t id = ids4[u];
-        if (id != cur) {
-          flush(cur, open_left ? 0 : -1);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) acc0[e] = acc1[e] = 0.f;
-          cur = id;
-          open_left = false;
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          if (has0) acc0[e] += r0[u].get(e);
-          if (has1) acc1[e] += r1[u].get(e);
-        }
-      }
-    }
-  }
-  const bool open_right = j1 < n && sorted_ids[j1] == cur;
-  flush(cur, open_left ? 0 : (open_right ? 1 : -1));
+  const SegSlotSink<SegAddRow> sink{{dtable, id_lo, id_hi}, part + s * 2 * d, d};
+  seg_walk<false>(dout, d, sorted_ids, order, n, V, j0, j1, seg_cols(d, cb_chunks), SegAllRows{}, sink, nullptr);
 }
 
 size_t seg_part_bytes(int64_t n, int64_t d) { return (size_t)ceil_div(n, SEG) * 2 * (size_t)d * sizeof(float); }
@@ -325,27 +240,35 @@ __global__ __launch_bounds__(256) void embedding_bwd_kernel(const T* __restrict_
   }
 }
 
-// scatter-add of the embedding gradient over ids SORTED by the caller (order[j] = original row of the j-th smallest id).
-// A wave walks SEG consecutive sorted entries; a lane owns 8-column chunks `lane` and `lane + 64` of the row (16-byte loads, four
-// rows requested before the first is consumed) and sums the rows of a run of equal ids in registers.  A run that lies entirely
-// inside the wave's stretch belongs to nobody else: its sum is added with a plain read-modify-write.  Only the (at most two) runs
-// that cross the stretch's ends use float atomics -- at 12 tokens per id that is one row in eleven (the atomic rate, 1.3 TB/s of added
-// bytes, was a third of this kernel's time when every run went that way, and 2-byte loads most of the rest).
-constexpr int EMB_SEG = 256;
+// scatter-add of the embedding gradient over ids SORTED by the caller (order[j] = original row of the j-th smallest id), d <= 1024:
+// seg_walk (seg_sum.h) over SEG consecutive sorted entries, the lane's chunks `lane` and `lane + 64` covering the whole row.  A run
+// that lies entirely inside the wave's stretch belongs to nobody else: its sum is added with a plain read-modify-write.  Only the (at
+// most two) runs that cross the stretch's ends use float atomics -- at 12 tokens per id that is one row in eleven (the atomic rate,
+// 1.3 TB/s of added bytes, was a third of this kernel's time when every run went that way, and 2-byte loads most of the rest).
+struct EmbAtomicSink : SegSlotSink<SegAddRow> {
+  __device__ __forceinline__ void cross(int64_t id, int, int64_t col, f32x4 lo, f32x4 hi) const {
+    float* dst = st.dtable + id * ld + col;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      atomicAdd(dst + e, lo[e]);
+      atomicAdd(dst + 4 + e, hi[e]);
+    }
+  }
+};
 template <typename T>
 __global__ __launch_bounds__(256) void embedding_bwd_sorted_kernel(const T* __restrict__ dout, const int64_t* __restrict__ sorted_ids,
                                                                     const int64_t* __restrict__ order, float* __restrict__ dtable,
-                                                                    int64_t n, int d, int64_t V, int det, int64_t id_lo, int64_t id_hi) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int64_t j0 = ((int64_t)blockIdx.x * 4 + wave) * EMB_SEG;
+                                                                    int64_t n, int64_t d, int64_t V, int det, int64_t id_lo, int64_t id_hi) {
+  int64_t j0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * SEG;
   if (j0 >= n) return;
-  int64_t j1 = j0 + EMB_SEG < n ? j0 + EMB_SEG : n;
+  int64_t j1 = j0 + SEG < n ? j0 + SEG : n;
   // [id_lo, id_hi): only the rows of this id range are produced (meant_embedding_bwd_sorted_range: the table's gradient in row
   // slices, each handed to its collective as soon as it is final).  The ids are sorted: a stretch outside the range leaves at once.
   if (sorted_ids[j1 - 1] < id_lo || sorted_ids[j0] >= id_hi) return;
   if (det) {
     // option "deterministic": no atomics.  A run belongs to the wave in whose stretch it STARTS: that wave follows it to its end
     // (however far), the others skip the part of their stretch that continues an earlier run.  Slow for a hot id; a debugging mode.
+    // After this no run crosses an end of [j0, j1), so the walk meets none that would go to the atomics.
     if (j0 > 0) {
       const int64_t prev = sorted_ids[j0 - 1];
       while (j0 < j1 && sorted_ids[j0] == prev) ++j0;
@@ -354,75 +277,8 @@ __global__ __launch_bounds__(256) void embedding_bwd_sorted_kernel(const T* __re
     const int64_t last = sorted_ids[j1 - 1];
     while (j1 < n && sorted_ids[j1] == last) ++j1;
   }
-  const int nch = d >> 3;                              // d % 8 == 0, d <= 1024
-  const bool has1 = lane + 64 < nch, has0 = lane < nch;
-  float acc0[8], acc1[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) acc0[e] = acc1[e] = 0.f;
-  int64_t cur = sorted_ids[j0];
-  bool shared = !det && j0 > 0 && sorted_ids[j0 - 1] == cur;   // the first run started in the previous stretch
-
-  auto flush = [&](int64_t id, bool atomic) {
-    if (id < 0 || id >= V || id < id_lo || id >= id_hi) return;
-    float* row = dtable + id * d;
-    if (atomic) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        if (has0) atomicAdd(row + lane * 8 + e, acc0[e]);
-        if (has1) atomicAdd(row + (lane + 64) * 8 + e, acc1[e]);
-      }
-    } else {
-      if (has0) {
-        Vec8<float> v = load8<float>(row + lane * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v.set(e, v.get(e) + acc0[e]);
-        store8<float>(row + lane * 8, v);
-      }
-      if (has1) {
-        Vec8<float> v = load8<float>(row + (lane + 64) * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v.set(e, v.get(e) + acc1[e]);
-        store8<float>(row + (lane + 64) * 8, v);
-      }
-    }
-  };
-
-  for (int64_t jb = j0; jb < j1; jb += 64) {
-    const int64_t jl = jb + lane < j1 ? jb + lane : j1 - 1;
-    const long long my_id = sorted_ids[jl], my_ord = order[jl];
-    const int cnt = (int)(j1 - jb < 64 ? j1 - jb : 64);
-    for (int t0 = 0; t0 < cnt; t0 += 4) {
-      Vec8<T> r0[4], r1[4];
-      long long ids4[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int t = t0 + u < cnt ? t0 + u : cnt - 1;
-        ids4[u] = __shfl(my_id, t, 64);
-        const long long ord = __shfl(my_ord, t, 64);
-        const T* src = dout + ord * d;
-        if (has0) r0[u] = load8s<T>(src + lane * 8);
-        if (has1) r1[u] = load8s<T>(src + (lane + 64) * 8);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        if (t0 + u >= cnt) break;
-        const int64_t id = ids4[u];
-        if (id != cur) {
-          flush(cur, shared);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) acc0[e] = acc1[e] = 0.f;
-          cur = id;
-          shared = false;
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          if (has0) acc0[e] += r0[u].get(e);
-          if (has1) acc1[e] += r1[u].get(e);
-        }
-      }
-    }
-  }
-  flush(cur, !det && (shared || (j1 < n && sorted_ids[j1] == cur)));   // ... or continues into the next stretch
+  const EmbAtomicSink sink{{{dtable, id_lo, id_hi}, nullptr, d}};
+  seg_walk<false>(dout, d, sorted_ids, order, n, V, j0, j1, seg_cols(d, 128), SegAllRows{}, sink, nullptr);
 }
 
 }  // namespace
@@ -523,22 +379,12 @@ extern "C" int meant_embedding_bwd_seg(const void* dout, const int64_t* sorted_i
   MEANT_REQUIRE(workspace && workspace_bytes >= need, MEANT_ERR_WORKSPACE, "embedding_bwd_seg: workspace of %zu bytes needed, %zu given", need, workspace_bytes);
   EMB_REQ(meant_aligned16(dout) && meant_aligned16(dtable) && meant_aligned16(workspace), "embedding_bwd_seg: 16-byte alignment");
   if (id_lo == id_hi) return MEANT_OK;
-  const int64_t nst = ceil_div(n, SEG);
-  const int chunks = (int)(d >> 3);
-  const int ncb = (int)ceil_div(chunks, 128);
-  const int cb_chunks = (int)ceil_div(chunks, ncb);
+  const SegColBlocks cb = seg_col_blocks(d, 2);
   hipStream_t st = (hipStream_t)stream;
   DISPATCH_DTYPE(dtype, T,
-                 hipLaunchKernelGGL(emb_seg_kernel<T>, dim3((unsigned)ceil_div(nst, 4), (unsigned)ncb), dim3(256), 0, st, (const T*)dout,
-                                    sorted_ids, order, dtable, (float*)workspace, n, d, V, id_lo, id_hi, cb_chunks));
-  if (nst > 1) {
-    int* longk = (int*)((char*)workspace + seg_part_bytes(n, d));
-    const SegAddRow add{dtable, id_lo, id_hi};
-    hipLaunchKernelGGL(seg_cross_kernel<SegAddRow>, dim3((unsigned)ceil_div(nst - 1, 4), (unsigned)ceil_div(d, 256)), dim3(256), 0, st, sorted_ids,
-                       (const float*)workspace, longk, add, n, d, V);
-    hipLaunchKernelGGL(seg_long_kernel<SegAddRow>, dim3((unsigned)(nst - 1), (unsigned)ceil_div(d, 64)), dim3(256), 0, st, sorted_ids,
-                       (const float*)workspace, (const int*)longk, add, d);
-  }
+                 hipLaunchKernelGGL(emb_seg_kernel<T>, dim3((unsigned)ceil_div(ceil_div(n, SEG), 4), (unsigned)cb.ncb), dim3(256), 0, st, (const T*)dout,
+                                    sorted_ids, order, dtable, (float*)workspace, n, d, V, id_lo, id_hi, cb.cb_chunks));
+  seg_cross_launch(SegAddRow{dtable, id_lo, id_hi}, sorted_ids, (const float*)workspace, (int*)((char*)workspace + seg_part_bytes(n, d)), n, d, V, st);
   MEANT_LAUNCH_CHECK("embedding_bwd_seg");
   meant_route_hit(ROUTE_EMB_SEG);
   return MEANT_OK;
@@ -557,32 +403,28 @@ extern "C" int meant_embedding_fwd(const float* table, const int64_t* ids, void*
   MEANT_LAUNCH_CHECK("embedding_fwd");
   return MEANT_OK;
 }
+// the sorted scatter-add over the ids of [id_lo, id_hi), behind both entries
+static int emb_sorted_launch(const char* what, const void* dout, const int64_t* sorted_ids, const int64_t* order, float* dtable, int64_t n,
+                             int64_t d, int64_t V, int64_t id_lo, int64_t id_hi, int dtype, void* stream) {
+  EMB_REQ(dout && sorted_ids && order && dtable && n > 0 && d > 0 && V > 0 && 0 <= id_lo && id_lo <= id_hi && id_hi <= V, "%s: bad argument", what);
+  MEANT_REQUIRE(d <= 1024 && d % 8 == 0, MEANT_ERR_UNSUPPORTED, "%s: d=%lld must be a multiple of 8 and <= 1024", what, (long long)d);
+  EMB_REQ(meant_aligned16(dout) && meant_aligned16(dtable), "%s: 16-byte alignment", what);
+  if (id_lo == id_hi) return MEANT_OK;
+  DISPATCH_DTYPE(dtype, T,
+                 hipLaunchKernelGGL(embedding_bwd_sorted_kernel<T>, dim3((unsigned)ceil_div(n, 4 * SEG)), dim3(256), 0, (hipStream_t)stream,
+                                    (const T*)dout, sorted_ids, order, dtable, n, d, V, meant_opt(MEANT_OPT_DETERMINISTIC) != 0, id_lo, id_hi));
+  MEANT_LAUNCH_CHECK(what);
+  return MEANT_OK;
+}
+
 extern "C" int meant_embedding_bwd_sorted(const void* dout, const int64_t* sorted_ids, const int64_t* order, float* dtable, int64_t n,
                                           int64_t d, int64_t V, int dtype, void* stream) {
-  EMB_REQ(dout && sorted_ids && order && dtable && n > 0 && d > 0 && V > 0, "embedding_bwd_sorted: bad argument");
-  MEANT_REQUIRE(d <= 1024 && d % 8 == 0, MEANT_ERR_UNSUPPORTED, "embedding_bwd_sorted: d=%lld must be a multiple of 8 and <= 1024", (long long)d);
-  EMB_REQ(meant_aligned16(dout) && meant_aligned16(dtable), "embedding_bwd_sorted: 16-byte alignment");
-  const int64_t nb = ceil_div(n, 4 * EMB_SEG);
-  DISPATCH_DTYPE(dtype, T,
-                 hipLaunchKernelGGL(embedding_bwd_sorted_kernel<T>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (const T*)dout,
-                                    sorted_ids, order, dtable, n, (int)d, V, meant_opt(MEANT_OPT_DETERMINISTIC) != 0, (int64_t)0, V));
-  MEANT_LAUNCH_CHECK("embedding_bwd_sorted");
-  return MEANT_OK;
+  return emb_sorted_launch("embedding_bwd_sorted", dout, sorted_ids, order, dtable, n, d, V, 0, V, dtype, stream);
 }
 
 extern "C" int meant_embedding_bwd_sorted_range(const void* dout, const int64_t* sorted_ids, const int64_t* order, float* dtable, int64_t n,
                                                 int64_t d, int64_t V, int64_t id_lo, int64_t id_hi, int dtype, void* stream) {
-  EMB_REQ(dout && sorted_ids && order && dtable && n > 0 && d > 0 && V > 0 && 0 <= id_lo && id_lo <= id_hi && id_hi <= V,
-         "embedding_bwd_sorted_range: bad argument");
-  MEANT_REQUIRE(d <= 1024 && d % 8 == 0, MEANT_ERR_UNSUPPORTED, "embedding_bwd_sorted_range: d=%lld must be a multiple of 8 and <= 1024", (long long)d);
-  EMB_REQ(meant_aligned16(dout) && meant_aligned16(dtable), "embedding_bwd_sorted_range: 16-byte alignment");
-  if (id_lo == id_hi) return MEANT_OK;
-  const int64_t nb = ceil_div(n, 4 * EMB_SEG);
-  DISPATCH_DTYPE(dtype, T,
-                 hipLaunchKernelGGL(embedding_bwd_sorted_kernel<T>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (const T*)dout,
-                                    sorted_ids, order, dtable, n, (int)d, V, meant_opt(MEANT_OPT_DETERMINISTIC) != 0, id_lo, id_hi));
-  MEANT_LAUNCH_CHECK("embedding_bwd_sorted_range");
-  return MEANT_OK;
+  return emb_sorted_launch("embedding_bwd_sorted_range", dout, sorted_ids, order, dtable, n, d, V, id_lo, id_hi, dtype, stream);
 }
 
 extern "C" int meant_embedding_bwd(const void* dout, const int64_t* ids, float* dtable, int64_t n, int64_t d, int64_t V, int dtype, void* stream) {

@@ -70,6 +70,12 @@ struct GemmBf16Args {
 int gemm_bf16_nt_launch(const GemmBf16Args& a, hipStream_t stream);
 bool gemm_bf16_nt_streams(const GemmBf16Args& a);   // the launch takes the streaming kernel over whole 256-row panels (what a panel list needs)
 int zero_panels_launch(bf16* C, int64_t ldc, int64_t cols, const int* panels, const int* count, int64_t npan, hipStream_t stream);
+// flags[list[i]] = 1 for i < *count (device memory; one list of the key-padding lists and its count), on a zeroed array of `len` bytes
+// (qkv_by_id.hip; the 64-row blocks of the by-id backward, the 256-row panels of the by-id forward)
+int live_flags_launch(const int* list, const int* count, uint8_t* flags, int64_t len, hipStream_t stream);
+// the by-id routes' table-sized GEMMs take V rows rounded up to whole 256-row panels
+constexpr int VPAD = 256;
+static inline int64_t vpad_rows(int64_t V) { return ceil_div(V, VPAD) * VPAD; }
 // dW[N,K] (float, +=) = dY[M,N]^T X[M,K], reduction over the token axis M; dbias[N] += colsum(dY)
 // ws: partial-sum workspace of gemm_bf16_tn_ws(M, N, K) bytes, used (and required) only with the `deterministic` option
 int gemm_bf16_tn_launch(const bf16* dY, int64_t lddy, const bf16* X, int64_t ldx, float* dW, float* dbias,

@@ -2,7 +2,7 @@
 //
 //   x[t] = table[id[t]]  ->  n[t] = RMSNorm_g(x[t])  ->  qkv_pre[t] = W' n[t] + b'
 // depends on id[t] alone, and its backward is linear in the incoming gradients for fixed x.  So with
-//   D[v] = sum of dqkv[t] over the tokens t that carry id v          (qkv_seg_kernel and the two cross-run passes of seg_sum.h)
+//   D[v] = sum of dqkv[t] over the tokens t that carry id v          (qkv_seg_kernel: the walk and the two cross-run passes of seg_sum.h)
 // the gradients are table-sized products through the library's own launchers:
 //   dW' += D^T Ntab,  db' += colsum(dqkv),  dNtab = D W',  (dXtab, dgain) = RMSNorm backward of (dNtab, table image),
 //   dtable[v] += dXtab[v]  (+ the residual gradient summed by id as meant_embedding_bwd_* sum it).
@@ -17,138 +17,41 @@
 
 namespace {
 
-#include "seg_sum.h"               // SEG sorted entries per wave (a stretch); the crossing-run passes seg_cross_kernel / seg_long_kernel
-constexpr int VPAD = 256;          // the GEMMs' token axis is V rounded up to this
+#include "seg_sum.h"               // SEG sorted entries per wave (a stretch); the walk and the crossing-run passes
 
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// live[b] = 1 for the 64-row blocks the key-padding lists name, on a zeroed array
-__global__ __launch_bounds__(256) void live_flags_kernel(const int* __restrict__ lists, uint8_t* __restrict__ live, int64_t nblk) {
+// flags[list[i]] = 1 for i < *count, on a zeroed array: the live 64-row blocks here, the live 256-row panels of the by-id forward
+__global__ __launch_bounds__(256) void live_flags_kernel(const int* __restrict__ list, const int* __restrict__ count, uint8_t* __restrict__ flags,
+                                                          int64_t len) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= nblk || i >= lists[0]) return;
-  const int b = lists[MEANT_KV_LIST_HDR + i];
-  if (b >= 0 && b < nblk) live[b] = 1;
+  if (i >= len || i >= *count) return;
+  const int b = list[i];
+  if (b >= 0 && b < len) flags[b] = 1;
 }
 
-// The segmented sum, after emb_seg_kernel (embedding.hip): a wave walks a stretch of SEG sorted entries, four rows requested before
-// the first is consumed, and sums a run of equal ids in registers.  grid.y cuts the 3 H Dh columns into blocks of at most 128 8-column
-// chunks (a lane owns two).  A run inside the stretch is final: its hi | lo images are stored.  The runs that cross the stretch's ends
-// leave fp32 partial sums in part[stretch][0] (came in from the left) / [1] (leaves to the right) for seg_cross_kernel /
-// seg_long_kernel (seg_sum.h, with the hi | lo store).  The k | v chunks (columns >= Dq) of a row in a dead 64-row block are never read: they are zeros.
+// The segmented sum: seg_walk (seg_sum.h) over a stretch of SEG sorted entries, as emb_seg_kernel (embedding.hip) runs it.  grid.y
+// cuts the 3 H Dh columns into blocks of at most 128 8-column chunks (a lane owns two).  A run inside the stretch is final: its
+// hi | lo images are stored.  The runs that cross the stretch's ends leave fp32 partial sums in part[stretch][0] (came in from the
+// left) / [1] (leaves to the right) for seg_cross_kernel / seg_long_kernel (seg_sum.h, with the hi | lo store).
 // cpart[stretch][:] = the column sums of the stretch's rows, for the bias gradient.
+// The rows policy: the k | v chunks (columns >= Dq) of a row in a dead 64-row block are never read: they are zeros.
+struct QkvLiveRows {
+  const uint8_t* live_blocks; bool kv[2];
+  __device__ __forceinline__ bool live(int64_t ord) const { return !live_blocks || live_blocks[ord >> 6] != 0; }
+  __device__ __forceinline__ bool reads(int k, bool row_live) const { return !kv[k] || row_live; }
+};
 __global__ __launch_bounds__(256) void qkv_seg_kernel(const bf16* __restrict__ dqkv, const int64_t* __restrict__ sorted_ids,
                                                        const int64_t* __restrict__ order, const uint8_t* __restrict__ live,
                                                        bf16* __restrict__ Dhi, bf16* __restrict__ Dlo, float* __restrict__ part,
                                                        float* __restrict__ cpart, int64_t n, int64_t N3, int64_t Dq, int64_t V,
                                                        int cb_chunks) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t s = (int64_t)blockIdx.x * 4 + wave;
+  const int64_t s = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int64_t j0 = s * SEG;
   if (j0 >= n) return;
   const int64_t j1 = j0 + SEG < n ? j0 + SEG : n;
-  const int c0 = blockIdx.y * cb_chunks;
-  const int left = (int)(N3 >> 3) - c0;
-  const int nch = left < cb_chunks ? left : cb_chunks;
-  const bool has0 = lane < nch, has1 = lane + 64 < nch;
-  const int64_t col0 = (int64_t)(c0 + lane) * 8, col1 = (int64_t)(c0 + lane + 64) * 8;
-  const bool kv0 = col0 >= Dq, kv1 = col1 >= Dq;
-  float acc0[8], acc1[8], cs0[8], cs1[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) acc0[e] = acc1[e] = cs0[e] = cs1[e] = 0.f;
-  int64_t cur = sorted_ids[j0];
-  bool open_left = j0 > 0 && sorted_ids[j0 - 1] == cur;
-
-  auto flush = [&](int64_t id, int slot) {
-    if (id < 0 || id >= V) return;
-    if (slot >= 0) {
-      float* row = part + (s * 2 + slot) * N3;
-      Vec8<float> v;
-      if (has0) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v.set(e, acc0[e]);
-        store8<float>(row + col0, v);
-      }
-      if (has1) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v.set(e, acc1[e]);
-        store8<float>(row + col1, v);
-      }
-      return;
-    }
-    Vec8<bf16> h, l;
-    if (has0) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        h.set(e, acc0[e]);
-        l.set(e, acc0[e] - h.get(e));
-      }
-      store8<bf16>(Dhi + id * N3 + col0, h);
-      store8<bf16>(Dlo + id * N3 + col0, l);
-    }
-    if (has1) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        h.set(e, acc1[e]);
-        l.set(e, acc1[e] - h.get(e));
-      }
-      store8<bf16>(Dhi + id * N3 + col1, h);
-      store8<bf16>(Dlo + id * N3 + col1, l);
-    }
-  };
-
-  for (int64_t jb = j0; jb < j1; jb += 64) {
-    const int64_t jl = jb + lane < j1 ? jb + lane : j1 - 1;
-    const long long my_id = sorted_ids[jl], my_ord = order[jl];
-    const int cnt = (int)(j1 - jb < 64 ? j1 - jb : 64);
-    for (int t0 = 0; t0 < cnt; t0 += 4) {
-      Vec8<bf16> r0[4], r1[4];
-      long long ids4[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int t = t0 + u < cnt ? t0 + u : cnt - 1;
-        ids4[u] = __shfl(my_id, t, 64);
-        const long long ord = __shfl(my_ord, t, 64);
-        const bool row_ok = ord >= 0 && ord < n;        // an order that is no permutation must not become an address
-        const bool kv_ok = !live || (row_ok && live[ord >> 6] != 0);
-        const bf16* src = dqkv + (row_ok ? ord : 0) * N3;
-        r0[u] = Vec8<bf16>{};
-        r1[u] = Vec8<bf16>{};
-        if (has0 && row_ok && (!kv0 || kv_ok)) r0[u] = load8s<bf16>(src + col0);
-        if (has1 && row_ok && (!kv1 || kv_ok)) r1[u] = load8s<bf16>(src + col1);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        if (t0 + u >= cnt) break;
-        const int64_t id = ids4[u];
-        if (id != cur) {
-          flush(cur, open_left ? 0 : -1);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) acc0[e] = acc1[e] = 0.f;
-          cur = id;
-          open_left = false;
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float a = r0[u].get(e), b = r1[u].get(e);
-          acc0[e] += a; cs0[e] += a;
-          acc1[e] += b; cs1[e] += b;
-        }
-      }
-    }
-  }
-  const bool open_right = j1 < n && sorted_ids[j1] == cur;
-  flush(cur, open_left ? 0 : (open_right ? 1 : -1));
-  Vec8<float> v;
-  if (has0) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v.set(e, cs0[e]);
-    store8<float>(cpart + s * N3 + col0, v);
-  }
-  if (has1) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v.set(e, cs1[e]);
-    store8<float>(cpart + s * N3 + col1, v);
-  }
+  const SegCols c = seg_cols(N3, cb_chunks);
+  const QkvLiveRows rows{live, {c.col[0] >= Dq, c.col[1] >= Dq}};
+  const SegSlotSink<SegStoreHiLo> sink{{Dhi, Dlo}, part + s * 2 * N3, N3};
+  seg_walk<true>(dqkv, N3, sorted_ids, order, n, V, j0, j1, c, rows, sink, cpart + s * N3);
 }
 
 // db[col] += the sum over the stretches of cpart[stretch][col]: 16 equal pieces of the stretch axis summed in order by 16 threads of
@@ -212,9 +115,9 @@ __global__ __launch_bounds__(256) void table_add_kernel(const float* __restrict_
 struct ByIdWs { size_t dxtab, dhi, dlo, ntab, rinv, dnlo, dna, dnr, ones, dn32, x32, part, cpart, longk, live, sub, sub_bytes, total; };
 ByIdWs byid_layout(int64_t n, int64_t d, int64_t N3, int64_t V) {
   ByIdWs w;
-  const int64_t Vp = ceil_div(V, VPAD) * VPAD, nst = ceil_div(n, SEG);
+  const int64_t Vp = vpad_rows(V), nst = ceil_div(n, SEG);
   size_t off = 0;
-  const auto take = [&off](size_t bytes) { const size_t o = off; off += al256(bytes); return o; };
+  const auto take = [&off](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
   w.dxtab = take((size_t)V * d * sizeof(float));
   w.dhi = take((size_t)Vp * N3 * sizeof(bf16));
   w.dlo = take((size_t)Vp * N3 * sizeof(bf16));
@@ -249,6 +152,12 @@ bool byid_shape_ok(int64_t n, int64_t d, int64_t N3, int64_t V) {
 
 }  // namespace
 
+int live_flags_launch(const int* list, const int* count, uint8_t* flags, int64_t len, hipStream_t stream) {
+  hipLaunchKernelGGL(live_flags_kernel, dim3((unsigned)ceil_div(len, 256)), dim3(256), 0, stream, list, count, flags, len);
+  MEANT_LAUNCH_CHECK("live_flags");
+  return MEANT_OK;
+}
+
 extern "C" size_t meant_qkv_embed_bwd_by_id_ws(int64_t n, int64_t d, int64_t N3, int64_t V) {
   return byid_shape_ok(n, d, N3, V) ? byid_layout(n, d, N3, V).total : 0;
 }
@@ -270,7 +179,7 @@ extern "C" int meant_qkv_embed_bwd_by_id(const void* dqkv, const void* dres, con
   hipStream_t st = (hipStream_t)stream;
   char* base = (char*)workspace;
   float* dxtab = (float*)(base + w.dxtab);
-  const int64_t Vp = ceil_div(V, VPAD) * VPAD, nst = ceil_div(n, SEG);
+  const int64_t Vp = vpad_rows(V), nst = ceil_div(n, SEG);
   int rc;
 
   if (stage & MEANT_BY_ID_SHARED) {
@@ -294,20 +203,13 @@ extern "C" int meant_qkv_embed_bwd_by_id(const void* dqkv, const void* dres, con
     if (live) {
       const int64_t nblk = n / 64;                       // the lists cover whole 64-row blocks: S % 256 == 0
       BYID_REQ(n % 64 == 0, "qkv_embed_bwd_by_id: key-padding lists need n %% 64 == 0");
-      hipLaunchKernelGGL(live_flags_kernel, dim3((unsigned)ceil_div(nblk, 256)), dim3(256), 0, st, (const int*)kv_lists, live, nblk);
+      rc = live_flags_launch((const int*)kv_lists + MEANT_KV_LIST_HDR, (const int*)kv_lists, live, nblk, st);
+      if (rc) return rc;
     }
-    const int chunks = (int)(N3 >> 3);
-    const int ncb = (int)ceil_div(chunks, 128);
-    const int cb_chunks = (int)ceil_div(chunks, ncb);
-    hipLaunchKernelGGL(qkv_seg_kernel, dim3((unsigned)ceil_div(nst, 4), (unsigned)ncb), dim3(256), 0, st, (const bf16*)dqkv, sorted_ids, order,
-                       (const uint8_t*)live, Dhi, Dlo, part, cpart, n, N3, N3 / 3, V, cb_chunks);
-    if (nst > 1) {
-      const SegStoreHiLo images{Dhi, Dlo};
-      hipLaunchKernelGGL(seg_cross_kernel<SegStoreHiLo>, dim3((unsigned)ceil_div(nst - 1, 4), (unsigned)ceil_div(N3, 256)), dim3(256), 0, st,
-                         sorted_ids, (const float*)part, longk, images, n, N3, V);
-      hipLaunchKernelGGL(seg_long_kernel<SegStoreHiLo>, dim3((unsigned)(nst - 1), (unsigned)ceil_div(N3, 64)), dim3(256), 0, st, sorted_ids,
-                         (const float*)part, (const int*)longk, images, N3);
-    }
+    const SegColBlocks cb = seg_col_blocks(N3, 2);
+    hipLaunchKernelGGL(qkv_seg_kernel, dim3((unsigned)ceil_div(nst, 4), (unsigned)cb.ncb), dim3(256), 0, st, (const bf16*)dqkv, sorted_ids, order,
+                       (const uint8_t*)live, Dhi, Dlo, part, cpart, n, N3, N3 / 3, V, cb.cb_chunks);
+    seg_cross_launch(SegStoreHiLo{Dhi, Dlo}, sorted_ids, (const float*)part, longk, n, N3, V, st);
     hipLaunchKernelGGL(qkv_colsum_kernel, dim3((unsigned)ceil_div(N3, 64)), dim3(256), 0, st, (const float*)cpart, db, nst, N3);
     MEANT_LAUNCH_CHECK("qkv_embed_bwd_by_id: segmented sum");
     // table-sized work

@@ -16,20 +16,8 @@
 
 namespace {
 
-constexpr int SEG = 256;           // sorted entries per wave (a stretch), as in seg_sum.h
-constexpr int VPAD = 256;          // the GEMM's row axis is V rounded up to this
+#include "seg_sum.h"               // SEG sorted entries per wave (a stretch), and the cut of a row into column blocks
 constexpr int PANEL = 256;         // rows of a key-padding panel (meant_kv_live_rows)
-
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// live[p] = 1 for the 256-row panels the key-padding lists name as live, on a zeroed array
-__global__ __launch_bounds__(256) void live_panels_kernel(const int* __restrict__ panels, const int* __restrict__ count, uint8_t* __restrict__ live,
-                                                           int64_t npan) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= npan || i >= *count) return;
-  const int p = panels[i];
-  if (p >= 0 && p < npan) live[p] = 1;
-}
 
 // The gather, the mirror image of qkv_seg_kernel: a wave walks a stretch of SEG sorted entries; grid.y cuts the 3 H Dh columns into
 // blocks of at most 64 8-column chunks, one per lane, so the four rotated pairs of a chunk stay in one lane.  A run of equal ids
@@ -112,9 +100,9 @@ __global__ __launch_bounds__(256) void qkv_gather_kernel(const float* __restrict
 struct FwdByIdWs { size_t ntab, rinv, p, live, total; };
 FwdByIdWs fwd_byid_layout(int64_t n, int64_t d, int64_t N3, int64_t V) {
   FwdByIdWs w;
-  const int64_t Vp = ceil_div(V, VPAD) * VPAD;
+  const int64_t Vp = vpad_rows(V);
   size_t off = 0;
-  const auto take = [&off](size_t bytes) { const size_t o = off; off += al256(bytes); return o; };
+  const auto take = [&off](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
   w.ntab = take((size_t)Vp * d * sizeof(bf16));
   w.rinv = take((size_t)V * sizeof(float));
   w.p = take((size_t)Vp * N3 * sizeof(float));
@@ -147,7 +135,7 @@ extern "C" size_t meant_qkv_embed_fwd_by_id_ws(int64_t n, int64_t d, int64_t N3,
 extern "C" int meant_qkv_embed_fwd_by_id_ok(int64_t n, int64_t d, int64_t N3, int64_t V) {
   if (!fwd_byid_shape_ok(n, d, N3, V) || N3 % 3 != 0 || (N3 / 3) % 256 != 0 || n % 256 != 0) return 0;
   if (meant_num_cus() <= 0) return 0;                  // no current device: the launcher's rule counts its compute units
-  const int64_t Vp = ceil_div(V, VPAD) * VPAD;
+  const int64_t Vp = vpad_rows(V);
   return gemm_bf16_nt_streams(shape_args(n, N3, d)) && gemm_bf16_nt_streams(shape_args(Vp, N3, d)) ? 1 : 0;
 }
 
@@ -178,7 +166,7 @@ extern "C" int meant_qkv_embed_fwd_by_id(const void* table_bf16, const float* ga
   bf16* ntab = (bf16*)(base + w.ntab);
   float *rinv = (float*)(base + w.rinv), *P = (float*)(base + w.p);
   uint8_t* live = listed ? (uint8_t*)(base + w.live) : nullptr;
-  const int64_t Vp = ceil_div(V, VPAD) * VPAD, nst = ceil_div(n, SEG), nblk = n / 64, npan = n / PANEL;
+  const int64_t Vp = vpad_rows(V), nst = ceil_div(n, SEG), nblk = n / 64, npan = n / PANEL;
 
   // 1. the norm on the table image, zero-padded to whole 256-row panels
   // The norm's launcher packs 1, 2 or 4 rows into a wave where the row count divides (norm.hip, norm_route), and the packed and the
@@ -202,13 +190,11 @@ extern "C" int meant_qkv_embed_fwd_by_id(const void* table_bf16, const float* ga
   if (rc) return rc;
   // 3. the gather
   const int* const lists = (const int*)kv_lists;
-  if (listed)
-    hipLaunchKernelGGL(live_panels_kernel, dim3((unsigned)ceil_div(npan, 256)), dim3(256), 0, st, lists + MEANT_KV_LIST_HDR + nblk, lists + 1, live, npan);
-  const int chunks = (int)(N3 >> 3);
-  const int ncb = (int)ceil_div(chunks, 64);
-  const int cb_chunks = (int)ceil_div(chunks, ncb);
-  hipLaunchKernelGGL(qkv_gather_kernel, dim3((unsigned)ceil_div(nst, 4), (unsigned)ncb), dim3(256), 0, st, (const float*)P, sorted_ids, order,
-                     (const uint8_t*)live, qa, qb, ka, kb, (bf16*)qkv, n, (int)N3, (int)D, Dh, rot ? R : 0, (int)S, V, cb_chunks);
+  if (listed) rc = live_flags_launch(lists + MEANT_KV_LIST_HDR + nblk, lists + 1, live, npan, st);
+  if (rc) return rc;
+  const SegColBlocks cb = seg_col_blocks(N3, 1);
+  hipLaunchKernelGGL(qkv_gather_kernel, dim3((unsigned)ceil_div(nst, 4), (unsigned)cb.ncb), dim3(256), 0, st, (const float*)P, sorted_ids, order,
+                     (const uint8_t*)live, qa, qb, ka, kb, (bf16*)qkv, n, (int)N3, (int)D, Dh, rot ? R : 0, (int)S, V, cb.cb_chunks);
   MEANT_LAUNCH_CHECK("qkv_embed_fwd_by_id: gather");
   meant_route_hit(ROUTE_QKV_FWD_BY_ID);
   // the k | v columns of dead panels: zeros, as meant_qkv_proj_fwd_live leaves them

@@ -1,7 +1,13 @@
-// The crossing-run passes of the segmented sums over sorted ids (embedding.hip: meant_embedding_bwd_seg; qkv_by_id.hip: the per-id sum
-// of dqkv).  The first pass of either -- a wave per stretch of SEG sorted entries -- leaves fp32 partial sums of the runs that cross
-// its stretch's ends in part[stretch][0] (the run came in from the left) and [stretch][1] (it starts here and leaves to the right);
-// the two kernels here add each such run's partials in an order that depends on the sorted ids alone and hand the sum to a Store:
+// The segmented sums over sorted ids (embedding.hip: meant_embedding_bwd_sorted[_range], meant_embedding_bwd_seg; qkv_by_id.hip: the
+// per-id sum of dqkv).  Two parts.
+//   seg_walk           the first pass, one definition for the three kernels: a wave walks a stretch of SEG sorted entries and sums
+//                      each run of equal ids in registers.  What differs between the kernels is compile-time policy: which rows'
+//                      chunks may be read (SegAllRows, or the q|k|v kernel's live-block test), where a finished sum goes (a Sink),
+//                      and whether the stretch's column sums are kept.
+//   seg_cross_kernel,  the crossing-run passes behind SegSlotSink: the walk leaves fp32 partial sums of the runs that cross its
+//   seg_long_kernel    stretch's ends in part[stretch][0] (the run came in from the left) and [stretch][1] (it starts here and leaves
+//                      to the right); the two kernels add each such run's partials in an order that depends on the sorted ids alone.
+// A finished sum goes to a Store:
 //   SegAddRow     dtable[id, :] += sum, for the ids of [id_lo, id_hi)
 //   SegStoreHiLo  the sum as two bf16 images, hi = bf16(sum), lo = bf16(sum - hi)
 // Included inside each translation unit's anonymous namespace.
@@ -33,6 +39,122 @@ struct SegStoreHiLo {
   }
 };
 
+// ------------------------------------------------------------------------------------------------
+// The walk's policies.
+// Rows: may the lane's chunk c (0 or 1) of row `ord` be read?  A chunk that may not counts as zeros.
+struct SegAllRows {
+  __device__ __forceinline__ bool live(int64_t) const { return true; }
+  __device__ __forceinline__ bool reads(int, bool) const { return true; }
+};
+// Sink: inside() takes the sum of a run that lies inside the stretch and so belongs to nobody else, cross() the partial sum of a run
+// that came in from the left (slot 0) or starts here and leaves to the right (slot 1); owns() is the id range in front of both.
+// SegSlotSink: the finished run goes to the Store, the partial sums to this stretch's two workspace rows.
+template <class Store>
+struct SegSlotSink {
+  Store st; float* part; int64_t ld;                                       // part: [2][ld], this stretch's
+  __device__ __forceinline__ bool owns(int64_t id) const { return st.owns(id); }
+  __device__ __forceinline__ void inside(int64_t id, int64_t col, f32x4 lo, f32x4 hi) const {
+    st.put(id, ld, col, lo);
+    st.put(id, ld, col + 4, hi);
+  }
+  __device__ __forceinline__ void cross(int64_t, int slot, int64_t col, f32x4 lo, f32x4 hi) const {
+    store8<float>(part + slot * ld + col, Vec8<float>{lo, hi});
+  }
+};
+
+// the lane's two 8-column chunks, `lane` and `lane + 64` of column block blockIdx.y (cb_chunks chunks to a block, seg_col_blocks)
+struct SegCols { int64_t col[2]; bool has[2]; };
+__device__ __forceinline__ SegCols seg_cols(int64_t width, int cb_chunks) {
+  const int lane = threadIdx.x & 63;
+  const int c0 = blockIdx.y * cb_chunks;                                   // this column block: chunks [c0, c0 + nch)
+  const int left = (int)(width >> 3) - c0;
+  const int nch = left < cb_chunks ? left : cb_chunks;
+  return {{(int64_t)(c0 + lane) * 8, (int64_t)(c0 + lane + 64) * 8}, {lane < nch, lane + 64 < nch}};
+}
+
+// One wave sums the rows src[order[j], :] of the sorted entries j of [j0, j1), run by run of equal ids.  Ids and row numbers are
+// broadcast from the lanes that loaded them, four rows (16-byte loads) are requested before the first is consumed, and a run's rows are
+// added in sorted order into one accumulator per column: every bit-reproducibility promise rests on that order.  A run is flushed when
+// the id changes and at the end; ids outside [0, V) and outside the sink's range are dropped there.  A run that is open on both sides
+// counts as "from the left".  With COLSUM, csum[col] = the sum of every row of the stretch, whatever its id.
+template <bool COLSUM, typename T, class Rows, class Sink>
+__device__ __forceinline__ void seg_walk(const T* __restrict__ src, int64_t ld, const int64_t* __restrict__ sorted_ids,
+                                         const int64_t* __restrict__ order, int64_t n, int64_t V, int64_t j0, int64_t j1, const SegCols& c,
+                                         const Rows& rows, const Sink& sink, float* __restrict__ csum) {
+  const int lane = threadIdx.x & 63;
+  float acc[2][8], cs[2][8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) acc[0][e] = acc[1][e] = cs[0][e] = cs[1][e] = 0.f;
+  int64_t cur = sorted_ids[j0];
+  bool open_left = j0 > 0 && sorted_ids[j0 - 1] == cur;                  // the first run started in an earlier stretch
+
+  // slot < 0: the run is this wave's alone
+  auto flush = [&](int64_t id, int slot) {
+    if (id < 0 || id >= V || !sink.owns(id)) return;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      if (!c.has[k]) continue;
+      const f32x4 lo = {acc[k][0], acc[k][1], acc[k][2], acc[k][3]}, hi = {acc[k][4], acc[k][5], acc[k][6], acc[k][7]};
+      if (slot < 0) sink.inside(id, c.col[k], lo, hi);
+      else sink.cross(id, slot, c.col[k], lo, hi);
+    }
+  };
+
+  for (int64_t jb = j0; jb < j1; jb += 64) {
+    const int64_t jl = jb + lane < j1 ? jb + lane : j1 - 1;
+    const long long my_id = sorted_ids[jl], my_ord = order[jl];
+    const int cnt = (int)(j1 - jb < 64 ? j1 - jb : 64);
+    for (int t0 = 0; t0 < cnt; t0 += 4) {
+      Vec8<T> r[4][2];
+      long long ids4[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int t = t0 + u < cnt ? t0 + u : cnt - 1;
+        ids4[u] = __shfl(my_id, t, 64);
+        const long long ord = __shfl(my_ord, t, 64);
+        const bool row_ok = ord >= 0 && ord < n;        // an order that is no permutation must not become an address
+        const bool live = row_ok && rows.live(ord);
+        const T* row = src + (row_ok ? ord : 0) * ld;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          r[u][k] = Vec8<T>{};
+          if (c.has[k] && row_ok && rows.reads(k, live)) r[u][k] = load8s<T>(row + c.col[k]);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (t0 + u >= cnt) break;
+        const int64_t id = ids4[u];
+        if (id != cur) {
+          flush(cur, open_left ? 0 : -1);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) acc[0][e] = acc[1][e] = 0.f;
+          cur = id;
+          open_left = false;
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+#pragma unroll
+          for (int k = 0; k < 2; ++k) {
+            const float a = r[u][k].get(e);
+            acc[k][e] += a;
+            if constexpr (COLSUM) cs[k][e] += a;
+          }
+        }
+      }
+    }
+  }
+  const bool open_right = j1 < n && sorted_ids[j1] == cur;
+  flush(cur, open_left ? 0 : (open_right ? 1 : -1));
+  if constexpr (COLSUM) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+      if (c.has[k])
+        store8<float>(csum + c.col[k], Vec8<float>{{cs[k][0], cs[k][1], cs[k][2], cs[k][3]}, {cs[k][4], cs[k][5], cs[k][6], cs[k][7]}});
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // The runs that cross stretch ends.  A run belongs to the stretch it STARTS in: its partial sums are slot 1 of that stretch and
 // slot 0 of every following stretch that begins with the same id (sorted ids: a contiguous range).
 // Short lists (at most SEG_SHORT partials; two for a typical id): one wave per (stretch, 256 columns) adds them in stretch order and
@@ -100,4 +222,25 @@ __global__ __launch_bounds__(256) void seg_long_kernel(const int64_t* __restrict
     __syncthreads();
   }
   if (p == 0 && active) st.put(id, d, col, red[0][tid & 15]);
+}
+
+// ------------------------------------------------------------------------------------------------
+// host side
+// the cut of a row of `width` columns into grid.y column blocks of at most 64 * per_lane 8-column chunks, as equal as they come
+struct SegColBlocks { int ncb, cb_chunks; };
+inline SegColBlocks seg_col_blocks(int64_t width, int per_lane) {
+  const int64_t chunks = width >> 3, ncb = ceil_div(chunks, 64 * per_lane);
+  return {(int)ncb, (int)ceil_div(chunks, ncb)};
+}
+
+// the two crossing-run passes over the partial sums a SegSlotSink<Store> walk left; longk: one int per stretch
+template <class Store>
+void seg_cross_launch(const Store& store, const int64_t* sorted_ids, const float* part, int* longk, int64_t n, int64_t d, int64_t V,
+                      hipStream_t st) {
+  const int64_t nst = ceil_div(n, SEG);
+  if (nst <= 1) return;
+  hipLaunchKernelGGL(seg_cross_kernel<Store>, dim3((unsigned)ceil_div(nst - 1, 4), (unsigned)ceil_div(d, 256)), dim3(256), 0, st, sorted_ids,
+                     part, longk, store, n, d, V);
+  hipLaunchKernelGGL(seg_long_kernel<Store>, dim3((unsigned)(nst - 1), (unsigned)ceil_div(d, 64)), dim3(256), 0, st, sorted_ids, part,
+                     (const int*)longk, store, d);
 }

@@ -19,7 +19,6 @@ constexpr int SEL_ROUNDS = 4;                          // 64-row rounds per wave
 constexpr int SEL_WAVE_SPAN = 64 * SEL_ROUNDS;
 constexpr int SEL_SPAN = (SEL_THREADS / 64) * SEL_WAVE_SPAN;      // rows per workgroup
 
-size_t sel_align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 __device__ __forceinline__ bool sel_labelled(int64_t t, int64_t V, int64_t ignore_index) {
   return t != ignore_index && t >= 0 && t < V;        // the predicate of softmax_ce_fwd / _bwd (optim.hip)
@@ -116,7 +115,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_scatter_kernel(const int64
 
 extern "C" size_t meant_select_rows_ws(int64_t T) {
   if (T <= 0 || T >= (1ll << 31)) return 0;
-  return sel_align256((size_t)ceil_div(T, SEL_SPAN) * sizeof(uint32_t));
+  return align256((size_t)ceil_div(T, SEL_SPAN) * sizeof(uint32_t));
 }
 
 extern "C" int meant_select_rows(const int64_t* target, int64_t T, int64_t V, int64_t ignore_index, int32_t* idx, int32_t* inv,
