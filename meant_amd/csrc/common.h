@@ -70,6 +70,8 @@ void meant_route_hit(int route);
 static inline bool meant_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 // aligned to one element of the activation type (4 bytes fp32, 2 bytes bf16): what the element-access kernels need
 static inline bool meant_aligned_elem(const void* p, int dtype) { return (reinterpret_cast<uintptr_t>(p) & (dtype == MEANT_F32 ? 3 : 1)) == 0; }
+// what a base pointer of a row kernel's 16-byte (vec) or element form needs
+static inline bool meant_aligned_rows(bool vec, const void* p, int dtype) { return vec ? meant_aligned16(p) : meant_aligned_elem(p, dtype); }
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }   // the regions of a workspace start on 256 bytes
 
@@ -79,11 +81,15 @@ template <> struct Vec8<float> {
   f32x4 lo, hi;
   __device__ __forceinline__ float get(int i) const { return i < 4 ? lo[i] : hi[i - 4]; }
   __device__ __forceinline__ void set(int i, float v) { if (i < 4) lo[i] = v; else hi[i - 4] = v; }
+  __device__ __forceinline__ float at(int i) const { return get(i); }    // the stored element, as it lies in memory
+  __device__ __forceinline__ void put(int i, float v) { set(i, v); }
 };
 template <> struct Vec8<bf16> {
   bf16x8 v;
   __device__ __forceinline__ float get(int i) const { return (float)v[i]; }
   __device__ __forceinline__ void set(int i, float x) { v[i] = (bf16)x; }
+  __device__ __forceinline__ bf16 at(int i) const { return v[i]; }       // the stored element: a copy does not go through float
+  __device__ __forceinline__ void put(int i, bf16 x) { v[i] = x; }
   __device__ __forceinline__ unsigned raw(int i) const {                 // the stored bits of element i
     typedef __attribute__((ext_vector_type(4))) unsigned uvec4;
     return (__builtin_bit_cast(uvec4, v)[i >> 1] >> ((i & 1) * 16)) & 0xffffu;
@@ -129,6 +135,31 @@ template <> __device__ __forceinline__ void store8<float>(float* p, const Vec8<f
 template <> __device__ __forceinline__ void store8<bf16>(bf16* p, const Vec8<bf16>& v) {
   *reinterpret_cast<bf16x8*>(p) = v.v;
 }
+// Up to 8 consecutive elements at p, the first n of them real: what lets a row kernel have one body for rows on the 16-byte grid and
+// off it.  VEC: load8 / store8 (STREAM: load8s / store8s), n ignored.  Otherwise element accesses of the stored bits, each guarded by
+// k < n: nothing is touched at or beyond p[n], absent elements load as zero.  chunks8: the 8-element chunks of a row of d either way.
+template <bool VEC> __device__ __forceinline__ int chunks8(int d) { return VEC ? d >> 3 : (d + 7) >> 3; }
+template <bool VEC, bool STREAM = false, typename T> __device__ __forceinline__ Vec8<T> load8n(const T* p, int n) {
+  if constexpr (VEC) return STREAM ? load8s<T>(p) : load8<T>(p);
+  else {
+    Vec8<T> r;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) r.put(k, k < n ? p[k] : T(0.f));
+    return r;
+  }
+}
+template <bool VEC, bool STREAM = false, typename T> __device__ __forceinline__ void store8n(T* p, const Vec8<T>& v, int n) {
+  if constexpr (VEC) {
+    if (STREAM) store8s<T>(p, v);
+    else store8<T>(p, v);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+      if (k < n) p[k] = v.at(k);
+  }
+}
+// element k of an fp32 parameter row read beside such a chunk, under the same guard
+template <bool VEC> __device__ __forceinline__ float param8(const float* p, int k, int n) { return VEC || k < n ? p[k] : 0.f; }
 
 __device__ __forceinline__ float to_f(float x) { return x; }
 __device__ __forceinline__ float to_f(bf16 x) { return (float)x; }
@@ -336,3 +367,9 @@ __device__ __forceinline__ bf16x8 pack_tr(u32x2 lo, u32x2 hi) {
     else if ((dtype) == MEANT_BF16) { using T = bf16; __VA_ARGS__; }            \
     else { meant_set_error("unknown dtype %d", (int)(dtype)); return MEANT_ERR_ARG; } \
   } while (0)
+// dtype x the 16-byte / element form of a row kernel (load8n above)
+#define DISPATCH_DTYPE_VEC(dtype, vec, T, VEC, ...)                              \
+  DISPATCH_DTYPE(dtype, T, {                                                    \
+    if (vec) { constexpr bool VEC = true; __VA_ARGS__; }                        \
+    else { constexpr bool VEC = false; __VA_ARGS__; }                           \
+  })

@@ -11,7 +11,8 @@
 //                              the regrouped attention's backward has already filled -- no separate tensor, no add pass.
 //   * meant_attn_cls_split_fwd/bwd -- the same for videos whose scores do not fit one workgroup's LDS: a workgroup per (video,
 //                              head, key segment), a small merge kernel in segment order; no atomics.
-//   * the element forms of gather_rows, token_shift and dropout for rows off the 16-byte grid (a TimeSformer at dim = 99 or 100).
+//   * gather_rows, token_shift and dropout also take rows off the 16-byte grid (a TimeSformer at dim = 99 or 100): the same kernel
+//     bodies by guarded element access (common.h load8n / store8n).
 // All HBM / latency bound and small next to the GEMMs (a few hundred MB per layer).
 #include "common.h"
 
@@ -19,38 +20,26 @@ namespace {
 
 constexpr int DIV_THREADS = 256;
 
-template <typename T>
+// A wave per row; a lane moves one 16-byte chunk (VEC) or, for rows that are only element-aligned (W % 8 != 0: the cls concatenation of a
+// TimeSformer at dim = 99 or 100), one column: a chunk of which one element is real, so a wave's accesses stay contiguous.
+template <typename T, bool VEC>
 __global__ __launch_bounds__(DIV_THREADS) void gather_rows_kernel(const T* __restrict__ src, const int* __restrict__ idx, const T* __restrict__ fill,
                                                                    T* __restrict__ dst, int64_t n, int W) {
+  constexpr int PER = VEC ? 8 : 1;                     // columns per lane
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int nch = W >> 3;
+  const int nch = VEC ? W >> 3 : W;
   for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < n; r += (int64_t)gridDim.x * 4) {
     const int id = idx[r];
     const T* s = id >= 0 ? src + (int64_t)id * W : fill;
     for (int ch = lane; ch < nch; ch += 64) {
       Vec8<T> v;
-      if (id >= 0 || (id == -2 && fill)) v = load8<T>(s + ch * 8);
+      if (id >= 0 || (id == -2 && fill)) v = load8n<VEC>(s + ch * PER, 1);
       else {
 #pragma unroll
         for (int k = 0; k < 8; ++k) v.set(k, 0.f);
       }
-      store8s<T>(dst + r * W + ch * 8, v);
+      store8n<VEC, true>(dst + r * W + ch * PER, v, 1);
     }
-  }
-}
-
-// The same gather by element access, for rows that are only element-aligned (W % 8 != 0: the cls concatenation of a TimeSformer at
-// dim = 99 or 100): a wave per row, a lane per column, the stored bits copied.  Nothing is touched at or beyond column W of a row.
-template <typename T>
-__global__ __launch_bounds__(DIV_THREADS) void gather_rows_elem_kernel(const T* __restrict__ src, const int* __restrict__ idx, const T* __restrict__ fill,
-                                                                        T* __restrict__ dst, int64_t n, int W) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < n; r += (int64_t)gridDim.x * 4) {
-    const int id = idx[r];
-    const T* s = id >= 0 ? src + (int64_t)id * W : fill;
-    const bool live = id >= 0 || (id == -2 && fill);
-    T* d = dst + r * W;
-    for (int c = lane; c < W; c += 64) d[c] = live ? s[c] : from_f<T>(0.f);
   }
 }
 
@@ -450,32 +439,34 @@ __global__ __launch_bounds__(DIV_THREADS) void attn_cls_merge_bwd_kernel(const f
 // time token shift (src/meant/timesformer_pytorch.py:28-53): of the patch tokens [b, f, n, d] the first d/3 columns come from
 // the NEXT frame, the second third stays, the third third comes from the PREVIOUS frame (zeros beyond the clip's ends); the
 // cls row and the columns past 3 * (d / 3) pass through.  transpose = the adjoint (the two shifts swap).  A thread moves 8
-// columns: one 16-byte copy when d / 3 is a multiple of 8 (no vector straddles a third), else element by element.
+// columns.  VEC (d % 8 == 0): one 16-byte copy when d / 3 is a multiple of 8 (no vector straddles a third), else each column from its
+// own source.  !VEC (d % 8 != 0, rows only element-aligned): that per-column path with the columns guarded by col < d, the stored bits
+// copied; the cls row goes through the guarded chunk copy.
 __device__ __forceinline__ int shift_of(int col, int chunk, int transpose) {
   const int which = col / chunk;                       // 0, 1, 2: shifted thirds; >= 3: the remainder columns
   const int sh = which == 0 ? 1 : (which == 2 ? -1 : 0);  // source frame = frame + sh
   return transpose ? -sh : sh;
 }
 
-template <typename T>
+template <typename T, bool VEC>
 __global__ __launch_bounds__(DIV_THREADS) void token_shift_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t B, int f, int n, int d,
                                                                    int chunk, int transpose) {
-  const int nch = d >> 3;
+  const int nch = chunks8<VEC>(d);
   const int64_t L = 1 + (int64_t)f * n, total = B * L * nch;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int ch = (int)(i % nch);
     const int64_t row = i / nch, b = row / L, t = row - b * L;
     int64_t src = row;
     bool zero = false;
-    if (t > 0 && (chunk & 7)) {                        // a vector may straddle a third: each column finds its own source
+    if (t > 0 && (!VEC || (chunk & 7))) {              // a chunk may straddle a third (off the 8-grid: always): each column finds its own source
       const int fr = (int)((t - 1) / n);
       Vec8<T> v;
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         const int col = ch * 8 + k, sh = shift_of(col, chunk, transpose), fi = fr + sh;
-        v.set(k, fi < 0 || fi >= f ? 0.f : to_f(x[(row + (int64_t)sh * n) * d + col]));
+        v.put(k, (!VEC && col >= d) || fi < 0 || fi >= f ? T(0.f) : x[(row + (int64_t)sh * n) * d + col]);
       }
-      store8<T>(y + row * d + ch * 8, v);
+      store8n<VEC>(y + row * d + ch * 8, v, d - ch * 8);
       continue;
     }
     if (t > 0) {
@@ -488,67 +479,35 @@ __global__ __launch_bounds__(DIV_THREADS) void token_shift_kernel(const T* __res
     if (zero) {
 #pragma unroll
       for (int k = 0; k < 8; ++k) v.set(k, 0.f);
-    } else v = load8<T>(x + src * d + ch * 8);
-    store8<T>(y + row * d + ch * 8, v);
+    } else v = load8n<VEC>(x + src * d + ch * 8, d - ch * 8);
+    store8n<VEC>(y + row * d + ch * 8, v, d - ch * 8);
   }
 }
 
 // inverted dropout y = x * keep / (1 - p) with the counter-based mask of the fused RMSNorm dropout (common.h keep_scale8): the
-// same (seed, element index) gives the same mask, so the backward is the same call on dy
-template <typename T>
-__global__ __launch_bounds__(DIV_THREADS) void dropout_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t n8, float p, uint64_t seed) {
+// same (seed, element index) gives the same mask, so the backward is the same call on dy.  Element i takes part i & 7 of the draw for
+// i >> 3, at any n.
+// NOTE the unit of `cnt`: GROUPS OF 8 for VEC (n % 8 == 0: the host passes n / 8), ELEMENTS otherwise (the host passes n).  The 16-byte
+// form keeps the argument list and the instructions it has always had that way; meant_dropout is the only caller.
+// !VEC still has two ways to touch memory, chosen per group at run time: with both bases 16-byte aligned (read off the pointers here;
+// the host's VEC only says n % 8 != 0) the full groups go through the 16-byte accesses and only the last, partial group element by
+// element; with an unaligned base every group does.
+template <typename T, bool VEC>
+__global__ __launch_bounds__(DIV_THREADS) void dropout_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t cnt, float p, uint64_t seed) {
+  const int64_t n8 = VEC ? cnt : (cnt + 7) >> 3;
+  const bool vec = VEC || ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x) {
     float km[8];
     keep_scale8(p, seed, (uint64_t)i * 8, km);
-    const Vec8<T> v = load8<T>(x + i * 8);
-    Vec8<T> o;
+    const int n = VEC || i * 8 + 8 <= cnt ? 8 : (int)(cnt - i * 8);          // real elements of this group
+    const bool whole = VEC || (vec && n == 8);
+    Vec8<T> v, o;
+    if (whole) v = load8n<true>(x + i * 8, n);
+    else v = load8n<false>(x + i * 8, n);
 #pragma unroll
     for (int k = 0; k < 8; ++k) o.set(k, v.get(k) * km[k]);
-    store8<T>(y + i * 8, o);
-  }
-}
-
-// The shift by element access, for d % 8 != 0 (rows only element-aligned): a thread moves up to 8 consecutive columns of one row,
-// each guarded by c < d and each finding its own source frame; the stored bits are copied.
-template <typename T>
-__global__ __launch_bounds__(DIV_THREADS) void token_shift_elem_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t B, int f, int n, int d,
-                                                                        int chunk, int transpose) {
-  const int nch = (d + 7) >> 3;
-  const int64_t L = 1 + (int64_t)f * n, total = B * L * nch;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int c0 = (int)(i % nch) * 8;
-    const int64_t row = i / nch, b = row / L, t = row - b * L;
-    const int fr = t > 0 ? (int)((t - 1) / n) : 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int col = c0 + k;
-      if (col >= d) break;
-      const int sh = t > 0 ? shift_of(col, chunk, transpose) : 0, fi = fr + sh;
-      y[row * d + col] = fi < 0 || fi >= f ? from_f<T>(0.f) : x[(row + (int64_t)sh * n) * d + col];
-    }
-  }
-}
-
-// dropout at any n: element i takes part i & 7 of the draw for i >> 3, as dropout_kernel and the norm kernels at odd widths.  vec:
-// both bases 16-byte aligned -- full groups of 8 go through the 16-byte path (the arithmetic and bits of dropout_kernel), the
-// last, partial group element by element; otherwise every group goes element by element.
-template <typename T>
-__global__ __launch_bounds__(DIV_THREADS) void dropout_elem_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t n, float p, uint64_t seed, int vec) {
-  const int64_t n8 = (n + 7) >> 3;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x) {
-    float km[8];
-    keep_scale8(p, seed, (uint64_t)i * 8, km);
-    if (vec && i * 8 + 8 <= n) {
-      const Vec8<T> v = load8<T>(x + i * 8);
-      Vec8<T> o;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) o.set(k, v.get(k) * km[k]);
-      store8<T>(y + i * 8, o);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 8; ++k)
-        if (i * 8 + k < n) y[i * 8 + k] = from_f<T>(to_f(x[i * 8 + k]) * km[k]);
-    }
+    if (whole) store8n<true>(y + i * 8, o, n);
+    else store8n<false>(y + i * 8, o, n);
   }
 }
 
@@ -563,18 +522,13 @@ inline int rows_blocks(int64_t n) {
 
 extern "C" int meant_gather_rows(const void* src, const int32_t* idx, const void* fill, void* dst, int64_t n, int64_t W, int dtype, void* stream) {
   DIV_REQ(src && idx && dst && n > 0 && W > 0 && W < (1LL << 30), "gather_rows: bad argument");
-  if (W % 8) {                                       // rows off the 16-byte grid: element access, element alignment
-    DIV_REQ(meant_aligned_elem(src, dtype) && meant_aligned_elem(dst, dtype) && (!fill || meant_aligned_elem(fill, dtype)), "gather_rows: element alignment");
-    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(gather_rows_elem_kernel<T>, dim3(rows_blocks(n)), dim3(DIV_THREADS), 0, (hipStream_t)stream, (const T*)src,
-                                                idx, (const T*)fill, (T*)dst, n, (int)W));
-    MEANT_LAUNCH_CHECK("gather_rows");
-    meant_route_hit(ROUTE_ROWS_ELEM);
-    return MEANT_OK;
-  }
-  DIV_REQ(meant_aligned16(src) && meant_aligned16(dst) && (!fill || meant_aligned16(fill)), "gather_rows: 16-byte alignment");
-  DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(gather_rows_kernel<T>, dim3(rows_blocks(n)), dim3(DIV_THREADS), 0, (hipStream_t)stream, (const T*)src, idx,
-                                              (const T*)fill, (T*)dst, n, (int)W));
+  const bool vec = W % 8 == 0;                       // rows off the 16-byte grid: element access, element alignment
+  DIV_REQ(meant_aligned_rows(vec, src, dtype) && meant_aligned_rows(vec, dst, dtype) && (!fill || meant_aligned_rows(vec, fill, dtype)),
+          "gather_rows: %s alignment", vec ? "16-byte" : "element");
+  DISPATCH_DTYPE_VEC(dtype, vec, T, VEC, hipLaunchKernelGGL((gather_rows_kernel<T, VEC>), dim3(rows_blocks(n)), dim3(DIV_THREADS), 0, (hipStream_t)stream,
+                                                            (const T*)src, idx, (const T*)fill, (T*)dst, n, (int)W));
   MEANT_LAUNCH_CHECK("gather_rows");
+  if (!vec) meant_route_hit(ROUTE_ROWS_ELEM);
   return MEANT_OK;
 }
 
@@ -741,43 +695,26 @@ extern "C" int meant_attn_cls_split_bwd(const void* qkv, const void* out, int64_
 extern "C" int meant_token_shift(const void* x, void* y, int64_t B, int64_t frames, int64_t n, int64_t d, int transpose, int dtype, void* stream) {
   DIV_REQ(x && y && x != y && B > 0 && frames > 0 && n > 0 && d >= 3 && d < (1LL << 30) && frames * n < (1LL << 30),
           "token_shift: bad argument (d >= 3)");
-  if (d % 8) {                                       // rows off the 16-byte grid: element access, element alignment
-    DIV_REQ(meant_aligned_elem(x, dtype) && meant_aligned_elem(y, dtype), "token_shift: element alignment");
-    int64_t nbe = ceil_div(B * (1 + frames * n) * ceil_div(d, 8), DIV_THREADS);
-    if (nbe > 8192) nbe = 8192;
-    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(token_shift_elem_kernel<T>, dim3((unsigned)nbe), dim3(DIV_THREADS), 0, (hipStream_t)stream, (const T*)x,
-                                                (T*)y, B, (int)frames, (int)n, (int)d, (int)(d / 3), transpose));
-    MEANT_LAUNCH_CHECK("token_shift");
-    meant_route_hit(ROUTE_ROWS_ELEM);
-    return MEANT_OK;
-  }
-  DIV_REQ(meant_aligned16(x) && meant_aligned16(y), "token_shift: 16-byte alignment");
-  const int64_t total = B * (1 + frames * n) * (d / 8);
-  int64_t nb = ceil_div(total, DIV_THREADS);
+  const bool vec = d % 8 == 0;                       // rows off the 16-byte grid: element access, element alignment
+  DIV_REQ(meant_aligned_rows(vec, x, dtype) && meant_aligned_rows(vec, y, dtype), "token_shift: %s alignment", vec ? "16-byte" : "element");
+  int64_t nb = ceil_div(B * (1 + frames * n) * ceil_div(d, 8), DIV_THREADS);
   if (nb > 8192) nb = 8192;
-  DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(token_shift_kernel<T>, dim3((unsigned)nb), dim3(DIV_THREADS), 0, (hipStream_t)stream, (const T*)x, (T*)y,
-                                              B, (int)frames, (int)n, (int)d, (int)(d / 3), transpose));
+  DISPATCH_DTYPE_VEC(dtype, vec, T, VEC, hipLaunchKernelGGL((token_shift_kernel<T, VEC>), dim3((unsigned)nb), dim3(DIV_THREADS), 0, (hipStream_t)stream,
+                                                            (const T*)x, (T*)y, B, (int)frames, (int)n, (int)d, (int)(d / 3), transpose));
   MEANT_LAUNCH_CHECK("token_shift");
+  if (!vec) meant_route_hit(ROUTE_ROWS_ELEM);
   return MEANT_OK;
 }
 
 extern "C" int meant_dropout(const void* x, void* y, int64_t n, float p, uint64_t seed, int dtype, void* stream) {
   DIV_REQ(x && y && n > 0 && p >= 0.f && p < 1.f, "dropout: bad argument (n > 0, 0 <= p < 1)");
-  if (n % 8) {                                       // a last, partial group of 8: 16-byte body + element tail, or all by element
-    DIV_REQ(meant_aligned_elem(x, dtype) && meant_aligned_elem(y, dtype), "dropout: element alignment");
-    const int vec = meant_aligned16(x) && meant_aligned16(y);
-    int64_t nbe = ceil_div(ceil_div(n, 8), DIV_THREADS);
-    if (nbe > 8192) nbe = 8192;
-    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(dropout_elem_kernel<T>, dim3((unsigned)nbe), dim3(DIV_THREADS), 0, (hipStream_t)stream, (const T*)x, (T*)y,
-                                                n, p, seed, vec));
-    MEANT_LAUNCH_CHECK("dropout");
-    meant_route_hit(ROUTE_ROWS_ELEM);
-    return MEANT_OK;
-  }
-  DIV_REQ(meant_aligned16(x) && meant_aligned16(y), "dropout: 16-byte alignment");
-  int64_t nb = ceil_div(n / 8, DIV_THREADS);
+  const bool vec = n % 8 == 0;                       // else a last, partial group of 8: 16-byte body + element tail, or all by element
+  DIV_REQ(meant_aligned_rows(vec, x, dtype) && meant_aligned_rows(vec, y, dtype), "dropout: %s alignment", vec ? "16-byte" : "element");
+  int64_t nb = ceil_div(ceil_div(n, 8), DIV_THREADS);
   if (nb > 8192) nb = 8192;
-  DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(dropout_kernel<T>, dim3((unsigned)nb), dim3(DIV_THREADS), 0, (hipStream_t)stream, (const T*)x, (T*)y, n / 8, p, seed));
+  DISPATCH_DTYPE_VEC(dtype, vec, T, VEC, hipLaunchKernelGGL((dropout_kernel<T, VEC>), dim3((unsigned)nb), dim3(DIV_THREADS), 0, (hipStream_t)stream,
+                                                            (const T*)x, (T*)y, vec ? n / 8 : n, p, seed));
   MEANT_LAUNCH_CHECK("dropout");
+  if (!vec) meant_route_hit(ROUTE_ROWS_ELEM);
   return MEANT_OK;
 }

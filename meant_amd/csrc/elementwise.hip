@@ -96,40 +96,23 @@ __global__ __launch_bounds__(EW_THREADS) void pad_copy2d_kernel(const TS* __rest
 }
 
 // ------------------------------------------------------------------------------------------------
-// y[r,:] = x[r,:] + v[r % period, :]
-template <typename T>
+// y[r,:] = x[r,:] + v[r % period, :].  The row kernels below have one body over load8n / store8n (common.h): VEC = 16-byte chunks of rows
+// that all start on 16 bytes, !VEC = the same chunks by guarded element access (widths off the 8-grid -- a model at text_dim + image_dim
+// = 150, a TimeSformer at an odd dim -- or unaligned bases), where nothing is touched at or beyond the last column of a row.
+template <typename T, bool VEC>
 __global__ __launch_bounds__(EW_THREADS) void add_rowvec_kernel(const T* __restrict__ x, const float* __restrict__ v,
                                                                  T* __restrict__ y, int64_t rows, int d, int64_t period) {
-  const int nch = d >> 3;
+  const int nch = chunks8<VEC>(d);
   const int64_t total = rows * nch;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t r = i / nch;
     const int ch = (int)(i - r * nch);
-    const Vec8<T> xv = load8<T>(x + r * d + ch * 8);
+    const Vec8<T> xv = load8n<VEC>(x + r * d + ch * 8, d - ch * 8);
     const float* vp = v + (r % period) * d + ch * 8;
     Vec8<T> o;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) o.set(k, xv.get(k) + vp[k]);
-    store8<T>(y + r * d + ch * 8, o);
-  }
-}
-// The same map by element access, for rows that are only element-aligned (d % 8 != 0: a model at text_dim + image_dim = 150) or an
-// unaligned base.  One thread = up to 8 consecutive columns of one row, each column guarded by c < d: neither x, v nor y is touched at
-// or beyond column d of a row.  The arithmetic of add_rowvec_kernel on the stored values.
-template <typename T>
-__global__ __launch_bounds__(EW_THREADS) void add_rowvec_elem_kernel(const T* __restrict__ x, const float* __restrict__ v,
-                                                                      T* __restrict__ y, int64_t rows, int d, int64_t period) {
-  const int nch = (d + 7) >> 3;
-  const int64_t total = rows * nch;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t r = i / nch;
-    const int c0 = (int)(i - r * nch) * 8;
-    const T* xp = x + r * d + c0;
-    const float* vp = v + (r % period) * d + c0;
-    T* yp = y + r * d + c0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-      if (c0 + k < d) yp[k] = from_f<T>(to_f(xp[k]) + vp[k]);
+    for (int k = 0; k < 8; ++k) o.set(k, xv.get(k) + param8<VEC>(vp, k, d - ch * 8));
+    store8n<VEC>(y + r * d + ch * 8, o, d - ch * 8);
   }
 }
 // dv[i][j] = sum over the rows r = i (mod period) of dy[r][j].  One workgroup = 64 consecutive (i, j) entries x 4 row groups (the
@@ -300,84 +283,48 @@ __global__ __launch_bounds__(EW_THREADS) void patchify_raw_kernel(const TI* __re
 
 // ------------------------------------------------------------------------------------------------
 // GEGLU (src/meant/timesformer_pytorch.py:60-63): h = [a | g] of width 2w per row -> y = a * gelu(g) of width w;
-// backward: dh = [dy * gelu(g) | dy * a * gelu'(g)].  One pass each, 16-byte accesses (w % 8 == 0; other widths: the element forms below).
-template <typename T>
+// backward: dh = [dy * gelu(g) | dy * a * gelu'(g)].  One pass each (!VEC: w % 8 != 0, w = 4 dim of a TimeSformer at an odd dim).
+template <typename T, bool VEC>
 __global__ __launch_bounds__(EW_THREADS) void geglu_fwd_kernel(const T* __restrict__ h, T* __restrict__ y, int64_t rows, int w) {
-  const int cw = w >> 3;
+  const int cw = chunks8<VEC>(w);
   const int64_t total = rows * cw;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t r = i / cw;
     const int c = (int)(i - r * cw) * 8;
-    const Vec8<T> a = load8s<T>(h + r * 2 * w + c), g = load8s<T>(h + r * 2 * w + w + c);
+    const Vec8<T> a = load8n<VEC, true>(h + r * 2 * w + c, w - c), g = load8n<VEC, true>(h + r * 2 * w + w + c, w - c);
     Vec8<T> o;
 #pragma unroll
     for (int k = 0; k < 8; ++k) o.set(k, a.get(k) * gelu_erf(g.get(k)));
-    store8s<T>(y + r * w + c, o);
+    store8n<VEC, true>(y + r * w + c, o, w - c);
   }
 }
-template <typename T>
+template <typename T, bool VEC>
 __global__ __launch_bounds__(EW_THREADS) void geglu_bwd_kernel(const T* __restrict__ h, const T* __restrict__ dy, T* __restrict__ dh,
                                                                 int64_t rows, int w) {
-  const int cw = w >> 3;
+  const int cw = chunks8<VEC>(w);
   const int64_t total = rows * cw;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t r = i / cw;
     const int c = (int)(i - r * cw) * 8;
-    const Vec8<T> a = load8s<T>(h + r * 2 * w + c), g = load8s<T>(h + r * 2 * w + w + c), d = load8s<T>(dy + r * w + c);
+    const Vec8<T> a = load8n<VEC, true>(h + r * 2 * w + c, w - c), g = load8n<VEC, true>(h + r * 2 * w + w + c, w - c),
+                  d = load8n<VEC, true>(dy + r * w + c, w - c);
     Vec8<T> da, dg;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       da.set(k, d.get(k) * gelu_erf(g.get(k)));
       dg.set(k, d.get(k) * a.get(k) * gelu_erf_grad(g.get(k)));
     }
-    store8s<T>(dh + r * 2 * w + c, da);
-    store8s<T>(dh + r * 2 * w + w + c, dg);
-  }
-}
-
-// The two by element access, for w % 8 != 0 (a TimeSformer at an odd dim: w = 4 dim, rows of h only element-aligned): a thread takes
-// up to 8 consecutive columns of one row, each guarded by c < w; the gelu / gelu' evaluation of the kernels above.
-template <typename T>
-__global__ __launch_bounds__(EW_THREADS) void geglu_fwd_elem_kernel(const T* __restrict__ h, T* __restrict__ y, int64_t rows, int w) {
-  const int cw = (w + 7) >> 3;
-  const int64_t total = rows * cw;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t r = i / cw;
-    const int c = (int)(i - r * cw) * 8;
-    const T* a = h + r * 2 * w + c;
-    const T* g = a + w;
-    T* o = y + r * w + c;
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-      if (c + k < w) o[k] = from_f<T>(to_f(a[k]) * gelu_erf(to_f(g[k])));
-  }
-}
-template <typename T>
-__global__ __launch_bounds__(EW_THREADS) void geglu_bwd_elem_kernel(const T* __restrict__ h, const T* __restrict__ dy, T* __restrict__ dh,
-                                                                     int64_t rows, int w) {
-  const int cw = (w + 7) >> 3;
-  const int64_t total = rows * cw;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t r = i / cw;
-    const int c = (int)(i - r * cw) * 8;
-    const T* a = h + r * 2 * w + c;
-    const T* g = a + w;
-    const T* d = dy + r * w + c;
-    T* da = dh + r * 2 * w + c;
-    T* dg = da + w;
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-      if (c + k < w) {
-        const float gk = to_f(g[k]), dk = to_f(d[k]);
-        da[k] = from_f<T>(dk * gelu_erf(gk));
-        dg[k] = from_f<T>(dk * to_f(a[k]) * gelu_erf_grad(gk));
-      }
+    store8n<VEC, true>(dh + r * 2 * w + c, da, w - c);
+    store8n<VEC, true>(dh + r * 2 * w + w + c, dg, w - c);
   }
 }
 
 // ------------------------------------------------------------------------------------------------
-// K8 mean over the sequence axis.  block = (g, 256-column slab): 32 chunks x 8 row groups.
-template <typename T, typename TO>
+// K8 mean over the sequence axis.  block = (g, 256-column slab): 32 chunks x 8 row groups; a row group sums its rows in ascending
+// order, the 8 row groups are combined in ascending order: no atomics, the same bits on every run and in both forms (!VEC: d, ld_out or
+// col_off off the 8-grid -- the concat of a model at text_dim = 100 writes the image means at col_off = 100 of rows of 150 -- or
+// unaligned bases; out / dout are then not touched outside [col_off, col_off + d) of a row).
+template <typename T, typename TO, bool VEC>
 __global__ __launch_bounds__(256) void meanpool_fwd_kernel(const T* __restrict__ x, TO* __restrict__ out, int64_t ld_out,
                                                             int64_t col_off, int S, int d) {
   __shared__ float red[8][32][9];
@@ -388,7 +335,7 @@ __global__ __launch_bounds__(256) void meanpool_fwd_kernel(const T* __restrict__
   if (chunk * 8 < d) {
     const T* base = x + g * (int64_t)S * d + chunk * 8;
     for (int s = rg; s < S; s += 8) {
-      const Vec8<T> v = load8<T>(base + (int64_t)s * d);
+      const Vec8<T> v = load8n<VEC>(base + (int64_t)s * d, d - chunk * 8);
 #pragma unroll
       for (int k = 0; k < 8; ++k) acc[k] += v.get(k);
     }
@@ -406,79 +353,27 @@ __global__ __launch_bounds__(256) void meanpool_fwd_kernel(const T* __restrict__
       for (int r = 0; r < 8; ++r) s += red[r][threadIdx.x][k];
       o.set(k, s * inv);
     }
-    store8<TO>(out + g * ld_out + col_off + chunk * 8, o);
+    // a whole chunk apart: with every store under its own test the compiler moves each sum behind its test and keeps all 64 partial
+    // sums in registers till then (67 VGPRs, an occupancy step)
+    if (VEC || d - chunk * 8 >= 8) store8n<VEC>(out + g * ld_out + col_off + chunk * 8, o, 8);
+    else store8n<VEC>(out + g * ld_out + col_off + chunk * 8, o, d - chunk * 8);
   }
 }
-template <typename T, typename TO>
+template <typename T, typename TO, bool VEC>
 __global__ __launch_bounds__(EW_THREADS) void meanpool_bwd_kernel(const TO* __restrict__ dout, int64_t ld_out, int64_t col_off,
                                                                    T* __restrict__ dx, int64_t G, int S, int d) {
-  const int nch = d >> 3;
+  const int nch = chunks8<VEC>(d);
   const int64_t total = G * S * (int64_t)nch;
   const float inv = 1.0f / (float)S;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int ch = (int)(i % nch);
     const int64_t gs = i / nch;
     const int64_t g = gs / S;
-    const Vec8<TO> v = load8<TO>(dout + g * ld_out + col_off + ch * 8);
+    const Vec8<TO> v = load8n<VEC>(dout + g * ld_out + col_off + ch * 8, d - ch * 8);
     Vec8<T> o;
 #pragma unroll
     for (int k = 0; k < 8; ++k) o.set(k, v.get(k) * inv);
-    store8<T>(dx + gs * d + ch * 8, o);
-  }
-}
-
-// The two pools by element access, for d, ld_out or col_off off the 8-grid (the concat of a model at text_dim = 100 writes the image
-// means at col_off = 100 of rows of 150) or unaligned bases.  The geometry and the order of every sum are those of the chunk kernels
-// above -- a thread owns up to 8 consecutive columns, a row group sums its rows in ascending order, the 8 row groups are combined in
-// ascending order: no atomics, the same bits on every run --, each column guarded by c < d: x / dx are not touched at or beyond
-// column d of a row, out / dout not outside [col_off, col_off + d) of a row.
-template <typename T, typename TO>
-__global__ __launch_bounds__(256) void meanpool_fwd_elem_kernel(const T* __restrict__ x, TO* __restrict__ out, int64_t ld_out,
-                                                                 int64_t col_off, int S, int d) {
-  __shared__ float red[8][32][9];
-  const int64_t g = blockIdx.x;
-  const int c0 = (blockIdx.y * 32 + (threadIdx.x & 31)) * 8;
-  const int rg = threadIdx.x >> 5;
-  float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (c0 < d) {
-    const T* base = x + g * (int64_t)S * d + c0;
-    for (int s = rg; s < S; s += 8) {
-      const T* xp = base + (int64_t)s * d;
-#pragma unroll
-      for (int k = 0; k < 8; ++k)
-        if (c0 + k < d) acc[k] += to_f(xp[k]);
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) red[rg][threadIdx.x & 31][k] = acc[k];
-  __syncthreads();
-  if (rg == 0 && c0 < d) {
-    const float inv = 1.0f / (float)S;
-    TO* op = out + g * ld_out + col_off + c0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      float s = 0.f;
-#pragma unroll
-      for (int r = 0; r < 8; ++r) s += red[r][threadIdx.x][k];
-      if (c0 + k < d) op[k] = from_f<TO>(s * inv);
-    }
-  }
-}
-template <typename T, typename TO>
-__global__ __launch_bounds__(EW_THREADS) void meanpool_bwd_elem_kernel(const TO* __restrict__ dout, int64_t ld_out, int64_t col_off,
-                                                                        T* __restrict__ dx, int64_t G, int S, int d) {
-  const int nch = (d + 7) >> 3;
-  const int64_t total = G * S * (int64_t)nch;
-  const float inv = 1.0f / (float)S;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int c0 = (int)(i % nch) * 8;
-    const int64_t gs = i / nch;
-    const int64_t g = gs / S;
-    const TO* sp = dout + g * ld_out + col_off + c0;
-    T* dp = dx + gs * d + c0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-      if (c0 + k < d) dp[k] = from_f<T>(to_f(sp[k]) * inv);
+    store8n<VEC>(dx + gs * d + ch * 8, o, d - ch * 8);
   }
 }
 
@@ -551,42 +446,32 @@ extern "C" int meant_add(const void* a, const void* b, void* y, int64_t n, int d
   return launch_ew2(a, b, y, n, dtype, stream, AddOp(), "add");
 }
 
+// grid of the GEGLU launches: the 16-byte form's has its own cap
+static dim3 geglu_grid(bool vec, int64_t rows, int64_t w) {
+  const int64_t nb = ceil_div(rows * (w >> 3), EW_THREADS);
+  return vec ? dim3((unsigned)(nb < 65535 * 8 ? nb : 65535 * 8)) : dim3(ew_blocks(rows * ceil_div(w, 8)));
+}
 extern "C" int meant_geglu_fwd(const void* h, void* y, int64_t rows, int64_t w, int dtype, void* stream) {
   EW_REQ(h && y && rows >= 0 && w > 0 && w < (1LL << 30), "geglu_fwd: bad argument");
-  if (w % 8) {                                       // rows off the 16-byte grid: element access, element alignment
-    EW_REQ(meant_aligned_elem(h, dtype) && meant_aligned_elem(y, dtype), "geglu_fwd: element alignment");
-    if (rows == 0) return MEANT_OK;
-    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(geglu_fwd_elem_kernel<T>, dim3(ew_blocks(rows * ceil_div(w, 8))), dim3(EW_THREADS), 0, (hipStream_t)stream,
-                                                (const T*)h, (T*)y, rows, (int)w));
-    MEANT_LAUNCH_CHECK("geglu_fwd");
-    meant_route_hit(ROUTE_ROWS_ELEM);
-    return MEANT_OK;
-  }
-  EW_REQ(meant_aligned16(h) && meant_aligned16(y), "geglu_fwd: 16-byte alignment");
+  const bool vec = w % 8 == 0;                       // rows off the 16-byte grid: element access, element alignment
+  EW_REQ(meant_aligned_rows(vec, h, dtype) && meant_aligned_rows(vec, y, dtype), "geglu_fwd: %s alignment", vec ? "16-byte" : "element");
   if (rows == 0) return MEANT_OK;
-  const int64_t total = rows * (w >> 3);
-  const dim3 grid((unsigned)(ceil_div(total, EW_THREADS) < 65535 * 8 ? ceil_div(total, EW_THREADS) : 65535 * 8)), block(EW_THREADS);
-  DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(geglu_fwd_kernel<T>, grid, block, 0, (hipStream_t)stream, (const T*)h, (T*)y, rows, (int)w));
+  DISPATCH_DTYPE_VEC(dtype, vec, T, VEC, hipLaunchKernelGGL((geglu_fwd_kernel<T, VEC>), geglu_grid(vec, rows, w), dim3(EW_THREADS), 0, (hipStream_t)stream,
+                                                            (const T*)h, (T*)y, rows, (int)w));
   MEANT_LAUNCH_CHECK("geglu_fwd");
+  if (!vec) meant_route_hit(ROUTE_ROWS_ELEM);
   return MEANT_OK;
 }
 extern "C" int meant_geglu_bwd(const void* h, const void* dy, void* dh, int64_t rows, int64_t w, int dtype, void* stream) {
   EW_REQ(h && dy && dh && rows >= 0 && w > 0 && w < (1LL << 30), "geglu_bwd: bad argument");
-  if (w % 8) {
-    EW_REQ(meant_aligned_elem(h, dtype) && meant_aligned_elem(dy, dtype) && meant_aligned_elem(dh, dtype), "geglu_bwd: element alignment");
-    if (rows == 0) return MEANT_OK;
-    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(geglu_bwd_elem_kernel<T>, dim3(ew_blocks(rows * ceil_div(w, 8))), dim3(EW_THREADS), 0, (hipStream_t)stream,
-                                                (const T*)h, (const T*)dy, (T*)dh, rows, (int)w));
-    MEANT_LAUNCH_CHECK("geglu_bwd");
-    meant_route_hit(ROUTE_ROWS_ELEM);
-    return MEANT_OK;
-  }
-  EW_REQ(meant_aligned16(h) && meant_aligned16(dy) && meant_aligned16(dh), "geglu_bwd: 16-byte alignment");
+  const bool vec = w % 8 == 0;
+  EW_REQ(meant_aligned_rows(vec, h, dtype) && meant_aligned_rows(vec, dy, dtype) && meant_aligned_rows(vec, dh, dtype), "geglu_bwd: %s alignment",
+         vec ? "16-byte" : "element");
   if (rows == 0) return MEANT_OK;
-  const int64_t total = rows * (w >> 3);
-  const dim3 grid((unsigned)(ceil_div(total, EW_THREADS) < 65535 * 8 ? ceil_div(total, EW_THREADS) : 65535 * 8)), block(EW_THREADS);
-  DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(geglu_bwd_kernel<T>, grid, block, 0, (hipStream_t)stream, (const T*)h, (const T*)dy, (T*)dh, rows, (int)w));
+  DISPATCH_DTYPE_VEC(dtype, vec, T, VEC, hipLaunchKernelGGL((geglu_bwd_kernel<T, VEC>), geglu_grid(vec, rows, w), dim3(EW_THREADS), 0, (hipStream_t)stream,
+                                                            (const T*)h, (const T*)dy, (T*)dh, rows, (int)w));
   MEANT_LAUNCH_CHECK("geglu_bwd");
+  if (!vec) meant_route_hit(ROUTE_ROWS_ELEM);
   return MEANT_OK;
 }
 
@@ -642,15 +527,9 @@ extern "C" int meant_pad_copy2d(const void* src, int64_t ld_src, int64_t cols_sr
 // 16-byte chunks where every row starts on one (d % 8 == 0, aligned bases); element by element otherwise
 extern "C" int meant_add_rowvec(const void* x, const float* v, void* y, int64_t rows, int64_t d, int64_t period, int dtype, void* stream) {
   EW_REQ(x && v && y && rows > 0 && d > 0 && d < (1LL << 30) && period > 0, "add_rowvec: bad argument");
-  if (d % 8 == 0 && meant_aligned16(x) && meant_aligned16(y)) {
-    DISPATCH_DTYPE(dtype, T,
-                   hipLaunchKernelGGL(add_rowvec_kernel<T>, dim3(ew_blocks(rows * (d / 8))), dim3(EW_THREADS), 0, (hipStream_t)stream,
-                                      (const T*)x, v, (T*)y, rows, (int)d, period));
-  } else {
-    DISPATCH_DTYPE(dtype, T,
-                   hipLaunchKernelGGL(add_rowvec_elem_kernel<T>, dim3(ew_blocks(rows * ceil_div(d, 8))), dim3(EW_THREADS), 0, (hipStream_t)stream,
-                                      (const T*)x, v, (T*)y, rows, (int)d, period));
-  }
+  const bool vec = d % 8 == 0 && meant_aligned16(x) && meant_aligned16(y);
+  DISPATCH_DTYPE_VEC(dtype, vec, T, VEC, hipLaunchKernelGGL((add_rowvec_kernel<T, VEC>), dim3(ew_blocks(rows * ceil_div(d, 8))), dim3(EW_THREADS), 0,
+                                                            (hipStream_t)stream, (const T*)x, v, (T*)y, rows, (int)d, period));
   MEANT_LAUNCH_CHECK("add_rowvec");
   return MEANT_OK;
 }
@@ -736,7 +615,7 @@ extern "C" int meant_patchify(const void* images, int images_dtype, void* patche
   return MEANT_OK;
 }
 
-// the chunk kernels for the shapes they have always taken (d, ld_out and col_off multiples of 8, aligned bases); the element forms otherwise
+// the 16-byte form for the shapes it has always taken (d, ld_out and col_off multiples of 8, aligned bases); the element form otherwise
 static bool meanpool_chunks(const void* x, const void* out, int64_t ld_out, int64_t col_off, int64_t d) {
   return d % 8 == 0 && ld_out % 8 == 0 && col_off % 8 == 0 && meant_aligned16(x) && meant_aligned16(out);
 }
@@ -746,15 +625,15 @@ extern "C" int meant_meanpool_fwd(const void* x, void* out, int64_t ld_out, int6
   EW_REQ(G < 2147483647LL && S < 2147483647LL && d < (1LL << 30), "meanpool_fwd: too many groups, rows or columns");
   const dim3 grid((unsigned)G, (unsigned)ceil_div(d, 256)), block(256);
   hipStream_t st = (hipStream_t)stream;
-#define POOL_FWD(KERNEL)                                                                                                                            \
+#define POOL_FWD(VEC)                                                                                                                               \
   do {                                                                                                                                              \
-    if (dtype == MEANT_F32 && out_dtype == MEANT_F32) hipLaunchKernelGGL((KERNEL<float, float>), grid, block, 0, st, (const float*)x, (float*)out, ld_out, col_off, (int)S, (int)d); \
-    else if (dtype == MEANT_BF16 && out_dtype == MEANT_F32) hipLaunchKernelGGL((KERNEL<bf16, float>), grid, block, 0, st, (const bf16*)x, (float*)out, ld_out, col_off, (int)S, (int)d); \
-    else if (dtype == MEANT_BF16 && out_dtype == MEANT_BF16) hipLaunchKernelGGL((KERNEL<bf16, bf16>), grid, block, 0, st, (const bf16*)x, (bf16*)out, ld_out, col_off, (int)S, (int)d); \
+    if (dtype == MEANT_F32 && out_dtype == MEANT_F32) hipLaunchKernelGGL((meanpool_fwd_kernel<float, float, VEC>), grid, block, 0, st, (const float*)x, (float*)out, ld_out, col_off, (int)S, (int)d); \
+    else if (dtype == MEANT_BF16 && out_dtype == MEANT_F32) hipLaunchKernelGGL((meanpool_fwd_kernel<bf16, float, VEC>), grid, block, 0, st, (const bf16*)x, (float*)out, ld_out, col_off, (int)S, (int)d); \
+    else if (dtype == MEANT_BF16 && out_dtype == MEANT_BF16) hipLaunchKernelGGL((meanpool_fwd_kernel<bf16, bf16, VEC>), grid, block, 0, st, (const bf16*)x, (bf16*)out, ld_out, col_off, (int)S, (int)d); \
     else { meant_set_error("meanpool_fwd: unsupported dtype combination"); return MEANT_ERR_UNSUPPORTED; }                                        \
   } while (0)
-  if (meanpool_chunks(x, out, ld_out, col_off, d)) POOL_FWD(meanpool_fwd_kernel);
-  else POOL_FWD(meanpool_fwd_elem_kernel);
+  if (meanpool_chunks(x, out, ld_out, col_off, d)) POOL_FWD(true);
+  else POOL_FWD(false);
 #undef POOL_FWD
   MEANT_LAUNCH_CHECK("meanpool_fwd");
   return MEANT_OK;
@@ -764,15 +643,15 @@ extern "C" int meant_meanpool_bwd(const void* dout, int64_t ld_out, int64_t col_
   EW_REQ(S < 2147483647LL && d < (1LL << 30), "meanpool_bwd: too many rows or columns");
   const dim3 grid(ew_blocks(G * S * ceil_div(d, 8))), block(EW_THREADS);
   hipStream_t st = (hipStream_t)stream;
-#define POOL_BWD(KERNEL)                                                                                                                            \
+#define POOL_BWD(VEC)                                                                                                                               \
   do {                                                                                                                                              \
-    if (dtype == MEANT_F32 && out_dtype == MEANT_F32) hipLaunchKernelGGL((KERNEL<float, float>), grid, block, 0, st, (const float*)dout, ld_out, col_off, (float*)dx, G, (int)S, (int)d); \
-    else if (dtype == MEANT_BF16 && out_dtype == MEANT_F32) hipLaunchKernelGGL((KERNEL<bf16, float>), grid, block, 0, st, (const float*)dout, ld_out, col_off, (bf16*)dx, G, (int)S, (int)d); \
-    else if (dtype == MEANT_BF16 && out_dtype == MEANT_BF16) hipLaunchKernelGGL((KERNEL<bf16, bf16>), grid, block, 0, st, (const bf16*)dout, ld_out, col_off, (bf16*)dx, G, (int)S, (int)d); \
+    if (dtype == MEANT_F32 && out_dtype == MEANT_F32) hipLaunchKernelGGL((meanpool_bwd_kernel<float, float, VEC>), grid, block, 0, st, (const float*)dout, ld_out, col_off, (float*)dx, G, (int)S, (int)d); \
+    else if (dtype == MEANT_BF16 && out_dtype == MEANT_F32) hipLaunchKernelGGL((meanpool_bwd_kernel<bf16, float, VEC>), grid, block, 0, st, (const float*)dout, ld_out, col_off, (bf16*)dx, G, (int)S, (int)d); \
+    else if (dtype == MEANT_BF16 && out_dtype == MEANT_BF16) hipLaunchKernelGGL((meanpool_bwd_kernel<bf16, bf16, VEC>), grid, block, 0, st, (const bf16*)dout, ld_out, col_off, (bf16*)dx, G, (int)S, (int)d); \
     else { meant_set_error("meanpool_bwd: unsupported dtype combination"); return MEANT_ERR_UNSUPPORTED; }                                        \
   } while (0)
-  if (meanpool_chunks(dout, dx, ld_out, col_off, d)) POOL_BWD(meanpool_bwd_kernel);
-  else POOL_BWD(meanpool_bwd_elem_kernel);
+  if (meanpool_chunks(dout, dx, ld_out, col_off, d)) POOL_BWD(true);
+  else POOL_BWD(false);
 #undef POOL_BWD
   MEANT_LAUNCH_CHECK("meanpool_bwd");
   return MEANT_OK;

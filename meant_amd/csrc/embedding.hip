@@ -197,35 +197,25 @@ size_t seg_part_bytes(int64_t n, int64_t d) { return (size_t)ceil_div(n, SEG) * 
 
 // ------------------------------------------------------------------------------------------------
 // embedding gather (one wave per token row) and scatter-add of its gradient (f32 atomics)
-template <typename T>
+// a lane moves one 8-column chunk (VEC) or, at d % 8 != 0 (rows of the table and of `out` are then only element-aligned), one column: a
+// chunk of which one element is real, so a wave's lanes walk consecutive columns of its row
+template <typename T, bool VEC>
 __global__ __launch_bounds__(256) void embedding_fwd_kernel(const float* __restrict__ table, const int64_t* __restrict__ ids,
                                                              T* __restrict__ out, int64_t n, int d, int64_t V) {
+  constexpr int PER = VEC ? 8 : 1;                     // columns per lane
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int nch = d >> 3;
+  const int nch = VEC ? d >> 3 : d;
   for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < n; r += (int64_t)gridDim.x * 4) {
     int64_t id = ids[r];
     id = id < 0 ? 0 : (id >= V ? V - 1 : id);
     const float* src = table + id * d;
     for (int ch = lane; ch < nch; ch += 64) {
-      const Vec8<float> v = load8<float>(src + ch * 8);
+      const Vec8<float> v = load8n<VEC>(src + ch * PER, 1);
       Vec8<T> o;
 #pragma unroll
       for (int k = 0; k < 8; ++k) o.set(k, v.get(k));
-      store8s<T>(out + r * d + ch * 8, o);
+      store8n<VEC, true>(out + r * d + ch * PER, o, 1);
     }
-  }
-}
-// the same gather element by element, for d % 8 != 0 (rows of the table and of `out` are then only element-aligned): a wave's lanes walk
-// consecutive columns e < d of its row
-template <typename T>
-__global__ __launch_bounds__(256) void embedding_fwd_elem_kernel(const float* __restrict__ table, const int64_t* __restrict__ ids,
-                                                                  T* __restrict__ out, int64_t n, int d, int64_t V) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < n; r += (int64_t)gridDim.x * 4) {
-    int64_t id = ids[r];
-    id = id < 0 ? 0 : (id >= V ? V - 1 : id);
-    const float* src = table + id * d;
-    for (int e = lane; e < d; e += 64) out[r * d + e] = from_f<T>(src[e]);
   }
 }
 template <typename T>
@@ -393,13 +383,8 @@ extern "C" int meant_embedding_bwd_seg(const void* dout, const int64_t* sorted_i
 extern "C" int meant_embedding_fwd(const float* table, const int64_t* ids, void* out, int64_t n, int64_t d, int64_t V, int dtype, void* stream) {
   EMB_REQ(table && ids && out && n > 0 && d > 0 && d < (1ll << 30) && V > 0, "embedding_fwd: bad argument");
   int64_t nb = ceil_div(n, 4); if (nb > 8192) nb = 8192;
-  if (d % 8 == 0) {
-    DISPATCH_DTYPE(dtype, T,
-                   hipLaunchKernelGGL(embedding_fwd_kernel<T>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, table, ids, (T*)out, n, (int)d, V));
-  } else {
-    DISPATCH_DTYPE(dtype, T,
-                   hipLaunchKernelGGL(embedding_fwd_elem_kernel<T>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, table, ids, (T*)out, n, (int)d, V));
-  }
+  DISPATCH_DTYPE_VEC(dtype, d % 8 == 0, T, VEC, hipLaunchKernelGGL((embedding_fwd_kernel<T, VEC>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream,
+                                                                   table, ids, (T*)out, n, (int)d, V));
   MEANT_LAUNCH_CHECK("embedding_fwd");
   return MEANT_OK;
 }

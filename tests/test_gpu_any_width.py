@@ -374,6 +374,162 @@ def test_aligned_shapes_keep_the_chunk_kernels_bits(dev, dt, dto):
     assert ((res[0][0][:, off:].double() - want).abs() <= (S + 2) * U32 * x.double().abs().amax(dim=1) + _u(dto) * want.abs()).all()
 
 
+def _sentinel_rows(rows, d, dtype, dev, shift=0):
+    """a SENTINEL-filled buffer of rows + 2 rows of d (+ shift elements in front) and its inner rows: the slice a kernel writes"""
+    buf = torch.full((shift + (rows + 2) * d,), SENTINEL, device=dev, dtype=dtype)
+    assert buf.data_ptr() % 16 == 0
+    return buf, buf[shift + d:shift + (rows + 1) * d].view(rows, d)
+
+
+def _sentinels_intact(buf, rows, d, shift=0):
+    got = buf.cpu()
+    return bool((got[:shift + d] == SENTINEL).all() and (got[shift + (rows + 1) * d:] == SENTINEL).all())
+
+
+def _rel64(a, b):
+    """max-abs error against the float64 reference b over b's largest magnitude (tests/test_gpu_timesformer_any.py::_rel)"""
+    return (a.double().cpu() - b).abs().max().item() / max(b.abs().max().item(), 1e-30)
+
+
+GUARD_WIDTHS = (9, 15, 17)      # one element past a chunk of 8, one short of two chunks, one past two: where a wrong guard shows
+GUARD_OPS = {"gather_rows": 1, "token_shift": 2, "geglu_fwd": 1, "geglu_bwd": 1, "dropout": 1, "add_rowvec": 0, "embedding_fwd": 0}
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("op", list(GUARD_OPS))
+def test_row_ops_write_their_slice_only(dev, dtype, op):
+    """the row-wise entries at widths 9, 15 and 17 (dropout: lengths), three rows (token_shift: two videos of 2 frames x 2 tokens): the
+    output is the inside of a buffer with a sentinel row in front and one behind, the inputs lie in NaN pools.  The slice against
+    torch at the op's tolerance elsewhere in the suite (tests/test_gpu_timesformer_any.py; add_rowvec: above; the embedding lookup is
+    one rounding of an fp32 value: exact in fp32, within u16 |value| in bf16), bit for bit where the op only moves data; every
+    sentinel intact; "rows_elem" counted once per launch by the entries that count it.  add_rowvec also at width 16 from bases one
+    element past a 16-byte boundary, where the alignment alone sends it to the element form (the pools there: the next test); dropout
+    both into an unaligned slice (every group by element) and from 16-byte aligned bases (16-byte groups and an element tail)."""
+    from meant_amd import _lib
+    lib, code, rs = _lib.lib, _code(dtype), np.random.RandomState(len(op))
+    u = _u(dtype)
+
+    def rnd(*shape, dt=dtype, lead=64):
+        v = t(rs.standard_normal(shape).astype("float32")).to(dt)
+        return v, _in_nan_pool(v, dt, dev, lead=lead)[1]
+
+    for d in GUARD_WIDTHS + ((16,) if op == "add_rowvec" else ()):
+        shift = 1 if d == 16 else 0
+        rows = 10 if op == "token_shift" else (1 if op == "dropout" else 3)
+        buf, out = _sentinel_rows(rows, 2 * d if op == "geglu_bwd" else d, dtype, dev, shift)
+        hits = _lib.route_count("rows_elem")
+        if op == "gather_rows":
+            (src, src_d), (fill, fill_d) = rnd(4, d), rnd(d)
+            idx = torch.tensor([2, -2, -1], dtype=torch.int32, device=dev)
+            _lib.check(lib.meant_gather_rows(src_d.data_ptr(), idx.data_ptr(), fill_d.data_ptr(), out.data_ptr(), 3, d, code, _st()), op)
+            assert torch.equal(out.cpu(), torch.stack((src[2], fill, torch.zeros(d, dtype=dtype)))), d
+        elif op == "token_shift":
+            from oracle import meant_oracle as O
+            (x, x_d), (yb, yb_d) = rnd(2, 5, d), rnd(2, 5, d)
+            xr = x.float().requires_grad_(True)
+            ref = O._TSPreTokenShift(2, lambda y: y)(xr)
+            ref.backward(yb.float())
+            _lib.check(lib.meant_token_shift(x_d.data_ptr(), out.data_ptr(), 2, 2, 2, d, 0, code, _st()), op)
+            assert torch.equal(out.cpu().view(2, 5, d), ref.detach().to(dtype)), d
+            assert _sentinels_intact(buf, rows, d), d
+            _lib.check(lib.meant_token_shift(yb_d.data_ptr(), out.data_ptr(), 2, 2, 2, d, 1, code, _st()), op)
+            assert torch.equal(out.cpu().view(2, 5, d), xr.grad.to(dtype)), d
+        elif op in ("geglu_fwd", "geglu_bwd"):
+            (h, h_d), (dy, dy_d) = rnd(3, 2 * d), rnd(3, d)
+            hr = h.double().requires_grad_(True)
+            a, g = hr.chunk(2, dim=-1)
+            yr = a * torch.nn.functional.gelu(g)
+            yr.backward(dy.double())
+            if op == "geglu_fwd":
+                _lib.check(lib.meant_geglu_fwd(h_d.data_ptr(), out.data_ptr(), 3, d, code, _st()), op)
+                assert _rel64(out, yr.detach()) <= (2e-5 if dtype == torch.float32 else 8e-3), d
+            else:
+                _lib.check(lib.meant_geglu_bwd(h_d.data_ptr(), dy_d.data_ptr(), out.data_ptr(), 3, d, code, _st()), op)
+                assert _rel64(out, hr.grad) <= (2e-5 if dtype == torch.float32 else 1e-2), d
+        elif op == "dropout":                                # keep_scale8's rule: element i takes part i & 7 of the draw for i >> 3, so the
+            x = t(rs.standard_normal(24).astype("float32"))  # 16-byte kernel on 24 elements gives the first d of them the same mask
+            x[x.abs() < 0.1] = 0.5
+            x = x.to(dtype)
+            x24, y24 = x.to(dev), torch.empty(24, device=dev, dtype=dtype)
+            _, x_d = _in_nan_pool(x[:d], dtype, dev)
+            _lib.check(lib.meant_dropout(x_d.data_ptr(), out.data_ptr(), d, 0.25, 1234, code, _st()), op)
+            assert _lib.route_count("rows_elem") == hits + 1, d
+            _lib.check(lib.meant_dropout(x24.data_ptr(), y24.data_ptr(), 24, 0.25, 1234, code, _st()), op)
+            got = out.cpu().view(-1)
+            assert torch.equal(got, y24.cpu()[:d]), d
+            kept = (x[:d].float() * torch.tensor(65536.0 / (65536.0 - 16384.0))).to(dtype)
+            assert torch.all((got == 0) | (got == kept)), d
+            # the route a model takes: both bases on 16 bytes, so 16-byte groups and an element tail (above, `out` starts d elements
+            # into its buffer: off 16 bytes at these d, every group by element)
+            buf16 = torch.full((16 + d + 16,), SENTINEL, device=dev, dtype=dtype)
+            out16 = buf16[16:16 + d]
+            assert x_d.data_ptr() % 16 == 0 and out16.data_ptr() % 16 == 0 and out.data_ptr() % 16 != 0
+            _lib.check(lib.meant_dropout(x_d.data_ptr(), out16.data_ptr(), d, 0.25, 1234, code, _st()), op)
+            assert _lib.route_count("rows_elem") == hits + 2, d
+            got16 = buf16.cpu()
+            assert torch.equal(got16[16:16 + d], got) and (got16[:16] == SENTINEL).all() and (got16[16 + d:] == SENTINEL).all(), d
+            hits += 1
+        elif op == "add_rowvec":
+            (x, x_d), (v, v_d) = rnd(3, d, lead=64 + shift), rnd(3, d, dt=torch.float32)
+            assert d != 16 or (x_d.data_ptr() % 16 != 0 and out.data_ptr() % 16 != 0)
+            _lib.check(lib.meant_add_rowvec(x_d.data_ptr(), v_d.data_ptr(), out.data_ptr(), 3, d, 3, code, _st()), op)
+            want = x.double() + v.double()
+            assert ((out.cpu().double() - want).abs() <= (u + U32) * want.abs() + 1e-30).all(), d
+        else:
+            table, table_d = rnd(5, d, dt=torch.float32)
+            ids = torch.tensor([4, -3, 7], device=dev)       # clamped to [0, V)
+            _lib.check(lib.meant_embedding_fwd(table_d.data_ptr(), ids.data_ptr(), out.data_ptr(), 3, d, 5, code, _st()), op)
+            want = table[[4, 0, 4]]
+            if dtype == torch.float32:
+                assert torch.equal(out.cpu(), want), d
+            else:
+                assert ((out.cpu().double() - want.double()).abs() <= U16 * want.double().abs()).all(), d
+        torch.cuda.synchronize()
+        assert _sentinels_intact(buf, rows, out.shape[1], shift), (op, d)
+        assert torch.isfinite(out.float()).all(), (op, d)
+        assert _lib.route_count("rows_elem") == hits + GUARD_OPS[op], (op, d)
+
+
+@pytest.mark.parametrize("dt,dto", POOL_DTYPES, ids=["f32_f32", "bf16_f32", "bf16_bf16"])
+def test_meanpool_width_16_from_bases_one_element_off(dev, dt, dto):
+    """d = 16 at col_off = 8 of rows of ld = 32 -- every width on the 8-grid -- with x, out, dout and dx one element past a 16-byte
+    boundary: the alignment alone sends both pools to the element form, where every chunk is a whole one.  Sentinels in front of,
+    behind and around the written slice (dout: NaN there), x in a NaN pool; the tolerances of test_meanpool_any_width; neither
+    entry counts under "rows_elem"."""
+    from meant_amd import _lib
+    rs = np.random.RandomState(16)
+    G, S, d, off, ld = 3, 5, 16, 8, 32
+    x = t(rs.standard_normal((G, S, d)).astype("float32")).to(dt)
+    _, xh = _in_nan_pool(x, dt, dev, lead=65)
+    obuf = torch.full((1 + (G + 2) * ld,), SENTINEL, device=dev, dtype=dto)
+    out = obuf[1 + ld:1 + (G + 1) * ld].view(G, ld)
+    assert xh.data_ptr() % 16 != 0 and out.data_ptr() % 16 != 0 and obuf.data_ptr() % 16 == 0
+    hits = _lib.route_count("rows_elem")
+    _lib.check(_lib.lib.meant_meanpool_fwd(xh.data_ptr(), out.data_ptr(), ld, off, G, S, d, _code(dt), _code(dto), _st()), "meanpool_fwd")
+    got = obuf.cpu()
+    inside = torch.zeros(1 + (G + 2) * ld, dtype=torch.bool)
+    inside[1 + ld:1 + (G + 1) * ld].view(G, ld)[:, off:off + d] = True
+    assert (got[~inside] == SENTINEL).all()
+    want = x.double().mean(dim=1)
+    res = got[inside].view(G, d).double()
+    bound = (S + 2) * U32 * x.double().abs().amax(dim=1) + _u(dto) * want.abs() + 1e-30
+    assert torch.isfinite(res).all() and ((res - want).abs() <= bound).all(), (res - want).abs().max().item()
+
+    dout = torch.full((G, ld), float("nan"), dtype=torch.float32)
+    dout[:, off:off + d] = t(rs.standard_normal((G, d)).astype("float32"))
+    _, dh = _in_nan_pool(dout, dto, dev, lead=65)
+    dbuf = torch.full((1 + (G + 2) * S * d,), SENTINEL, device=dev, dtype=dt)
+    dx = dbuf[1 + S * d:1 + (G + 1) * S * d].view(G, S, d)
+    assert dh.data_ptr() % 16 != 0 and dx.data_ptr() % 16 != 0
+    _lib.check(_lib.lib.meant_meanpool_bwd(dh.data_ptr(), ld, off, dx.data_ptr(), G, S, d, _code(dt), _code(dto), _st()), "meanpool_bwd")
+    got = dbuf.cpu()
+    assert (got[:1 + S * d] == SENTINEL).all() and (got[1 + (G + 1) * S * d:] == SENTINEL).all()
+    want = (dh.cpu().double()[:, off:off + d] / S)[:, None, :].expand(G, S, d)
+    res = got[1 + S * d:1 + (G + 1) * S * d].view(G, S, d).double()
+    assert torch.isfinite(res).all() and ((res - want).abs() <= (2 * U32 + _u(dt)) * want.abs() + 1e-30).all()
+    assert _lib.route_count("rows_elem") == hits
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # 4. ops.linear, bf16, output widths off the grid
 def _rand(rs, *shape, scale=1.0):

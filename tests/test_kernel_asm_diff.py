@@ -85,3 +85,30 @@ def test_an_extra_kernel_is_reported():
     new = tool.split_kernels(_kernel("_Z3fooPf", 1, A) + _kernel("_Z3bazPf", 0, B))
     assert tool.diff_kernels(old, new) == ([], ["_Z3bazPf"], [])
     assert tool.diff_kernels(new, old) == (["_Z3bazPf"], [], [])
+
+
+def _template_kernel(name, ordinal, body):
+    """a kernel as a template instantiation is listed: the body returns to its own section, named after the symbol, behind the descriptor"""
+    text = _kernel(name, ordinal, body)
+    own = f'\t.section\t.text.{name},"axG",@progbits,{name},comdat\n'
+    return own + text.replace("\t.text\n", own)
+
+
+def test_a_renamed_kernel_with_the_same_code_is_paired():
+    """foo<float> becomes foo<float, true> with the same instructions; bar<float> becomes bar<float, true> with another instruction
+    and is not paired; nothing is paired with a kernel that exists on both sides"""
+    tool = _tool()
+    old = tool.split_kernels(_template_kernel("_Z3fooIfEvPT_", 0, A) + _template_kernel("_Z3barIfEvPT_", 1, B) + _kernel("_Z3bazPf", 2, A))
+    new = tool.split_kernels(_template_kernel("_Z3barIfLb1EEvPT_", 3, B.replace("v6", "v7")) + _kernel("_Z3bazPf", 4, A)
+                             + _template_kernel("_Z3fooIfLb1EEvPT_", 5, A))
+    assert any("_Z3fooIfEvPT_" in line for line in old["_Z3fooIfEvPT_"][0]), "the body names its own symbol"
+    only_old, only_new, differ = tool.diff_kernels(old, new)
+    assert (only_old, only_new, differ) == (["_Z3barIfEvPT_", "_Z3fooIfEvPT_"], ["_Z3barIfLb1EEvPT_", "_Z3fooIfLb1EEvPT_"], [])
+    assert tool.pair_renamed(old, new, only_old, only_new) == [("_Z3fooIfEvPT_", "_Z3fooIfLb1EEvPT_")]
+
+
+def test_a_rename_with_a_changed_descriptor_is_not_paired():
+    tool = _tool()
+    old = tool.split_kernels(_template_kernel("_Z3fooIfEvPT_", 0, A))
+    new = tool.split_kernels(_template_kernel("_Z3fooIfLb1EEvPT_", 0, A).replace(".amdhsa_next_free_vgpr 12", ".amdhsa_next_free_vgpr 13"))
+    assert tool.pair_renamed(old, new, *tool.diff_kernels(old, new)[:2]) == []

@@ -7,7 +7,9 @@ function ordinal in local labels is normalised.
     tools/kernel_asm_diff.py OLD_TREE NEW_TREE [-j JOBS]
 
 Prints the kernels only in OLD, only in NEW, and the ones that differ; exit status 1 if any list is non-empty.  A host-side
-refactor must leave all three lists empty.  The comparison is textual: no instruction is looked for or interpreted."""
+refactor must leave all three lists empty.  A kernel only in OLD and one only in NEW whose text and descriptor are equal once each
+kernel's own symbol is replaced by a placeholder (a kernel that gained a template argument keeps its code under a new mangled name)
+are listed as "renamed, same code" instead and do not count.  The comparison is textual: no instruction is looked for or interpreted."""
 import argparse
 import concurrent.futures
 import glob
@@ -81,6 +83,22 @@ def diff_kernels(old, new):
     return only_old, only_new, differ
 
 
+def pair_renamed(old, new, only_old, only_new):
+    """[(old symbol, new symbol)]: kernels of the two one-sided lists whose code is equal apart from their own symbol (which the
+    body names in its `.section .text.<symbol>` line and the descriptor in its operands); equal candidates pair in sorted order"""
+    def anonymous(name, entry):
+        return tuple(tuple(line.replace(name, "<self>") for line in part) for part in entry)
+    by_code = {}
+    for n in only_new:
+        by_code.setdefault(anonymous(n, new[n]), []).append(n)
+    pairs = []
+    for o in only_old:
+        same = by_code.get(anonymous(o, old[o]))
+        if same:
+            pairs.append((o, same.pop(0)))
+    return pairs
+
+
 def first_difference(a, b):
     """the first differing line pair of two (body, descriptor) entries, for the report"""
     for part, (x, y) in zip(("text", "descriptor"), zip(a, b)):
@@ -122,6 +140,12 @@ def main():
             sides.append(kernels)
     old, new = sides
     only_old, only_new, differ = diff_kernels(old, new)
+    renamed = pair_renamed(old, new, only_old, only_new)
+    only_old = [n for n in only_old if n not in {o for o, _ in renamed}]
+    only_new = [n for n in only_new if n not in {c for _, c in renamed}]
+    print(f"renamed, same code: {len(renamed)}")
+    for o, c in renamed:
+        print(f"  {o} -> {c}")
     for title, names in (("only in old", only_old), ("only in new", only_new)):
         print(f"{title}: {len(names)}")
         for n in names:
@@ -129,7 +153,8 @@ def main():
     print(f"differ: {len(differ)}")
     for n in differ:
         print(f"  {n}: {first_difference(old[n], new[n])}")
-    print(f"kernel_asm_diff: {len(old)} kernels old, {len(new)} new, {len(only_old)} only old, {len(only_new)} only new, {len(differ)} differ")
+    print(f"kernel_asm_diff: {len(old)} kernels old, {len(new)} new, {len(renamed)} renamed with the same code, {len(only_old)} only old, "
+          f"{len(only_new)} only new, {len(differ)} differ")
     return 1 if (only_old or only_new or differ) else 0
 
 

@@ -8,6 +8,9 @@ every C ABI call and a sha256 of every result.  Run it on two checkouts that sha
     python tools/step_digest.py --out this
     python tools/step_digest.py --compare parent_a parent_b this
 
+(A change to the kernels alone is the other way round: one checkout, MEANT_LIB_PATH set to the parent's library for parent_a and parent_b
+and to this tree's for the third run.)
+
 Writes OUT.trace (one line per library call: name, every non-pointer argument, null / ptr for the pointers) and OUT.digests (per case:
 sha256 of the output, of the input gradient, of every parameter gradient in named_parameters() order, and the peak of allocated bytes).
 Library option `deterministic` is on and every case starts from the same torch.manual_seed."""
@@ -152,6 +155,72 @@ def cases(M, ops, _lib, dev):
 
     for dtype in (F32, BF):
         yield f"divided_attention-{tier[dtype]}", divided(dtype)
+
+    def timesformer_odd(dim, heads, dim_head, dtype):     # layers at a width off the 8-grid: gather_rows, token_shift, geglu and dropout
+        def run():                                        # by element access (tests/test_gpu_timesformer_any.py, the "dim99" / "dim100" shapes)
+            m = M.TimeSformer(dim=dim, heads=heads, dim_head=dim_head, num_frames=3, image_size=32, patch_size=16, depth=1, num_classes=3,
+                              channels=3, shift_tokens=True, attn_dropout=0.1, ff_dropout=0.1).to(dev).train()
+            m.compute_dtype = dtype
+            video = torch.from_numpy(np.random.RandomState(dim).standard_normal((2, 3, 3, 32, 32)).astype("float32")).to(dev)
+            out = m(video)
+            (out.float() * torch.arange(1, out.numel() + 1, device=dev).view_as(out)).sum().backward()
+            return out, {k: p.grad for k, p in m.named_parameters()}
+        return run
+
+    for dim, heads, dim_head in ((99, 3, 20), (100, 2, 16)):
+        for dtype in (F32, BF):
+            yield f"timesformer-{dim}-depth1-{tier[dtype]}", timesformer_odd(dim, heads, dim_head, dtype)
+
+    def rows_elem(entry, dtype):                          # one call per row-wise entry at a shape of its element form
+        def run():
+            lib, check, code, st = _lib.lib, _lib.check, (_lib.BF16 if dtype == BF else _lib.F32), torch.cuda.current_stream().cuda_stream
+            rs = np.random.RandomState(len(entry))
+
+            def rnd(*shape, dt=dtype):
+                return torch.from_numpy(rs.standard_normal(shape).astype("float32")).to(dev).to(dt)
+
+            def full(*shape, dt=dtype):                   # outputs start from a fill, so an element that is not written shows in the digest
+                return torch.full(shape, 7.0, device=dev, dtype=dt)
+            p = lambda t: t.data_ptr()
+            if entry == "add_rowvec":
+                x, v, y = rnd(10, 150), rnd(5, 150, dt=F32), full(10, 150)
+                check(lib.meant_add_rowvec(p(x), p(v), p(y), 10, 150, 5, code, st), entry)
+                return y, {}
+            if entry == "meanpool":                       # the image means of a model at text_dim = 100, image_dim = 50
+                x, out, dx = rnd(3, 5, 50), full(3, 150, dt=F32), full(3, 5, 50)
+                check(lib.meant_meanpool_fwd(p(x), p(out), 150, 100, 3, 5, 50, code, _lib.F32, st), entry)
+                check(lib.meant_meanpool_bwd(p(out), 150, 100, p(dx), 3, 5, 50, code, _lib.F32, st), entry)
+                return out, {"dx": dx}
+            if entry == "gather_rows":
+                src, fill, dst = rnd(41, 99), rnd(99), full(47, 99)
+                idx = torch.from_numpy(np.concatenate((rs.permutation(41), [-1, -2, 0, -2, -1, 40])).astype("int32")).to(dev)
+                check(lib.meant_gather_rows(p(src), p(idx), p(fill), p(dst), 47, 99, code, st), entry)
+                return dst, {}
+            if entry == "token_shift":
+                x, y, yt = rnd(2, 13, 99), full(2, 13, 99), full(2, 13, 99)
+                check(lib.meant_token_shift(p(x), p(y), 2, 3, 4, 99, 0, code, st), entry)
+                check(lib.meant_token_shift(p(x), p(yt), 2, 3, 4, 99, 1, code, st), entry)
+                return y, {"transpose": yt}
+            if entry == "geglu":
+                h, dy, y, dh = rnd(131, 396), rnd(131, 198), full(131, 198), full(131, 396)
+                check(lib.meant_geglu_fwd(p(h), p(y), 131, 198, code, st), entry)
+                check(lib.meant_geglu_bwd(p(h), p(dy), p(dh), 131, 198, code, st), entry)
+                return y, {"dh": dh}
+            if entry == "dropout":                        # aligned bases: 16-byte groups and an element tail; one element off: all by element
+                x, y, yo = rnd(8005), full(8005), full(8006)
+                xo = torch.cat((x[:1], x))[1:]
+                check(lib.meant_dropout(p(x), p(y), 8005, 0.25, 1234, code, st), entry)
+                check(lib.meant_dropout(p(xo), p(yo[1:]), 8005, 0.25, 1234, code, st), entry)
+                return y, {"off_by_one": yo}
+            table, out = rnd(50, 100, dt=F32), full(37, 100)
+            ids = torch.from_numpy(rs.randint(-1, 52, 37).astype("int64")).to(dev)
+            check(lib.meant_embedding_fwd(p(table), p(ids), p(out), 37, 100, 50, code, st), entry)
+            return out, {}
+        return run
+
+    for entry in ("add_rowvec", "meanpool", "gather_rows", "token_shift", "geglu", "dropout", "embedding_fwd"):
+        for dtype in (F32, BF):
+            yield f"rows_elem-{entry}-{tier[dtype]}", rows_elem(entry, dtype)
 
     def folded(pooled):
         def run():
