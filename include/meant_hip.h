@@ -114,6 +114,18 @@ void meant_route_reset(void);
 /* tiles the streaming GEMM's workgroups took from another XCD's counter, summed over all launches on the current
  * device so far; synchronises the device (test diagnostics) */
 int64_t meant_debug_nt_steals(void);
+/* which route counters one bf16 GEMM launch would hit, from the launchers' own classifiers: nothing is launched, no device is
+ * needed, the options are read as they are set.  op: "nt" (Linear forward / input gradient, C[M,N] = A[M,K] B[N,K]^T), "tn" (weight
+ * gradient dW[N,K] over M token rows) or "tn_rows" (the same over a list of live 64-row blocks).  facts: what the rule reads of
+ * an "nt" launch beside its shape, a sum of meant_route_fact (C's / the residual's row stride is no multiple of 8 elements; a
+ * residual is given; the residual -- without one, A -- is C itself); 0 < rot_S < 2^31: the rotary epilogue with sequences of rot_S rows.
+ * num_cus: the compute-unit count to decide for (meant_num_cus() on a device).  names (char[names_bytes]) receives the counter
+ * names in hit order, space-separated, e.g. "nt_overlap nt256s", "nt_split nt256s nt128", "tn_tail gemm_f32 tn256".
+ * Returns 1 if an "nt" launch runs the streaming kernel over whole 256-row panels (what a key-padding panel list and the by-id
+ * forward need), 0 otherwise, a negative meant_status on a bad argument or a buffer too small. */
+enum meant_route_fact { MEANT_FACT_LDC_OFF8 = 1, MEANT_FACT_LDR_OFF8 = 2, MEANT_FACT_RESIDUAL = 4, MEANT_FACT_ALIAS_C = 8 };
+int meant_debug_gemm_route(const char* op, int64_t M, int64_t N, int64_t K, int facts, int64_t rot_S, int num_cus, void* names,
+                           size_t names_bytes);
 
 /* ---- RMSNorm ---------------------------------------------------- utils/rms_norm.py:40-57
  * y = scale * x * rinv,  rinv = 1 / (||x||_2 / sqrt(d) + eps)   (eps outside the sqrt)

@@ -1,16 +1,13 @@
 // extern "C" entry points for Linear and the attention core: argument checks + dtype dispatch.
 #include "internal.h"
 
-// preconditions of the MFMA bf16 NT kernels (global_load_lds moves 16-byte pieces; vector epilogue stores).  K % 64 != 0 runs on the
-// K-tail forms of the one-tile kernels (gemm_bf16.hip); the RMSNorm-into-Linear fold entries below keep K % 64 == 0.
-static bool bf16_nt_ok(const void* a, int64_t lda, const void* b, int64_t ldb, int64_t K) {
-  return K >= 8 && (K % 8) == 0 && (lda % 8) == 0 && (ldb % 8) == 0 && meant_aligned16(a) && meant_aligned16(b);
-}
+// The preconditions of the MFMA bf16 kernels are gemm_bf16_nt_ok / gemm_bf16_tn_ok (gemm_bf16.hip).  K % 64 != 0 runs on the K-tail forms
+// of the one-tile kernels there; the RMSNorm-into-Linear fold entries below keep K % 64 == 0.
 
 // the exact-f32 GEMM on row-major operands, C[M,N] = A B^T with A [M,K] and B [N,K] ("NT": Linear forward and input gradient), or
 // C[M,N] += A^T B with A [K,M] and B [K,N] ("TN": the weight gradient).  `storage`: dtype of A and B; C takes it too in the NT form
 // and is float in the TN form.  The caller adds bias / residual / epilogue.
-static GemmF32Args f32_rowmajor(bool tn, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int64_t M, int64_t N,
+GemmF32Args f32_rowmajor(bool tn, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int64_t M, int64_t N,
                                 int64_t K, int storage) {
   GemmF32Args a{};
   a.in_dtype = storage; a.out_dtype = tn ? MEANT_F32 : storage;
@@ -31,7 +28,7 @@ extern "C" int meant_linear_fwd(const void* x, int64_t ldx, const void* w, const
   MEANT_REQUIRE(!(epilogue & MEANT_EPI_RESIDUAL) || residual, MEANT_ERR_ARG, "linear_fwd: residual epilogue without residual pointer");
   if (!(epilogue & MEANT_EPI_RESIDUAL)) residual = nullptr;
   // bf16 at odd shapes (K not a multiple of 8, unaligned rows: e.g. the class head): the exact-f32 path on bf16 storage
-  if (dtype == MEANT_F32 || (dtype == MEANT_BF16 && !bf16_nt_ok(x, ldx, w, K, K))) {
+  if (dtype == MEANT_F32 || (dtype == MEANT_BF16 && !gemm_bf16_nt_ok(x, ldx, w, K, K))) {
     MEANT_REQUIRE(!residual || ldr == ldy, MEANT_ERR_UNSUPPORTED, "linear_fwd(%s): residual stride must equal output stride",
                   dtype == MEANT_F32 ? "f32" : "bf16 generic");
     GemmF32Args a = f32_rowmajor(false, x, ldx, w, K, y, ldy, M, N, K, dtype);
@@ -39,10 +36,8 @@ extern "C" int meant_linear_fwd(const void* x, int64_t ldx, const void* w, const
     return gemm_f32_launch(a, (hipStream_t)stream);
   }
   if (dtype == MEANT_BF16) {
-    GemmBf16Args a{};
-    a.A = (const bf16*)x; a.lda = ldx; a.B = (const bf16*)w; a.ldb = K; a.C = (bf16*)y; a.ldc = ldy;
-    a.M = M; a.N = N; a.K = K; a.bias = bias; a.residual = (const bf16*)residual; a.ldr = ldr; a.preact = (bf16*)preact;
-    a.epilogue = epilogue;
+    GemmBf16Args a = gemm_bf16_nt_args(x, ldx, w, y, ldy, M, N, K);
+    a.bias = bias; a.residual = (const bf16*)residual; a.ldr = ldr; a.preact = (bf16*)preact; a.epilogue = epilogue;
     return gemm_bf16_nt_launch(a, (hipStream_t)stream);
   }
   meant_set_error("linear_fwd: unknown dtype %d", dtype);
@@ -53,11 +48,10 @@ extern "C" int meant_linear_fwd_f32out(const void* x, int64_t ldx, const void* w
                                        int64_t N, int64_t K, void* stream) {
   MEANT_REQUIRE(x && w && y, MEANT_ERR_ARG, "linear_fwd_f32out: null pointer");
   MEANT_REQUIRE(M > 0 && N > 0 && K > 0 && ldx >= K && ldy >= N, MEANT_ERR_ARG, "linear_fwd_f32out: bad shape M=%lld N=%lld K=%lld", (long long)M, (long long)N, (long long)K);
-  MEANT_REQUIRE(bf16_nt_ok(x, ldx, w, K, K) && meant_aligned16(y), MEANT_ERR_UNSUPPORTED,
+  MEANT_REQUIRE(gemm_bf16_nt_ok(x, ldx, w, K, K) && meant_aligned16(y), MEANT_ERR_UNSUPPORTED,
                 "linear_fwd_f32out: needs K %% 8 == 0, ldx %% 8 == 0 and 16-byte aligned operands");
-  GemmBf16Args a{};
-  a.A = (const bf16*)x; a.lda = ldx; a.B = (const bf16*)w; a.ldb = K; a.C = (bf16*)y; a.ldc = ldy;
-  a.M = M; a.N = N; a.K = K; a.bias = bias; a.epilogue = GEMM_EPI_F32_OUT;
+  GemmBf16Args a = gemm_bf16_nt_args(x, ldx, w, y, ldy, M, N, K);
+  a.bias = bias; a.epilogue = GEMM_EPI_F32_OUT;
   return gemm_bf16_nt_launch(a, (hipStream_t)stream);
 }
 
@@ -79,11 +73,10 @@ extern "C" int meant_qkv_proj_fwd_live(const void* x, int64_t ldx, const void* w
   const bool rot = qa != nullptr;
   MEANT_REQUIRE(!rot || (qb && ka && kb && R > 0 && R % 2 == 0 && R <= Dh), MEANT_ERR_ARG, "qkv_proj_fwd: bad rotary tables");
   const int64_t D = (int64_t)H * Dh, N = 3 * D;
-  const bool fused = rot && dtype == MEANT_BF16 && bf16_nt_ok(x, ldx, w, K, K) && Dh % 8 == 0 && R % 8 == 0;
+  const bool fused = rot && dtype == MEANT_BF16 && gemm_bf16_nt_ok(x, ldx, w, K, K) && Dh % 8 == 0 && R % 8 == 0;
   if (fused) {
-    GemmBf16Args a{};
-    a.A = (const bf16*)x; a.lda = ldx; a.B = (const bf16*)w; a.ldb = K; a.C = (bf16*)qkv; a.ldc = N;
-    a.M = M; a.N = N; a.K = K; a.bias = bias;
+    GemmBf16Args a = gemm_bf16_nt_args(x, ldx, w, qkv, N, M, N, K);
+    a.bias = bias;
     a.rot_qa = qa; a.rot_qb = qb; a.rot_ka = ka; a.rot_kb = kb;
     a.rot_S = (int)S; a.rot_D = (int)D; a.rot_Dh = Dh; a.rot_R = R;
     if (listed) {
@@ -117,14 +110,9 @@ extern "C" int meant_linear_bwd_dx(const void* dy, int64_t lddy, const void* wT,
                                    int64_t K, int dtype, void* stream) {
   MEANT_REQUIRE(dy && wT && dx, MEANT_ERR_ARG, "linear_bwd_dx: null pointer");
   MEANT_REQUIRE(M > 0 && N > 0 && K > 0 && lddy >= N && lddx >= K, MEANT_ERR_ARG, "linear_bwd_dx: bad shape");
-  if (dtype == MEANT_F32 || (dtype == MEANT_BF16 && !bf16_nt_ok(dy, lddy, wT, N, N)))
+  if (dtype == MEANT_F32 || (dtype == MEANT_BF16 && !gemm_bf16_nt_ok(dy, lddy, wT, N, N)))
     return gemm_f32_launch(f32_rowmajor(false, dy, lddy, wT, N, dx, lddx, M, K, N, dtype), (hipStream_t)stream);
-  if (dtype == MEANT_BF16) {
-    GemmBf16Args a{};
-    a.A = (const bf16*)dy; a.lda = lddy; a.B = (const bf16*)wT; a.ldb = N; a.C = (bf16*)dx; a.ldc = lddx;
-    a.M = M; a.N = K; a.K = N;
-    return gemm_bf16_nt_launch(a, (hipStream_t)stream);
-  }
+  if (dtype == MEANT_BF16) return gemm_bf16_nt_launch(gemm_bf16_nt_args(dy, lddy, wT, dx, lddx, M, K, N), (hipStream_t)stream);
   meant_set_error("linear_bwd_dx: unknown dtype %d", dtype);
   return MEANT_ERR_ARG;
 }
@@ -138,12 +126,11 @@ extern "C" int meant_linear_fwd_rowscale(const void* x, int64_t ldx, const void*
                                          int64_t K, int epilogue, int dtype, void* stream) {
   MEANT_REQUIRE(x && w && y && row_scale, MEANT_ERR_ARG, "linear_fwd_rowscale: null pointer");
   MEANT_REQUIRE(M > 0 && N > 0 && K > 0 && ldx >= K && ldy >= N, MEANT_ERR_ARG, "linear_fwd_rowscale: bad shape");
-  MEANT_REQUIRE(dtype == MEANT_BF16 && K % 64 == 0 && bf16_nt_ok(x, ldx, w, K, K) && (ldy & 7) == 0 && !(epilogue & MEANT_EPI_SIGMOID),
+  MEANT_REQUIRE(dtype == MEANT_BF16 && K % 64 == 0 && gemm_bf16_nt_ok(x, ldx, w, K, K) && (ldy & 7) == 0 && !(epilogue & MEANT_EPI_SIGMOID),
                 MEANT_ERR_UNSUPPORTED, "linear_fwd_rowscale: bf16 tier, K %% 64 == 0, 16-byte aligned rows only");
   MEANT_REQUIRE(!(epilogue & MEANT_EPI_RESIDUAL) || residual, MEANT_ERR_ARG, "linear_fwd_rowscale: residual epilogue without residual pointer");
-  GemmBf16Args a{};
-  a.A = (const bf16*)x; a.lda = ldx; a.B = (const bf16*)w; a.ldb = K; a.C = (bf16*)y; a.ldc = ldy;
-  a.M = M; a.N = N; a.K = K; a.bias = bias; a.residual = (epilogue & MEANT_EPI_RESIDUAL) ? (const bf16*)residual : nullptr; a.ldr = ldr;
+  GemmBf16Args a = gemm_bf16_nt_args(x, ldx, w, y, ldy, M, N, K);
+  a.bias = bias; a.residual = (epilogue & MEANT_EPI_RESIDUAL) ? (const bf16*)residual : nullptr; a.ldr = ldr;
   a.preact = (bf16*)preact; a.epilogue = epilogue; a.row_scale = row_scale;
   return gemm_bf16_nt_launch(a, (hipStream_t)stream);
 }
@@ -155,12 +142,10 @@ extern "C" int meant_linear_bwd_dx_norm(const void* dy_scaled, int64_t lddy, con
                                         int64_t M, int64_t N, int64_t K, int dtype, void* stream) {
   MEANT_REQUIRE(dy_scaled && wT && x && coef && dx, MEANT_ERR_ARG, "linear_bwd_dx_norm: null pointer");
   MEANT_REQUIRE(M > 0 && N > 0 && K > 0 && lddy >= N && lddx >= K && ldx >= K, MEANT_ERR_ARG, "linear_bwd_dx_norm: bad shape");
-  MEANT_REQUIRE(dtype == MEANT_BF16 && N % 64 == 0 && bf16_nt_ok(dy_scaled, lddy, wT, N, N) && (lddx & 7) == 0 && (ldx & 7) == 0 &&
+  MEANT_REQUIRE(dtype == MEANT_BF16 && N % 64 == 0 && gemm_bf16_nt_ok(dy_scaled, lddy, wT, N, N) && (lddx & 7) == 0 && (ldx & 7) == 0 &&
                 meant_aligned16(x) && (!dres || ((lddres & 7) == 0 && meant_aligned16(dres))),
                 MEANT_ERR_UNSUPPORTED, "linear_bwd_dx_norm: bf16 tier, N %% 64 == 0, 16-byte aligned rows only");
-  GemmBf16Args a{};
-  a.A = (const bf16*)dy_scaled; a.lda = lddy; a.B = (const bf16*)wT; a.ldb = N; a.C = (bf16*)dx; a.ldc = lddx;
-  a.M = M; a.N = K; a.K = N;
+  GemmBf16Args a = gemm_bf16_nt_args(dy_scaled, lddy, wT, dx, lddx, M, K, N);
   a.residual = (const bf16*)dres; a.ldr = lddres;
   a.sub = (const bf16*)x; a.ldsub = ldx; a.sub_coef = coef;
   if (dres_pooled) {                                   // + dres_pooled[m / group_rows, :] / group_rows: the gradient of mean_s(x)
@@ -178,7 +163,7 @@ extern "C" int meant_linear_bwd_dw(const void* dy, int64_t lddy, const void* x, 
                                    int64_t N, int64_t K, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
   MEANT_REQUIRE(dy && x && dw, MEANT_ERR_ARG, "linear_bwd_dw: null pointer");
   MEANT_REQUIRE(M > 0 && N > 0 && K > 0 && lddy >= N && ldx >= K, MEANT_ERR_ARG, "linear_bwd_dw: bad shape");
-  if (dtype == MEANT_F32 || (dtype == MEANT_BF16 && (N < 8 || K < 8 || (lddy & 7) || (ldx & 7) || !meant_aligned16(dy) || !meant_aligned16(x)))) {
+  if (dtype == MEANT_F32 || (dtype == MEANT_BF16 && !gemm_bf16_tn_ok(dy, lddy, x, ldx, N, K))) {
     int rc = gemm_f32_launch(f32_rowmajor(true, dy, lddy, x, ldx, dw, K, N, K, M, dtype), (hipStream_t)stream);
     if (rc) return rc;
     if (dbias) return colsum_launch(dy, lddy, dbias, M, N, dtype, 1, (hipStream_t)stream);
@@ -198,7 +183,7 @@ extern "C" int meant_linear_bwd_dw_rows(const void* dy, int64_t lddy, const void
   if (dtype != MEANT_BF16) return meant_linear_bwd_dw(dy, lddy, x, ldx, dw, dbias, M, N, K, dtype, workspace, workspace_bytes, stream);
   MEANT_REQUIRE(dy && x && dw, MEANT_ERR_ARG, "linear_bwd_dw_rows: null pointer");
   MEANT_REQUIRE(M > 0 && N > 0 && K > 0 && lddy >= N && ldx >= K, MEANT_ERR_ARG, "linear_bwd_dw_rows: bad shape");
-  if (N < 8 || K < 8 || (lddy & 7) || (ldx & 7) || !meant_aligned16(dy) || !meant_aligned16(x))
+  if (!gemm_bf16_tn_ok(dy, lddy, x, ldx, N, K))
     return meant_linear_bwd_dw(dy, lddy, x, ldx, dw, dbias, M, N, K, dtype, workspace, workspace_bytes, stream);
   return gemm_bf16_tn_rows_launch((const bf16*)dy, lddy, (const bf16*)x, ldx, dw, dbias, rows_list, rows_count, M, N, K, workspace, workspace_bytes,
                                   (hipStream_t)stream);

@@ -66,6 +66,7 @@ enum meant_route_id {
   MEANT_ROUTE_COUNT
 };
 void meant_route_hit(int route);
+const char* meant_route_name(int route);   // the name meant_route_count knows the counter by
 
 static inline bool meant_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 // aligned to one element of the activation type (4 bytes fp32, 2 bytes bf16): what the element-access kernels need

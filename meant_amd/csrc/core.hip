@@ -157,6 +157,7 @@ std::atomic<long long> g_route[MEANT_ROUTE_COUNT];
 }  // namespace
 
 void meant_route_hit(int route) { g_route[route].fetch_add(1, std::memory_order_relaxed); }
+const char* meant_route_name(int route) { return k_routes[route]; }
 
 extern "C" int64_t meant_route_count(const char* route) {
   if (!route) return -1;

@@ -27,6 +27,8 @@
 #include <type_traits>
 #include <atomic>
 #include <mutex>
+#include <string>
+#include <string.h>
 #include <unordered_map>
 
 namespace {
@@ -65,7 +67,8 @@ __device__ __forceinline__ const bf16* nt_tail_src(const bf16* __restrict__ g, i
 
 // ------------------------------------------------------------------------------------------------
 // NT kernel
-// stage one 128 x 64 bf16 tile (rows row0.., columns k0..k0+63 of a K-contiguous matrix) into LDS.
+// stage a wave's 32 rows of a 64-column bf16 tile (rows row0.., columns k0..k0+63 of a K-contiguous matrix) into LDS: the 128-row
+// tile of this kernel (4 waves) and the 256-row tile of the one-tile 256 x 256 kernel below (8 waves; 32 pieces of 1 KiB).
 // wave w issues DMA pieces 4w..4w+3; piece i covers tile rows 8i..8i+7 (8 lanes per 128-byte row).
 template <bool KTAIL>
 __device__ __forceinline__ void nt_stage(const bf16* __restrict__ g, int64_t ld, int64_t row0, int64_t nrows, int64_t k0,
@@ -251,22 +254,6 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_nt_kernel(GemmBf16Args a, in
 constexpr int B2 = 256;
 constexpr int T2_BYTES = B2 * BK * 2;              // 32 KiB per operand per stage
 
-// 32 pieces of 1 KiB (8 rows each) per tile; wave w issues pieces 4w .. 4w+3
-template <bool KTAIL>
-__device__ __forceinline__ void nt256_stage(const bf16* __restrict__ g, int64_t ld, int64_t row0, int64_t nrows, int64_t k0,
-                                             char* lds_tile, int wave, int lane, int64_t K) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int piece = wave * 4 + i;
-    const int r = piece * 8 + (lane >> 3);
-    const int c = (lane & 7) ^ ((r >> 1) & 7);
-    int64_t gr = row0 + r;
-    gr = gr < nrows ? gr : nrows - 1;
-    if (KTAIL) glds16(nt_tail_src(g, ld, gr, k0 + c * 8, K), lds_tile + piece * 1024);
-    else glds16(g + gr * ld + k0 + c * 8, lds_tile + piece * 1024);
-  }
-}
-
 template <bool KTAIL>
 __global__ __launch_bounds__(512, 2) void gemm_bf16_nt256_kernel(GemmBf16Args a, int ntm, int ntn) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -283,8 +270,8 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt256_kernel(GemmBf16Args a,
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  nt256_stage<KTAIL>(a.A, a.lda, m0, a.M, 0, smem, wave, lane, a.K);
-  nt256_stage<KTAIL>(a.B, a.ldb, n0, a.N, 0, smem + T2_BYTES, wave, lane, a.K);
+  nt_stage<KTAIL>(a.A, a.lda, m0, a.M, 0, smem, wave, lane, a.K);
+  nt_stage<KTAIL>(a.B, a.ldb, n0, a.N, 0, smem + T2_BYTES, wave, lane, a.K);
   __syncthreads();
 
   const int frow = lane & 15, fkg = lane >> 4;
@@ -297,10 +284,10 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt256_kernel(GemmBf16Args a,
     // K-loop; issuing late instead -- after the MFMAs -- exposes the load latency at the barrier and measured -10 %).
     const bool late = __builtin_amdgcn_readfirstlane(threadIdx.x) >= 256;
     if (!late && kt + 1 < nk) {
-      nt256_stage<KTAIL>(a.A, a.lda, m0, a.M, (int64_t)(kt + 1) * BK, nxt, wave, lane, a.K);
-      nt256_stage<KTAIL>(a.B, a.ldb, n0, a.N, (int64_t)(kt + 1) * BK, nxt + T2_BYTES, wave, lane, a.K);
-      nt256_stage<KTAIL>(a.A, a.lda, m0, a.M, (int64_t)(kt + 1) * BK, nxt, wave + 4, lane, a.K);
-      nt256_stage<KTAIL>(a.B, a.ldb, n0, a.N, (int64_t)(kt + 1) * BK, nxt + T2_BYTES, wave + 4, lane, a.K);
+      nt_stage<KTAIL>(a.A, a.lda, m0, a.M, (int64_t)(kt + 1) * BK, nxt, wave, lane, a.K);
+      nt_stage<KTAIL>(a.B, a.ldb, n0, a.N, (int64_t)(kt + 1) * BK, nxt + T2_BYTES, wave, lane, a.K);
+      nt_stage<KTAIL>(a.A, a.lda, m0, a.M, (int64_t)(kt + 1) * BK, nxt, wave + 4, lane, a.K);
+      nt_stage<KTAIL>(a.B, a.ldb, n0, a.N, (int64_t)(kt + 1) * BK, nxt + T2_BYTES, wave + 4, lane, a.K);
     }
     const char* At = cur + (wm * 128) * 128;
     const char* Bt = cur + T2_BYTES + (wn * 64) * 128;
@@ -698,6 +685,13 @@ __device__ __forceinline__ void glds16_x4(const void* sbase, const unsigned (&v)
                "global_load_lds_dwordx4 %2, %4 offset:2048\n\tglobal_load_lds_dwordx4 %3, %4 offset:3072"
                ::"v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "s"((const char*)sbase - 3072), "s"(lds) : "memory");
 }
+// the workgroup barrier of the two ping-pong kernels (this one and the 256 x 256 dW kernel), fenced against the scheduler on both sides
+#define PP_BAR()                          \
+  do {                                    \
+    __builtin_amdgcn_sched_barrier(0);    \
+    __builtin_amdgcn_s_barrier();         \
+    __builtin_amdgcn_sched_barrier(0);    \
+  } while (0)
 typedef const __attribute__((address_space(4))) unsigned* kernarg_words_t;
 static_assert(sizeof(GemmBf16Args) % 4 == 0, "kernarg copy by words");
 
@@ -792,13 +786,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt256p_kernel(GemmBf16Args a
   // prefetch cursors: what the B pieces (one step ahead) and the A pieces (two steps ahead) of the CURRENT step read
   const bf16* qB = pB + BK;
   const bf16* qA = pA + 2 * BK;
-
-#define PP_BAR()                          \
-  do {                                    \
-    __builtin_amdgcn_sched_barrier(0);    \
-    __builtin_amdgcn_s_barrier();         \
-    __builtin_amdgcn_sched_barrier(0);    \
-  } while (0)
 
   const int frow = lane & 15, fkg = lane >> 4;
   // fragment read offsets inside a slot: row i*16 + frow, chunk (ks*4 + fkg) ^ ((row >> 1) & 7); i adds 2048 bytes, ks flips bit 6
@@ -957,7 +944,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt256p_kernel(GemmBf16Args a
       if (has_next) origin(next, pAn, pBn, m0n, n0n);
     }
   }
-#undef PP_BAR
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the cursors' last (unused) pieces
   leave();
 }
@@ -1204,12 +1190,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn256p_kernel(const bf16* __
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
   }
-#define PP_BAR()                          \
-  do {                                    \
-    __builtin_amdgcn_sched_barrier(0);    \
-    __builtin_amdgcn_s_barrier();         \
-    __builtin_amdgcn_sched_barrier(0);    \
-  } while (0)
   const unsigned sbase = lds_addr(smem);
   int sA = 0;
   unsigned ya = sbase, xa = sbase + T2_BYTES, dXs = lds0 + 3 * T2_BYTES, dYs = lds0 + 4 * T2_BYTES;
@@ -1413,11 +1393,106 @@ extern "C" int64_t meant_debug_nt_steals(void) {
   return n;
 }
 
-// does this launch take the streaming kernel with whole row panels (the M % 256 == 0 form)?  The launcher's own route test, for callers that
-// hand it a panel list.
-bool gemm_bf16_nt_streams(const GemmBf16Args& a) {
-  return a.M >= 1024 && a.M % B2 == 0 && a.N % 256 == 0 && ceil_div(a.M, B2) * (a.N / B2) * 2 >= meant_num_cus() && meant_opt(MEANT_OPT_NT_STREAM) != 0 &&
-         a.K % BK == 0 && a.K >= 4 * BK && (a.ldc & 7) == 0 && (!a.residual || (a.ldr & 7) == 0);
+// ---- "the MFMA kernels can take these operands" (global_load_lds moves 16-byte pieces): what the entry points of api.hip ask before they
+// choose between these kernels and the exact f32 engine, and what the launchers below require.  K % 64 != 0 runs on the K-tail forms
+// of the one-tile NT kernels.
+static bool nt_k_ok(int64_t K) { return K >= 8 && K % 8 == 0; }
+static bool rows16(const void* p, int64_t ldp, const void* q, int64_t ldq) {
+  return (ldp % 8) == 0 && (ldq % 8) == 0 && meant_aligned16(p) && meant_aligned16(q);
+}
+bool gemm_bf16_nt_ok(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t K) { return nt_k_ok(K) && rows16(A, lda, B, ldb); }
+bool gemm_bf16_tn_ok(const void* dY, int64_t lddy, const void* X, int64_t ldx, int64_t N, int64_t K) {
+  return N >= 8 && K >= 8 && rows16(dY, lddy, X, ldx);
+}
+
+// ---- which kernel a bf16 NT GEMM takes ---------------------------------------------------------------------------------------------
+// nt_plan is the one statement of the rule.  It is pure -- no launch, no route counter, no error; options through meant_opt, the
+// compute-unit count an argument -- so the launcher, gemm_bf16_nt_streams and meant_debug_gemm_route read the same decision.
+enum NtKind { NT128, NT256, NT256S };                  // 128 x 128 one-tile, 256 x 256 one-tile, 256 x 256 streaming (ping-pong)
+struct NtPlan {
+  NtKind kind;
+  bool ktail;                                          // K % 64 != 0: the K-tail forms of the two one-tile kernels; never the streaming, split or overlap routes
+  bool overlap;                                        // NT256S over a ragged M: the last row tile ends at row M
+  int64_t split_rows;                                  // != 0: rows [0, split_rows) and the < 256 rows behind them are planned and launched on their own
+  int64_t ntm, ntn;                                    // tiles of the kind's size along M and N
+  int grid, rotP;                                      // NT256S: workgroups; rotary panel walk (see the kernel's `origin`)
+};
+
+static int64_t nt_ldc_h(const GemmBf16Args& a) { return (a.epilogue & GEMM_EPI_F32_OUT) ? 2 * a.ldc : a.ldc; }   // C's row stride in 2-byte units
+
+static NtPlan nt_plan(const GemmBf16Args& a, int ncus) {
+  NtPlan p{};
+  p.ktail = a.K % BK != 0;
+  // big tall problems: 256 x 256 tiles (half the operand bytes per FLOP) -- once there are enough of them to occupy at least
+  // half the CUs (the temporal encoder's 1536^2 Linears make 36: four times as many 128 x 128 tiles finish in a third of the time)
+  const bool big = a.M >= 1024 && a.N % 256 == 0 && ceil_div(a.M, B2) * (a.N / B2) * 2 >= ncus;
+  p.kind = big ? NT256 : NT128;
+  p.ntm = ceil_div(a.M, big ? B2 : BM); p.ntn = ceil_div(a.N, big ? B2 : BN);
+  // the streaming kernel (ping-pong form: the two waves of a SIMD alternate between MFMA and load halves) needs four K-steps;
+  // shorter K goes to the one-tile kernel.  Option nt_stream = 0 forces the one-tile-per-workgroup kernel (A/B measurements)
+  const bool can_stream = big && meant_opt(MEANT_OPT_NT_STREAM) != 0 && !p.ktail && a.K >= 4 * BK && (a.ldc & 7) == 0 && (!a.residual || (a.ldr & 7) == 0);
+  if (can_stream && a.M % B2 != 0) {
+    // Ragged M, option nt_ragged = 1 (default): the streaming kernel takes all of it; its last row tile is moved up so that it
+    // ENDS at row M and recomputes up to 255 rows of its neighbour.  Every element of C is a function of its own row of A
+    // and column of W with a fixed K order, so both tiles store identical bits (no cost in the K-loop, no second launch:
+    // the 32 trailing rows of the TimeSformer's 75 296 tokens cost 12 extra launches of 13-97 us per layer as a split).
+    // Needs an out-of-place epilogue: a residual (or A) that aliases C would be read after the neighbour's store.
+    const auto overlaps = [](const void* x, int64_t ldx, const void* y, int64_t ldy, int64_t rows) {
+      const char *x0 = (const char*)x, *y0 = (const char*)y;
+      return x && y && x0 < y0 + rows * ldy * 2 && y0 < x0 + rows * ldx * 2;
+    };
+    const int64_t ldc_h = nt_ldc_h(a);
+    p.overlap = meant_opt(MEANT_OPT_NT_RAGGED) != 0 && !overlaps(a.C, ldc_h, a.residual, a.ldr, a.M) && !overlaps(a.C, ldc_h, a.sub, a.ldsub, a.M) &&
+                !overlaps(a.C, ldc_h, a.A, a.lda, a.M) && (!a.preact || !overlaps(a.preact, a.ldc, a.A, a.lda, a.M));
+    // nt_ragged = 0 (or aliasing operands): the streaming kernel takes the first floor(M / 256) * 256 rows, the remaining < 256 rows go
+    // to the 128 x 128 kernel as a second launch (row-local epilogues only: the rotary epilogue indexes its tables by the
+    // absolute row, so it splits only where the boundary is a multiple of the sequence length; otherwise all of it stays one-tile).
+    const int64_t m_full = (a.M / B2) * B2;
+    if (!p.overlap && (!a.rot_qa || m_full % a.rot_S == 0)) p.split_rows = m_full;
+  }
+  if (can_stream && (a.M % B2 == 0 || p.overlap)) p.kind = NT256S;
+  if (p.kind != NT256S) return p;
+  int ncu = ncus & ~7;
+  const int cap = meant_opt(MEANT_OPT_NT_GRID_CAP) & ~7;       // tests: fewer workgroups => more tiles each, dry XCDs steal
+  if (cap >= 8 && cap < ncu) ncu = cap;
+  p.grid = (int)(p.ntm * p.ntn < ncu ? ((p.ntm * p.ntn + 7) / 8) * 8 : ncu);
+  // rotary mode: panels of one position range after the other (see the kernel's `origin`)
+  if (a.rot_qa && a.rot_S % B2 == 0 && a.rot_S / B2 > 1 && a.rot_S / B2 < 256 && a.M % B2 == 0 && p.ntm % (a.rot_S / B2) == 0) p.rotP = (int)(a.rot_S / B2);
+  return p;
+}
+
+// the streaming kernel over whole 256-row panels: the only route a panel list is legal on, and the one the by-id forward must match
+static bool nt_streams(const NtPlan& p) { return p.kind == NT256S && !p.overlap && !p.split_rows; }
+bool gemm_bf16_nt_streams(const GemmBf16Args& a) { return nt_streams(nt_plan(a, meant_num_cus())); }
+
+// One launch as its plans spell it: the route counters in hit order through `hit`, the kernel launches through `leaf(args, plan)` -- once,
+// or for the head and the tail of a split, which are planned again.  The launcher counts and launches with it; meant_debug_gemm_route
+// names the counters and launches nothing, so the order is stated here alone.
+template <typename Hit, typename Leaf>
+static int nt_walk(const GemmBf16Args& a, int ncus, Hit&& hit, Leaf&& leaf) {
+  const NtPlan p = nt_plan(a, ncus);
+  if (a.rot_qa) hit(ROUTE_NT_ROT);
+  MEANT_REQUIRE(p.ntm * p.ntn < 2147483647LL, MEANT_ERR_UNSUPPORTED, "gemm_bf16_nt: grid too large");
+  if (!p.split_rows) {
+    if (p.overlap) hit(ROUTE_NT_OVERLAP);
+    hit(p.kind == NT256S ? (a.rot_qa ? ROUTE_NT256S_ROT : ROUTE_NT256S) : p.kind == NT256 ? (p.ktail ? ROUTE_NT256K : ROUTE_NT256) : (p.ktail ? ROUTE_NT128K : ROUTE_NT128));
+    return leaf(a, p);
+  }
+  const int64_t m_full = p.split_rows;
+  GemmBf16Args head = a, tail = a;
+  head.M = m_full;
+  tail.M = a.M - m_full;
+  tail.A = a.A + m_full * a.lda;
+  tail.C = a.C + m_full * nt_ldc_h(a);
+  if (a.residual) tail.residual = a.residual + m_full * a.ldr;
+  if (a.preact) tail.preact = a.preact + m_full * a.ldc;
+  if (a.row_scale) tail.row_scale = a.row_scale + m_full;
+  if (a.sub) { tail.sub = a.sub + m_full * a.ldsub; tail.sub_coef = a.sub_coef + m_full; }
+  MEANT_REQUIRE(!a.bres || m_full % a.bres_rows == 0, MEANT_ERR_UNSUPPORTED, "gemm_bf16_nt: broadcast residual across the head / tail split");
+  if (a.bres) tail.bres = a.bres + (m_full / a.bres_rows) * a.N;
+  hit(ROUTE_NT_SPLIT);
+  const int rc = nt_walk(head, ncus, hit, leaf);
+  return rc ? rc : nt_walk(tail, ncus, hit, leaf);
 }
 
 // zero the `cols` columns at C of the 256-row panels panels[0 .. *count) (device memory): the k | v rows nobody computed
@@ -1432,253 +1507,191 @@ int zero_panels_launch(bf16* C, int64_t ldc, int64_t cols, const int* panels, co
 int gemm_bf16_nt_launch(const GemmBf16Args& a, hipStream_t stream) {
   MEANT_REQUIRE(a.A && a.B && a.C, MEANT_ERR_ARG, "gemm_bf16_nt: null pointer");
   MEANT_REQUIRE(!a.rot_qa || (a.rot_D > 0 && a.col0 >= 0 && a.col0 % a.rot_D == 0 && a.N % a.rot_D == 0 && a.col0 + a.N <= 3 * (int64_t)a.rot_D &&
-                              a.rot_Dh % 8 == 0 && a.rot_R % 8 == 0 && (a.ldc & 7) == 0 && a.rot_D % a.rot_Dh == 0),
+                              a.rot_Dh % 8 == 0 && a.rot_R % 8 == 0 && (a.ldc & 7) == 0 && a.rot_D % a.rot_Dh == 0 && a.rot_S > 0),
                 MEANT_ERR_ARG, "gemm_bf16_nt: rotary epilogue needs whole q / k / v sections of H*Dh columns, Dh %% 8 == 0, rot_dim %% 8 == 0");
   MEANT_REQUIRE(!a.panel_list || (a.rot_qa && a.panel_count && gemm_bf16_nt_streams(a)), MEANT_ERR_UNSUPPORTED,
                 "gemm_bf16_nt: a panel list needs the rotary epilogue on the streaming kernel");
-  MEANT_REQUIRE(a.K >= 8 && a.K % 8 == 0, MEANT_ERR_UNSUPPORTED, "gemm_bf16_nt: K=%lld must be a multiple of 8 (use the fp32 tier otherwise)", (long long)a.K);
-  MEANT_REQUIRE((a.lda % 8) == 0 && (a.ldb % 8) == 0 && meant_aligned16(a.A) && meant_aligned16(a.B), MEANT_ERR_ARG,
+  MEANT_REQUIRE(nt_k_ok(a.K), MEANT_ERR_UNSUPPORTED, "gemm_bf16_nt: K=%lld must be a multiple of 8 (use the fp32 tier otherwise)", (long long)a.K);
+  MEANT_REQUIRE(gemm_bf16_nt_ok(a.A, a.lda, a.B, a.ldb, a.K), MEANT_ERR_ARG,
                 "gemm_bf16_nt: operands must be 16-byte aligned with row strides that are multiples of 8");
-  MEANT_RAISE_LDS(gemm_bf16_nt256_kernel<false>, 4 * T2_BYTES);
-  const bool ktail = a.K % BK != 0;                    // K-tail forms of the two one-tile kernels; never the streaming, split or overlap routes
-  MEANT_RAISE_LDS((gemm_bf16_nt256p_kernel<NTE_PLAIN>), RING * T2_BYTES);
-  MEANT_RAISE_LDS((gemm_bf16_nt256p_kernel<NTE_RES>), RING * T2_BYTES);
-  MEANT_RAISE_LDS((gemm_bf16_nt256p_kernel<NTE_GELU_PRE>), RING * T2_BYTES);
-  MEANT_RAISE_LDS((gemm_bf16_nt256p_kernel<NTE_ROT>), RING * T2_BYTES);
-  MEANT_RAISE_LDS((gemm_bf16_nt256p_kernel<NTE_EXT>), RING * T2_BYTES);
-  MEANT_RAISE_LDS((gemm_bf16_nt256p_kernel<NTE_GENERIC>), RING * T2_BYTES);
   const bool ext = a.row_scale || a.sub || a.bres;
   const bool act = (a.epilogue & (MEANT_EPI_GELU | MEANT_EPI_SIGMOID)) != 0;
   const bool f32out = (a.epilogue & GEMM_EPI_F32_OUT) != 0;
   MEANT_REQUIRE(!f32out || (!a.rot_qa && !ext && !a.residual && !a.preact && !act && !a.panel_list), MEANT_ERR_UNSUPPORTED,
                 "gemm_bf16_nt: float output with rotary / activation / residual / preact / extended operands");
   MEANT_REQUIRE(!f32out || meant_aligned16(a.C), MEANT_ERR_ARG, "gemm_bf16_nt: float output must be 16-byte aligned");
-  const int64_t ldc_h = f32out ? 2 * a.ldc : a.ldc;    // C's row stride in 2-byte units
   MEANT_REQUIRE(!a.bres || (a.bres_rows > 0 && (a.N & 7) == 0 && meant_aligned16(a.bres)), MEANT_ERR_ARG, "gemm_bf16_nt: bad broadcast residual");
   MEANT_REQUIRE(!ext || (!a.rot_qa && !(a.epilogue & MEANT_EPI_SIGMOID)), MEANT_ERR_UNSUPPORTED, "gemm_bf16_nt: extended epilogue with rotary / sigmoid");
   MEANT_REQUIRE(!a.rot_qa || (!a.residual && !a.preact && !act), MEANT_ERR_UNSUPPORTED, "gemm_bf16_nt: rotary epilogue with residual / activation / preact");
   MEANT_REQUIRE(!a.sub || (a.sub_coef && (a.ldsub & 7) == 0 && meant_aligned16(a.sub)), MEANT_ERR_ARG, "gemm_bf16_nt: bad sub operand");
-  if (a.rot_qa) meant_route_hit(ROUTE_NT_ROT);
-  // big tall problems: 256 x 256 tiles (half the operand bytes per FLOP) -- once there are enough of them to occupy at least
-  // half the CUs (the temporal encoder's 1536^2 Linears make 36: four times as many 128 x 128 tiles finish in a third of the time)
-  if (a.M >= 1024 && a.N % 256 == 0 && ceil_div(a.M, B2) * (a.N / B2) * 2 >= meant_num_cus()) {
-    const int64_t ntm2 = ceil_div(a.M, B2), ntn2 = a.N / B2;
-    MEANT_REQUIRE(ntm2 * ntn2 < 2147483647LL, MEANT_ERR_UNSUPPORTED, "gemm_bf16_nt: grid too large");
-    // option nt_stream = 0 forces the one-tile-per-workgroup kernel (A/B measurements)
-    const bool stream_ok = meant_opt(MEANT_OPT_NT_STREAM) != 0 && !ktail;
-    // Ragged M, option nt_ragged = 1 (default): the streaming kernel takes all of it; its last row tile is moved up so that it
-    // ENDS at row M and recomputes up to 255 rows of its neighbour.  Every element of C is a function of its own row of A
-    // and column of W with a fixed K order, so both tiles store identical bits (no cost in the K-loop, no second launch:
-    // the 32 trailing rows of the TimeSformer's 75 296 tokens cost 12 extra launches of 13-97 us per layer as a split).
-    // Needs an out-of-place epilogue: a residual (or A) that aliases C would be read after the neighbour's store.
-    const auto overlaps = [](const void* p, int64_t ld, const void* q, int64_t ldq, int64_t rows) {
-      const char *p0 = (const char*)p, *q0 = (const char*)q;
-      return p && q && p0 < q0 + rows * ldq * 2 && q0 < p0 + rows * ld * 2;
+  // one launch: `g` is `a`, or the head or the tail of its split (the same epilogue, so the checks above and ext / act / f32out hold for it)
+  return nt_walk(a, meant_num_cus(), meant_route_hit, [&](const GemmBf16Args& g, const NtPlan& p) -> int {
+    const auto one_tile = [&](auto kernel, int threads, size_t lds, const char* name) -> int {
+      MEANT_RAISE_LDS(kernel, lds);
+      hipLaunchKernelGGL(kernel, dim3((unsigned)(p.ntm * p.ntn)), dim3(threads), lds, stream, g, (int)p.ntm, (int)p.ntn);
+      MEANT_LAUNCH_CHECK(name);
+      return MEANT_OK;
     };
-    const bool ragged_overlap = stream_ok && meant_opt(MEANT_OPT_NT_RAGGED) != 0 && a.M % B2 != 0 && a.K >= 4 * BK && (a.ldc & 7) == 0 &&
-                                (!a.residual || (a.ldr & 7) == 0) && !overlaps(a.C, ldc_h, a.residual, a.ldr, a.M) &&
-                                !overlaps(a.C, ldc_h, a.sub, a.ldsub, a.M) &&
-                                !overlaps(a.C, ldc_h, a.A, a.lda, a.M) && (!a.preact || !overlaps(a.preact, a.ldc, a.A, a.lda, a.M));
-    // nt_ragged = 0 (or aliasing operands): the streaming kernel takes the first floor(M / 256) * 256 rows, the remaining < 256 rows go
-    // to the 128 x 128 kernel as a second launch (row-local epilogues only: the rotary epilogue indexes its tables by the
-    // absolute row, so it splits only where the boundary is a multiple of the sequence length).
-    const int64_t m_full = (a.M / B2) * B2;
-    if (!ragged_overlap && stream_ok && m_full >= 1024 && m_full != a.M && a.K >= 4 * BK && (a.ldc & 7) == 0 && (!a.residual || (a.ldr & 7) == 0) &&
-        (!a.rot_qa || m_full % a.rot_S == 0)) {
-      GemmBf16Args head = a, tail = a;
-      head.M = m_full;
-      tail.M = a.M - m_full;
-      tail.A = a.A + m_full * a.lda;
-      tail.C = a.C + m_full * ldc_h;
-      if (a.residual) tail.residual = a.residual + m_full * a.ldr;
-      if (a.preact) tail.preact = a.preact + m_full * a.ldc;
-      if (a.row_scale) tail.row_scale = a.row_scale + m_full;
-      if (a.sub) { tail.sub = a.sub + m_full * a.ldsub; tail.sub_coef = a.sub_coef + m_full; }
-      MEANT_REQUIRE(!a.bres || m_full % a.bres_rows == 0, MEANT_ERR_UNSUPPORTED, "gemm_bf16_nt: broadcast residual across the head / tail split");
-      if (a.bres) tail.bres = a.bres + (m_full / a.bres_rows) * a.N;
-      meant_route_hit(ROUTE_NT_SPLIT);
-      const int rc = gemm_bf16_nt_launch(head, stream);
-      return rc ? rc : gemm_bf16_nt_launch(tail, stream);
-    }
-    // the streaming kernel (ping-pong form: the two waves of a SIMD alternate between MFMA and load halves) needs four K-steps;
-    // shorter K goes to the one-tile kernel below
-    if (stream_ok && (a.M % B2 == 0 || ragged_overlap) && a.K >= 4 * BK && (a.ldc & 7) == 0 && (!a.residual || (a.ldr & 7) == 0)) {
-      if (ragged_overlap) meant_route_hit(ROUTE_NT_OVERLAP);
-      int ncu = meant_num_cus() & ~7;
-      const int cap = meant_opt(MEANT_OPT_NT_GRID_CAP) & ~7;     // tests: fewer workgroups => more tiles each, dry XCDs steal
-      if (cap >= 8 && cap < ncu) ncu = cap;
-      const int grid = (int)(ntm2 * ntn2 < ncu ? ((ntm2 * ntn2 + 7) / 8) * 8 : ncu);
-      // Tile counters: one slot per (device, stream).  Launches on one stream execute in order and a launch leaves its
-      // slot zeroed (last workgroup out), so a slot is never shared by two launches in flight -- by construction, not by
-      // distance.  A stream beyond the table's capacity gets the fixed walk (sched = nullptr).  Option nt_dynamic = 0 forces it.
-      const int dynmode = meant_opt(MEANT_OPT_NT_DYNAMIC);
-      TileSched* sched = (dynmode != 0 && grid <= 512) ? tile_sched_for(stream) : nullptr;
-      meant_route_hit(a.rot_qa ? ROUTE_NT256S_ROT : ROUTE_NT256S);
-      const dim3 g3((unsigned)grid), b3(512);
-      // rotary mode: panels of one position range after the other (see the kernel's `origin`)
-      int rotP = 0;
-      if (a.rot_qa && a.rot_S % B2 == 0 && a.rot_S / B2 > 1 && a.rot_S / B2 < 256 && a.M % B2 == 0 && ntm2 % (a.rot_S / B2) == 0) rotP = (int)(a.rot_S / B2);
-      // the epilogue's options as a template parameter (see nt256_wave_epilogue): the combinations the models run get straight-line
-      // code, anything else the generic instantiation with run-time flags
-      int emode = NTE_GENERIC;
-      if (a.rot_qa) emode = NTE_ROT;
-      else if (f32out) emode = NTE_GENERIC;
-      else if (ext) emode = NTE_EXT;
-      else if (!a.residual && !a.preact && !act) emode = NTE_PLAIN;
-      else if (a.residual && !a.preact && !act) emode = NTE_RES;
-      else if (!a.residual && a.preact && (a.epilogue & MEANT_EPI_GELU) && !(a.epilogue & MEANT_EPI_SIGMOID)) emode = NTE_GELU_PRE;
-#define PP_LAUNCH(MODE_) hipLaunchKernelGGL((gemm_bf16_nt256p_kernel<MODE_>), g3, b3, RING * T2_BYTES, stream, a, (int)ntm2, (int)ntn2, sched, dynmode | (rotP << 16))
-      switch (emode) {
-        case NTE_PLAIN: PP_LAUNCH(NTE_PLAIN); break;
-        case NTE_RES: PP_LAUNCH(NTE_RES); break;
-        case NTE_GELU_PRE: PP_LAUNCH(NTE_GELU_PRE); break;
-        case NTE_ROT: PP_LAUNCH(NTE_ROT); break;
-        case NTE_EXT: PP_LAUNCH(NTE_EXT); break;
-        default: PP_LAUNCH(NTE_GENERIC); break;
-      }
-#undef PP_LAUNCH
-    } else if (ktail) {
-      MEANT_RAISE_LDS(gemm_bf16_nt256_kernel<true>, 4 * T2_BYTES);
-      meant_route_hit(ROUTE_NT256K);
-      hipLaunchKernelGGL(gemm_bf16_nt256_kernel<true>, dim3((unsigned)(ntm2 * ntn2)), dim3(512), 4 * T2_BYTES, stream, a, (int)ntm2, (int)ntn2);
-    } else {
-      meant_route_hit(ROUTE_NT256);
-      hipLaunchKernelGGL(gemm_bf16_nt256_kernel<false>, dim3((unsigned)(ntm2 * ntn2)), dim3(512), 4 * T2_BYTES, stream, a, (int)ntm2, (int)ntn2);
-    }
-    MEANT_LAUNCH_CHECK("gemm_bf16_nt256");
-    return MEANT_OK;
-  }
-  const int64_t ntm = ceil_div(a.M, BM), ntn = ceil_div(a.N, BN);
-  MEANT_REQUIRE(ntm * ntn < 2147483647LL, MEANT_ERR_UNSUPPORTED, "gemm_bf16_nt: grid too large");
-  const size_t lds = 128 * (128 + 4) * sizeof(float);   // 67584 B: covers the 64 KiB of staging buffers too
-  if (ktail) {
-    MEANT_RAISE_LDS(gemm_bf16_nt_kernel<true>, lds);
-    meant_route_hit(ROUTE_NT128K);
-    hipLaunchKernelGGL(gemm_bf16_nt_kernel<true>, dim3((unsigned)(ntm * ntn)), dim3(256), lds, stream, a, (int)ntm, (int)ntn);
-    MEANT_LAUNCH_CHECK("gemm_bf16_nt_ktail");
-    return MEANT_OK;
-  }
-  MEANT_RAISE_LDS(gemm_bf16_nt_kernel<false>, lds);
-  meant_route_hit(ROUTE_NT128);
-  hipLaunchKernelGGL(gemm_bf16_nt_kernel<false>, dim3((unsigned)(ntm * ntn)), dim3(256), lds, stream, a, (int)ntm, (int)ntn);
-  MEANT_LAUNCH_CHECK("gemm_bf16_nt");
-  return MEANT_OK;
+    const size_t lds128 = 128 * (128 + 4) * sizeof(float);   // 67584 B: covers the 64 KiB of staging buffers too
+    if (p.kind == NT128)
+      return p.ktail ? one_tile(gemm_bf16_nt_kernel<true>, 256, lds128, "gemm_bf16_nt_ktail") : one_tile(gemm_bf16_nt_kernel<false>, 256, lds128, "gemm_bf16_nt");
+    if (p.kind == NT256)
+      return p.ktail ? one_tile(gemm_bf16_nt256_kernel<true>, 512, 4 * T2_BYTES, "gemm_bf16_nt256")
+                     : one_tile(gemm_bf16_nt256_kernel<false>, 512, 4 * T2_BYTES, "gemm_bf16_nt256");
+    // Tile counters: one slot per (device, stream).  Launches on one stream execute in order and a launch leaves its
+    // slot zeroed (last workgroup out), so a slot is never shared by two launches in flight -- by construction, not by
+    // distance.  A stream beyond the table's capacity gets the fixed walk (sched = nullptr).  Option nt_dynamic = 0 forces it.
+    const int dynmode = meant_opt(MEANT_OPT_NT_DYNAMIC);
+    TileSched* sched = (dynmode != 0 && p.grid <= 512) ? tile_sched_for(stream) : nullptr;
+    const auto streaming = [&](auto mode) -> int {
+      MEANT_RAISE_LDS((gemm_bf16_nt256p_kernel<mode.value>), RING * T2_BYTES);
+      hipLaunchKernelGGL((gemm_bf16_nt256p_kernel<mode.value>), dim3((unsigned)p.grid), dim3(512), RING * T2_BYTES, stream, g, (int)p.ntm, (int)p.ntn,
+                         sched, dynmode | (p.rotP << 16));
+      MEANT_LAUNCH_CHECK("gemm_bf16_nt256");
+      return MEANT_OK;
+    };
+    // the epilogue's options as a template parameter (see nt256_wave_epilogue): the combinations the models run get straight-line
+    // code, anything else the generic instantiation with run-time flags
+    using std::integral_constant;
+    if (g.rot_qa) return streaming(integral_constant<int, NTE_ROT>{});
+    if (f32out) return streaming(integral_constant<int, NTE_GENERIC>{});
+    if (ext) return streaming(integral_constant<int, NTE_EXT>{});
+    if (!g.residual && !g.preact && !act) return streaming(integral_constant<int, NTE_PLAIN>{});
+    if (g.residual && !g.preact && !act) return streaming(integral_constant<int, NTE_RES>{});
+    if (!g.residual && g.preact && (g.epilogue & MEANT_EPI_GELU) && !(g.epilogue & MEANT_EPI_SIGMOID)) return streaming(integral_constant<int, NTE_GELU_PRE>{});
+    return streaming(integral_constant<int, NTE_GENERIC>{});
+  });
 }
 
 static int tn_tail(const bf16* dY, int64_t lddy, const bf16* X, int64_t ldx, float* dW, float* dbias, int64_t M, int64_t N, int64_t K,
                    hipStream_t stream) {
   // fewer than 64 trailing token rows: exact generic kernel, accumulating into the same dW / dbias
   meant_route_hit(ROUTE_TN_TAIL);
-  GemmF32Args g{};
-  g.in_dtype = MEANT_BF16; g.out_dtype = MEANT_F32;
-  g.A = dY; g.B = X; g.C = dW;
-  g.M = N; g.N = K; g.K = M; g.nb1 = 1; g.nb2 = 1;
-  g.sA[2] = 1; g.sA[3] = lddy; g.sB[2] = ldx; g.sB[3] = 1; g.sC[2] = K; g.sC[3] = 1;
-  g.alpha = 1.f; g.accumulate = 1;
-  int rc = gemm_f32_launch(g, stream);
+  int rc = gemm_f32_launch(f32_rowmajor(true, dY, lddy, X, ldx, dW, K, N, K, M, MEANT_BF16), stream);
   if (rc) return rc;
   if (dbias) return colsum_launch(dY, lddy, dbias, M, N, MEANT_BF16, 1, stream);
   return MEANT_OK;
 }
 
-// launch geometry of the 256 x 256 dW kernel (shared by the launcher and the workspace query)
-static void tn256_geometry(int64_t M, int64_t N, int64_t K, int64_t& splits2, int64_t& rows2) {
-  // one resident block per CU: size the launch to whole rounds of the CU count (a lone block in an extra
-  // round would cost a full round of time) -- one round when every block still gets >= 32 tiles of 64 rows
-  int ncu = meant_num_cus();
-  if (ncu <= 0) ncu = 256;
-  const int64_t tiles2 = (N / 256) * (K / 256);
-  splits2 = ncu / tiles2;
-  if (splits2 < 1) splits2 = 1;
-  const int64_t max2 = ceil_div(M, 32 * TN_BKM);
-  if (splits2 > max2) splits2 = max2;
-  rows2 = ceil_div(ceil_div(M, splits2), TN_BKM) * TN_BKM;
-  splits2 = ceil_div(M, rows2);
+// ---- which kernel a dW GEMM takes, and its launch geometry: read by the workspace query, both launchers and meant_debug_gemm_route.
+// Pure, as nt_plan is.  `listed`: the caller has a list of live 64-row blocks the 256 x 256 kernel may reduce over.
+enum TnKind { TN128 = ROUTE_TN128, TN256 = ROUTE_TN256, TN256_DET = ROUTE_TN256_DET, TN256_ROWS = ROUTE_TN256_ROWS };   // a kind is its route counter
+struct TnPlan {
+  TnKind kind;
+  int64_t tail_rows, rows;                             // M % 64 trailing token rows (the exact generic kernel) and the rows in front of them (0: no MFMA launch)
+  int64_t ntn, ntk;                                    // tiles of the kind's size along N and K
+  int64_t splits, rows_per;                            // the token axis in `splits` parts of rows_per rows (a multiple of 64)
+  size_t ws_bytes;                                     // TN256_DET: the splits' partial sums and partial bias sums
+};
+
+static TnPlan tn_plan(int64_t M, int64_t N, int64_t K, bool listed, int ncus) {
+  const bool det = meant_opt(MEANT_OPT_DETERMINISTIC) != 0;
+  TnPlan p{};
+  p.tail_rows = M % TN_BKM;
+  p.rows = M = M - p.tail_rows;
+  const bool t256 = N % 256 == 0 && K % 256 == 0 && M >= 4096;
+  // the list form has no deterministic variant and no tail; whatever it does not take runs the full reduction
+  p.kind = !t256 ? TN128 : det ? TN256_DET : listed && p.tail_rows == 0 && M / TN_BKM < (1LL << 30) ? TN256_ROWS : TN256;
+  if (M == 0) return p;
+  p.ntn = ceil_div(N, t256 ? 256 : 128); p.ntk = ceil_div(K, t256 ? 256 : 128);
+  // 256 x 256, one resident block per CU: size the launch to whole rounds of the CU count (a lone block in an extra
+  // round would cost a full round of time) -- one round when every block still gets >= 32 tiles of 64 rows.
+  // 128 x 128: split the token axis so that the launch has >= ~4 blocks per CU
+  p.splits = t256 ? (ncus > 0 ? ncus : 256) / (p.ntn * p.ntk) : ceil_div(1024, p.ntn * p.ntk);
+  const int64_t max_splits = ceil_div(M, t256 ? 32 * TN_BKM : 256);
+  if (p.splits > max_splits) p.splits = max_splits;
+  if (p.splits < 1 || (det && !t256)) p.splits = 1;    // 128 x 128, deterministic: every output element has exactly one writer
+  p.rows_per = ceil_div(ceil_div(M, p.splits), TN_BKM) * TN_BKM;   // each split is a multiple of 64 rows
+  p.splits = ceil_div(M, p.rows_per);
+  if (p.kind == TN256_DET) p.ws_bytes = (size_t)(p.splits * N * K + p.splits * p.ntk * 4 * N) * sizeof(float);
+  return p;
 }
-static bool tn256_ok(int64_t M, int64_t N, int64_t K) { return N % 256 == 0 && K % 256 == 0 && M >= 4096; }
 
 size_t gemm_bf16_tn_ws(int64_t M, int64_t N, int64_t K) {
-  if (!meant_opt(MEANT_OPT_DETERMINISTIC)) return 0;
-  M -= M % TN_BKM;
-  if (!tn256_ok(M, N, K)) return 0;
-  int64_t splits2, rows2;
-  tn256_geometry(M, N, K, splits2, rows2);
-  return (size_t)(splits2 * N * K + splits2 * (K / 256) * 4 * N) * sizeof(float);
+  return meant_opt(MEANT_OPT_DETERMINISTIC) ? tn_plan(M, N, K, false, meant_num_cus()).ws_bytes : 0;   // (no device look-up without the option)
+}
+
+// dW over all token rows (rows == nullptr) or over a list of 64-row blocks of the token axis (gemm_bf16_tn256p_kernel<false, true>): dW += sum
+// over the listed blocks; every row of dY outside them is zero by the caller's word, so whatever the list form does not take -- the
+// deterministic option, shapes the 256 x 256 kernel does not serve -- runs the full reduction instead and adds the same sums.
+int gemm_bf16_tn_rows_launch(const bf16* dY, int64_t lddy, const bf16* X, int64_t ldx, float* dW, float* dbias, const int* rows,
+                             const int* rows_count, int64_t M, int64_t N, int64_t K, void* ws, size_t ws_bytes, hipStream_t stream) {
+  MEANT_REQUIRE(rows16(dY, lddy, X, ldx), MEANT_ERR_ARG, "gemm_bf16_tn: operands must be 16-byte aligned with row strides that are multiples of 8");
+  MEANT_REQUIRE(gemm_bf16_tn_ok(dY, lddy, X, ldx, N, K), MEANT_ERR_UNSUPPORTED, "gemm_bf16_tn: N and K must be >= 8");
+  const TnPlan p = tn_plan(M, N, K, rows && rows_count, meant_num_cus());   // the splits are sized for the full M: a list's count is known on the device only
+  if (p.tail_rows) {
+    int rc = tn_tail(dY + p.rows * lddy, lddy, X + p.rows * ldx, ldx, dW, dbias, p.tail_rows, N, K, stream);
+    if (rc || p.rows == 0) return rc;
+  }
+  if (p.kind != TN128) {
+    float *part = nullptr, *pbias = nullptr;
+    if (p.kind == TN256_DET) {
+      MEANT_REQUIRE(ws && ws_bytes >= p.ws_bytes && meant_aligned16(ws), MEANT_ERR_WORKSPACE,
+                    "linear_bwd_dw (deterministic): workspace of %zu bytes needed (meant_linear_bwd_dw_ws), got %zu", p.ws_bytes, ws_bytes);
+      part = (float*)ws;
+      pbias = part + p.splits * N * K;
+    }
+    meant_route_hit(p.kind);
+    // the one launch site of the 256 x 256 dW kernel.  Its `rows_per_split` argument is two things: the token rows of a split in the two
+    // plain forms; in the list form, where a split's share follows from *rows_count on the device, the NUMBER of splits.
+    const int64_t rows_per_or_splits = p.kind == TN256_ROWS ? p.splits : p.rows_per;
+    const auto launch = [&](auto det, auto listed, const char* name) -> int {
+      MEANT_RAISE_LDS((gemm_bf16_tn256p_kernel<det.value, listed.value>), RING * T2_BYTES);
+      hipLaunchKernelGGL((gemm_bf16_tn256p_kernel<det.value, listed.value>), dim3((unsigned)(p.ntn * p.ntk * p.splits)), dim3(512), RING * T2_BYTES, stream,
+                         dY, lddy, X, ldx, dW, dbias, p.rows, N, K, (int)p.ntn, (int)p.ntk, rows_per_or_splits, part, pbias,
+                         listed.value ? rows : nullptr, listed.value ? rows_count : nullptr);
+      MEANT_LAUNCH_CHECK(name);
+      return MEANT_OK;
+    };
+    if (p.kind == TN256_ROWS) return launch(std::false_type{}, std::true_type{}, "gemm_bf16_tn256<rows>");
+    if (p.kind == TN256) return launch(std::false_type{}, std::false_type{}, "gemm_bf16_tn256");
+    const int rc = launch(std::true_type{}, std::false_type{}, "gemm_bf16_tn256<det>");
+    if (rc) return rc;
+    hipLaunchKernelGGL(tn256_reduce_kernel, dim3((unsigned)ceil_div(N * K / 4, 256)), dim3(256), 0, stream, part, dbias ? pbias : nullptr, dW, dbias,
+                       N, K, (int)p.ntk, (int)(p.ntn * p.ntk), (int)p.splits);
+    MEANT_LAUNCH_CHECK("tn256_reduce");
+    return MEANT_OK;
+  }
+  MEANT_RAISE_LDS(gemm_bf16_tn_kernel, 4 * TN_TILE_BYTES);
+  meant_route_hit(p.kind);
+  hipLaunchKernelGGL(gemm_bf16_tn_kernel, dim3((unsigned)(p.ntn * p.ntk * p.splits)), dim3(256), 4 * TN_TILE_BYTES, stream, dY, lddy, X,
+                     ldx, dW, p.rows, N, K, (int)p.ntn, (int)p.ntk, p.rows_per);
+  MEANT_LAUNCH_CHECK("gemm_bf16_tn");
+  if (dbias) return colsum_launch(dY, lddy, dbias, p.rows, N, MEANT_BF16, 1, stream);
+  return MEANT_OK;
 }
 
 int gemm_bf16_tn_launch(const bf16* dY, int64_t lddy, const bf16* X, int64_t ldx, float* dW, float* dbias, int64_t M, int64_t N,
                         int64_t K, void* ws, size_t ws_bytes, hipStream_t stream) {
-  const bool det = meant_opt(MEANT_OPT_DETERMINISTIC) != 0;
-  MEANT_REQUIRE((lddy % 8) == 0 && (ldx % 8) == 0 && meant_aligned16(dY) && meant_aligned16(X), MEANT_ERR_ARG,
-                "gemm_bf16_tn: operands must be 16-byte aligned with row strides that are multiples of 8");
-  MEANT_REQUIRE(N >= 8 && K >= 8, MEANT_ERR_UNSUPPORTED, "gemm_bf16_tn: N and K must be >= 8");
-  const int64_t Mtail = M % TN_BKM;
-  if (Mtail) {
-    const int64_t Mmain = M - Mtail;
-    int rc = tn_tail(dY + Mmain * lddy, lddy, X + Mmain * ldx, ldx, dW, dbias, Mtail, N, K, stream);
-    if (rc || Mmain == 0) return rc;
-    M = Mmain;
-  }
-  if (tn256_ok(M, N, K)) {
-    const int64_t ntn2 = N / 256, ntk2 = K / 256;
-    int64_t splits2, rows2;
-    tn256_geometry(M, N, K, splits2, rows2);
-    const dim3 grid((unsigned)(ntn2 * ntk2 * splits2));
-    if (det) {
-      const size_t need = (size_t)(splits2 * N * K + splits2 * ntk2 * 4 * N) * sizeof(float);
-      MEANT_REQUIRE(ws && ws_bytes >= need && meant_aligned16(ws), MEANT_ERR_WORKSPACE,
-                    "linear_bwd_dw (deterministic): workspace of %zu bytes needed (meant_linear_bwd_dw_ws), got %zu", need, ws_bytes);
-      float* part = (float*)ws;
-      float* pbias = part + splits2 * N * K;
-      meant_route_hit(ROUTE_TN256_DET);
-      MEANT_RAISE_LDS(gemm_bf16_tn256p_kernel<true>, RING * T2_BYTES);
-      hipLaunchKernelGGL(gemm_bf16_tn256p_kernel<true>, grid, dim3(512), RING * T2_BYTES, stream, dY, lddy, X, ldx, dW, dbias, M, N, K, (int)ntn2,
-                         (int)ntk2, rows2, part, pbias, (const int*)nullptr, (const int*)nullptr);
-      MEANT_LAUNCH_CHECK("gemm_bf16_tn256<det>");
-      hipLaunchKernelGGL(tn256_reduce_kernel, dim3((unsigned)ceil_div(N * K / 4, 256)), dim3(256), 0, stream, part, dbias ? pbias : nullptr, dW, dbias,
-                         N, K, (int)ntk2, (int)(ntn2 * ntk2), (int)splits2);
-      MEANT_LAUNCH_CHECK("tn256_reduce");
-      return MEANT_OK;
-    }
-    meant_route_hit(ROUTE_TN256);
-    MEANT_RAISE_LDS(gemm_bf16_tn256p_kernel<false>, RING * T2_BYTES);
-    hipLaunchKernelGGL(gemm_bf16_tn256p_kernel<false>, grid, dim3(512), RING * T2_BYTES, stream, dY, lddy, X, ldx, dW, dbias, M, N, K, (int)ntn2,
-                       (int)ntk2, rows2, (float*)nullptr, (float*)nullptr, (const int*)nullptr, (const int*)nullptr);
-    MEANT_LAUNCH_CHECK("gemm_bf16_tn256");
-    return MEANT_OK;
-  }
-  const int64_t ntn = ceil_div(N, 128), ntk = ceil_div(K, 128);
-  // split the token axis so that the launch has >= ~4 blocks per CU; each split is a multiple of 64 rows
-  int64_t splits = ceil_div(1024, ntn * ntk);
-  const int64_t max_splits = ceil_div(M, 256);
-  if (splits > max_splits) splits = max_splits;
-  if (splits < 1 || det) splits = 1;                 // deterministic: every output element has exactly one writer
-  int64_t rows_per = ceil_div(ceil_div(M, splits), TN_BKM) * TN_BKM;
-  splits = ceil_div(M, rows_per);
-  MEANT_RAISE_LDS(gemm_bf16_tn_kernel, 4 * TN_TILE_BYTES);
-  meant_route_hit(ROUTE_TN128);
-  hipLaunchKernelGGL(gemm_bf16_tn_kernel, dim3((unsigned)(ntn * ntk * splits)), dim3(256), 4 * TN_TILE_BYTES, stream, dY, lddy, X,
-                     ldx, dW, M, N, K, (int)ntn, (int)ntk, rows_per);
-  MEANT_LAUNCH_CHECK("gemm_bf16_tn");
-  if (dbias) return colsum_launch(dY, lddy, dbias, M, N, MEANT_BF16, 1, stream);
-  return MEANT_OK;
+  return gemm_bf16_tn_rows_launch(dY, lddy, X, ldx, dW, dbias, nullptr, nullptr, M, N, K, ws, ws_bytes, stream);
 }
 
-// The same over a list of 64-row blocks of the token axis (gemm_bf16_tn256p_kernel<false, true>): dW += sum over the listed blocks; every row
-// of dY outside them is zero by the caller's word, so whatever the list form does not take -- the deterministic option, shapes the
-// 256 x 256 kernel does not serve -- runs the full reduction instead and adds the same sums.
-int gemm_bf16_tn_rows_launch(const bf16* dY, int64_t lddy, const bf16* X, int64_t ldx, float* dW, float* dbias, const int* rows,
-                             const int* rows_count, int64_t M, int64_t N, int64_t K, void* ws, size_t ws_bytes, hipStream_t stream) {
-  const bool listed = rows && rows_count && !meant_opt(MEANT_OPT_DETERMINISTIC) && M % TN_BKM == 0 && tn256_ok(M, N, K) && (lddy % 8) == 0 &&
-                      (ldx % 8) == 0 && meant_aligned16(dY) && meant_aligned16(X) && M / TN_BKM < (1LL << 30);
-  if (!listed) return gemm_bf16_tn_launch(dY, lddy, X, ldx, dW, dbias, M, N, K, ws, ws_bytes, stream);
-  const int64_t ntn2 = N / 256, ntk2 = K / 256;
-  int64_t splits2, rows2;
-  tn256_geometry(M, N, K, splits2, rows2);             // sized for the full M: the count is known on the device only
-  meant_route_hit(ROUTE_TN256_ROWS);
-  MEANT_RAISE_LDS((gemm_bf16_tn256p_kernel<false, true>), RING * T2_BYTES);
-  hipLaunchKernelGGL((gemm_bf16_tn256p_kernel<false, true>), dim3((unsigned)(ntn2 * ntk2 * splits2)), dim3(512), RING * T2_BYTES, stream, dY, lddy,
-                     X, ldx, dW, dbias, M, N, K, (int)ntn2, (int)ntk2, splits2, (float*)nullptr, (float*)nullptr, rows, rows_count);
-  MEANT_LAUNCH_CHECK("gemm_bf16_tn256<rows>");
-  return MEANT_OK;
+// ---- diagnostics: the route counters a launch would hit, in hit order, from the plans above and nothing else (no launch, no device)
+extern "C" int meant_debug_gemm_route(const char* op, int64_t M, int64_t N, int64_t K, int facts, int64_t rot_S, int num_cus, void* names,
+                                      size_t names_bytes) {
+  const bool nt = op && !strcmp(op, "nt"), tn_rows = op && !strcmp(op, "tn_rows");
+  MEANT_REQUIRE((nt || tn_rows || (op && !strcmp(op, "tn"))) && M > 0 && N > 0 && K > 0 && rot_S >= 0 && rot_S < (1LL << 31) && names, MEANT_ERR_ARG,
+                "debug_gemm_route: op is \"nt\", \"tn\" or \"tn_rows\"; positive shape; 0 <= rot_S < 2^31; a buffer for the names");
+  std::string s;
+  const auto name = [&s](int route) { (s += s.empty() ? "" : " ") += meant_route_name(route); };
+  int rc = 0;
+  if (nt) {
+    // addresses that are never dereferenced: the rule reads strides, null / non-null and whether an operand's rows overlap C's
+    GemmBf16Args a = gemm_bf16_nt_args(nullptr, K, nullptr, nullptr, ceil_div(N, 8) * 8 + ((facts & MEANT_FACT_LDC_OFF8) ? 1 : 0), M, N, K);
+    a.ldr = ceil_div(N, 8) * 8 + ((facts & MEANT_FACT_LDR_OFF8) ? 1 : 0);
+    a.C = reinterpret_cast<bf16*>(uintptr_t(1) << 40);
+    const bf16* const apart = a.C + M * a.ldc;         // the first address behind C's rows
+    a.A = (facts & MEANT_FACT_ALIAS_C) && !(facts & MEANT_FACT_RESIDUAL) ? a.C : apart;
+    if (facts & MEANT_FACT_RESIDUAL) a.residual = (facts & MEANT_FACT_ALIAS_C) ? a.C : apart;
+    if (rot_S > 0) { a.rot_qa = reinterpret_cast<const float*>(apart); a.rot_S = (int)rot_S; }
+    rc = nt_walk(a, num_cus, name, [](const GemmBf16Args&, const NtPlan&) { return (int)MEANT_OK; });
+    if (!rc) rc = nt_streams(nt_plan(a, num_cus)) ? 1 : 0;
+  } else {
+    const TnPlan p = tn_plan(M, N, K, tn_rows, num_cus);
+    if (p.tail_rows) { name(ROUTE_TN_TAIL); name(ROUTE_GEMM_F32); }    // the exact engine counts its own launch
+    if (p.rows) name(p.kind);
+  }
+  MEANT_REQUIRE(s.size() < names_bytes, MEANT_ERR_WORKSPACE, "debug_gemm_route: %zu bytes needed for the names, got %zu", s.size() + 1, names_bytes);
+  memcpy(names, s.c_str(), s.size() + 1);
+  return rc;
 }

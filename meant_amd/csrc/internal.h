@@ -21,6 +21,9 @@ struct GemmF32Args {
   int ksplit = 0;           // 0: never split K; -1: the launcher may split K over several workgroups per tile (float atomics)
 };
 int gemm_f32_launch(const GemmF32Args& a, hipStream_t stream);
+// its arguments for row-major operands (api.hip): C[M,N] = A B^T ("NT"), or, tn, C[M,N] += A^T B in float
+GemmF32Args f32_rowmajor(bool tn, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int64_t M, int64_t N, int64_t K,
+                         int storage);
 
 // rotate 8 consecutive columns (4 pairs) with table rows A[0..7], B[0..7]: the rotary epilogue of the NT GEMMs (gemm_bf16.hip) and
 // the by-id forward's gather (qkv_fwd_by_id.hip), which must give the bits of the streaming GEMM's epilogue.  That kernel's build
@@ -67,8 +70,19 @@ struct GemmBf16Args {
   int col0 = 0;
   const int* panel_list = nullptr; const int* panel_count = nullptr;
 };
+// the plain product C[M,N] = A[M,K] B[N,K]^T with B dense (row stride K); the caller adds bias and the epilogue's operands
+inline GemmBf16Args gemm_bf16_nt_args(const void* A, int64_t lda, const void* B, void* C, int64_t ldc, int64_t M, int64_t N, int64_t K) {
+  GemmBf16Args a{};
+  a.A = (const bf16*)A; a.lda = lda; a.B = (const bf16*)B; a.ldb = K; a.C = (bf16*)C; a.ldc = ldc;
+  a.M = M; a.N = N; a.K = K;
+  return a;
+}
 int gemm_bf16_nt_launch(const GemmBf16Args& a, hipStream_t stream);
 bool gemm_bf16_nt_streams(const GemmBf16Args& a);   // the launch takes the streaming kernel over whole 256-row panels (what a panel list needs)
+// the MFMA kernels can take these operands: 16-byte aligned, row strides multiples of 8; K >= 8 and K % 8 == 0 (NT), N >= 8 and K >= 8 (TN).
+// Anything else is for the exact f32 engine (gemm_f32_launch).
+bool gemm_bf16_nt_ok(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t K);
+bool gemm_bf16_tn_ok(const void* dY, int64_t lddy, const void* X, int64_t ldx, int64_t N, int64_t K);
 int zero_panels_launch(bf16* C, int64_t ldc, int64_t cols, const int* panels, const int* count, int64_t npan, hipStream_t stream);
 // flags[list[i]] = 1 for i < *count (device memory; one list of the key-padding lists and its count), on a zeroed array of `len` bytes
 // (qkv_by_id.hip; the 64-row blocks of the by-id backward, the 256-row panels of the by-id forward)

@@ -115,12 +115,8 @@ bool fwd_byid_shape_ok(int64_t n, int64_t d, int64_t N3, int64_t V) {
   return n > 0 && d > 0 && N3 > 0 && V > 0 && n < (1ll << 31) && V < (1ll << 31) && d % 8 == 0 && N3 % 24 == 0 && N3 < (1ll << 22) && d < (1ll << 22);
 }
 
-// the two products the route stands for, as the launcher of the NT GEMM would see them
-GemmBf16Args shape_args(int64_t M, int64_t N, int64_t K) {
-  GemmBf16Args a{};
-  a.M = M; a.N = N; a.K = K; a.lda = K; a.ldb = K; a.ldc = N;
-  return a;
-}
+// a product the route stands for, as the launcher of the NT GEMM would see it
+GemmBf16Args shape_args(int64_t M, int64_t N, int64_t K) { return gemm_bf16_nt_args(nullptr, K, nullptr, nullptr, N, M, N, K); }
 
 }  // namespace
 

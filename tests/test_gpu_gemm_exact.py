@@ -110,6 +110,10 @@ QKV_STREAM = [(512, 256, 1), (512, 768, 1), (512, 768, 0), (196, 256, 1)]   # (S
 QKV_ONE = [(64, "nt128"), (72, "nt128k"), (200, "nt128k")]                  # K at G, S, H, Dh, R = 3, 24, 2, 16, 8
 QKV_TALL_ONE_TILE = [(128, "nt256"), (200, "nt256k")]                       # K at the S = 512 shape of QKV_STREAM
 EXT = ["nt256s", "nt_overlap", "nt128"]
+DW_TN128 = [(64, 8, 136), (128, 72, 72), (320, 136, 8), (1024, 72, 136), (1024, 264, 136)]
+DW_TN_TAIL = [(1, 72, 136), (63, 136, 72), (64 + 37, 72, 72), (320 + 37, 136, 136)]
+DW_TN256_M, DW_TN256_NK = [4096, 4288, 4288 + 37], [(256, 256), (512, 256), (256, 512)]
+DW_ROWS_M = [4096, 4288]                                                    # the row-list cases, at N, K = 256, 512
 
 
 def few_workgroups_shape(cus):
@@ -387,7 +391,7 @@ def run_dw(L, dev, M, N, K, *, dbias=True, rows=None, ops=None, what="", dtype=B
 
 
 @pytest.mark.parametrize("det", [0, 1], ids=["atomics", "det"])
-@pytest.mark.parametrize("M,N,K", [(64, 8, 136), (128, 72, 72), (320, 136, 8), (1024, 72, 136), (1024, 264, 136)])
+@pytest.mark.parametrize("M,N,K", DW_TN128)
 def test_dw_tn128(L, dev, M, N, K, det):
     """128 x 128 dW kernel; 320 and 1024 rows split unevenly over the token axis (64-row units)"""
     with case(L, f"dw tn128 ({M},{N},{K})", deterministic=det) as c:
@@ -396,7 +400,7 @@ def test_dw_tn128(L, dev, M, N, K, det):
             c.routes(tn128=1)
 
 
-@pytest.mark.parametrize("M,N,K", [(1, 72, 136), (63, 136, 72), (64 + 37, 72, 72), (320 + 37, 136, 136)])
+@pytest.mark.parametrize("M,N,K", DW_TN_TAIL)
 def test_dw_tn_tail(L, dev, M, N, K):
     """fewer than 64 trailing token rows go through the exact engine into the same accumulators"""
     with case(L, f"dw tn_tail ({M},{N},{K})") as c:
@@ -405,8 +409,8 @@ def test_dw_tn_tail(L, dev, M, N, K):
 
 
 @pytest.mark.parametrize("det", [0, 1], ids=["atomics", "det"])
-@pytest.mark.parametrize("M", [4096, 4288, 4288 + 37])
-@pytest.mark.parametrize("N,K", [(256, 256), (512, 256), (256, 512)])
+@pytest.mark.parametrize("M", DW_TN256_M)
+@pytest.mark.parametrize("N,K", DW_TN256_NK)
 def test_dw_tn256(L, dev, M, N, K, det):
     """256 x 256 dW kernel: even splits, the uneven splits of 67 blocks, a tail behind them; atomics and ordered partial sums both equal
     the integers, hence each other"""
@@ -432,7 +436,7 @@ def _blocks_case(L, dev, c, M, blocks, rows, det, what, live_rows=None):
 
 
 @pytest.mark.parametrize("det", [0, 1], ids=["list", "det"])
-@pytest.mark.parametrize("M", [4096, 4288])
+@pytest.mark.parametrize("M", DW_ROWS_M)
 @pytest.mark.parametrize("pick", ["one", "all", "alternate", "last"])
 def test_dw_rows_hand_made_lists(L, dev, M, pick, det):
     nblk = M // 64
