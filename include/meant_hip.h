@@ -105,7 +105,9 @@ int meant_get_option(const char* name, int* value);
  * (every meant_score_capture launch), "auroc_rank" (every meant_auroc_rank call with n > 0), "ce_soft_wave" / "ce_soft_block"
  * (meant_ce_probs_soft by form), "vqa_score" (every meant_vqa_score_update launch), "grad_stats" (every meant_grad_stats_f32 call
  * with n > 0), "optim_step" (every meant_optim_step_f32 launch), "qkv_by_id" (every meant_qkv_embed_bwd_by_id call that runs its
- * shared stage) and "qkv_fwd_by_id" (every meant_qkv_embed_fwd_by_id call));
+ * shared stage), "qkv_fwd_by_id" (every meant_qkv_embed_fwd_by_id call), "ce_hard_wave" / "ce_hard_block" (meant_ce_probs_hard by
+ * form), "ce_hard_vocab" (every meant_softmax_ce_hard_fwd launch), "ce_probs" (every meant_ce_probs launch) and "softmax_ce"
+ * (every meant_softmax_ce_fwd launch));
  * -1 for an unknown name.  The names label routes, not kernels: "nt256s" / "nt256s_rot" count launches of the streaming
  * GEMM (whichever kernel implements it), "nt_split" the ragged head + tail split.  Tests use it to prove that a shape
  * reaches the kernel it is meant to exercise. */
@@ -691,6 +693,52 @@ int meant_auroc_rank(const uint32_t* keys, const int32_t* labels, int64_t n, int
  * or C within 1024 of 2^31: MEANT_ERR_UNSUPPORTED; both before any launch. */
 int meant_ce_probs_soft(const float* probs, int64_t ldp, const void* target, int64_t ldt, int target_dtype,
                         float* row_loss, float* loss, float* dprobs, int64_t ldd, int64_t B, int64_t C, void* stream);
+/* ---- hard-label cross-entropy with class weights, label smoothing and ignore_index ---------------------------------------------
+ * torch's F.cross_entropy(x, y, weight=w, label_smoothing=eps, ignore_index=) for integer targets y int64.  weight: NULL (w_c = 1)
+ * or C floats; W = sum_c w_c (C without weights); eps in [0, 1].  A row counts iff y != ignore_index && 0 <= y < C (the predicate
+ * of meant_softmax_ce_fwd and meant_select_rows).  For a row that counts, with logp = log_softmax(x):
+ *   row_loss = (1 - eps) w_y (-logp_y) + (eps / C) sum_c w_c (-logp_c),   row_w = w_y (the same bits),
+ *   d row_loss / d x_j = (1 - eps) w_y (p_j - [j == y]) + (eps / C) (W p_j - w_j),
+ * and loss = sum row_loss / sum row_w over the rows that count; 0, with zero gradients, when no row counts or the denominator is 0
+ * (this library's convention, not torch's NaN).  A row that does not count has row_loss = row_w = 0 and an exact-zero gradient row;
+ * its logits are never read (they may hold NaN or inf) and no address is formed from its target.  Evaluated with M = max_c x_c,
+ * S = sum_c exp(x_c - M), -logp_c = log S + (M - x_c): the smoothing term is W log S + sum_c w_c (M - x_c), and no term grows with a
+ * shift of the row.  A -inf logit is a masked column (probability 0) at eps == 0; with eps > 0 a -inf column is outside the contract
+ * (torch gives inf or NaN there, and so may these entries).  A negative or non-finite class weight is the caller's business: the
+ * entries do not look for one and compute what the formulas give.
+ * stats: a device block of MEANT_CE_STATS_BYTES, 8-byte aligned, OVERWRITTEN by every call that takes one:
+ *   float loss @0, float gscale = 1 / den @4 (0 if den == 0), double num @8, double den @16, int64 n_counted @24 (rows that count),
+ *   int64 n_ignored @32 (y == ignore_index), int64 n_invalid @40 (every other y outside [0, C)).
+ * meant_ce_hard_reduce: the block from row_loss, row_w float [T] and target int64 [T]: one workgroup, the rows that count added in
+ * double in an order fixed by T (the entries of the other rows are not read).  T == 0 gives zeros.
+ * meant_ce_probs_hard: the class head's form on f32 rows probs [B, ldp]: row_loss, row_w [B], dprobs (optional, [B, ldd], must not
+ * alias probs) = d row_loss / d probs, NOT yet divided by the denominator (multiply by stats' gscale), and the block, in two launches.
+ * Forms (route names): "ce_hard_wave" for C <= 1024, a wave per row, four rows per workgroup; "ce_hard_block" above, a 256-thread
+ * workgroup per row, the row in registers up to C = 4096 (read once, the gradient written once) and read twice beyond.  Nothing at
+ * or beyond column C of a row is addressed; rows may start at any element.
+ * meant_softmax_ce_hard_fwd / _bwd: the large-vocabulary form on logits act [T, ld] (V <= ld valid columns, ld % 8 == 0), the shape
+ * of meant_softmax_ce_fwd / _bwd, which keep serving calls without weights and smoothing.  fwd: one read of each row that counts
+ * into row_loss, row_w [T] and stat float [T, 4] = (M, log S, A = (1 - eps) w_y + eps W / V, a = (1 - eps) w_y), then the block;
+ * route name "ce_hard_vocab".  bwd: dlogits[t, j] = (A softmax_j - a [j == y] - (eps / V) w_j) * gscale[0] for j < V, exact zeros
+ * for the padding columns and for the rows that do not count; gscale is a device scalar (d loss * the block's gscale); dlogits may
+ * alias logits.  weight, when given, is read per column by the forward and the backward at eps > 0 and at the target alone otherwise.
+ * No atomics in any of the four: the same call gives the same bits, whatever "deterministic" says.
+ * A null pointer (weight, and dprobs, may be null), eps outside [0, 1] or not finite, B <= 0 (T < 0), C <= 0, a row stride below C,
+ * ld % 8 != 0, an unknown dtype, a misaligned operand (element size; stats 8 bytes; the large-vocabulary form: logits, dlogits,
+ * weight and stat 16 bytes), dprobs == probs or row_w == row_loss: MEANT_ERR_ARG; more than 2^31 - 1 workgroups (B, T; B / 4 in the
+ * wave form) or C within 1024 of 2^31: MEANT_ERR_UNSUPPORTED; both before any launch. */
+enum meant_ce_stats_layout { MEANT_CE_STATS_BYTES = 48 };
+int meant_ce_hard_reduce(const float* row_loss, const float* row_w, const int64_t* target, int64_t T, int64_t C,
+                         int64_t ignore_index, void* stats, void* stream);
+int meant_ce_probs_hard(const float* probs, int64_t ldp, const int64_t* target, const float* weight, float eps,
+                        int64_t ignore_index, float* row_loss, float* row_w, float* dprobs, int64_t ldd, int64_t B, int64_t C,
+                        void* stats, void* stream);
+int meant_softmax_ce_hard_fwd(const void* logits, int64_t ld, const int64_t* target, const float* weight, float eps, int64_t T,
+                              int64_t V, int64_t ignore_index, float* row_loss, float* row_w, float* stat, void* stats, int dtype,
+                              void* stream);
+int meant_softmax_ce_hard_bwd(const void* logits, int64_t ld, const int64_t* target, const float* weight, float eps,
+                              const float* stat, int64_t T, int64_t V, int64_t ignore_index, const float* gscale, void* dlogits,
+                              int dtype, void* stream);
 /* VQA score counts.  For each row: j = argmax over the C score columns in torch's order (lowest index on a tie, a NaN above
  * everything: the rule of meant_metrics_update); w = target[b, j].  scores [B, lds], target [B, ldt], each MEANT_F32 | MEANT_BF16.
  * state = int64 [4], zeroed once by the caller, only ever added to: sum_fx += llrint((double)w * 2^32), rows += 1; a row whose w is

@@ -14,5 +14,6 @@ from .modules import (  # noqa: F401
 
 from . import parallel, train, data, metrics  # noqa: F401,E402
 from .metrics import f1_metrics, auroc, vqa_score, metric_group  # noqa: F401,E402
+from .train import cross_entropy_on_probs, balanced_class_weights  # noqa: F401,E402
 
 __version__ = "0.1.0"

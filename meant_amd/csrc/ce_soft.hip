@@ -16,6 +16,7 @@
 // Determinism: no atomics.  Every sum has an order fixed by (C, form); a second launch of ONE workgroup adds the B row losses in an
 // order fixed by B (in double) and OVERWRITES loss[0].  The `deterministic` option has nothing to switch.
 #include "common.h"
+#include "ce_rows.h"
 
 namespace {
 
@@ -24,33 +25,6 @@ constexpr int CS_NR = 16;                              // columns per lane held 
 constexpr int CS_WAVE_MAXC = 64 * CS_NR;               // 1024: the cut between the wave and the block form
 constexpr int CS_REG_MAXC = CS_THREADS * CS_NR;        // 4096: the block form keeps the row in registers up to here
 constexpr int CS_UNROLL = 4;                           // streaming pass: columns per thread and step
-
-// sums / maxima over the G threads that share a row, every thread gets the result.  G == 64: butterflies.  G == 256: the four
-// waves' results through LDS, added in wave order; every thread of the workgroup must call (two barriers).
-template <int G, int N>
-__device__ __forceinline__ void group_sum(float (&v)[N], float* lds) {
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] = wave_sum(v[i]);
-  if (G == 64) return;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();                                     // the previous call's readers are done with lds
-  if (lane == 0)
-#pragma unroll
-    for (int i = 0; i < N; ++i) lds[wave * N + i] = v[i];
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] = (lds[i] + lds[N + i]) + (lds[2 * N + i] + lds[3 * N + i]);
-}
-template <int G>
-__device__ __forceinline__ float group_max(float v, float* lds) {
-  v = wave_max(v);
-  if (G == 64) return v;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) lds[wave] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(lds[0], lds[1]), fmaxf(lds[2], lds[3]));
-}
 
 // ---- the row in registers: G = 64 (C <= 1024, a wave per row) or G = 256 (C <= 4096, a workgroup per row) ------------------------
 template <typename TT, int G>

@@ -63,6 +63,7 @@ enum meant_route_id {
   ROUTE_METRICS_ROWS, ROUTE_METRICS_WAVE, ROUTE_METRICS_LABELS, ROUTE_TN256_ROWS, ROUTE_ATTN_CLS_SPLIT, ROUTE_ROWS_ELEM,
   ROUTE_SCORE_CAPTURE, ROUTE_AUROC_RANK, ROUTE_CE_SOFT_WAVE, ROUTE_CE_SOFT_BLOCK, ROUTE_VQA_SCORE,
   ROUTE_GRAD_STATS, ROUTE_OPTIM_STEP, ROUTE_QKV_BY_ID, ROUTE_QKV_FWD_BY_ID,
+  ROUTE_CE_HARD_WAVE, ROUTE_CE_HARD_BLOCK, ROUTE_CE_HARD_VOCAB, ROUTE_CE_PROBS, ROUTE_SOFTMAX_CE,
   MEANT_ROUTE_COUNT
 };
 void meant_route_hit(int route);

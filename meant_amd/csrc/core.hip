@@ -152,6 +152,9 @@ const char* const k_routes[MEANT_ROUTE_COUNT] = {
     "grad_stats", "optim_step",     // every meant_grad_stats_f32 call with n > 0; every meant_optim_step_f32 launch
     "qkv_by_id",                    // every meant_qkv_embed_bwd_by_id call that runs its shared (per-id) stage
     "qkv_fwd_by_id",                // every meant_qkv_embed_fwd_by_id call
+    "ce_hard_wave", "ce_hard_block",   // meant_ce_probs_hard by form (C <= 1024: a wave per row / above: a workgroup per row)
+    "ce_hard_vocab",                // every meant_softmax_ce_hard_fwd launch
+    "ce_probs", "softmax_ce",       // every meant_ce_probs launch; every meant_softmax_ce_fwd launch (the routes calls without options keep)
 };
 std::atomic<long long> g_route[MEANT_ROUTE_COUNT];
 }  // namespace

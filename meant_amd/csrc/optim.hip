@@ -231,6 +231,7 @@ extern "C" int meant_ce_probs(const float* probs, const int64_t* target, float* 
   MEANT_REQUIRE(probs && target && loss_accum && B > 0 && C > 0, MEANT_ERR_ARG, "ce_probs: bad argument");
   hipLaunchKernelGGL(ce_probs_kernel, dim3((unsigned)ceil_div(B, 256)), dim3(256), 0, (hipStream_t)stream, probs, target, loss_accum, dprobs, B, C);
   MEANT_LAUNCH_CHECK("ce_probs");
+  meant_route_hit(ROUTE_CE_PROBS);
   return MEANT_OK;
 }
 
@@ -243,6 +244,7 @@ extern "C" int meant_softmax_ce_fwd(const void* logits, int64_t ld, const int64_
   DISPATCH_DTYPE(dtype, Tt, hipLaunchKernelGGL(softmax_ce_fwd_kernel<Tt>, dim3((unsigned)T), dim3(256), 0, (hipStream_t)stream,
                                                (const Tt*)logits, ld, target, (int)V, ignore_index, row_loss, lse));
   MEANT_LAUNCH_CHECK("softmax_ce_fwd");
+  meant_route_hit(ROUTE_SOFTMAX_CE);
   return MEANT_OK;
 }
 

@@ -851,8 +851,11 @@ class meant_language_pretrainer(nn.Module):
             return ops.vocab_linear(self._head_features(x), h.decoder.weight, h.decoder.bias)
         return h(x)
 
-    def loss(self, words, attention_mask, labels, ignore_index: int = -100, labelled_only=None):
-        """labelled_only (None: the attribute of that name, initially MEANT_MLM_LABELLED_ONLY, default 1): a RobertaLMHead-shaped head
+    def loss(self, words, attention_mask, labels, ignore_index: int = -100, labelled_only=None, label_smoothing: float = 0.0,
+             class_weight=None):
+        """label_smoothing, class_weight ([V]): F.cross_entropy's label_smoothing and weight, on either route below; with both at
+        their defaults the plain loss kernels run as before.
+        labelled_only (None: the attribute of that name, initially MEANT_MLM_LABELLED_ONLY, default 1): a RobertaLMHead-shaped head
         -- row-wise from its dense layer to the loss -- runs on the rows that carry a label alone (utils/custom_datasets.py:46-54
         labels 15 % of the positions): same loss, same gradients up to the order of fp32 sums.  The rows are selected HERE, before
         the encoder stack is enqueued: the labels are ready, and reading the count back (labels on the device; labels on the host
@@ -871,11 +874,12 @@ class meant_language_pretrainer(nn.Module):
         if sel is None and not labels.is_cuda:           # host labels on the all-rows route: uploaded here, as select_rows would have
             labels = labels.to(x.device)
         if not roberta:
-            return ops.softmax_cross_entropy(h(x), labels, ignore_index)
+            return ops.softmax_cross_entropy(h(x), labels, ignore_index, weight=class_weight, label_smoothing=label_smoothing)
         if sel is not None:
             x = ops.take_rows(x.reshape(T, x.shape[-1]), sel.idx, sel.inv, m)
             labels = sel.target_sel[:m]
-        return ops.vocab_linear_cross_entropy(self._head_features(x), h.decoder.weight, h.decoder.bias, labels, ignore_index)
+        return ops.vocab_linear_cross_entropy(self._head_features(x), h.decoder.weight, h.decoder.bias, labels, ignore_index,
+                                              class_weight=class_weight, label_smoothing=label_smoothing)
 
 
 # ------------------------------------------------------------------------------------------

@@ -1981,6 +1981,87 @@ class _SoftmaxCE(torch.autograd.Function):
         return dl, None, None, None
 
 
+# ---- hard-label cross-entropy options: class weights, label smoothing (include/meant_hip.h, csrc/ce_hard.hip) --------------------
+CE_STATS_FLOATS = _lib.CE_STATS_BYTES // 4      # the device block of meant_ce_hard_reduce, counted in floats
+IGNORE_NONE = -2 ** 63                     # the ignore_index handed down where the caller has none
+
+
+def ce_options(weight, label_smoothing, C: int, device=None, what: str = "cross_entropy"):
+    """(weight as a contiguous, 16-byte aligned float32 [C] on `device`, or None; label_smoothing as a float in [0, 1]); ValueError
+    for anything else.  A negative or non-finite class weight is not looked for: the kernels compute what the formulas give."""
+    eps = float(label_smoothing)
+    if not 0.0 <= eps <= 1.0:                          # false for a NaN too
+        raise ValueError(f"{what}: label_smoothing must lie in [0, 1], got {label_smoothing!r}")
+    if weight is None:
+        return None, eps
+    w = weight if torch.is_tensor(weight) else torch.as_tensor(weight, dtype=torch.float32)
+    if w.dim() != 1 or w.numel() != C or w.dtype.is_complex:
+        raise ValueError(f"{what}: weight must hold one value per class, [{C}], got {tuple(w.shape)}")
+    w = w.detach().to(device=device if device is not None else w.device, dtype=torch.float32).contiguous()
+    if w.data_ptr() % 16:
+        w = w.clone()
+    return w, eps
+
+
+class CEStats(NamedTuple):
+    """the device block of meant_ce_hard_reduce, read back (one host read: diagnostics, not the step)"""
+    loss: float
+    gscale: float
+    num: float
+    den: float
+    n_counted: int
+    n_ignored: int
+    n_invalid: int
+
+
+def ce_stats(block: torch.Tensor) -> CEStats:
+    """CEStats of a float32 tensor whose first CE_STATS_FLOATS elements are the block"""
+    b = block.detach()[:CE_STATS_FLOATS].cpu().contiguous()
+    f, d, i = b, b.view(torch.float64), b.view(torch.int64)
+    return CEStats(float(f[0]), float(f[1]), float(d[1]), float(d[2]), int(i[3]), int(i[4]), int(i[5]))
+
+
+class _SoftmaxCEHard(torch.autograd.Function):
+    """_SoftmaxCE with class weights and label smoothing: F.cross_entropy(logits[:, :V], target, weight=, label_smoothing=,
+    ignore_index=) on the row-padded buffer, loss 0 where the denominator is 0.  Forward: the rows, then the ordered reduction
+    into a device block (loss, 1 / denominator, counts); backward: one pass.  No host read, no ATen reduction, no atomics."""
+
+    @staticmethod
+    def forward(ctx, logits_pad, target, V, ignore_index, weight, eps):
+        _need_gpu(logits_pad, target, weight)
+        logits_pad = _c(logits_pad)
+        T, ld = logits_pad.shape
+        assert ld % 8 == 0 and V <= ld
+        tgt = _c(target.long())
+        # one buffer: the block, stat [T, 4] (16-byte aligned behind the 48-byte block), row_loss [T], row_w [T]
+        buf = torch.empty(CE_STATS_FLOATS + 6 * T, device=logits_pad.device, dtype=torch.float32)
+        base, f = buf.data_ptr(), 4 * CE_STATS_FLOATS
+        check(lib.meant_softmax_ce_hard_fwd(_p(logits_pad), ld, _p(tgt), _p(weight), eps, T, V, int(ignore_index), base + f + 16 * T,
+                                            base + f + 20 * T, base + f, base, _dt(logits_pad), _stream()), "softmax_ce_hard_fwd")
+        ctx.save_for_backward(logits_pad, tgt, buf, weight)
+        ctx.V, ctx.ignore_index, ctx.eps = int(V), int(ignore_index), eps
+        ctx.mark_non_differentiable(buf)
+        return buf[0], buf
+
+    @staticmethod
+    def backward(ctx, dloss, _dbuf):
+        logits_pad, tgt, buf, weight = ctx.saved_tensors
+        T, ld = logits_pad.shape
+        g = (dloss.float() * buf[1]).reshape(1).contiguous()
+        dl = torch.empty_like(logits_pad)
+        check(lib.meant_softmax_ce_hard_bwd(_p(logits_pad), ld, _p(tgt), _p(weight), ctx.eps, buf.data_ptr() + 4 * CE_STATS_FLOATS, T, ctx.V,
+                                            ctx.ignore_index, _p(g), _p(dl), _dt(logits_pad), _stream()), "softmax_ce_hard_bwd")
+        return dl, None, None, None, None, None
+
+
+def _softmax_ce(logits_pad, target, V, ignore_index, weight, label_smoothing, what):
+    """the loss of a padded logits buffer: the plain pair without options, the weighted / smoothed pair with them"""
+    if weight is None and label_smoothing == 0.0:
+        return _SoftmaxCE.apply(logits_pad, target, V, ignore_index)
+    w, eps = ce_options(weight, label_smoothing, V, logits_pad.device, what)
+    return _SoftmaxCEHard.apply(logits_pad, target, V, ignore_index, w, eps)[0]
+
+
 class _VocabLinear(torch.autograd.Function):
     """x W^T + b on W [V, d] with the output rows padded to Vp = ceil(V / 256) * 256 columns.  The padded bf16 copy of W
     (forward) and its transpose (input gradient) come from the weight cache keyed on the real parameter, so they are
@@ -2028,12 +2109,16 @@ def vocab_linear(x, weight, bias=None):
     return _vocab_logits_padded(x, weight, bias)[..., :weight.shape[0]]
 
 
-def vocab_linear_cross_entropy(x, weight, bias, target, ignore_index: int = -100, rows: str = "all"):
+def vocab_linear_cross_entropy(x, weight, bias, target, ignore_index: int = -100, rows: str = "all", class_weight=None,
+                               label_smoothing: float = 0.0):
     """CrossEntropyLoss(vocab_linear(x).view(-1, V), target.view(-1)) without ever slicing or re-homing the logits:
     the padded logits buffer goes straight into the fused loss and its gradient straight back into the GEMMs.
     rows = "labelled": the GEMMs and the loss run on the rows that carry a label alone (select_rows / take_rows; the
     count rounded up by padded_rows, the padding being zero rows with the ignore target) -- the same loss and gradients
-    up to the order of fp32 sums, with the rows of dx that the loss ignores exact zeros as before."""
+    up to the order of fp32 sums, with the rows of dx that the loss ignores exact zeros as before.
+    class_weight ([V], F.cross_entropy's `weight`; named apart from the matrix `weight`) and label_smoothing: torch's semantics, on
+    the weighted / smoothed kernel pair; a row's loss does not depend on which other rows are present, so rows = "labelled" means
+    the same with them.  Without them the plain pair runs as before."""
     if rows not in ("all", "labelled"):
         raise ValueError(f"vocab_linear_cross_entropy: rows must be 'all' or 'labelled', got {rows!r}")
     V = weight.shape[0]
@@ -2044,7 +2129,8 @@ def vocab_linear_cross_entropy(x, weight, bias, target, ignore_index: int = -100
             x = take_rows(x.reshape(-1, x.shape[-1]), sel.idx, sel.inv, m)
             target = sel.target_sel[:m]
     lp = _vocab_logits_padded(x, weight, bias)
-    return _SoftmaxCE.apply(lp.reshape(-1, lp.shape[-1]), target.reshape(-1), V, ignore_index)
+    return _softmax_ce(lp.reshape(-1, lp.shape[-1]), target.reshape(-1), V, ignore_index, class_weight, label_smoothing,
+                       "vocab_linear_cross_entropy")
 
 
 # ---- the labelled rows of an MLM batch (utils/custom_datasets.py:46-54: 15 % of the positions; the rest carry -100) ----------
@@ -2121,15 +2207,20 @@ def take_rows(x2d, idx, inv, m: int):
     return _TakeRows.apply(x2d, idx, inv, int(m))
 
 
-def softmax_cross_entropy(logits, target, ignore_index: int = -100):
+def softmax_cross_entropy(logits, target, ignore_index: int = -100, weight=None, label_smoothing: float = 0.0):
     """mean CE over the last axis of `logits` ([..., V], any leading shape, any strides) against integer targets.
-    Rows are re-homed once into a buffer with an 8-element-aligned stride when they are not already laid out so."""
+    Rows are re-homed once into a buffer with an 8-element-aligned stride when they are not already laid out so.
+    weight ([V] class weights) and label_smoothing (in [0, 1]): F.cross_entropy's arguments of those names -- the weighted mean
+    sum(row_loss) / sum(w_target) over the rows that count, 0 where that denominator is 0.  With both at their defaults the call
+    takes the plain kernel pair, bit for bit as before."""
+    if weight is not None or label_smoothing != 0.0:
+        ce_options(weight, label_smoothing, logits.shape[-1], None, "softmax_cross_entropy")     # argument errors before any device work
     V = logits.shape[-1]
     l2 = logits.reshape(-1, V)
     Vp = (V + 7) // 8 * 8
     if Vp != V or not l2.is_contiguous():
         l2 = torch.nn.functional.pad(l2, (0, Vp - V))
-    return _SoftmaxCE.apply(l2, target.reshape(-1), V, ignore_index)
+    return _softmax_ce(l2, target.reshape(-1), V, ignore_index, weight, label_smoothing, "softmax_cross_entropy")
 
 
 # ---------------------------------------------------------------------------------------------

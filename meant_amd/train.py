@@ -69,16 +69,82 @@ class _CEOnProbsSoft(torch.autograd.Function):
         return dp * dloss, None
 
 
-def cross_entropy_on_probs(probs: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+class _CEOnProbsHard(torch.autograd.Function):
+    """F.cross_entropy(probabilities, target, weight=, label_smoothing=, ignore_index=) for class indices: the rows (loss, weight and
+    the unnormalised gradient in one launch), then the ordered reduction into a device block.  No atomics, no host read."""
+
+    @staticmethod
+    def forward(ctx, probs, target, weight, eps, ignore_index):
+        ops._need_gpu(probs, target, weight)
+        p = probs if probs.dtype == torch.float32 else probs.float()
+        t = ops._c(target.long())
+        B, C = p.shape
+        p, ldp = ops._rows(p)                                               # a column slice of a wider block is read in place
+        n = ops.CE_STATS_FLOATS
+        buf = torch.empty(n + 2 * B, device=p.device, dtype=torch.float32)  # the block, row_loss [B], row_w [B]
+        dp = torch.empty(B, C, device=p.device, dtype=torch.float32)
+        base = buf.data_ptr()
+        check(lib.meant_ce_probs_hard(ops._p(p), ldp, ops._p(t), ops._p(weight), eps, ignore_index, base + 4 * n, base + 4 * (n + B),
+                                      ops._p(dp), C, B, C, base, ops._stream()), "ce_probs_hard")
+        ctx.save_for_backward(dp, buf)
+        ctx.mark_non_differentiable(buf)
+        return buf[0], buf
+
+    @staticmethod
+    def backward(ctx, dloss, _dbuf):
+        dp, buf = ctx.saved_tensors
+        return dp * (dloss * buf[1]), None, None, None, None               # buf[1]: 1 / sum of the counted rows' weights, or 0
+
+
+def cross_entropy_on_probs(probs: torch.Tensor, target: torch.Tensor, *, weight=None, label_smoothing: float = 0.0,
+                           ignore_index: Optional[int] = None) -> torch.Tensor:
     """nn.CrossEntropyLoss()(probs, target) of probabilities [B, C]: target [B] of class indices (any integer type), or a
     floating-point [B, C] of class probabilities / answer weights (rows need not sum to 1, may be all zero), read in place as
-    float32 or bfloat16 with its row stride, any other float type widened to float32."""
+    float32 or bfloat16 with its row stride, any other float type widened to float32.
+    weight ([C] class weights), label_smoothing (in [0, 1]) and ignore_index, for class indices: torch's
+    CrossEntropyLoss(weight=, label_smoothing=, ignore_index=) -- sum(row_loss) / sum(w_target) over the rows whose target is not
+    ignore_index and lies in [0, C).  Apart from torch: a target outside [0, C) is left out like an ignored one instead of raising,
+    and where no row counts or the weights of those that do sum to 0 the loss is 0 with zero gradients, not NaN.  With all three
+    at their defaults class indices take the plain kernel as before (a target outside [0, C) poisons its loss with NaN)."""
+    plain = weight is None and label_smoothing == 0.0 and ignore_index is None
     if target.dtype.is_floating_point and target.dim() == 2:
+        if not plain:
+            raise ValueError("cross_entropy_on_probs: weight, label_smoothing and ignore_index go with class-index targets [B]; "
+                             "class-probability targets [B, C] take none of them")
         if target.shape != probs.shape:
             raise ValueError(f"cross_entropy_on_probs: a class-probability target must have the shape of probs {tuple(probs.shape)}, "
                              f"got {tuple(target.shape)}")
         return _CEOnProbsSoft.apply(probs, target)
-    return _CEOnProbs.apply(probs, target)
+    if plain:
+        return _CEOnProbs.apply(probs, target)
+    if probs.dim() != 2 or target.dim() != 1 or target.shape[0] != probs.shape[0]:
+        raise ValueError(f"cross_entropy_on_probs: probs [B, C] and target [B], got {tuple(probs.shape)} and {tuple(target.shape)}")
+    w, eps = ops.ce_options(weight, label_smoothing, probs.shape[1], probs.device, "cross_entropy_on_probs")
+    return _CEOnProbsHard.apply(probs, target, w, eps, ops.IGNORE_NONE if ignore_index is None else int(ignore_index))[0]
+
+
+def balanced_class_weights(labels_or_counts: torch.Tensor, C: int, counts: bool = False) -> torch.Tensor:
+    """float32 [C] of n / (C * count_c), sklearn's "balanced" class weights, 0 for a class without examples; on the device of the
+    argument, with no host read.  labels_or_counts: integer labels of any shape (those outside [0, C) -- an ignore value -- are
+    left out of the counts and of n), or, with counts=True, the [C] per-class counts themselves, e.g. the ntarget slice
+    f1_metrics.state[2 * C:3 * C] of a first epoch, whose weights the next epoch's loss can take."""
+    C = int(C)
+    if C <= 0:
+        raise ValueError(f"balanced_class_weights: C must be positive, got {C}")
+    v = labels_or_counts if torch.is_tensor(labels_or_counts) else torch.as_tensor(labels_or_counts)
+    if counts:
+        if v.numel() != C:
+            raise ValueError(f"balanced_class_weights: {C} class counts expected, got {tuple(v.shape)}")
+        cnt = v.reshape(C).double()
+    else:
+        if v.dtype.is_floating_point or v.dtype == torch.bool:
+            raise ValueError(f"balanced_class_weights: labels must be integers, got {v.dtype} (per-class counts go with counts=True)")
+        lab = v.reshape(-1).long()
+        ok = (lab >= 0) & (lab < C)
+        cnt = torch.zeros(C, device=lab.device, dtype=torch.int64).scatter_add_(0, torch.where(ok, lab, torch.zeros_like(lab)),
+                                                                                ok.long()).double()
+    w = cnt.sum() / (C * cnt)
+    return torch.where(cnt > 0, w, torch.zeros_like(w)).float()
 
 
 # ---------------------------------------------------------------------------------------------
@@ -340,7 +406,8 @@ class TrainStep:
 
     def __init__(self, model: torch.nn.Module, lr: float = 5e-5, weight_decay: float = 1e-2, max_grad_norm: float = 1.0,
                  bucket_mb: float = 64.0, direct_grads: bool = True, micro_batches: int = 1, metrics=None,
-                 optimizer: str = "adamw", nonfinite: Optional[str] = None, loss_scale=None, clip_scaled: bool = False):
+                 optimizer: str = "adamw", nonfinite: Optional[str] = None, loss_scale=None, clip_scaled: bool = False,
+                 class_weight=None, label_smoothing: float = 0.0, ignore_index: Optional[int] = None):
         """micro_batches: run a step's batch as this many equal slices, one forward/backward each, gradients accumulated in the
         reducer's buckets (reducer.no_sync) -- the same gradients with 1/micro_batches of the activations in flight (the
         reference's CLI default of 12 encoder layers at 128 samples per GPU).
@@ -354,7 +421,12 @@ class TrainStep:
         with the defaults the tail is FusedAdamW, unguarded; optimizer="adam", nonfinite="skip" or any loss_scale builds GuardedAdam
         instead -- a step with an inf or NaN gradient (a class index outside [0, C) poisons one, as does an overflow) is skipped on
         the device and counted (opt.steps_skipped()), every micro-batch's loss goes through opt.scale() before backward, and the
-        loss returned stays the unscaled one"""
+        loss returned stays the unscaled one
+        class_weight ([C]), label_smoothing, ignore_index: the arguments of cross_entropy_on_probs for class-index targets (the
+        weight is kept as a float32 tensor on the model's device; balanced_class_weights makes one from labels or counts).  Each
+        micro-batch is normalised by its OWN denominator -- the weights of its counted rows -- and scaled by 1 / micro_batches:
+        with weights or ignored rows that is the mean of the micro-batches' weighted means, not the weighted mean of the whole
+        batch (the two agree when every micro-batch has the same denominator)"""
         if optimizer not in ("adamw", "adam"):
             raise ValueError(f"TrainStep: optimizer must be 'adamw' or 'adam', got {optimizer!r}")
         if nonfinite not in (None, "skip"):
@@ -370,13 +442,26 @@ class TrainStep:
             self._scale = self.opt.scale
         self.micro_batches = max(1, int(micro_batches))
         self.metrics = metrics
+        self.label_smoothing = float(label_smoothing)
+        self.ignore_index = None if ignore_index is None else int(ignore_index)
+        self.class_weight = None
+        if class_weight is not None:
+            dev = next((p.device for p in model.parameters()), None)
+            w = class_weight if torch.is_tensor(class_weight) else torch.as_tensor(class_weight, dtype=torch.float32)
+            self.class_weight = ops.ce_options(w, self.label_smoothing, w.numel(), dev, "TrainStep")[0]
+        else:
+            ops.ce_options(None, self.label_smoothing, 0, None, "TrainStep")
+
+    def _loss(self, out, target):
+        return cross_entropy_on_probs(out, target, weight=self.class_weight, label_smoothing=self.label_smoothing,
+                                      ignore_index=self.ignore_index)
 
     def __call__(self, *inputs, target):
         self.reducer.prepare()
         k = self.micro_batches
         if k == 1:
             out = self.model(*inputs)
-            loss = cross_entropy_on_probs(out, target)
+            loss = self._loss(out, target)
             (loss if self._scale is None else self._scale(loss)).backward()
         else:
             B = target.shape[0]
@@ -388,11 +473,11 @@ class TrainStep:
                 if i < k - 1:
                     with self.reducer.no_sync():
                         o = self.model(*part)
-                        li = cross_entropy_on_probs(o, target[sl]) * (1.0 / k)
+                        li = self._loss(o, target[sl]) * (1.0 / k)
                         (li if self._scale is None else self._scale(li)).backward()
                 else:
                     o = self.model(*part)
-                    li = cross_entropy_on_probs(o, target[sl]) * (1.0 / k)
+                    li = self._loss(o, target[sl]) * (1.0 / k)
                     (li if self._scale is None else self._scale(li)).backward()
                 outs.append(o.detach())
                 loss = loss + li.detach()
