@@ -35,169 +35,10 @@ __device__ __forceinline__ void phi_tab_to_lds(float* dst) {
 }
 
 
-// d_part / offset: the partial and the bias form of utils/rms_norm.py:44-57 (RMSNorm(d, p, bias=True)): the statistics are taken over
-// the first d_part = int(d p) elements of a row only (d_part == d: the full-width form the MEANT path uses), and `offset` (float [d],
-// may be null) is added to the scaled result.
-template <typename T>
-__global__ __launch_bounds__(NORM_THREADS) void rmsnorm_fwd_kernel(const T* __restrict__ x, const float* __restrict__ scale,
-                                                                    T* __restrict__ y, float* __restrict__ rinv_out,
-                                                                    int64_t rows, int d, float eps, float drop_p,
-                                                                    uint64_t seed, int d_part = 0, const float* __restrict__ offset = nullptr) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int nchunk = d >> 3;
-  if (d_part <= 0) d_part = d;
-  const float inv_sqrt_d = rsqrtf((float)d_part);
-  for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < rows; row += (int64_t)gridDim.x * 4) {
-    const T* xr = x + row * d;
-    Vec8<T> v[MAXC];
-    float ss = 0.f;
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) {
-      const int ch = lane + c * 64;
-      if (ch < nchunk) {
-        v[c] = load8<T>(xr + ch * 8);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { const float f = v[c].get(i); ss += ch * 8 + i < d_part ? f * f : 0.f; }
-      }
-    }
-    ss = wave_sum(ss);
-    const float r = 1.0f / (sqrtf(ss) * inv_sqrt_d + eps);
-    if (lane == 0) rinv_out[row] = r;
-    T* yr = y + row * d;
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) {
-      const int ch = lane + c * 64;
-      if (ch < nchunk) {
-        const f32x4 g0 = *reinterpret_cast<const f32x4*>(scale + ch * 8);
-        const f32x4 g1 = *reinterpret_cast<const f32x4*>(scale + ch * 8 + 4);
-        Vec8<T> o;
-        float km[8] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
-        if (drop_p > 0.f) keep_scale8(drop_p, seed, (uint64_t)row * d + ch * 8, km);
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-          o.set(i, (i < 4 ? g0[i] : g1[i - 4]) * (v[c].get(i) * r) * km[i] + (offset ? offset[ch * 8 + i] : 0.f));
-        store8<T>(yr + ch * 8, o);
-      }
-    }
-  }
-}
-
-// dx_j = r * g_j dy_j  -  x_j * c * r^2 / (n sqrt(d)),  c = sum_i g_i dy_i x_i,  n sqrt(d) = (1/r - eps) d
-// partial form (d_part < d): the statistics see the first d_part elements only, so the second term exists for j < d_part alone and
-// n sqrt(d_part) = (1/r - eps) d_part; partial_off (may be null): per-block column sums of dy, the gradient of the offset
-template <typename T>
-__global__ __launch_bounds__(NORM_THREADS) void rmsnorm_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
-                                                                    const float* __restrict__ scale,
-                                                                    const float* __restrict__ rinv, T* __restrict__ dx,
-                                                                    float* __restrict__ partial, int64_t rows, int d,
-                                                                    float eps, float drop_p, uint64_t seed,
-                                                                    const T* __restrict__ dres, const T* __restrict__ gelu_pre,
-                                                                    int d_part = 0, float* __restrict__ partial_off = nullptr) {
-  __shared__ float red[4][512];   // reused per chunk: [wave][64 lanes * 8]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int nchunk = d >> 3;
-  if (d_part <= 0) d_part = d;
-  float gacc[MAXC][8], oacc[MAXC][8];
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c)
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { gacc[c][i] = 0.f; oacc[c][i] = 0.f; }
-
-  for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < rows; row += (int64_t)gridDim.x * 4) {
-    const T* xr = x + row * d;
-    const T* dyr = dy + row * d;
-    const float r = rinv[row];
-    Vec8<T> xv[MAXC];
-    float gd[MAXC][8];
-    float cdot = 0.f;
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) {
-      const int ch = lane + c * 64;
-      if (ch < nchunk) {
-        xv[c] = load8<T>(xr + ch * 8);
-        const Vec8<T> dv = load8<T>(dyr + ch * 8);
-        const f32x4 g0 = *reinterpret_cast<const f32x4*>(scale + ch * 8);
-        const f32x4 g1 = *reinterpret_cast<const f32x4*>(scale + ch * 8 + 4);
-        float km[8] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
-        if (drop_p > 0.f) keep_scale8(drop_p, seed, (uint64_t)row * d + ch * 8, km);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const float dyi = dv.get(i) * km[i];
-          const float xi = xv[c].get(i);
-          if (partial_off) oacc[c][i] += dyi;
-          gacc[c][i] += dyi * xi * r;
-          const float t = (i < 4 ? g0[i] : g1[i - 4]) * dyi;
-          gd[c][i] = t;
-          cdot += t * xi;
-        }
-      }
-    }
-    cdot = wave_sum(cdot);
-    const float nsd = (1.0f / r - eps) * (float)d_part;     // ||x_part|| * sqrt(d_part)
-    const float k = nsd > 0.f ? cdot * r * r / nsd : 0.f;
-    T* dxr = dx + row * d;
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) {
-      const int ch = lane + c * 64;
-      if (ch < nchunk) {
-        Vec8<T> o;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) o.set(i, r * gd[c][i] - (ch * 8 + i < d_part ? k * xv[c].get(i) : 0.f));
-        if (dres) {                                  // gradient arriving through the residual branch that shares x
-          const Vec8<T> rv = load8<T>(dres + row * d + ch * 8);
-#pragma unroll
-          for (int i = 0; i < 8; ++i) o.set(i, o.get(i) + rv.get(i));
-        }
-        if (gelu_pre) {                              // x = gelu(pre): chain through the activation in the same pass
-          const Vec8<T> pv = load8<T>(gelu_pre + row * d + ch * 8);
-#pragma unroll
-          for (int i = 0; i < 8; ++i) o.set(i, o.get(i) * gelu_grad_t<T>(pv.get(i)));
-        }
-        store8<T>(dxr + ch * 8, o);
-      }
-    }
-  }
-  // block reduction of the gain-gradient partials: 4 waves -> 1 row of `partial`
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c) {
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 8; ++i) red[wave][lane * 8 + i] = gacc[c][i];
-    __syncthreads();
-    if (wave == 0) {
-      const int ch = lane + c * 64;
-      if (ch < nchunk) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const float s = red[0][lane * 8 + i] + red[1][lane * 8 + i] + red[2][lane * 8 + i] + red[3][lane * 8 + i];
-          partial[(int64_t)blockIdx.x * d + ch * 8 + i] = s;
-        }
-      }
-    }
-  }
-  if (partial_off) {
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) {
-      __syncthreads();
-#pragma unroll
-      for (int i = 0; i < 8; ++i) red[wave][lane * 8 + i] = oacc[c][i];
-      __syncthreads();
-      if (wave == 0) {
-        const int ch = lane + c * 64;
-        if (ch < nchunk) {
-#pragma unroll
-          for (int i = 0; i < 8; ++i)
-            partial_off[(int64_t)blockIdx.x * d + ch * 8 + i] = red[0][lane * 8 + i] + red[1][lane * 8 + i] + red[2][lane * 8 + i] + red[3][lane * 8 + i];
-        }
-      }
-    }
-  }
-}
-
 // ------------------------------------------------------------------------------------------------
 // Packed-row variants for the widths the encoder uses.  One wave takes R consecutive rows as ONE flat run of
 // R * d / 8 chunks dealt lane-cyclically, C = R * d / 512 chunks per lane, every lane equally loaded
-// (d = 768: R = 2, C = 3 -- the generic kernel gives half the lanes two chunks and the other half one), all loads of
+// (d = 768: R = 2, C = 3 -- one wave per row gives half the lanes two chunks and the other half one), all loads of
 // a row group issued before the first use, and twice the waves per CU in flight.
 template <typename T, int C>
 __global__ __launch_bounds__(NORM_THREADS) void rmsnorm_fwd_packed_kernel(const T* __restrict__ x, const float* __restrict__ scale,
@@ -621,137 +462,54 @@ __global__ __launch_bounds__(NORM_THREADS) void colreduce_kernel(const float* __
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(NORM_THREADS) void layernorm_fwd_kernel(const T* __restrict__ x, const float* __restrict__ gamma,
-                                                                      const float* __restrict__ beta, T* __restrict__ y,
-                                                                      float* __restrict__ stats, int64_t rows, int d, float eps) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int nchunk = d >> 3;
-  for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < rows; row += (int64_t)gridDim.x * 4) {
-    const T* xr = x + row * d;
-    Vec8<T> v[MAXC];
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) {
-      const int ch = lane + c * 64;
-      if (ch < nchunk) {
-        v[c] = load8<T>(xr + ch * 8);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) s += v[c].get(i);
-      }
-    }
-    const float mean = wave_sum(s) / (float)d;
-    float q = 0.f;
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) {
-      const int ch = lane + c * 64;
-      if (ch < nchunk) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { const float t = v[c].get(i) - mean; q += t * t; }
-      }
-    }
-    const float rstd = rsqrtf(wave_sum(q) / (float)d + eps);
-    if (lane == 0) { stats[row * 2] = mean; stats[row * 2 + 1] = rstd; }
-    T* yr = y + row * d;
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) {
-      const int ch = lane + c * 64;
-      if (ch < nchunk) {
-        Vec8<T> o;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) o.set(i, (v[c].get(i) - mean) * rstd * gamma[ch * 8 + i] + beta[ch * 8 + i]);
-        store8<T>(yr + ch * 8, o);
-      }
-    }
-  }
-}
-
-// one wave per row; dgamma/dbeta partials per block written to partial[2][gridDim][d]
-template <typename T>
-__global__ __launch_bounds__(NORM_THREADS) void layernorm_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
-                                                                      const float* __restrict__ gamma,
-                                                                      const float* __restrict__ stats, T* __restrict__ dx,
-                                                                      float* __restrict__ partial, int64_t rows, int d) {
-  __shared__ float red[4][512];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int nchunk = d >> 3;
-  float ga[MAXC][8], ba[MAXC][8];
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c)
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { ga[c][i] = 0.f; ba[c][i] = 0.f; }
-  for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < rows; row += (int64_t)gridDim.x * 4) {
-    const float mean = stats[row * 2], rstd = stats[row * 2 + 1];
-    float xh[MAXC][8], gd[MAXC][8];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) {
-      const int ch = lane + c * 64;
-      if (ch < nchunk) {
-        const Vec8<T> xv = load8<T>(x + row * d + ch * 8);
-        const Vec8<T> dv = load8<T>(dy + row * d + ch * 8);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const float h = (xv.get(i) - mean) * rstd;
-          const float dyi = dv.get(i);
-          xh[c][i] = h;
-          ga[c][i] += dyi * h;
-          ba[c][i] += dyi;
-          const float t = dyi * gamma[ch * 8 + i];
-          gd[c][i] = t;
-          s1 += t;
-          s2 += t * h;
-        }
-      }
-    }
-    s1 = wave_sum(s1) / (float)d;
-    s2 = wave_sum(s2) / (float)d;
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) {
-      const int ch = lane + c * 64;
-      if (ch < nchunk) {
-        Vec8<T> o;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) o.set(i, rstd * (gd[c][i] - s1 - xh[c][i] * s2));
-        store8<T>(dx + row * d + ch * 8, o);
-      }
-    }
-  }
-  for (int which = 0; which < 2; ++which) {
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) {
-      __syncthreads();
-#pragma unroll
-      for (int i = 0; i < 8; ++i) red[wave][lane * 8 + i] = which ? ba[c][i] : ga[c][i];
-      __syncthreads();
-      if (wave == 0) {
-        const int ch = lane + c * 64;
-        if (ch < nchunk) {
-#pragma unroll
-          for (int i = 0; i < 8; ++i)
-            partial[((int64_t)which * gridDim.x + blockIdx.x) * d + ch * 8 + i] =
-                red[0][lane * 8 + i] + red[1][lane * 8 + i] + red[2][lane * 8 + i] + red[3][lane * 8 + i];
-        }
-      }
-    }
-  }
-}
-
 // ------------------------------------------------------------------------------------------------
-// Wide and odd-width rows: every shape the kernels above do not take (d > 2048, or d % 8 != 0).  One 256-thread workgroup
-// per row, grid-stride over rows with at most norm_blocks(rows) workgroups (so the backward's per-block partial rows fit
-// meant_rmsnorm_bwd_ws).  Thread t owns chunks t, t + 256, ... of V elements of a row: V = 8 (16-byte loads) when d % 8 == 0;
-// V = 1 otherwise -- a row of such a width is not 16-byte aligned, and these shapes take element loads throughout (a
-// correctness route, not a tuned one).  A slice of WIDE_SLICE elements is WIDE_CPT chunks per thread: a row of one slice
-// (d <= 8192) stays in registers between the reduction and the write (one read and one write per element); a longer row is
-// read again, slice by slice, for each later pass (expected from L2).  Row sums: wave_sum, then a fixed-order combine of
-// the four waves through LDS.
+// The unpacked rows: every shape the packed kernels above do not take, RMSNorm (full, partial, offset, dropout) and LayerNorm,
+// forward and backward.  One kernel family; a row belongs to a TEAM of threads, of two sizes:
+//   TEAM = 64  (NORM_ROW:  d % 8 == 0 and d <= 2048): one wave per row, the workgroup's four waves on four rows at a time;
+//   TEAM = 256 (NORM_WIDE: d > 2048, or d % 8 != 0):  the whole workgroup on one row.
+// Grid-stride over rows with at most norm_blocks(rows) workgroups (so the backward's per-block partial rows fit
+// meant_rmsnorm_bwd_ws).  Member m of a team owns chunks m, m + TEAM, ... of V elements of a row: V = 8 (16-byte loads) when
+// d % 8 == 0; V = 1 otherwise -- a row of such a width is not 16-byte aligned, and these shapes take element loads throughout
+// (a correctness route, not a tuned one; TEAM = 256 only).  A slice of Team::SLICE elements is WIDE_CPT chunks per member: a row
+// of one slice (TEAM = 64: always; TEAM = 256: d <= 8192) stays in registers between the reduction and the write (one read and
+// one write per element); a longer row is read again, slice by slice, for each later pass (expected from L2).  Row sums: a
+// thread's chunks in order, elements in order, then wave_sum, and for TEAM = 256 a fixed-order combine of the four waves
+// through LDS.  The backward's column sums over a workgroup's rows end in its one partial row (partial_row below).
 constexpr int WIDE_SLICE = 8192;
-template <int V> constexpr int WIDE_CPT = WIDE_SLICE / (NORM_THREADS * V);
 constexpr int64_t NORM_MAX_D = 2147483647LL - WIDE_SLICE;   // the column index of a slice chunk stays an int
 
+// sum over the workgroup, the same value in every thread (red: 4 floats of LDS)
+__device__ __forceinline__ float block_sum(float v, float* red) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  const float s = (red[0] + red[1]) + (red[2] + red[3]);
+  __syncthreads();
+  return s;
+}
+
+// the threads that own a row: everything the kernel bodies below need to know about the two sizes
+template <int TEAM> struct Team {
+  static_assert(TEAM == 64 || TEAM == NORM_THREADS, "a wave or the workgroup");
+  static constexpr int PER_BLOCK = NORM_THREADS / TEAM;                 // teams, so rows in flight, per workgroup
+  static constexpr int SLICE = TEAM == 64 ? MAXC * 512 : WIDE_SLICE;    // MAXC chunks of 8 per member either way
+  static constexpr int SUM_LDS = TEAM == 64 ? 1 : 4;                    // floats sum() needs (TEAM = 64: none, the array is never touched)
+  static constexpr int BWD_LDS = TEAM == 64 ? PER_BLOCK * 512 : SUM_LDS;   // floats sum() and partial_row() need
+  static __device__ __forceinline__ int team() { return TEAM == 64 ? (int)threadIdx.x >> 6 : 0; }
+  static __device__ __forceinline__ int member() { return TEAM == 64 ? (int)threadIdx.x & 63 : (int)threadIdx.x; }
+  static __device__ __forceinline__ int slices(int d) { return TEAM == 64 ? 1 : (d + SLICE - 1) / SLICE; }   // TEAM = 64: a constant, no slice loop is compiled
+  // sum over the team, the same value in every member
+  static __device__ __forceinline__ float sum(float v, float* red) {
+    if constexpr (TEAM == 64) return wave_sum(v);
+    else return block_sum(v, red);
+  }
+};
+template <int V, int TEAM> constexpr int WIDE_CPT = Team<TEAM>::SLICE / (TEAM * V);
+
 // first column of chunk c of slice s of this thread
-template <int V> __device__ __forceinline__ int wide_col(int s, int c) { return s * WIDE_SLICE + ((int)threadIdx.x + c * NORM_THREADS) * V; }
+template <int V, int TEAM> __device__ __forceinline__ int wide_col(int s, int c) {
+  return s * Team<TEAM>::SLICE + (Team<TEAM>::member() + c * TEAM) * V;
+}
 
 template <typename T, int V> __device__ __forceinline__ void wide_load(const T* p, float (&f)[V]) {
   if constexpr (V == 8) {
@@ -797,56 +555,86 @@ template <int V> __device__ __forceinline__ void wide_keep(float p, uint64_t see
     m[0] = s;
   }
 }
-// sum over the workgroup, the same value in every thread (red: 4 floats of LDS)
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const float s = (red[0] + red[1]) + (red[2] + red[3]);
-  __syncthreads();
-  return s;
+// chunk c of a workgroup's partial row `prow` from its teams' register sums `acc` over their (one-slice) rows; called by all threads.
+// TEAM = 256: the one team's sums as they are; TEAM = 64: the four waves' sums added in wave order through LDS (red: [4][512] floats)
+template <int V, int TEAM>
+__device__ __forceinline__ void partial_row(float* prow, int c, const float (&acc)[V], int d, float* red) {
+  using Tm = Team<TEAM>;
+  const int col = wide_col<V, TEAM>(0, c);
+  if constexpr (TEAM == 64) {
+    const int m = Tm::member() * V;
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < V; ++i) red[Tm::team() * 512 + m + i] = acc[i];
+    __syncthreads();
+    if (Tm::team() == 0 && col < d) {
+#pragma unroll
+      for (int i = 0; i < V; ++i) prow[col + i] = red[m + i] + red[512 + m + i] + red[1024 + m + i] + red[1536 + m + i];
+    }
+  } else if (col < d) {
+#pragma unroll
+    for (int i = 0; i < V; ++i) prow[col + i] = acc[i];
+  }
 }
 
-// the arguments and the result of rmsnorm_fwd_kernel, any d
-template <typename T, int V>
+// a chunk of a row as it waits in registers between the RMSNorm forward's statistics and its write: floats, but with one wave per row
+// in the storage type -- 16 registers fewer in the bf16 tier, which keeps that kernel at six waves per SIMD (75 VGPRs; 102 with floats)
+template <typename T, int V, int TEAM> struct RowChunk {
+  float f[V];
+  __device__ __forceinline__ void load(const T* p) { wide_load<T, V>(p, f); }
+  __device__ __forceinline__ float get(int i) const { return f[i]; }
+};
+template <typename T> struct RowChunk<T, 8, 64> {
+  Vec8<T> v;
+  __device__ __forceinline__ void load(const T* p) { v = load8<T>(p); }
+  __device__ __forceinline__ float get(int i) const { return v.get(i); }
+};
+
+// d_part / offset: the partial and the bias form of utils/rms_norm.py:44-57 (RMSNorm(d, p, bias=True)): the statistics are taken over
+// the first d_part = int(d p) elements of a row only (d_part == d: the full-width form the MEANT path uses), and `offset` (float [d],
+// may be null) is added to the scaled result.  The offset is loaded like the gain (wide_param): read element by element, its
+// 8 addresses per chunk were kept in registers across the row loop, 32 VGPRs that cost the bf16 tier two waves per SIMD.
+template <typename T, int V, int TEAM>
 __global__ __launch_bounds__(NORM_THREADS) void rmsnorm_fwd_wide_kernel(const T* __restrict__ x, const float* __restrict__ scale,
                                                                          T* __restrict__ y, float* __restrict__ rinv_out, int64_t rows,
                                                                          int d, float eps, float drop_p, uint64_t seed, int d_part,
                                                                          const float* __restrict__ offset) {
-  __shared__ float red[4];
-  constexpr int CPT = WIDE_CPT<V>;
-  const int ns = (d + WIDE_SLICE - 1) / WIDE_SLICE;
+  using Tm = Team<TEAM>;
+  __shared__ float red[Tm::SUM_LDS];
+  constexpr int CPT = WIDE_CPT<V, TEAM>;
+  const int ns = Tm::slices(d);
   const float inv_sqrt_d = rsqrtf((float)d_part);
-  for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
+  for (int64_t row = (int64_t)blockIdx.x * Tm::PER_BLOCK + Tm::team(); row < rows; row += (int64_t)gridDim.x * Tm::PER_BLOCK) {
     const T* xr = x + row * d;
     T* yr = y + row * d;
-    float v[CPT][V];
+    RowChunk<T, V, TEAM> v[CPT];
     float ss = 0.f;
     for (int s = 0; s < ns; ++s) {
 #pragma unroll
       for (int c = 0; c < CPT; ++c) {
-        const int col = wide_col<V>(s, c);
+        const int col = wide_col<V, TEAM>(s, c);
         if (col < d) {
-          wide_load<T, V>(xr + col, v[c]);
+          v[c].load(xr + col);
 #pragma unroll
-          for (int i = 0; i < V; ++i) ss += col + i < d_part ? v[c][i] * v[c][i] : 0.f;
+          for (int i = 0; i < V; ++i) ss += col + i < d_part ? v[c].get(i) * v[c].get(i) : 0.f;
         }
       }
     }
-    ss = block_sum(ss, red);
+    ss = Tm::sum(ss, red);
     const float r = 1.0f / (sqrtf(ss) * inv_sqrt_d + eps);
-    if (threadIdx.x == 0) rinv_out[row] = r;
+    if (Tm::member() == 0) rinv_out[row] = r;
     for (int s = 0; s < ns; ++s) {
 #pragma unroll
       for (int c = 0; c < CPT; ++c) {
-        const int col = wide_col<V>(s, c);
+        const int col = wide_col<V, TEAM>(s, c);
         if (col < d) {
-          if (ns > 1) wide_load<T, V>(xr + col, v[c]);
-          float g[V], km[V], o[V];
+          if (ns > 1) v[c].load(xr + col);
+          float g[V], km[V], o[V], ofs[V];
           wide_param<V>(scale + col, g);
+          if (offset) wide_param<V>(offset + col, ofs);
           wide_keep<V>(drop_p, seed, (uint64_t)row * d + col, km);
 #pragma unroll
-          for (int i = 0; i < V; ++i) o[i] = g[i] * (v[c][i] * r) * km[i] + (offset ? offset[col + i] : 0.f);
+          for (int i = 0; i < V; ++i) o[i] = g[i] * (v[c].get(i) * r) * km[i] + (offset ? ofs[i] : 0.f);
           wide_store<T, V>(yr + col, o);
         }
       }
@@ -867,19 +655,24 @@ __device__ __forceinline__ void rms_bwd_in(const T* dy, const T* x, const float*
   for (int i = 0; i < V; ++i) { dyv[i] *= km[i]; gd[i] = g[i] * dyv[i]; }
 }
 
-// the arguments and the results of rmsnorm_bwd_kernel, any d (OFF: partial_off is written).  The gain (and offset) gradient
-// sums of the block's rows stay in registers for a one-slice row; for a longer row they are kept in the block's own partial
-// row itself (each column read and written by one thread only, no atomics)
-template <typename T, int V, bool OFF>
+// dx_j = r * g_j dy_j  -  x_j * c * r^2 / (n sqrt(d)),  c = sum_i g_i dy_i x_i,  n sqrt(d) = (1/r - eps) d
+// partial form (d_part < d): the statistics see the first d_part elements only, so the second term exists for j < d_part alone and
+// n sqrt(d_part) = (1/r - eps) d_part; partial_off (OFF): per-block column sums of dy, the gradient of the offset.
+// dres: the gradient that arrives through the residual branch sharing x; gelu_pre: x = gelu(pre), chained through the activation
+// in the same pass.  The gain (and offset) gradient sums of a team's rows stay in registers for a one-slice row and end in the
+// block's partial row through partial_row; for a longer row they are kept in the block's own partial row itself (each column
+// read and written by one thread only, no atomics)
+template <typename T, int V, int TEAM, bool OFF>
 __global__ __launch_bounds__(NORM_THREADS) void rmsnorm_bwd_wide_kernel(const T* __restrict__ dy, const T* __restrict__ x,
                                                                          const float* __restrict__ scale, const float* __restrict__ rinv,
                                                                          T* __restrict__ dx, float* __restrict__ partial, int64_t rows,
                                                                          int d, float eps, float drop_p, uint64_t seed,
                                                                          const T* __restrict__ dres, const T* __restrict__ gelu_pre,
                                                                          int d_part, float* __restrict__ partial_off) {
-  __shared__ float red[4];
-  constexpr int CPT = WIDE_CPT<V>;
-  const int ns = (d + WIDE_SLICE - 1) / WIDE_SLICE;
+  using Tm = Team<TEAM>;
+  __shared__ float red[Tm::BWD_LDS];
+  constexpr int CPT = WIDE_CPT<V, TEAM>;
+  const int ns = Tm::slices(d);
   const bool resident = ns == 1;
   float* prow = partial + (int64_t)blockIdx.x * d;
   float* orow = OFF ? partial_off + (int64_t)blockIdx.x * d : nullptr;
@@ -892,14 +685,14 @@ __global__ __launch_bounds__(NORM_THREADS) void rmsnorm_bwd_wide_kernel(const T*
     for (int s = 0; s < ns; ++s)
 #pragma unroll
       for (int c = 0; c < CPT; ++c) {
-        const int col = wide_col<V>(s, c);
+        const int col = wide_col<V, TEAM>(s, c);
         if (col < d) {
 #pragma unroll
           for (int i = 0; i < V; ++i) { prow[col + i] = 0.f; if (OFF) orow[col + i] = 0.f; }
         }
       }
   }
-  for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
+  for (int64_t row = (int64_t)blockIdx.x * Tm::PER_BLOCK + Tm::team(); row < rows; row += (int64_t)gridDim.x * Tm::PER_BLOCK) {
     const int64_t off = row * d;
     const float r = rinv[row];
     float xv[CPT][V], gd[CPT][V];
@@ -907,7 +700,7 @@ __global__ __launch_bounds__(NORM_THREADS) void rmsnorm_bwd_wide_kernel(const T*
     for (int s = 0; s < ns; ++s) {
 #pragma unroll
       for (int c = 0; c < CPT; ++c) {
-        const int col = wide_col<V>(s, c);
+        const int col = wide_col<V, TEAM>(s, c);
         if (col < d) {
           float dyv[V];
           rms_bwd_in<T, V>(dy, x, scale, off, col, drop_p, seed, xv[c], dyv, gd[c]);
@@ -921,13 +714,13 @@ __global__ __launch_bounds__(NORM_THREADS) void rmsnorm_bwd_wide_kernel(const T*
         }
       }
     }
-    cdot = block_sum(cdot, red);
+    cdot = Tm::sum(cdot, red);
     const float nsd = (1.0f / r - eps) * (float)d_part;     // ||x_part|| * sqrt(d_part)
     const float k = nsd > 0.f ? cdot * r * r / nsd : 0.f;
     for (int s = 0; s < ns; ++s) {
 #pragma unroll
       for (int c = 0; c < CPT; ++c) {
-        const int col = wide_col<V>(s, c);
+        const int col = wide_col<V, TEAM>(s, c);
         if (col < d) {
           if (!resident) {
             float dyv[V];
@@ -940,7 +733,7 @@ __global__ __launch_bounds__(NORM_THREADS) void rmsnorm_bwd_wide_kernel(const T*
             float rv[V];
             wide_load<T, V>(dres + off + col, rv);
 #pragma unroll
-            for (int i = 0; i < V; ++i) o[i] = from_f<T>(o[i]) + rv[i];       // rounded as the generic kernel's Vec8 sum
+            for (int i = 0; i < V; ++i) o[i] = from_f<T>(o[i]) + rv[i];       // each folded pass starts from the value its own pass would have read
           }
           if (gelu_pre) {
             float pv[V];
@@ -956,24 +749,22 @@ __global__ __launch_bounds__(NORM_THREADS) void rmsnorm_bwd_wide_kernel(const T*
   if (resident) {
 #pragma unroll
     for (int c = 0; c < CPT; ++c) {
-      const int col = wide_col<V>(0, c);
-      if (col < d) {
-#pragma unroll
-        for (int i = 0; i < V; ++i) { prow[col + i] = gacc[c][i]; if (OFF) orow[col + i] = oacc[c][i]; }
-      }
+      partial_row<V, TEAM>(prow, c, gacc[c], d, red);
+      if constexpr (OFF) partial_row<V, TEAM>(orow, c, oacc[c], d, red);
     }
   }
 }
 
-// the arguments and the result of layernorm_fwd_kernel, any d; the variance is taken about the mean in a pass of its own
-template <typename T, int V>
+// stats[row] = (mean, rstd); the variance is taken about the mean in a pass of its own
+template <typename T, int V, int TEAM>
 __global__ __launch_bounds__(NORM_THREADS) void layernorm_fwd_wide_kernel(const T* __restrict__ x, const float* __restrict__ gamma,
                                                                            const float* __restrict__ beta, T* __restrict__ y,
                                                                            float* __restrict__ stats, int64_t rows, int d, float eps) {
-  __shared__ float red[4];
-  constexpr int CPT = WIDE_CPT<V>;
-  const int ns = (d + WIDE_SLICE - 1) / WIDE_SLICE;
-  for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
+  using Tm = Team<TEAM>;
+  __shared__ float red[Tm::SUM_LDS];
+  constexpr int CPT = WIDE_CPT<V, TEAM>;
+  const int ns = Tm::slices(d);
+  for (int64_t row = (int64_t)blockIdx.x * Tm::PER_BLOCK + Tm::team(); row < rows; row += (int64_t)gridDim.x * Tm::PER_BLOCK) {
     const T* xr = x + row * d;
     T* yr = y + row * d;
     float v[CPT][V];
@@ -981,7 +772,7 @@ __global__ __launch_bounds__(NORM_THREADS) void layernorm_fwd_wide_kernel(const 
     for (int s = 0; s < ns; ++s) {
 #pragma unroll
       for (int c = 0; c < CPT; ++c) {
-        const int col = wide_col<V>(s, c);
+        const int col = wide_col<V, TEAM>(s, c);
         if (col < d) {
           wide_load<T, V>(xr + col, v[c]);
 #pragma unroll
@@ -989,12 +780,12 @@ __global__ __launch_bounds__(NORM_THREADS) void layernorm_fwd_wide_kernel(const 
         }
       }
     }
-    const float mean = block_sum(sm, red) / (float)d;
+    const float mean = Tm::sum(sm, red) / (float)d;
     float q = 0.f;
     for (int s = 0; s < ns; ++s) {
 #pragma unroll
       for (int c = 0; c < CPT; ++c) {
-        const int col = wide_col<V>(s, c);
+        const int col = wide_col<V, TEAM>(s, c);
         if (col < d) {
           if (ns > 1) wide_load<T, V>(xr + col, v[c]);
 #pragma unroll
@@ -1002,12 +793,12 @@ __global__ __launch_bounds__(NORM_THREADS) void layernorm_fwd_wide_kernel(const 
         }
       }
     }
-    const float rstd = rsqrtf(block_sum(q, red) / (float)d + eps);
-    if (threadIdx.x == 0) { stats[row * 2] = mean; stats[row * 2 + 1] = rstd; }
+    const float rstd = rsqrtf(Tm::sum(q, red) / (float)d + eps);
+    if (Tm::member() == 0) { stats[row * 2] = mean; stats[row * 2 + 1] = rstd; }
     for (int s = 0; s < ns; ++s) {
 #pragma unroll
       for (int c = 0; c < CPT; ++c) {
-        const int col = wide_col<V>(s, c);
+        const int col = wide_col<V, TEAM>(s, c);
         if (col < d) {
           if (ns > 1) wide_load<T, V>(xr + col, v[c]);
           float g[V], b[V], o[V];
@@ -1022,6 +813,17 @@ __global__ __launch_bounds__(NORM_THREADS) void layernorm_fwd_wide_kernel(const 
   }
 }
 
+// x * y rounded on its own, never contracted into the add that takes it.  The LayerNorm backward's row sums need it: s1 takes
+// gamma * dy and s2 takes (gamma dy) * xhat, both products with other readers, and whether the build fuses them into the sums
+// depends on how it packs the two chains -- in the TEAM = 64 form it did, one unit in the last place of dx away from the separate
+// one-wave-per-row kernel this body replaced (profiles/norm_team_refactor.txt, section 4).  With the two products pinned, dx keeps those
+// bits at both team sizes.  The other a * b + c of these kernels (the ga / gacc updates, gd - s1 - xh * s2) are the compiler's to
+// contract; they came out the same at both team sizes, and tools/debug_norm_ab.py against the build before is the check that they still do.
+__device__ __forceinline__ float mul_rn(float x, float y) {
+#pragma clang fp contract(off)
+  return x * y;
+}
+
 // one chunk of the LayerNorm backward's inputs: x-hat, dy, gamma * dy
 template <typename T, int V>
 __device__ __forceinline__ void ln_bwd_in(const T* dy, const T* x, const float* gamma, int64_t off, int col, float mean, float rstd,
@@ -1031,18 +833,19 @@ __device__ __forceinline__ void ln_bwd_in(const T* dy, const T* x, const float* 
   wide_load<T, V>(dy + off + col, dyv);
   wide_param<V>(gamma + col, g);
 #pragma unroll
-  for (int i = 0; i < V; ++i) { xh[i] = (xv[i] - mean) * rstd; gd[i] = dyv[i] * g[i]; }
+  for (int i = 0; i < V; ++i) { xh[i] = (xv[i] - mean) * rstd; gd[i] = mul_rn(dyv[i], g[i]); }
 }
 
-// the arguments and the results of layernorm_bwd_kernel (partial[2][gridDim][d]), any d; gradient sums as in rmsnorm_bwd_wide_kernel
-template <typename T, int V>
+// dgamma / dbeta partials per block written to partial[2][gridDim][d]; gradient sums as in rmsnorm_bwd_wide_kernel
+template <typename T, int V, int TEAM>
 __global__ __launch_bounds__(NORM_THREADS) void layernorm_bwd_wide_kernel(const T* __restrict__ dy, const T* __restrict__ x,
                                                                            const float* __restrict__ gamma, const float* __restrict__ stats,
                                                                            T* __restrict__ dx, float* __restrict__ partial, int64_t rows,
                                                                            int d) {
-  __shared__ float red[4];
-  constexpr int CPT = WIDE_CPT<V>;
-  const int ns = (d + WIDE_SLICE - 1) / WIDE_SLICE;
+  using Tm = Team<TEAM>;
+  __shared__ float red[Tm::BWD_LDS];
+  constexpr int CPT = WIDE_CPT<V, TEAM>;
+  const int ns = Tm::slices(d);
   const bool resident = ns == 1;
   float* grow = partial + (int64_t)blockIdx.x * d;
   float* brow = partial + ((int64_t)gridDim.x + blockIdx.x) * d;
@@ -1055,14 +858,14 @@ __global__ __launch_bounds__(NORM_THREADS) void layernorm_bwd_wide_kernel(const 
     for (int s = 0; s < ns; ++s)
 #pragma unroll
       for (int c = 0; c < CPT; ++c) {
-        const int col = wide_col<V>(s, c);
+        const int col = wide_col<V, TEAM>(s, c);
         if (col < d) {
 #pragma unroll
           for (int i = 0; i < V; ++i) { grow[col + i] = 0.f; brow[col + i] = 0.f; }
         }
       }
   }
-  for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
+  for (int64_t row = (int64_t)blockIdx.x * Tm::PER_BLOCK + Tm::team(); row < rows; row += (int64_t)gridDim.x * Tm::PER_BLOCK) {
     const int64_t off = row * d;
     const float mean = stats[row * 2], rstd = stats[row * 2 + 1];
     float xh[CPT][V], gd[CPT][V];
@@ -1070,26 +873,26 @@ __global__ __launch_bounds__(NORM_THREADS) void layernorm_bwd_wide_kernel(const 
     for (int s = 0; s < ns; ++s) {
 #pragma unroll
       for (int c = 0; c < CPT; ++c) {
-        const int col = wide_col<V>(s, c);
+        const int col = wide_col<V, TEAM>(s, c);
         if (col < d) {
           float dyv[V];
           ln_bwd_in<T, V>(dy, x, gamma, off, col, mean, rstd, xh[c], dyv, gd[c]);
 #pragma unroll
           for (int i = 0; i < V; ++i) {
             s1 += gd[c][i];
-            s2 += gd[c][i] * xh[c][i];
+            s2 += mul_rn(gd[c][i], xh[c][i]);
             if (resident) { ga[c][i] += dyv[i] * xh[c][i]; ba[c][i] += dyv[i]; }
             else { grow[col + i] += dyv[i] * xh[c][i]; brow[col + i] += dyv[i]; }
           }
         }
       }
     }
-    s1 = block_sum(s1, red) / (float)d;
-    s2 = block_sum(s2, red) / (float)d;
+    s1 = Tm::sum(s1, red) / (float)d;
+    s2 = Tm::sum(s2, red) / (float)d;
     for (int s = 0; s < ns; ++s) {
 #pragma unroll
       for (int c = 0; c < CPT; ++c) {
-        const int col = wide_col<V>(s, c);
+        const int col = wide_col<V, TEAM>(s, c);
         if (col < d) {
           if (!resident) {
             float dyv[V];
@@ -1106,11 +909,8 @@ __global__ __launch_bounds__(NORM_THREADS) void layernorm_bwd_wide_kernel(const 
   if (resident) {
 #pragma unroll
     for (int c = 0; c < CPT; ++c) {
-      const int col = wide_col<V>(0, c);
-      if (col < d) {
-#pragma unroll
-        for (int i = 0; i < V; ++i) { grow[col + i] = ga[c][i]; brow[col + i] = ba[c][i]; }
-      }
+      partial_row<V, TEAM>(grow, c, ga[c], d, red);
+      partial_row<V, TEAM>(brow, c, ba[c], d, red);
     }
   }
 }
@@ -1125,10 +925,11 @@ inline int packed_blocks_bwd(int64_t groups) { return clamp_blocks(ceil_div(grou
 inline int norm_blocks(int64_t rows) { return clamp_blocks(ceil_div(rows, 4), NORM_MAX_BLOCKS); }
 inline size_t dtype_bytes(int dtype) { return dtype == MEANT_BF16 ? 2 : 4; }
 
-// Which kernel family a shape runs on; the only place that knows the widths.
-//   NORM_WIDE:   d % 8 != 0 or d > MAXC * 512 = 2048: the *_wide_kernel family, V = 8 elements per load if d % 8 == 0, else V = 1;
+// Which kernels a shape runs on; the only place that knows the widths.  NORM_ROW and NORM_WIDE are the two team sizes of the one
+// unpacked family (the *_wide_kernel templates, switch_vt below).
+//   NORM_WIDE:   d % 8 != 0 or d > MAXC * 512 = 2048: TEAM = 256, one workgroup per row, V = 8 elements per load if d % 8 == 0, else V = 1;
 //   NORM_PACKED: R = 1, 2 or 4 rows per wave with R * d / 8 = C * 64 chunks, C <= 3 per lane (so d <= 1536), and rows % R == 0;
-//   NORM_ROW:    every other d <= 2048, one wave per row (also what a packing shape gets from a caller that cannot pack).
+//   NORM_ROW:    every other d <= 2048: TEAM = 64, one wave per row, V = 8 (also what a packing shape gets from a caller that cannot pack).
 enum NormKind { NORM_PACKED, NORM_ROW, NORM_WIDE };
 struct NormRoute { NormKind kind; int R, C, V; };
 inline NormRoute norm_route(int64_t rows, int64_t d, bool may_pack = true) {
@@ -1143,10 +944,13 @@ inline bool norm_aligned(const NormRoute& nr, const void* p, size_t elt) {
   return nr.V == 8 ? meant_aligned16(p) : (reinterpret_cast<uintptr_t>(p) % elt) == 0;
 }
 
-// compile-time switches over the chunks per lane C and the vector width V: f(Int<N>{}) for the runtime value
+// compile-time switches over the chunks per lane C of a packed route and over (V, TEAM) of an unpacked one: f(Int<N>{}...) for
+// the runtime value; <8, 64>, <8, 256> and <1, 256> are the only (V, TEAM) instantiated
 template <int N> using Int = std::integral_constant<int, N>;
 template <typename F> inline int switch_c(int C, F&& f) { return C == 1 ? f(Int<1>{}) : C == 2 ? f(Int<2>{}) : f(Int<3>{}); }
-template <typename F> inline int switch_v(int V, F&& f) { return V == 8 ? f(Int<8>{}) : f(Int<1>{}); }
+template <typename F> inline int switch_vt(const NormRoute& nr, F&& f) {
+  return nr.kind == NORM_ROW ? f(Int<8>{}, Int<64>{}) : nr.V == 8 ? f(Int<8>{}, Int<256>{}) : f(Int<1>{}, Int<256>{});
+}
 
 // the ordered reductions of per-block partial rows every backward ends with: out1 from `partial`, out2 (if not null) from the plane after it
 inline int norm_colsums(const float* partial, int nb, int64_t d, float* out1, float* out2, int accumulate2, void* stream) {
@@ -1159,16 +963,11 @@ inline int norm_colsums(const float* partial, int nb, int64_t d, float* out1, fl
 
 // ---- launchers: each kernel template is named here and nowhere else ----
 inline int launched(const char* name) { MEANT_LAUNCH_CHECK(name); return MEANT_OK; }
-// the one-wave-per-row and the wide forward
+// the unpacked forward, one wave or one workgroup per row
 int launch_fwd_unpacked(const char* name, const NormRoute& nr, const void* x, const float* scale, void* y, float* rinv, int64_t rows, int64_t d,
                         float eps, float drop_p, uint64_t seed, int64_t d_part, const float* offset, int dtype, void* stream) {
-  if (nr.kind == NORM_ROW) {
-    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(rmsnorm_fwd_kernel<T>, dim3(norm_blocks(rows)), dim3(NORM_THREADS), 0, (hipStream_t)stream,
-                                                (const T*)x, scale, (T*)y, rinv, rows, (int)d, eps, drop_p, seed, (int)d_part, offset));
-    return launched(name);
-  }
-  return switch_v(nr.V, [&](auto v) -> int {
-    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((rmsnorm_fwd_wide_kernel<T, v.value>), dim3(norm_blocks(rows)), dim3(NORM_THREADS), 0,
+  return switch_vt(nr, [&](auto v, auto team) -> int {
+    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((rmsnorm_fwd_wide_kernel<T, v.value, team.value>), dim3(norm_blocks(rows)), dim3(NORM_THREADS), 0,
                                                 (hipStream_t)stream, (const T*)x, scale, (T*)y, rinv, rows, (int)d, eps, drop_p, seed,
                                                 (int)d_part, offset));
     return launched(name);
@@ -1219,34 +1018,25 @@ int launch_bwd_packed(const char* name, const NormRoute& nr, int nbp, const void
   });
 }
 
-// the one-wave-per-row and the wide backward; partial_off (may be null): the plane of the offset gradient's partial rows
+// the unpacked backward; partial_off (may be null): the plane of the offset gradient's partial rows
 int launch_bwd_unpacked(const char* name, const NormRoute& nr, int nb, const void* dy, const void* x, const float* scale, const float* rinv,
                         void* dx, float* partial, int64_t rows, int64_t d, float eps, float drop_p, uint64_t seed, const void* dres,
                         const void* gelu_pre, int64_t d_part, float* partial_off, int dtype, void* stream) {
-  if (nr.kind == NORM_ROW) {
-    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(rmsnorm_bwd_kernel<T>, dim3(nb), dim3(NORM_THREADS), 0, (hipStream_t)stream, (const T*)dy,
-                                                (const T*)x, scale, rinv, (T*)dx, partial, rows, (int)d, eps, drop_p, seed, (const T*)dres,
-                                                (const T*)gelu_pre, (int)d_part, partial_off));
-    return launched(name);
-  }
-  auto wide = [&](auto v, auto off) -> int {
-    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((rmsnorm_bwd_wide_kernel<T, v.value, off.value>), dim3(nb), dim3(NORM_THREADS), 0,
+  auto launch = [&](auto v, auto team, auto off) -> int {
+    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((rmsnorm_bwd_wide_kernel<T, v.value, team.value, off.value>), dim3(nb), dim3(NORM_THREADS), 0,
                                                 (hipStream_t)stream, (const T*)dy, (const T*)x, scale, rinv, (T*)dx, partial, rows, (int)d, eps,
                                                 drop_p, seed, (const T*)dres, (const T*)gelu_pre, (int)d_part, partial_off));
     return launched(name);
   };
-  return switch_v(nr.V, [&](auto v) -> int { return partial_off ? wide(v, std::true_type{}) : wide(v, std::false_type{}); });
+  return switch_vt(nr, [&](auto v, auto team) -> int {
+    return partial_off ? launch(v, team, std::true_type{}) : launch(v, team, std::false_type{});
+  });
 }
 
 int launch_ln_fwd(const char* name, const NormRoute& nr, const void* x, const float* gamma, const float* beta, void* y, float* stats,
                   int64_t rows, int64_t d, float eps, int dtype, void* stream) {
-  if (nr.kind == NORM_ROW) {
-    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(layernorm_fwd_kernel<T>, dim3(norm_blocks(rows)), dim3(NORM_THREADS), 0, (hipStream_t)stream,
-                                                (const T*)x, gamma, beta, (T*)y, stats, rows, (int)d, eps));
-    return launched(name);
-  }
-  return switch_v(nr.V, [&](auto v) -> int {
-    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((layernorm_fwd_wide_kernel<T, v.value>), dim3(norm_blocks(rows)), dim3(NORM_THREADS), 0,
+  return switch_vt(nr, [&](auto v, auto team) -> int {
+    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((layernorm_fwd_wide_kernel<T, v.value, team.value>), dim3(norm_blocks(rows)), dim3(NORM_THREADS), 0,
                                                 (hipStream_t)stream, (const T*)x, gamma, beta, (T*)y, stats, rows, (int)d, eps));
     return launched(name);
   });
@@ -1254,14 +1044,9 @@ int launch_ln_fwd(const char* name, const NormRoute& nr, const void* x, const fl
 
 int launch_ln_bwd(const char* name, const NormRoute& nr, int nb, const void* dy, const void* x, const float* gamma, const float* stats, void* dx,
                   float* partial, int64_t rows, int64_t d, int dtype, void* stream) {
-  if (nr.kind == NORM_ROW) {
-    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL(layernorm_bwd_kernel<T>, dim3(nb), dim3(NORM_THREADS), 0, (hipStream_t)stream, (const T*)dy,
-                                                (const T*)x, gamma, stats, (T*)dx, partial, rows, (int)d));
-    return launched(name);
-  }
-  return switch_v(nr.V, [&](auto v) -> int {
-    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((layernorm_bwd_wide_kernel<T, v.value>), dim3(nb), dim3(NORM_THREADS), 0, (hipStream_t)stream,
-                                                (const T*)dy, (const T*)x, gamma, stats, (T*)dx, partial, rows, (int)d));
+  return switch_vt(nr, [&](auto v, auto team) -> int {
+    DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((layernorm_bwd_wide_kernel<T, v.value, team.value>), dim3(nb), dim3(NORM_THREADS), 0,
+                                                (hipStream_t)stream, (const T*)dy, (const T*)x, gamma, stats, (T*)dx, partial, rows, (int)d));
     return launched(name);
   });
 }
@@ -1275,7 +1060,8 @@ int rmsnorm_fwd_any(const char* name, bool may_pack, const void* x, const float*
   MEANT_REQUIRE(drop_p >= 0.f && drop_p < 1.f, MEANT_ERR_ARG, "%s: drop_p out of range", name);
   const NormRoute nr = norm_route(rows, d, may_pack);
   const size_t eb = dtype_bytes(dtype);
-  MEANT_REQUIRE(norm_aligned(nr, x, eb) && norm_aligned(nr, y, eb) && norm_aligned(nr, scale, 4), MEANT_ERR_ARG, "%s: alignment", name);
+  MEANT_REQUIRE(norm_aligned(nr, x, eb) && norm_aligned(nr, y, eb) && norm_aligned(nr, scale, 4) && (!offset || norm_aligned(nr, offset, 4)),
+                MEANT_ERR_ARG, "%s: alignment", name);      // offset: read in 16-byte loads at V = 8, as the gain is
   if (rows == 0) return MEANT_OK;
   if (nr.kind == NORM_PACKED) return launch_fwd_packed(name, nr, x, scale, y, rinv, rows, d, eps, drop_p, seed, dtype, stream);
   return launch_fwd_unpacked(name, nr, x, scale, y, rinv, rows, d, eps, drop_p, seed, d_part, offset, dtype, stream);
@@ -1428,6 +1214,9 @@ extern "C" int meant_layernorm_fwd(const void* x, const float* gamma, const floa
   MEANT_REQUIRE(rows > 0 && d > 0 && d <= NORM_MAX_D, MEANT_ERR_UNSUPPORTED, "layernorm_fwd: unsupported d=%lld", (long long)d);
   const NormRoute nr = norm_route(rows, d, false);
   const size_t eb = dtype_bytes(dtype);
+  // One wave per row is not checked, as it never was: x and y were always read in 16-byte loads there; gamma and beta (and gamma in
+  // the backward) were read element by element and are now read in 16-byte loads like the gain, which the global loads of gfx950
+  // perform at any float address: a parameter pointer off a 16-byte boundary is served on this route, more slowly.
   MEANT_REQUIRE(nr.kind != NORM_WIDE || (norm_aligned(nr, x, eb) && norm_aligned(nr, y, eb) && norm_aligned(nr, gamma, 4) && norm_aligned(nr, beta, 4)),
                 MEANT_ERR_ARG, "layernorm_fwd: alignment");
   return launch_ln_fwd("layernorm_fwd", nr, x, gamma, beta, y, stats, rows, d, eps, dtype, stream);

@@ -285,7 +285,7 @@ def emulate_rinv(x, eps, d_part=None, defect=None):
 
 
 def emulate_rms_bwd(dy, x, gain, r, eps, tier, d_part=None, defect=None, gelu_grad=None):
-    """(dx as the tier stores it, dgain): norm.hip's rmsnorm_bwd_kernel / _packed_kernel"""
+    """(dx as the tier stores it, dgain): norm.hip's rmsnorm_bwd_wide_kernel / rmsnorm_bwd_packed_kernel"""
     d = x.shape[1]
     d_stat = d if d_part is None or defect == "partial_all_columns" else d_part
     gd = gain * dy
@@ -316,7 +316,7 @@ def emulate_rmsnorm(t, tier, d_part=None, with_offset=False, defect=None):
 
 
 def emulate_layernorm(t, tier, defect=None):
-    """the two-pass statistics of layernorm_fwd_kernel, rstd = rsqrt(var + eps), and layernorm_bwd_kernel"""
+    """the two-pass statistics of layernorm_fwd_wide_kernel, rstd = rsqrt(var + eps), and layernorm_bwd_wide_kernel"""
     x, dy, gamma, beta, eps = t["x"].float(), t["dy"].float(), t["gamma"].float(), t["beta"].float(), torch.tensor(t["eps"], dtype=torch.float32)
     d = x.shape[1]
     mean = _chunked_sum(x) / d

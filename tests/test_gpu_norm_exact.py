@@ -249,7 +249,7 @@ def run_rms_bwd(L, dev, dtype, rows, d, *, extras=False, d_part=None, doffset=Fa
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
 @pytest.mark.parametrize("d,rows", ROW_CASES)
 def test_rmsnorm_bwd_one_wave_per_row(L, dev, dtype, d, rows):
-    """rmsnorm_bwd_kernel<T>"""
+    """rmsnorm_bwd_wide_kernel<T, 8, 64, false>: one wave per row, the four waves' sums folded through LDS (partial_row)"""
     assert norm_route(rows, d)[0] == "row"
     if rows == BIG_ROWS:
         assert rows > 4 * norm_blocks(rows) and rows % 4, "the grid-stride loop has to run a second, ragged pass"
@@ -273,7 +273,7 @@ def test_rmsnorm_bwd_packed(L, dev, dtype, d, R, C, kind):
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
 @pytest.mark.parametrize("d,rows", WIDE_CASES)
 def test_rmsnorm_bwd_wide(L, dev, dtype, d, rows):
-    """rmsnorm_bwd_wide_kernel<T, V, false>: V = 1 off multiples of 8, else V = 8; resident up to one slice"""
+    """rmsnorm_bwd_wide_kernel<T, V, 256, false>: one workgroup per row; V = 1 off multiples of 8, else V = 8; resident up to one slice"""
     assert norm_route(rows, d) == ("wide", 0, 0, 8 if d % 8 == 0 else 1)
     assert rows > norm_blocks(rows), "every workgroup takes more than one row"
     if rows > 4 * NORM_MAX_BLOCKS:
@@ -292,7 +292,7 @@ def test_rmsnorm_bwd_with_residual_gradient_and_gelu(L, dev, dtype, d, rows):
 @pytest.mark.parametrize("doffset", [False, True], ids=["plain", "doffset"])
 @pytest.mark.parametrize("d,d_part", PARTIAL)
 def test_rmsnorm_partial_bwd(L, dev, dtype, d, d_part, doffset):
-    """rmsnorm_bwd_kernel<T> (d = 520) and rmsnorm_bwd_wide_kernel<T, 1, OFF> (d = 100): the offset gradient in the second plane"""
+    """rmsnorm_bwd_wide_kernel<T, 8, 64, OFF> (d = 520) and <T, 1, 256, OFF> (d = 100): the offset gradient in the second plane"""
     assert norm_route(PARTIAL_ROWS, d, may_pack=False)[0] == ("row" if d == 520 else "wide")
     run_rms_bwd(L, dev, dtype, PARTIAL_ROWS, d, d_part=d_part, doffset=doffset, what=f"rmsnorm_partial_bwd d={d} d_part={d_part}")
 
@@ -374,7 +374,7 @@ def test_rmsnorm_bwd_pooled_row_group_loop(L, dev, dtype):
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
 @pytest.mark.parametrize("d,rows", ROW_CASES + WIDE_CASES)
 def test_layernorm_bwd(L, dev, dtype, d, rows):
-    """layernorm_bwd_kernel<T> (d % 8 == 0, d <= 2048: LayerNorm never packs) and layernorm_bwd_wide_kernel<T, V>"""
+    """layernorm_bwd_wide_kernel<T, 8, 64> (d % 8 == 0, d <= 2048: LayerNorm never packs) and <T, V, 256>"""
     what = f"layernorm_bwd d={d} rows={rows}"
     kind = norm_route(rows, d, may_pack=False)[0]
     assert kind == ("row" if d % 8 == 0 and d <= 2048 else "wide")

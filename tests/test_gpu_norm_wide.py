@@ -1,5 +1,6 @@
-"""RMSNorm / LayerNorm at the widths the one-row-per-wave kernels do not take (d > 2048, or d % 8 != 0): the one-row-per-workgroup
-kernels of csrc/norm.hip (rmsnorm_*_wide_kernel, layernorm_*_wide_kernel) against the CPU oracle / eager fp32 PyTorch, both tiers."""
+"""RMSNorm / LayerNorm at the widths one wave per row does not take (d > 2048, or d % 8 != 0): the one-row-per-workgroup form
+(TEAM = 256) of the unpacked kernels of csrc/norm.hip (rmsnorm_*_wide_kernel, layernorm_*_wide_kernel) against the CPU oracle /
+eager fp32 PyTorch, both tiers."""
 import numpy as np
 import pytest
 import torch

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the individual HIP kernels through the C ABI (GPU box only).
-usage: python tools/bench_kernels.py [gemm|attn|norm|all]"""
+usage: python tools/bench_kernels.py [gemm|attn|norm|norm_rows|all]   (norm_rows: the one-wave-per-row part of norm alone)"""
 import math
 import sys
 import os
@@ -69,9 +69,39 @@ def bench_norm():
         print(f"  fwd rows={rows} d={d}: {t*1e3:7.3f} ms  {2*rows*d*2/t/1e9:7.0f} GB/s")
         dx = torch.empty_like(x); ds = torch.empty(d, device=dev)
         wsb = lib.meant_rmsnorm_bwd_ws(rows, d); ws = torch.empty(wsb, device=dev, dtype=torch.uint8)
-        f = lambda: check(lib.meant_rmsnorm_bwd(y.data_ptr(), x.data_ptr(), g.data_ptr(), r.data_ptr(), dx.data_ptr(), ds.data_ptr(), rows, d, 1e-8, 0.0, 0, BF16, ws.data_ptr(), wsb, st()))
+        f = lambda: check(lib.meant_rmsnorm_bwd(y.data_ptr(), x.data_ptr(), g.data_ptr(), r.data_ptr(), dx.data_ptr(), ds.data_ptr(), rows, d, 1e-8, 0.0, 0, None, None, BF16, ws.data_ptr(), wsb, st()))
         t = timeit(f)
         print(f"  bwd rows={rows} d={d}: {t*1e3:7.3f} ms  {3*rows*d*2/t/1e9:7.0f} GB/s")
+
+
+def bench_norm_rows(windows=5):
+    """the one-wave-per-row route: LayerNorm (never packs) at the token count of tools/bench_timesformer.py's default model, RMSNorm at an
+    odd row count (cannot pack) and at d = 2048 (four chunks per lane); bf16, median and spread of `windows` windows of 20 launches"""
+    dev = "cuda"
+    print("== one wave per row (bf16): median ms of %d windows [min .. max]" % windows)
+
+    def line(tag, rows, d, f, passes):
+        ts = sorted(timeit(f) for _ in range(windows))
+        med = ts[windows // 2]
+        print(f"  {tag} rows={rows} d={d}: {med*1e3:7.4f} ms [{ts[0]*1e3:.4f} .. {ts[-1]*1e3:.4f}]  {passes*rows*d*2/med/1e9:7.0f} GB/s", flush=True)
+
+    for kind, rows, d in [("layernorm", 16 * (1 + 12 * 196), 768), ("rmsnorm", 12289, 768), ("rmsnorm", 4096, 2048)]:
+        x = torch.randn(rows, d, device=dev).bfloat16(); dy = torch.randn(rows, d, device=dev).bfloat16()
+        g = torch.ones(d, device=dev); b = torch.zeros(d, device=dev)
+        y = torch.empty_like(x); dx = torch.empty_like(x); dg = torch.empty(d, device=dev); db = torch.empty(d, device=dev)
+        wsb = lib.meant_rmsnorm_bwd_ws(rows, d); ws = torch.empty(wsb, device=dev, dtype=torch.uint8)
+        if kind == "layernorm":
+            stats = torch.empty(rows, 2, device=dev)
+            fwd = lambda: check(lib.meant_layernorm_fwd(x.data_ptr(), g.data_ptr(), b.data_ptr(), y.data_ptr(), stats.data_ptr(), rows, d, 1e-5, BF16, st()))
+            bwd = lambda: check(lib.meant_layernorm_bwd(dy.data_ptr(), x.data_ptr(), g.data_ptr(), stats.data_ptr(), dx.data_ptr(), dg.data_ptr(), db.data_ptr(),
+                                                        rows, d, BF16, ws.data_ptr(), wsb, st()))
+        else:
+            r = torch.empty(rows, device=dev)
+            fwd = lambda: check(lib.meant_rmsnorm_fwd(x.data_ptr(), g.data_ptr(), y.data_ptr(), r.data_ptr(), rows, d, 1e-8, 0.0, 0, BF16, st()))
+            bwd = lambda: check(lib.meant_rmsnorm_bwd(dy.data_ptr(), x.data_ptr(), g.data_ptr(), r.data_ptr(), dx.data_ptr(), dg.data_ptr(), rows, d, 1e-8, 0.0, 0,
+                                                      None, None, BF16, ws.data_ptr(), wsb, st()))
+        line(kind + " fwd", rows, d, fwd, 2)
+        line(kind + " bwd", rows, d, bwd, 3)
 
 
 def bench_attn():
@@ -102,5 +132,7 @@ if __name__ == "__main__":
         bench_gemm()
     if what in ("norm", "all"):
         bench_norm()
+    if what in ("norm", "norm_rows", "all"):
+        bench_norm_rows()
     if what in ("attn", "all"):
         bench_attn()

@@ -69,8 +69,9 @@ def chain(tag, rows, d, DT, x, dy, g, r, pre, gen, group_rows):
 
 
 # the smallest shape of each route: packed R = 4 C = 1 | packed C = 2 | packed R = 2 C = 3 | one wave per row (odd row count) |
-# one wave per row (C would be 4) | wide V = 8 | wide V = 1 | wide, two slices
-for rows, d in ((8, 128), (4, 1024), (4, 768), (5, 768), (4, 2048), (3, 2056), (3, 100), (2, 8200)):
+# one wave per row (C would be 4) | wide V = 8 | wide V = 1 | wide, two slices | one wave per row with ragged lanes (65 chunks) and a
+# second grid-stride pass (more than 4 x 1024 rows)
+for rows, d in ((8, 128), (4, 1024), (4, 768), (5, 768), (4, 2048), (3, 2056), (3, 100), (2, 8200), (4103, 520)):
     for DT in (1, 0):
         gen = torch.Generator().manual_seed(1000 * rows + d)
         cast = (lambda z: z.bfloat16()) if DT else (lambda z: z.float())
@@ -85,6 +86,9 @@ for rows, d in ((8, 128), (4, 1024), (4, 768), (5, 768), (4, 2048), (3, 2056), (
             out[f"{tag} fwd{nm} y"] = y.clone(); out[f"{tag} fwd{nm} rinv"] = r.clone()
             check(lib.meant_rmsnorm_bwd(p_(dy), p_(x), p_(g), p_(r), p_(dx), p_(ds), rows, d, 1e-8, p, seed, None, None, DT, p_(ws), wsb, st))
             out[f"{tag} bwd{nm} dx"] = dx.clone(); out[f"{tag} bwd{nm} dscale"] = ds.clone()
+        for nm, dres, gp in (("bwd+dres", dy, None), ("bwd+dres+gelu", dy, x)):
+            check(lib.meant_rmsnorm_bwd(p_(dy), p_(x), p_(g), p_(r), p_(dx), p_(ds), rows, d, 1e-8, 0.0, 0, p_(dres), p_(gp), DT, p_(ws), wsb, st))
+            out[f"{tag} {nm} dx"] = dx.clone(); out[f"{tag} {nm} dscale"] = ds.clone()
         check(lib.meant_layernorm_fwd(p_(x), p_(g), p_(b), p_(y), p_(stats), rows, d, 1e-5, DT, st))
         out[f"{tag} ln fwd y"] = y.clone(); out[f"{tag} ln fwd stats"] = stats.clone()
         check(lib.meant_layernorm_bwd(p_(dy), p_(x), p_(g), p_(stats), p_(dx), p_(ds), p_(do), rows, d, DT, p_(ws), wsb, st))
