@@ -9,6 +9,7 @@ from .attention import attention  # noqa: F401
 from .meant import meant, languageEncoder, visionEncoder, temporalEncoder  # noqa: F401
 from .meant_vision import meant_vision  # noqa: F401
 from .meant_tweet import meant_tweet  # noqa: F401
+from .meant_tweet_price import meantTweetPrice  # noqa: F401
 from .meant_vqa import meant_vqa  # noqa: F401
 from .xPosAttention import xPosAttention  # noqa: F401
 from .temporal import temporal  # noqa: F401

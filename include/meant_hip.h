@@ -470,6 +470,45 @@ int meant_meanpool_fwd(const void* x, void* out, int64_t ld_out, int64_t col_off
 int meant_meanpool_bwd(const void* dout, int64_t ld_out, int64_t col_off, void* dx, int64_t G, int64_t S, int64_t d,
                        int dtype, int out_dtype, void* stream);
 
+/* ---- learned softmax pooling of the token axis ------- src/meant/meant_tweet.py:173,259-261, src/meant/meant_timesformer.py:274,336-338
+ * lang_prep = Linear(d, d) -> LayerNorm(d) -> GELU -> Linear(d, 1) -> Softmax over the sequence, then pooled = sum_s w_s x_s.  The first
+ * Linear is meant_linear_fwd; everything behind it is two passes forward and two backward.  With T = G S token rows, h [T, d] the first
+ * Linear's output, n = LayerNorm(h) gamma + beta (biased variance), a = gelu_erf(n):
+ *   meant_ln_gelu_dot_fwd   score[t] = a[t, :] . w2 + b2 from one read of h (the row stays in registers); n and a are never written.
+ *                           score: float [rows]; stats: float [rows, 2] = (mean, rstd) as meant_layernorm_fwd keeps them; b2: float [1] on the
+ *                           device (or NULL: 0).
+ *   meant_softmax_pool_fwd  per sequence g: w[g, :] = softmax_s(score[g, :]) over the positions the mask keeps (0 elsewhere),
+ *                           out[g, col_off : col_off + d] = sum_s w[g, s] x[g, s, :] in a [G, ld_out] buffer of out_dtype, under the contract of
+ *                           meant_meanpool_fwd for ld_out, col_off and out_dtype.  key_mask: NULL or [G, S] of mask_kind (a meant_mask_dtype), 0
+ *                           = the position is left out; a sequence with every position left out gives w = 0 and out = 0.  w: float [G, S], kept
+ *                           for the backward.
+ *   meant_softmax_pool_bwd  dx[g, s, :] = w[g, s] dout[g, :] (act), dscore[g, s] = w[g, s] (r[g, s] - sum_t w[g, t] r[g, t]) with the row dots
+ *                           r[g, s] = x[g, s, :] . dout[g, :] -- the second term from the dots themselves in a fixed order, one read of x.
+ *   meant_ln_gelu_dot_bwd   recomputes n and a from h and stats in float (exact-erf GELU and derivative); dh (act) = the LayerNorm backward of
+ *                           dn = dscore w2 gelu_erf'(n); dgamma, dbeta and dw2 = sum_rows dscore a (float [d], overwritten) through per-block
+ *                           partial rows in the workspace, reduced in a fixed order.  workspace: meant_ln_gelu_dot_bwd_ws(rows, d) bytes.
+ * The gradient of b2 is exactly zero (a softmax does not see a shift) and no entry computes it.
+ * Any d > 0, S >= 1, G >= 1, both tiers: 16-byte accesses where d % 8 == 0 (the pool: and ld_out, col_off) and the bases are 16-byte aligned,
+ * element access otherwise; nothing is touched at or beyond column d of a row, out / dout not outside [col_off, col_off + d).  All sums
+ * are ordered, no atomics: two runs give the same bits.  rows, d, S, G <= 0, a null pointer, an unknown dtype or mask_kind: MEANT_ERR_ARG
+ * before any launch. */
+int meant_ln_gelu_dot_fwd(const void* h, const float* gamma, const float* beta, const float* w2, const float* b2, float* score,
+                          float* stats, int64_t rows, int64_t d, float eps, int dtype, void* stream);
+int meant_softmax_pool_fwd(const void* x, const float* score, const void* key_mask, int mask_kind, float* w, void* out, int64_t ld_out,
+                           int64_t col_off, int64_t G, int64_t S, int64_t d, int dtype, int out_dtype, void* stream);
+int meant_softmax_pool_bwd(const void* dout, int64_t ld_out, int64_t col_off, const void* x, const float* w, void* dx, float* dscore,
+                           int64_t G, int64_t S, int64_t d, int dtype, int out_dtype, void* stream);
+size_t meant_ln_gelu_dot_bwd_ws(int64_t rows, int64_t d);
+int meant_ln_gelu_dot_bwd(const float* dscore, const void* h, const float* stats, const float* gamma, const float* beta, const float* w2,
+                          void* dh, float* dgamma, float* dbeta, float* dw2, int64_t rows, int64_t d, int dtype, void* workspace,
+                          size_t workspace_bytes, void* stream);
+/* the price columns of the fork's Stocknet fusion (src/meant/meant_tweet_price.py:208, torch.cat((pooled, prices), dim=2)):
+ * out[r, col_off + c] (float, row stride ld_out) = (float)src[r, c] for c < cols; src dense [rows, cols] of price_dtype, a meant_price_dtype.
+ * Element access; nothing else of out is touched. */
+enum meant_price_dtype { MEANT_PRICE_F32 = 0, MEANT_PRICE_BF16 = 1, MEANT_PRICE_F64 = 2, MEANT_PRICE_F16 = 3 };
+int meant_price_cols(const void* src, int price_dtype, float* out, int64_t ld_out, int64_t col_off, int64_t rows, int64_t cols,
+                     void* stream);
+
 /* ---- small elementwise helpers ---- */
 /* y[r, :] = x[r, :] + v[(r mod period), :]  (temp_embedding add, meant/meant.py:141-142).  Any d > 0: 16-byte accesses where
  * d % 8 == 0 and x, y are 16-byte aligned, element by element otherwise; nothing is touched at or beyond column d of a row. */

@@ -17,6 +17,7 @@ Reference map (file:line under the reference root):
   meant_vision         meant/meant_vision.py:79-165
   meant_tweet          meant/meant_tweet.py:85-167
   meant_vqa            meant/meant_vqa.py:143-234
+  meantTweetPrice      src/meant/meant_tweet_price.py:139-219 (the fork's Stocknet model; lang_prep: src/meant/meant_tweet.py:173,259-261)
 """
 from __future__ import annotations
 
@@ -344,12 +345,19 @@ class xPosAttention(_MHA):
 
 
 class temporal(_MHA):
-    """meant/temporal.py:12-60: the query is the last lag step only (:39), keys/values all L steps."""
+    """meant/temporal.py:12-60: the query is the last lag step only (:39), keys/values all L steps.
+    fork=True: the form of src/meant/temporal.py:11-74, which differs in three places: the Linear named `k` produces the keys and `v`
+    the values (:45), the scores are divided by sqrt(Dh) (:52), and the result is [B, dim], without the length-1 lag axis (:72)."""
 
-    def __init__(self, num_heads, dim, mask=False, droput=0.):
+    def __init__(self, num_heads, dim, mask=False, droput=0., fork=False):
         super().__init__(num_heads, dim, mask, droput)
+        self.fork = fork
 
     def forward(self, input):
+        if self.fork:
+            o = ops.temporal_attention(input, self.q.weight, self.q.bias, self.k.weight, self.k.bias, self.v.weight, self.v.bias,
+                                       self.num_heads, scale=1.0 / math.sqrt(self.Dh))
+            return self.multi_mad(o.view(o.shape[0], o.shape[-1]))
         o = ops.temporal_attention(input, self.q.weight, self.q.bias, self.v.weight, self.v.bias, self.k.weight, self.k.bias,
                                    self.num_heads)
         return self.multi_mad(o)
@@ -435,13 +443,17 @@ class languageEncoder(nn.Module):
 
 class temporalEncoder(nn.Module):
     """meant/meant.py:124-145; `norms=False` gives the variant of meant/meant_vision.py:79-105 and
-    meant/meant_tweet.py:85-110 (no RMSNorms, so temp_encode has 3 entries)."""
+    meant/meant_tweet.py:85-110 (no RMSNorms, so temp_encode has 3 entries).  `dropout` (a probability, 0.0 included) gives the form of
+    the fork's src/meant/meant_tweet_price.py:113-136: RMSNorms, an nn.Dropout at index 4 -- so the closing Linear is entry 5 -- and the
+    fork's own temporal attention (temporal(fork=True)); its output is [B, dim]."""
 
-    def __init__(self, dim, num_heads, lag, norms=True):
+    def __init__(self, dim, num_heads, lag, norms=True, dropout=None):
         super().__init__()
         self.dim, self.num_heads, self.lag = dim, num_heads, lag
         self.temp_embedding = nn.Parameter(torch.randn(1, lag, dim))
-        if norms:
+        if dropout is not None:
+            mods = [RMSNorm(dim), Linear(dim, dim), temporal(num_heads, dim, fork=True), RMSNorm(dim), nn.Dropout(dropout), Linear(dim, dim)]
+        elif norms:
             mods = [RMSNorm(dim), Linear(dim, dim), temporal(num_heads, dim), RMSNorm(dim), Linear(dim, dim)]
         else:
             mods = [Linear(dim, dim), temporal(num_heads, dim), Linear(dim, dim)]
@@ -450,6 +462,10 @@ class temporalEncoder(nn.Module):
     def forward(self, x):
         x = ops.add_rowvec(x, self.temp_embedding)
         for mod in self.temp_encode:
+            if isinstance(mod, nn.Dropout):
+                if self.training and mod.p > 0:
+                    x = ops.dropout(x, mod.p, _seed())
+                continue
             x = mod(x)
         return x
 
@@ -502,10 +518,11 @@ def _ckpt_setting(model):
     return v if isinstance(v, bool) else int(v)
 
 
-def _run_stack(encoders, x, *args, checkpoint=False, tokens=None):
+def _run_stack(encoders, x, *args, checkpoint=False, tokens=None, pool_tail=True):
     """all encoder layers of one stack; returns either the token tensor, or -- with POOL_LAST_LINEAR -- the
     (h, res, weight, bias) part that ops.pool_linear_cat pools.  checkpoint: bool, or the number of leading layers to recompute.
-    tokens: a _TokenIds for the first layer in place of x (None then); that layer is never recomputed (_by_id_source saw to it)"""
+    tokens: a _TokenIds for the first layer in place of x (None then); that layer is never recomputed (_by_id_source saw to it)
+    pool_tail=False: always the token tensor (a caller whose pooling is not the mean over the tokens)"""
     n = len(encoders)
     rows, d = (tokens.ids.numel(), tokens.table.shape[1]) if tokens is not None else (x.numel() // x.shape[-1], x.shape[-1])
     # big stacks fold their norms into the consumer Linears.  Decided ONCE per stack and passed down as an argument: the layers run
@@ -519,7 +536,7 @@ def _run_stack(encoders, x, *args, checkpoint=False, tokens=None):
                 raise RuntimeError("meant_amd: the by-id first layer cannot run under activation recomputation")
             kw["tokens"] = tokens
         last = enc.encode2[-1]
-        if POOL_LAST_LINEAR and i == n - 1 and isinstance(last, Linear):
+        if POOL_LAST_LINEAR and pool_tail and i == n - 1 and isinstance(last, Linear):
             h, res = _run_encoder(enc, x, *args, checkpoint=ck, pool=True, fold=fold, **kw)
             return (h, res, last.weight, last.bias)
         x = _run_encoder(enc, x, *args, checkpoint=ck, fold=fold, **kw)
@@ -761,6 +778,77 @@ class meant_tweet(nn.Module):
         for enc in self.temporal_encoding:
             fused = enc(fused)
         return _head(self.mlpHead, fused).squeeze(dim=1).float()
+
+
+class meantTweetPrice(nn.Module):
+    """src/meant/meant_tweet_price.py:139-219, the fork's Stocknet model: tweets and a [B, lag, price_dim] block of price features, no
+    images.  The pooled text and the prices share one row of dim = text_dim + price_dim floats (:208), which the temporal encoders
+    (the file's own: RMSNorms, a Dropout at index 4, the fork's temporal attention) and the LayerNorm head read; that tail is fp32 in
+    both tiers.  `txt_classtkn` is registered and unused, as in the fork.
+
+    pool='mean' is the forward as the fork wrote it (:208).  pool='softmax' registers `lang_prep` as src/meant/meant_tweet.py:173 does
+    and pools with its learned softmax over the tokens (:259-261; ops.softmax_pool).  The fork zero-pads the tokens to
+    `sequence_length` in front of lang_prep (:250-254); that is reproduced for S == sequence_length only (nothing to pad), and a
+    shorter batch raises instead of being pooled without the padding rows' share of the softmax.
+
+    mask_pool (attribute, default False) is this project's addition: the fork's pooling sees no mask, so padding tokens take part
+    in the softmax; with mask_pool = True the attention_mask is handed to the pool and they are left out."""
+
+    def __init__(self, text_dim, price_dim, lag, num_classes, embedding, sequence_length=128, flash=False, num_heads=8, num_encoders=1,
+                 num_temporal_encoders=1, channels=4, pool='mean'):
+        super().__init__()
+        if pool not in ('mean', 'softmax'):
+            raise ValueError(f"meantTweetPrice: pool must be 'mean' or 'softmax', got {pool!r}")
+        self.lag, self.price_dim, self.text_dim = lag, price_dim, text_dim
+        self.dim = text_dim + price_dim
+        self.num_heads = num_heads
+        self.sequence_length = sequence_length
+        self.embedding = nn.ModuleList([embedding])
+        self.languageEncoders = nn.ModuleList([languageEncoder(text_dim, num_heads, dropout=0.4, flash=flash) for _ in range(num_encoders)])
+        for enc in self.languageEncoders:
+            enc.encode2[4].p = 0.4                          # this file's languageEncoder passes `dropout` to both Dropouts (:57,:66)
+        self.temporal_encoding = nn.ModuleList([temporalEncoder(self.dim, num_heads, lag, dropout=0.0) for _ in range(num_temporal_encoders)])
+        self.mlpHead = nn.ModuleList([LayerNorm(self.dim), Linear(self.dim, num_classes), nn.Sigmoid()])
+        self.txt_classtkn = nn.Parameter(torch.randn(1, lag, 1, text_dim))
+        if pool == 'softmax':
+            self.lang_prep = nn.Sequential(Linear(text_dim, text_dim), LayerNorm(text_dim), nn.GELU(), Linear(text_dim, 1), nn.Softmax(dim=2))
+        self.pool = pool
+        self.mask_pool = False
+        self.compute_dtype = None
+
+    def forward(self, tweets, prices, attention_mask=None):
+        if self.pool not in ('mean', 'softmax'):
+            raise ValueError(f"meantTweetPrice: pool must be 'mean' or 'softmax', got {self.pool!r}")
+        B, S = tweets.shape[0], tweets.shape[2]
+        G = B * self.lag
+        if self.pool == 'softmax' and S < self.sequence_length:
+            raise ValueError(f"meantTweetPrice(pool='softmax'): {S} tokens per sequence, sequence_length = {self.sequence_length}.  The reference "
+                             "zero-pads the tokens to sequence_length before lang_prep, and the padding rows take their share of the "
+                             "softmax; this model reproduces that for S == sequence_length only.  Pad the batch to sequence_length.")
+        if tuple(prices.shape) != (B, self.lag, self.price_dim):
+            raise ValueError(f"meantTweetPrice: prices must be [B, lag, price_dim] = {(B, self.lag, self.price_dim)}, got {tuple(prices.shape)}")
+        dt = resolve_compute_dtype(self, None)
+        ids2 = tweets.reshape(G, S)
+        tok = _by_id_source(self.embedding, ids2, dt, self.languageEncoders)
+        words = _embed(self.embedding, ids2, dt) if tok is None else None
+        if attention_mask is not None:
+            attention_mask = attention_mask.reshape(G, attention_mask.shape[2])
+        fused = ops.price_buffer(prices, self.text_dim)      # float [G, dim], the price columns filled
+        if self.pool == 'mean':
+            words = _run_stack(self.languageEncoders, words, attention_mask, tokens=tok)
+            fused = ops.into_cols(_pool_parts(dt, words), fused, 0)
+        else:
+            words = _run_stack(self.languageEncoders, words, attention_mask, tokens=tok, pool_tail=False)
+            lp = self.lang_prep
+            fused = ops.softmax_pool(words, lp[0].weight, lp[0].bias, lp[1].weight, lp[1].bias, lp[3].weight, lp[3].bias,
+                                     key_mask=attention_mask if self.mask_pool else None, eps=lp[1].eps, out=fused, col_off=0)
+        fused = fused.view(B, self.lag, self.dim)
+        # :210-211 hands every encoder the same tensor and keeps the last one's output; each encoder adds its temp_embedding to that
+        # tensor IN PLACE (:133), so the last one reads the fused rows plus the embeddings of all encoders in front of it
+        for enc in self.temporal_encoding[:-1]:
+            fused = ops.add_rowvec(fused, enc.temp_embedding)
+        out = self.temporal_encoding[-1](fused)
+        return _head(self.mlpHead, out).squeeze(dim=1).float()
 
 
 class meant_vqa(nn.Module):

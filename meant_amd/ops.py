@@ -1175,7 +1175,7 @@ class _TemporalAttention(torch.autograd.Function):
     """meant/temporal.py:34-56 up to multi_mad: q from the last lag step, k/v from all L."""
 
     @staticmethod
-    def forward(ctx, x, wq, bq, wk, bk, wv, bv, num_heads):
+    def forward(ctx, x, wq, bq, wk, bk, wv, bv, num_heads, scale=None):
         _need_gpu(x, wq)
         B, L, d = x.shape
         D = wq.shape[0]
@@ -1189,7 +1189,7 @@ class _TemporalAttention(torch.autograd.Function):
         kv, _ = _linear_fwd_raw(x2, wkv_c, torch.cat([bk.detach(), bv.detach()]).float().contiguous(), None, EPI_NONE, False)
         o = torch.empty((B, D), device=x.device, dtype=x.dtype)
         p = torch.empty((B, num_heads, L), device=x.device, dtype=torch.float32)
-        scale = 1.0 / math.sqrt(Dh * num_heads)
+        scale = 1.0 / math.sqrt(Dh * num_heads) if scale is None else float(scale)
         check(lib.meant_temporal_attn_fwd(_p(q), _p(kv), _p(o), _p(p), B, L, num_heads, Dh, scale, _dt(x), _stream()),
               "temporal_attn_fwd")
         ctx.save_for_backward(x2, q, kv, p)
@@ -1216,11 +1216,13 @@ class _TemporalAttention(torch.autograd.Function):
         lc = last.contiguous()
         check(lib.meant_add(_p(lc), _p(dxl), _p(tmp), B * d, _dt(dx), _stream()), "add")
         dx[:, L - 1, :] = tmp
-        return dx, dwq, dbq, dwkv[:D], dbkv[:D], dwkv[D:], dbkv[D:], None
+        return dx, dwq, dbq, dwkv[:D], dbkv[:D], dwkv[D:], dbkv[D:], None, None
 
 
-def temporal_attention(x, wq, bq, wk, bk, wv, bv, num_heads):
-    return _TemporalAttention.apply(x, wq, bq, wk, bk, wv, bv, num_heads)
+def temporal_attention(x, wq, bq, wk, bk, wv, bv, num_heads, scale=None):
+    """scale: the factor on q . k; None = 1 / sqrt(Dh * num_heads) (meant/temporal.py:44).  The fork's src/meant/temporal.py:52 divides
+    by sqrt(Dh)."""
+    return _TemporalAttention.apply(x, wq, bq, wk, bk, wv, bv, num_heads, scale)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1400,6 +1402,166 @@ def pooled_linear_cat(parts, compute_dtype):
     of everything after the pooling"""
     out_dtype = torch.float32 if TAIL_FP32 else compute_dtype
     return _PooledLinearCat.apply(out_dtype, *[t for p in parts for t in p])
+
+
+def _pool_out(out, col_off, G, d, device, what):
+    """(buffer, row stride, column offset) of a pooled result: a fresh float [G, d], or the caller's [G, ld] concat buffer (float32 or
+    bfloat16, unit column stride), written in columns [col_off, col_off + d) only"""
+    if out is None:
+        if col_off:
+            raise ValueError(f"{what}: col_off = {col_off} without an `out` buffer")
+        return torch.empty((G, d), device=device, dtype=torch.float32), d, 0
+    if out.dim() != 2 or out.shape[0] != G or out.stride(1) != 1 or (G > 1 and out.stride(0) < out.shape[1]):
+        raise ValueError(f"{what}: out must be [G = {G}, ld] with unit column stride, got {tuple(out.shape)} strides {out.stride()}")
+    if col_off < 0 or col_off + d > out.shape[1]:
+        raise ValueError(f"{what}: columns [{col_off}, {col_off + d}) do not fit rows of {out.shape[1]}")
+    if out.requires_grad:
+        raise ValueError(f"{what}: out is overwritten in place and must not require a gradient")
+    _dt(out)
+    return out, (out.stride(0) if G > 1 else max(out.shape[1], out.stride(0))), int(col_off)
+
+
+class _SoftmaxPool(torch.autograd.Function):
+    """pooled[g, :] = sum_s w[g, s] x[g, s, :],  w = softmax_s(Linear(d, 1)(GELU(LayerNorm(Linear(d, d)(x))))): the fork's lang_prep
+    (src/meant/meant_tweet.py:173,259-261).  h = x W1^T + b1 is the library's Linear; behind it two passes forward
+    (meant_ln_gelu_dot_fwd, meant_softmax_pool_fwd: the normalised and the activated tensor never exist) and two backward
+    (meant_softmax_pool_bwd, meant_ln_gelu_dot_bwd), then the Linear's own backward.  dx is the direct path w dout plus the W1 path
+    dh W1: the dX GEMM takes the direct path as its residual operand (the NT product of meant_linear_fwd on the transposed weight,
+    EPI_RESIDUAL) wherever that GEMM runs at the layer's own width -- every width of the fp32 tier, d % 8 == 0 in the bf16 tier; a
+    bf16 d off the 8-grid takes the zero-padded dX product of _linear_bwd_npad and one meant_add.  b2 gets no gradient from the
+    library: a softmax does not see a shift, so it is exactly zero."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, gamma, beta, w2, b2, key_mask, eps, out, col_off):
+        _need_gpu(x, w1, b1, gamma, beta, w2, b2, key_mask, out)
+        x = _c(x)
+        G, S, d = x.shape
+        T = G * S
+        dev = x.device
+        xd = x.view(T, d)
+        x2, w_c = _k_pad(xd, w1)
+        bias_f = _c(b1.detach().float()) if b1 is not None else None
+        h, _ = _linear_fwd_raw(x2, w_c, bias_f, None, EPI_NONE, False)
+        g, b, u = _c(gamma.detach().float()), _c(beta.detach().float()), _c(w2.detach().float()).view(-1)
+        shift = _c(b2.detach().float()).view(-1) if b2 is not None else None
+        score = torch.empty(T, device=dev, dtype=torch.float32)
+        stats = torch.empty((T, 2), device=dev, dtype=torch.float32)
+        check(lib.meant_ln_gelu_dot_fwd(_p(h), _p(g), _p(b), _p(u), _p(shift), _p(score), _p(stats), T, d, eps, _dt(x), _stream()),
+              "ln_gelu_dot_fwd")
+        km, kind = None, 0
+        if key_mask is not None:
+            if key_mask.numel() != T:
+                raise ValueError(f"softmax_pool: key_mask must have G * S = {T} elements, got {tuple(key_mask.shape)}")
+            km = _c(key_mask if key_mask.dtype in _MASK_DTYPES else key_mask.float())
+            kind = _MASK_DTYPES[km.dtype]
+        w = torch.empty((G, S), device=dev, dtype=torch.float32)
+        buf, ld, off = _pool_out(out, col_off, G, d, dev, "softmax_pool")
+        check(lib.meant_softmax_pool_fwd(_p(xd), _p(score), _p(km), kind, _p(w), _p(buf), ld, off, G, S, d, _dt(x), _dt(buf), _stream()),
+              "softmax_pool_fwd")
+        if out is not None:
+            ctx.mark_dirty(out)
+        ctx.w1, ctx.b1 = w1, b1
+        _claim(w1, "softmax_pool"); _claim(b1, "softmax_pool")
+        ctx.meta = (G, S, d, off, buf.dtype, w2.shape, None if b2 is None else b2.shape)
+        ctx.save_for_backward(xd, x2 if x2 is not xd else None, h, stats, g, b, u, w)
+        return buf
+
+    @staticmethod
+    def backward(ctx, dout):
+        xd, x2, h, stats, g, b, u, w = ctx.saved_tensors
+        x2 = xd if x2 is None else x2
+        G, S, d, off, out_dtype, w2_shape, b2_shape = ctx.meta
+        T, dev, dti = G * S, xd.device, _dt(xd)
+        dout, ld = _rows(dout if dout.dtype == out_dtype else dout.to(out_dtype))
+        dx_direct = torch.empty_like(xd)
+        dscore = torch.empty((G, S), device=dev, dtype=torch.float32)
+        check(lib.meant_softmax_pool_bwd(_p(dout), ld, off, _p(xd), _p(w), _p(dx_direct), _p(dscore), G, S, d, dti, _dt(dout), _stream()),
+              "softmax_pool_bwd")
+        dh = torch.empty_like(h)
+        dgamma, dbeta, dw2 = (torch.empty(d, device=dev, dtype=torch.float32) for _ in range(3))
+        wsb = lib.meant_ln_gelu_dot_bwd_ws(T, d)
+        ws = _ws(wsb, dev)
+        check(lib.meant_ln_gelu_dot_bwd(_p(dscore), _p(h), _p(stats), _p(g), _p(b), _p(u), _p(dh), _p(dgamma), _p(dbeta), _p(dw2), T, d, dti,
+                                        _p(ws), wsb, _stream()), "ln_gelu_dot_bwd")
+        has_bias = ctx.b1 is not None
+        need_dx = ctx.needs_input_grad[0]
+        residual_route = need_dx and not (xd.dtype == torch.bfloat16 and d % 8)
+        dxw, dw1, db1 = _linear_bwd_raw(dh, x2, (ctx.w1,), need_dx and not residual_route, has_bias, bias_param=ctx.b1, site="softmax_pool", K=d)
+        dx = None
+        if residual_route:
+            wT = weights.get((ctx.w1,), xd.dtype, True)                        # [d, d]: dx = dh W1 is the NT product of dh and W1^T
+            dx = torch.empty_like(xd)
+            check(lib.meant_linear_fwd(_p(dh), d, _p(wT), None, _p(dx_direct), d, _p(dx), d, None, T, d, d, EPI_RESIDUAL, dti, _stream()),
+                  "linear_fwd (dX + direct path)")
+        elif need_dx:
+            dx = torch.empty_like(xd)
+            check(lib.meant_add(_p(dx_direct), _p(dxw), _p(dx), T * d, dti, _stream()), "add")
+        db2 = None if b2_shape is None else torch.zeros(b2_shape, device=dev, dtype=torch.float32)
+        return (dx.view(G, S, d) if dx is not None else None), dw1, db1, dgamma, dbeta, dw2.view(w2_shape), db2, None, None, None, None
+
+
+def softmax_pool(x, w1, b1, gamma, beta, w2, b2, key_mask=None, eps=1e-5, out=None, col_off=0):
+    """x [G, S, d] -> float [G, d]: the learned softmax pooling of the token axis (see _SoftmaxPool).  w1 [d, d], b1 [d]: the first
+    Linear; gamma, beta [d]: the LayerNorm; w2 [1, d], b2 [1]: the score Linear.  key_mask [G, S] (any of the attention-mask dtypes,
+    0 = the position is left out; a sequence with nothing kept pools to zeros) or None.  With `out` ([G, ld], float32 or bfloat16),
+    the result is written into its columns [col_off, col_off + d) -- a concat buffer whose other columns stay as they are -- and
+    `out` is returned."""
+    if x.dim() != 3:
+        raise ValueError(f"softmax_pool: x must be [G, S, d], got {tuple(x.shape)}")
+    G, S, d = x.shape
+    if G <= 0 or S <= 0 or d <= 0:
+        raise ValueError(f"softmax_pool: empty input {tuple(x.shape)}")
+    if tuple(w1.shape) != (d, d) or w2.numel() != d or gamma.numel() != d or beta.numel() != d:
+        raise ValueError(f"softmax_pool: parameter shapes do not match d = {d}")
+    return _SoftmaxPool.apply(x, w1, b1, gamma, beta, w2, b2, key_mask, float(eps), out, int(col_off))
+
+
+_PRICE_DTYPES = {torch.float32: _lib.PRICE_F32, torch.bfloat16: _lib.PRICE_BF16, torch.float64: _lib.PRICE_F64, torch.float16: _lib.PRICE_F16}
+
+
+def price_buffer(prices, text_dim: int):
+    """float [rows, text_dim + price_dim] with (float)prices in columns [text_dim, text_dim + price_dim) by one cast-copy: the row buffer
+    of the fork's torch.cat((pooled, prices), dim=2) (src/meant/meant_tweet_price.py:208), whose first text_dim columns a pooling op
+    fills in place (softmax_pool / into_cols with out=).  prices [..., price_dim] float64, float32, float16 or bfloat16; no gradient."""
+    if prices.dtype not in _PRICE_DTYPES:
+        raise TypeError(f"meant_amd: prices must be float64, float32, float16 or bfloat16, got {prices.dtype}")
+    _need_gpu(prices)
+    p = _c(prices.detach())
+    cols = p.shape[-1]
+    rows = p.numel() // cols
+    buf = torch.empty((rows, text_dim + cols), device=p.device, dtype=torch.float32)
+    check(lib.meant_price_cols(_p(p), _PRICE_DTYPES[p.dtype], _p(buf), text_dim + cols, text_dim, rows, cols, _stream()), "price_cols")
+    return buf
+
+
+class _IntoCols(torch.autograd.Function):
+    """out[:, col_off : col_off + d] = src (cast to out's type) in place; the gradient of src is that column block of dout"""
+
+    @staticmethod
+    def forward(ctx, src, out, col_off):
+        _need_gpu(src, out)
+        src, lds = _rows(src)
+        G, d = src.shape
+        buf, ld, off = _pool_out(out, col_off, G, d, src.device, "into_cols")
+        check(lib.meant_pad_copy2d(_p(src), lds, d, _dt(src), buf.data_ptr() + off * buf.element_size(), ld, d, _dt(buf), G, _stream()),
+              "pad_copy2d")
+        ctx.mark_dirty(out)
+        ctx.meta = (d, off, src.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        d, off, dtype = ctx.meta
+        dout, ld = _rows(dout)
+        dsrc = torch.empty((dout.shape[0], d), device=dout.device, dtype=dtype)
+        check(lib.meant_pad_copy2d(dout.data_ptr() + off * dout.element_size(), ld, d, _dt(dout), _p(dsrc), d, d, _dt(dsrc), dout.shape[0],
+                                   _stream()), "pad_copy2d")
+        return dsrc, None, None
+
+
+def into_cols(src, out, col_off=0):
+    """src [G, d] (float32 or bfloat16) written into columns [col_off, col_off + d) of the concat buffer `out` [G, ld]; returns out"""
+    return _IntoCols.apply(src, out, int(col_off))
 
 
 class _AddRowVec(torch.autograd.Function):
