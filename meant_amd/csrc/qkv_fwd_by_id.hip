@@ -20,17 +20,124 @@ namespace {
 constexpr int PANEL = 256;         // rows of a key-padding panel (meant_kv_live_rows)
 
 // The gather, the mirror image of qkv_seg_kernel: a wave walks a stretch of SEG sorted entries; grid.y cuts the 3 H Dh columns into
-// blocks of at most 64 8-column chunks, one per lane, so the four rotated pairs of a chunk stay in one lane.  A run of equal ids
-// reads its row of P once.  Four tokens are in flight: their rows (where the id changes) and rotary table rows are requested
-// before the first is rotated, rounded and stored, 16 bytes per lane.  The k | v chunks (columns >= D) of a token in a dead panel
-// are not written (the caller zeroes those panels).
+// blocks of at most 64 8-column chunks, one per lane, so the four rotated pairs of a chunk stay in one lane; the cut falls on multiples
+// of 8 chunks (gather_col_blocks), so every block's stores cover whole 128-byte lines of a row of qkv.  The k | v chunks (columns >= D)
+// of a token in a dead panel are not written (the caller zeroes those panels).
+// What a token needs -- its id, its row of qkv, its offset into the rotary tables, its panel's flag -- is formed once per lane for 64
+// entries, a block ahead, and broadcast.  The rows travel in two register sets of GATHER_G tokens: while one is rotated, rounded and
+// stored (16 bytes per lane), the other is on its way, and the set after it is requested before the first one's stores are issued:
+// the memory counter retires in order, so a load behind a store would wait for that store.  For the same reason the last loads of
+// a set are issued by every lane every time (a lane that rotates nothing repeats the block's first rotated chunk): the number of
+// loads behind a set is then known when it is waited for.
+//   ROT (a block with rotated chunks: q and k)  a run of equal ids reads its row of P once; the rotary table rows per token
+//   otherwise (v)                               the row of P per token: the repeats of a run are cache hits, and no load hangs on a branch
+constexpr int GATHER_G = 2;        // 124 registers, four waves per SIMD; 4 tokens per set: 220 and two, and measured slower
+struct GatherBlock { int id, ord, off, kv_ok; };       // 64 sorted entries, one per lane
+template <bool ROT>
+struct GatherSet;
+template <>
+struct GatherSet<true> { Vec8<float> r[GATHER_G], A[GATHER_G], B[GATHER_G]; int ord[GATHER_G]; bool st[GATHER_G]; };
+template <>
+struct GatherSet<false> { Vec8<float> r[GATHER_G]; int ord[GATHER_G]; bool st[GATHER_G]; };
+inline SegColBlocks gather_col_blocks(int64_t width) {
+  const SegColBlocks cb = seg_col_blocks(width, 1);
+  const int cut = (cb.cb_chunks + 7) & ~7;               // <= 64: seg_col_blocks gives at most 64 chunks to a block
+  return {(int)ceil_div(width >> 3, cut), cut};
+}
+
+// has: the lane has a chunk, at column col (a lane without one mirrors the first and stores nothing); rot_on: the chunk is rotated,
+// by the table rows tabA / tabB + the token's offset (a lane that rotates nothing: the block's first rotated chunk's)
+template <bool ROT>
+__device__ __forceinline__ void gather_walk(const float* __restrict__ P, const int64_t* __restrict__ sorted_ids, const int64_t* __restrict__ order,
+                                            const uint8_t* __restrict__ live, const float* __restrict__ tabA, const float* __restrict__ tabB,
+                                            bf16* __restrict__ qkv, int64_t n, int N3, int R, int S, int64_t V, int64_t j0, int64_t j1, int col,
+                                            bool has, bool kv, bool rot_on) {
+  const int lane = threadIdx.x & 63;
+  int cur = -1;
+  Vec8<float> row{};
+
+  // Ids and row numbers are below 2^31 both (the launcher checks n and V); anything that is no id of the table or no row of qkv
+  // becomes -1 and is skipped.  Past the end: the last entry again.  The panel's flag follows once the row numbers have arrived.
+  auto entries = [&](int64_t jb) {
+    const int64_t jl = jb + lane < j1 ? jb + lane : j1 - 1;
+    const long long id64 = sorted_ids[jl], ord64 = order[jl];
+    GatherBlock b;
+    b.id = id64 >= 0 && id64 < V ? (int)id64 : -1;
+    b.ord = ord64 >= 0 && ord64 < n ? (int)ord64 : -1;
+    b.off = b.ord >= 0 ? (b.ord % S) * R : 0;           // the token's rows of the rotary tables
+    b.kv_ok = 1;
+    return b;
+  };
+  auto flags = [&](const GatherBlock& b) { return !live || (b.ord >= 0 && live[b.ord / PANEL] != 0) ? 1 : 0; };
+  // the tokens [t0, t0 + GATHER_G) of a block; those past cnt repeat the last one and store nothing
+  auto request = [&](const GatherBlock& b, int t0, int cnt, GatherSet<ROT>& g) {
+#pragma unroll
+    for (int u = 0; u < GATHER_G; ++u) {
+      const int t = t0 + u < cnt ? t0 + u : (cnt ? cnt - 1 : 0);
+      const int id = __builtin_amdgcn_readlane(b.id, t);
+      const int ord = __builtin_amdgcn_readlane(b.ord, t);
+      g.ord[u] = ord;
+      g.st[u] = t0 + u < cnt && id >= 0 && ord >= 0 && has && (!kv || __builtin_amdgcn_readlane(b.kv_ok, t) != 0);
+      if constexpr (ROT) {
+        if (id != cur) {                                // wave-uniform
+          cur = id;
+          if (id >= 0) row = load8<float>(P + (int64_t)id * N3 + col);
+        }
+        g.r[u] = row;
+        const int o = __builtin_amdgcn_readlane(b.off, t);
+        g.A[u] = load8<float>(tabA + o);
+        g.B[u] = load8<float>(tabB + o);
+      } else {
+        g.r[u] = load8<float>(P + (int64_t)(id >= 0 ? id : 0) * N3 + col);
+      }
+    }
+  };
+  auto store = [&](const GatherSet<ROT>& g) {
+#pragma unroll
+    for (int u = 0; u < GATHER_G; ++u) {
+      if (!g.st[u]) continue;
+      float v[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = g.r[u].get(e);
+      if constexpr (ROT) {
+        if (rot_on) rot_apply8(v, g.A[u].lo, g.A[u].hi, g.B[u].lo, g.B[u].hi);
+      }
+      Vec8<bf16> o;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o.set(e, v[e]);
+      store8s<bf16>(qkv + (int64_t)g.ord[u] * N3 + col, o);
+    }
+  };
+
+  GatherSet<ROT> ga, gb;
+  GatherBlock blk = entries(j0), nxt = entries(j0 + 64);
+  blk.kv_ok = flags(blk);
+  request(blk, 0, (int)(j1 - j0 < 64 ? j1 - j0 : 64), ga);
+  for (int64_t jb = j0; jb < j1; jb += 64) {
+    const int cnt = (int)(j1 - jb < 64 ? j1 - jb : 64);
+    const int ncnt = jb + 64 < j1 ? (int)(j1 - jb - 64 < 64 ? j1 - jb - 64 : 64) : 0;     // past the end: nothing is stored
+    const GatherBlock after = entries(jb + 128);
+    nxt.kv_ok = flags(nxt);
+    for (int t0 = 0; t0 < cnt; t0 += 2 * GATHER_G) {
+      request(blk, t0 + GATHER_G, cnt, gb);
+      store(ga);
+      const bool last = t0 + 2 * GATHER_G >= cnt;      // the set after the second one opens the next block
+      const GatherBlock from{last ? nxt.id : blk.id, last ? nxt.ord : blk.ord, last ? nxt.off : blk.off, last ? nxt.kv_ok : blk.kv_ok};
+      request(from, last ? 0 : t0 + 2 * GATHER_G, last ? ncnt : cnt, ga);
+      store(gb);
+    }
+    blk = nxt;
+    nxt = after;
+  }
+}
+
 __global__ __launch_bounds__(256) void qkv_gather_kernel(const float* __restrict__ P, const int64_t* __restrict__ sorted_ids,
                                                           const int64_t* __restrict__ order, const uint8_t* __restrict__ live,
                                                           const float* __restrict__ qa, const float* __restrict__ qb,
                                                           const float* __restrict__ ka, const float* __restrict__ kb, bf16* __restrict__ qkv,
                                                           int64_t n, int N3, int D, int Dh, int R, int S, int64_t V, int cb_chunks) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t s = (int64_t)blockIdx.x * 4 + wave;
+  const int64_t s = seg_uniform64((int64_t)blockIdx.x * 4 + wave);         // a wave's stretch: the same in every lane
   const int64_t j0 = s * SEG;
   if (j0 >= n) return;
   const int64_t j1 = j0 + SEG < n ? j0 + SEG : n;
@@ -43,58 +150,17 @@ __global__ __launch_bounds__(256) void qkv_gather_kernel(const float* __restrict
   const int c = (col - sec * D) % Dh;
   const bool rot_on = qa != nullptr && sec < 2 && c < R;
   const bool kv = sec >= 1;
-  const float* const tabA = (sec == 1 ? ka : qa) + (rot_on ? c : 0);
-  const float* const tabB = (sec == 1 ? kb : qb) + (rot_on ? c : 0);
-  long long cur = -1;
-  Vec8<float> row{};
-
-  for (int64_t jb = j0; jb < j1; jb += 64) {
-    const int64_t jl = jb + lane < j1 ? jb + lane : j1 - 1;
-    const long long id64 = sorted_ids[jl], ord64 = order[jl];
-    // below 2^31 both (the launcher checks n and V); anything that is no id of the table or no row of qkv becomes -1 and is skipped
-    const int my_id = id64 >= 0 && id64 < V ? (int)id64 : -1;
-    const int my_ord = ord64 >= 0 && ord64 < n ? (int)ord64 : -1;
-    const int cnt = (int)(j1 - jb < 64 ? j1 - jb : 64);
-    for (int t0 = 0; t0 < cnt; t0 += 4) {
-      Vec8<float> r4[4], A4[4], B4[4];
-      int ord4[4];
-      bool st4[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int t = t0 + u < cnt ? t0 + u : cnt - 1;
-        const int id = __builtin_amdgcn_readlane(my_id, t);
-        const int ord = __builtin_amdgcn_readlane(my_ord, t);
-        if (id != cur) {                                  // wave-uniform
-          cur = id;
-          if (id >= 0) row = load8<float>(P + (int64_t)id * N3 + col);
-        }
-        r4[u] = row;
-        ord4[u] = ord;
-        const bool tok = t0 + u < cnt && id >= 0 && ord >= 0;
-        const bool kv_ok = !live || (tok && live[ord / PANEL] != 0);
-        st4[u] = tok && has && (!kv || kv_ok);
-        A4[u] = Vec8<float>{};
-        B4[u] = Vec8<float>{};
-        if (st4[u] && rot_on) {
-          const int o = (ord % S) * R;
-          A4[u] = load8<float>(tabA + o);
-          B4[u] = load8<float>(tabB + o);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        if (!st4[u]) continue;
-        float v[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = r4[u].get(e);
-        if (rot_on) rot_apply8(v, A4[u].lo, A4[u].hi, B4[u].lo, B4[u].hi);
-        Vec8<bf16> o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o.set(e, v[e]);
-        store8s<bf16>(qkv + (int64_t)ord4[u] * N3 + col, o);
-      }
-    }
+  // the block's first rotated chunk, for the lanes that rotate nothing; none: the block takes the walk without tables
+  const unsigned long long rot_lanes = __ballot(rot_on);
+  if (rot_lanes == 0) {
+    gather_walk<false>(P, sorted_ids, order, live, nullptr, nullptr, qkv, n, N3, R, S, V, j0, j1, col, has, kv, false);
+    return;
   }
+  const int first = __builtin_ctzll(rot_lanes);
+  const int rsec = __builtin_amdgcn_readlane(sec, first), rc = __builtin_amdgcn_readlane(c, first);
+  const float* const tabA = (rot_on ? (sec == 1 ? ka : qa) + c : (rsec == 1 ? ka : qa) + rc);
+  const float* const tabB = (rot_on ? (sec == 1 ? kb : qb) + c : (rsec == 1 ? kb : qb) + rc);
+  gather_walk<true>(P, sorted_ids, order, live, tabA, tabB, qkv, n, N3, R, S, V, j0, j1, col, has, kv, rot_on);
 }
 
 struct FwdByIdWs { size_t ntab, rinv, p, live, total; };
@@ -188,7 +254,7 @@ extern "C" int meant_qkv_embed_fwd_by_id(const void* table_bf16, const float* ga
   const int* const lists = (const int*)kv_lists;
   if (listed) rc = live_flags_launch(lists + MEANT_KV_LIST_HDR + nblk, lists + 1, live, npan, st);
   if (rc) return rc;
-  const SegColBlocks cb = seg_col_blocks(N3, 1);
+  const SegColBlocks cb = gather_col_blocks(N3);
   hipLaunchKernelGGL(qkv_gather_kernel, dim3((unsigned)ceil_div(nst, 4), (unsigned)cb.ncb), dim3(256), 0, st, (const float*)P, sorted_ids, order,
                      (const uint8_t*)live, qa, qb, ka, kb, (bf16*)qkv, n, (int)N3, (int)D, Dh, rot ? R : 0, (int)S, V, cb.cb_chunks);
   MEANT_LAUNCH_CHECK("qkv_embed_fwd_by_id: gather");

@@ -62,26 +62,49 @@ struct SegSlotSink {
   }
 };
 
-// the lane's two 8-column chunks, `lane` and `lane + 64` of column block blockIdx.y (cb_chunks chunks to a block, seg_col_blocks)
-struct SegCols { int64_t col[2]; bool has[2]; };
+// the lane's two 8-column chunks, `lane` and `lane + 64` of column block blockIdx.y (cb_chunks chunks to a block, seg_col_blocks), and
+// the block's first column
+struct SegCols { int64_t col[2]; bool has[2]; int64_t first; };
 __device__ __forceinline__ SegCols seg_cols(int64_t width, int cb_chunks) {
   const int lane = threadIdx.x & 63;
   const int c0 = blockIdx.y * cb_chunks;                                   // this column block: chunks [c0, c0 + nch)
   const int left = (int)(width >> 3) - c0;
   const int nch = left < cb_chunks ? left : cb_chunks;
-  return {{(int64_t)(c0 + lane) * 8, (int64_t)(c0 + lane + 64) * 8}, {lane < nch, lane + 64 < nch}};
+  return {{(int64_t)(c0 + lane) * 8, (int64_t)(c0 + lane + 64) * 8}, {lane < nch, lane + 64 < nch}, (int64_t)c0 * 8};
 }
 
-// One wave sums the rows src[order[j], :] of the sorted entries j of [j0, j1), run by run of equal ids.  Ids and row numbers are
-// broadcast from the lanes that loaded them, four rows (16-byte loads) are requested before the first is consumed, and a run's rows are
-// added in sorted order into one accumulator per column: every bit-reproducibility promise rests on that order.  A run is flushed when
-// the id changes and at the end; ids outside [0, V) and outside the sink's range are dropped there.  A run that is open on both sides
-// counts as "from the left".  With COLSUM, csum[col] = the sum of every row of the stretch, whatever its id.
+// a 64-bit value that is the same in every lane of the wave, and lane t (the same t in every lane) of a per-lane one: through the scalar
+// unit, so that what hangs on them (row bases, the loop's own counters) is scalar too
+__device__ __forceinline__ long long seg_uniform64(long long v) {
+  const unsigned lo = __builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = __builtin_amdgcn_readfirstlane((int)(v >> 32));
+  return (long long)(((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ long long seg_lane64(long long v, int t) {
+  const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)v, t), hi = __builtin_amdgcn_readlane((int)(v >> 32), t);
+  return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+// 64 sorted entries, one per lane: the id, the row, and the row's flags (SEG_ROW_OK: the row number is one of src; SEG_ROW_LIVE:
+// the rows policy's flag for it)
+struct SegBlock { long long id, ord; int flags; };
+constexpr int SEG_ROW_OK = 1, SEG_ROW_LIVE = 2;
+// four rows on their way: the lane's two chunks of each, whether a chunk counts (or is zeros), and the rows' ids
+template <typename T>
+struct SegSet { Vec8<T> r[4][2]; bool on[4][2]; long long id[4]; };
+
+// One wave sums the rows src[order[j], :] of the sorted entries j of [j0, j1), run by run of equal ids.  Ids, row numbers and row flags
+// are loaded 64 entries at a time, a block ahead, and broadcast from the lanes that loaded them.  The rows (16-byte loads) travel in
+// two register sets of four: while one set is added, the other is on its way, and the set after it is requested before the second is
+// touched, across the 64-entry blocks too, so four to eight rows are in flight at any time.  A run's rows are added in sorted order
+// into one accumulator per column: every bit-reproducibility promise rests on that order.  A run is flushed when the id changes and at
+// the end; ids outside [0, V) and outside the sink's range are dropped there.  A run that is open on both sides counts as "from the
+// left".  With COLSUM, csum[col] = the sum of every row of the stretch, whatever its id.
 template <bool COLSUM, typename T, class Rows, class Sink>
 __device__ __forceinline__ void seg_walk(const T* __restrict__ src, int64_t ld, const int64_t* __restrict__ sorted_ids,
-                                         const int64_t* __restrict__ order, int64_t n, int64_t V, int64_t j0, int64_t j1, const SegCols& c,
+                                         const int64_t* __restrict__ order, int64_t n, int64_t V, int64_t j0_, int64_t j1_, const SegCols& c,
                                          const Rows& rows, const Sink& sink, float* __restrict__ csum) {
   const int lane = threadIdx.x & 63;
+  const int64_t j0 = seg_uniform64(j0_), j1 = seg_uniform64(j1_);         // a wave's stretch: the same in every lane
   float acc[2][8], cs[2][8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) acc[0][e] = acc[1][e] = cs[0][e] = cs[1][e] = 0.f;
@@ -100,49 +123,79 @@ __device__ __forceinline__ void seg_walk(const T* __restrict__ src, int64_t ld, 
     }
   };
 
-  for (int64_t jb = j0; jb < j1; jb += 64) {
+  // the entries jb + lane of a block (past the end: the last entry again), and their flags once the row numbers have arrived
+  auto entries = [&](int64_t jb) {
     const int64_t jl = jb + lane < j1 ? jb + lane : j1 - 1;
-    const long long my_id = sorted_ids[jl], my_ord = order[jl];
-    const int cnt = (int)(j1 - jb < 64 ? j1 - jb : 64);
-    for (int t0 = 0; t0 < cnt; t0 += 4) {
-      Vec8<T> r[4][2];
-      long long ids4[4];
+    return SegBlock{sorted_ids[jl], order[jl], 0};
+  };
+  auto flags = [&](const SegBlock& b) {
+    const bool row_ok = b.ord >= 0 && b.ord < n;        // an order that is no permutation must not become an address
+    return !row_ok ? 0 : (rows.live(b.ord) ? SEG_ROW_OK | SEG_ROW_LIVE : SEG_ROW_OK);
+  };
+  // The four rows of the block's entries [t0, t0 + 4); those past cnt repeat the last one and are not added.  Every lane loads
+  // every time -- a chunk that is not to be read (no such chunk, no such row, a dead row) reads the block's first chunk of row 0
+  // and counts as zeros (SegSet::on) -- so that the number of loads behind a set is known when the set is waited for: the memory
+  // counter retires in order, and a load that may or may not have been issued would turn every wait into a wait for everything.
+  auto request = [&](const SegBlock& b, int t0, int cnt, SegSet<T>& g) {
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int t = t0 + u < cnt ? t0 + u : cnt - 1;
-        ids4[u] = __shfl(my_id, t, 64);
-        const long long ord = __shfl(my_ord, t, 64);
-        const bool row_ok = ord >= 0 && ord < n;        // an order that is no permutation must not become an address
-        const bool live = row_ok && rows.live(ord);
-        const T* row = src + (row_ok ? ord : 0) * ld;
+    for (int u = 0; u < 4; ++u) {
+      const int t = t0 + u < cnt ? t0 + u : cnt - 1;
+      g.id[u] = seg_lane64(b.id, t);
+      const long long ord = seg_lane64(b.ord, t);
+      const int fl = __builtin_amdgcn_readlane(b.flags, t);
+      const bool row_ok = (fl & SEG_ROW_OK) != 0, live = (fl & SEG_ROW_LIVE) != 0;
+      const T* row = src + (row_ok ? ord : 0) * ld;
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {
-          r[u][k] = Vec8<T>{};
-          if (c.has[k] && row_ok && rows.reads(k, live)) r[u][k] = load8s<T>(row + c.col[k]);
-        }
+      for (int k = 0; k < 2; ++k) {
+        g.on[u][k] = row_ok && rows.reads(k, live);
+        g.r[u][k] = load8s<T>(c.has[k] && g.on[u][k] ? row + c.col[k] : src + c.first);
+      }
+    }
+  };
+  auto add = [&](int t0, int cnt, const SegSet<T>& g) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (t0 + u >= cnt) break;
+      const int64_t id = g.id[u];
+      if (id != cur) {
+        flush(cur, open_left ? 0 : -1);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[0][e] = acc[1][e] = 0.f;
+        cur = id;
+        open_left = false;
       }
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        if (t0 + u >= cnt) break;
-        const int64_t id = ids4[u];
-        if (id != cur) {
-          flush(cur, open_left ? 0 : -1);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) acc[0][e] = acc[1][e] = 0.f;
-          cur = id;
-          open_left = false;
-        }
+      for (int k = 0; k < 2; ++k) {
+        const Vec8<T> v = g.on[u][k] ? g.r[u][k] : Vec8<T>{};
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-#pragma unroll
-          for (int k = 0; k < 2; ++k) {
-            const float a = r[u][k].get(e);
-            acc[k][e] += a;
-            if constexpr (COLSUM) cs[k][e] += a;
-          }
+          const float a = v.get(e);
+          acc[k][e] += a;
+          if constexpr (COLSUM) cs[k][e] += a;
         }
       }
     }
+  };
+
+  SegSet<T> ga, gb;
+  SegBlock blk = entries(j0), nxt = entries(j0 + 64);
+  blk.flags = flags(blk);
+  request(blk, 0, (int)(j1 - j0 < 64 ? j1 - j0 : 64), ga);
+  for (int64_t jb = j0; jb < j1; jb += 64) {
+    const int cnt = (int)(j1 - jb < 64 ? j1 - jb : 64);
+    const int ncnt = jb + 64 < j1 ? (int)(j1 - jb - 64 < 64 ? j1 - jb - 64 : 64) : 1;      // past the end: the last entry, not added
+    const SegBlock after = entries(jb + 128);
+    nxt.flags = flags(nxt);
+    for (int t0 = 0; t0 < cnt; t0 += 8) {
+      request(blk, t0 + 4, cnt, gb);
+      add(t0, cnt, ga);
+      const bool last = t0 + 8 >= cnt;                 // the set after the second one opens the next block
+      const SegBlock from{last ? nxt.id : blk.id, last ? nxt.ord : blk.ord, last ? nxt.flags : blk.flags};
+      request(from, last ? 0 : t0 + 8, last ? ncnt : cnt, ga);
+      add(t0 + 4, cnt, gb);
+    }
+    blk = nxt;
+    nxt = after;
   }
   const bool open_right = j1 < n && sorted_ids[j1] == cur;
   flush(cur, open_left ? 0 : (open_right ? 1 : -1));
